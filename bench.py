@@ -20,7 +20,12 @@ every rank (direct sends and receives into the final buffers, ``distributed.Segm
 timed region and always reported beside it (``allgather.ms``, ``segments_per_s_including_allgather``); rank 0 then
 runs the whole problem alone (``single_gpu_same_workload``) so that the speed-up is measured inside one run.
 
-The JSON line also carries ``roofline`` (``definition_version`` 3: the DOMINANT kernel by HIP-event time — the longer of march and
+A plain run sets up, warms up, times the K steps and prints one JSON line: ``metric``, ``value`` (segments/s), ``unit``,
+``higher_is_better``, ``dtype``, ``ms_per_step`` (one timed step, host clock) and the workload's ``config``.  Everything else below
+is measured only with ``--full``.  ``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float64;
+``dump_outputs``), so that two builds can be compared output for output: the workload is deterministic, no RNG.
+
+With ``--full`` the JSON line also carries ``roofline`` (``definition_version`` 3: the DOMINANT kernel by HIP-event time — the longer of march and
 record kernel: SURVEY §8(d)'s algorithmic bytes per launch ÷ its duration against the 8 TB/s HBM peak; ``record_kernel``: the kernel
 that writes the 44-B records with its own 48 B per segment, whatever its share; ``pipeline_frac``: 45 B per segment ÷ the whole
 step; ``march``: the march's own limits — latency / issue — with real bytes by counters; ``traffic`` only when the committed PMC
@@ -85,6 +90,32 @@ def pmc_traffic():
                  if "FETCH_SIZE" in v and "WRITE_SIZE" in v}, "profiles/r06/pmc_summary.json (same library, sha256 match)")
     except Exception as e:
         return {}, "no PMC summary: %r" % (e,)
+
+
+DUMP_SAMPLE = 1 << 19      # records written by --dump-outputs when a step makes more: a fixed, seeded sample
+DUMP_SEED = 20240607
+DUMP_LIMIT = 64 << 20      # bytes written by --dump-outputs at most
+
+
+def dump_outputs(dt, directory):
+    """--dump-outputs: what the last step handed its caller (rt_fetch_offsets, rt_fetch_volumes, rt_fetch_segments), as
+    ``directory/<name>.npy`` in float64 — offsets, status, volumes and the six record arrays.  A step with more than
+    DUMP_SAMPLE records keeps them at a fixed, seeded sample of sorted indices (``record_index.npy``).  Returns the names."""
+    off, st = dt.fetch_offsets()
+    out = {"offsets": off, "status": st, "volumes": dt.fetch_volumes()}
+    total = int(off[-1])
+    room = (DUMP_LIMIT - 8 * sum(a.size for a in out.values())) // (8 * 7)  # six record arrays + their indices
+    n_keep = max(0, min(total, DUMP_SAMPLE, room))
+    idx = np.arange(total) if n_keep == total else np.sort(np.random.default_rng(DUMP_SEED).choice(total, n_keep, replace=False))
+    seg = dt.fetch_segments()
+    out["record_index"] = idx
+    for k in ("px", "py", "qx", "qy", "ell", "element"):
+        out[k] = seg[k][idx]
+    del seg
+    os.makedirs(directory, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(directory, k + ".npy"), np.asarray(a, np.float64))
+    return sorted(out)
 
 
 def kernel_names(stats):
@@ -485,19 +516,29 @@ def _main(real_stdout):
     ap.add_argument("--n-azim", type=int, default=128)
     ap.add_argument("--delta", type=float, default=1e-3)
     ap.add_argument("--mesh", default="pincell.msh")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; records sampled above %d)" % DUMP_SAMPLE)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel times and roofline, latency, e2e, the downstream "
+                         "consumers, concurrency, config5_single_gpu, cpu_baseline; N > 1: per-rank balance, all-gather-v, same problem "
+                         "on one GPU.  The options below refine what --full measures")
     ap.add_argument("--latency-steps", type=int, default=200, help="extra single steps for the p50/p95 latency (N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-concurrent", action="store_true", help="skip the extra two-batches-in-flight measurement")
     ap.add_argument("--no-extras", action="store_true", help="skip e2e, latency, config5_single_gpu / single_gpu_same_workload")
     ap.add_argument("--sharded-sweep", action="store_true",
-                    help="N > 1: also time the sharded transport sweep (rt_sweep per rank + point-to-point exchange of the fluxes that leave a "
-                         "shard); off by default: its RCCL exchange has only run over gloo and a one-rank group so far, and the headline line "
-                         "must not depend on it")
+                    help="N > 1, with --full: also time the sharded transport sweep (rt_sweep per rank + point-to-point exchange of the "
+                         "fluxes that leave a shard); off by default: its RCCL exchange has only run over gloo and a one-rank group so far, "
+                         "and the headline line must not depend on it")
     ap.add_argument("--extras-timeout", type=int, default=300,
-                    help="N > 1: seconds after which rank 0 prints the headline line without the extras (all-gather-v, same problem on one "
-                         "GPU) if they have not returned, and every rank leaves; 0: wait for ever")
+                    help="N > 1, with --full: seconds after which rank 0 prints the headline line without the extras (all-gather-v, same "
+                         "problem on one GPU) if they have not returned, and every rank leaves; 0: wait for ever")
     ap.add_argument("--force-dist", action="store_true", help="development: run the multi-GPU code path with a one-rank RCCL group")
     args = ap.parse_args()
+    if args.sharded_sweep and not args.full:
+        ap.error("--sharded-sweep is measured with --full")
+    full = args.full
+    extras = full and not args.no_extras
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # Plain `python bench.py --gpus N`: this process becomes the launcher — it starts the N ranks with torch.distributed.run as a
@@ -608,20 +649,25 @@ def _main(real_stdout):
     drain()
     sync()
     elapsed = time.perf_counter() - t0
-    # ---- the same K steps again with the library's HIP events on (option "timing"): per-kernel durations, measured live on
-    #      the stream the kernels are launched on — what `roofline` and `kernel_ms` report; never part of `value`
+    # ---- what the last timed step computed (rank 0's shard and the all-reduced volumes when N > 1), before anything else runs
+    if args.dump_outputs and rank == 0:
+        dump_outputs(dt, args.dump_outputs)
+    # ---- --full: the same K steps again with the library's HIP events on (option "timing"): per-kernel durations, measured live
+    #      on the stream the kernels are launched on — what `roofline` and `kernel_ms` report; never part of `value`
     kern = {"march": 0.0, "compact": 0.0, "scan": 0.0, "volumes": 0.0, "plan": 0.0, "total": 0.0}
-    dmesh.set_option("timing", 1)
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-        tm = dt.timing()  # HIP events recorded on the launch stream inside rt_segmentize
-        for k in kern:
-            kern[k] += tm[k]
-    drain()
-    sync()
-    elapsed_with_events = time.perf_counter() - t0
-    dmesh.set_option("timing", 0)
+    elapsed_with_events = None
+    if full:
+        dmesh.set_option("timing", 1)
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+            tm = dt.timing()  # HIP events recorded on the launch stream inside rt_segmentize
+            for k in kern:
+                kern[k] += tm[k]
+        drain()
+        sync()
+        elapsed_with_events = time.perf_counter() - t0
+        dmesh.set_option("timing", 0)
     n_failed, _, _ = dt.failed()  # tracks on which the reference itself would have thrown (never fatal here:
     #                               a rank that exits alone would deadlock the others)
     stats = dt.stats()
@@ -632,7 +678,7 @@ def _main(real_stdout):
     #      (its launch and whatever of its latency the next march does not cover) is the difference; load balance per rank
     per_rank = None
     allreduce_exposed_ms = None
-    if dist_on:
+    if dist_on and full:
         dmesh.set_enqueue_hook(None)
         sync()
         t0 = time.perf_counter()
@@ -668,7 +714,7 @@ def _main(real_stdout):
     line_lock = threading.Lock()
     line_printed = [False]
     watchdog = None
-    if world > 1 and args.extras_timeout > 0:
+    if world > 1 and full and args.extras_timeout > 0:
         def _give_up():
             with line_lock:
                 if line_printed[0]:
@@ -702,7 +748,7 @@ def _main(real_stdout):
 
     # ---- N > 1: reassemble the global segment list on every rank (RCCL all-gather-v), always reported
     allgather = None
-    if world > 1 or args.force_dist:
+    if full and (world > 1 or args.force_dist):
         p = dt.device_pointers()
         off = torch.as_tensor(rtd.DevArray(p["offsets"], dt.n + 1, "<i8", dt), device=dev)
         local = {"counts": off[1:] - off[:-1]}
@@ -737,7 +783,7 @@ def _main(real_stdout):
     # ---- N > 1: the consumer that never gathers — a transport sweep over every rank's own tracks (rt_sweep on the shard's staging
     #      rows), the fluxes that leave a shard exchanged by RCCL send/recv pairs, the tallies all-reduced (distributed.ShardedSweep)
     sharded_sweep = None
-    if dist_on and args.sharded_sweep and not args.no_extras:
+    if dist_on and args.sharded_sweep and extras:
         if rehearsal:
             sharded_sweep = {"skipped": "rehearsal (the exchange needs device tensors on an RCCL group; tests/test_gpu_sharded_sweep.py covers it over gloo)"}
         else:
@@ -769,7 +815,7 @@ def _main(real_stdout):
 
     # ---- extras measured outside the timed region (rank 0)
     latency = e2e = same_workload = config5 = None
-    if rank == 0 and not args.no_extras and not dist_on:
+    if rank == 0 and extras and not dist_on:
         # single-step latency distribution
         lat = []
         for _ in range(max(args.latency_steps, 0)):
@@ -801,13 +847,13 @@ def _main(real_stdout):
             e2e["tracks_h2d_again_ms"] = None
         one_shot(e2e)
     downstream_sweep = None
-    if rank == 0 and not args.no_extras and not dist_on:
+    if rank == 0 and extras and not dist_on:
         try:
             downstream_sweep = sweep_bench(rt, tg, aq, dmesh, dt, local_total, max(3, args.steps // 2))
         except Exception as e:  # pragma: no cover
             downstream_sweep = {"error": repr(e)}
     downstream = None
-    if rank == 0 and not args.no_extras and not dist_on:
+    if rank == 0 and extras and not dist_on:
         # a consumer that stays on the GPU: Segment.τ for 7 energy groups from the device-resident records
         try:
             G = 7
@@ -820,13 +866,13 @@ def _main(real_stdout):
                           "note": "τ[s,g] = Σt[element[s],g]·ℓ[s] over the records where they lie (rt_fill_tau); outside `value`"}
         except Exception as e:  # pragma: no cover
             downstream = {"error": repr(e)}
-    if not args.no_extras and world > 1:
+    if extras and world > 1:
         # the same global problem on rank 0's GPU alone, in the same run: the N=1 point of this strong-scaling line
         sync()
         if rank == 0:
             same_workload = single_gpu_run(rt, _capi, wl, local_rank, max(3, args.steps // 4), 2, stream.cuda_stream, tg=tg)
         sync()
-    if rank == 0 and not args.no_extras and world == 1 and not dist_on and wkey == "c3":
+    if rank == 0 and extras and world == 1 and not dist_on and wkey == "c3":
         try:
             config5 = single_gpu_run(rt, _capi, WORKLOADS["c5"], local_rank, 5, 2, stream.cuda_stream, e2e=True)
         except Exception as e:  # pragma: no cover
@@ -834,44 +880,45 @@ def _main(real_stdout):
 
     if rank == 0:
         ms_per_step = t_max / args.steps * 1e3
-        names = kernel_names(stats)
-        traffic, traffic_src = pmc_traffic()
-        per_kernel = []
-        bps_by_phase = bytes_per_segment(stats)
-        for key in ("march", "compact", "scan"):
-            ms = kern[key] / args.steps
-            bps = bps_by_phase[key]
-            per_kernel.append({"kernel": names[key], "ms_avg": ms, "bytes_per_segment": bps,
-                               "achieved_GBs": bps * local_total / (ms * 1e-3) / 1e9 if ms > 0 else 0.0,
-                               "traffic": traffic.get(names[key]) if wkey == "c3" and world == 1 else None})
-        # The roofline's kernel is the one that moves SURVEY §8(d)'s bytes — the record-writing kernel (k_materialise_lin: 4 B read +
-        # 44 B written per segment; k_compact3 for calls that march with exact steps) — priced with its own bytes and its own HIP-event
-        # time.  The march writes 4 B per segment and is bound by its lanes' dependent chains: it is reported as such (`march`: real
-        # bytes and VALU issue by counters when the committed PMC passes belong to this library), never priced with bytes it does not move.
-        rec_k = next(k for k in per_kernel if k["kernel"] == names["compact"])
-        march_k = next(k for k in per_kernel if k["kernel"] == names["march"])
-        # definition_version 3 (round 6): `roofline` is the DOMINANT kernel by HIP-event time again (rounds 1-4; round 5 named the
-        # record kernel whatever its share) — SURVEY §8(d)'s 45 B per segment x the segments of a launch ÷ that kernel's duration when
-        # it is the march (which stages 4 B per segment: `march` says what it is bound by), the record kernel's own 48 B when it is
-        # the record kernel; the record kernel always has its own object, `roofline.record_kernel`.
-        dom_is_march = march_k["ms_avg"] >= rec_k["ms_avg"]
-        dom_k = march_k if dom_is_march else rec_k
-        dom_bps = STEP_BYTES_PER_SEGMENT if dom_is_march else rec_k["bytes_per_segment"]
-        achieved = dom_bps * local_total / (dom_k["ms_avg"] * 1e-3) / 1e9 if dom_k["ms_avg"] > 0 else 0.0
-        step_GBs = STEP_BYTES_PER_SEGMENT * global_segments / (ms_per_step * 1e-3) / 1e9
-        tr_all = [k["traffic"] for k in per_kernel]
-        traffic_ratio = (sum(tr_all) / (STEP_BYTES_PER_SEGMENT * local_total)) if all(t is not None for t in tr_all) else None
-        march_pmc = PMC_KERNELS.get(names["march"], {}) if (wkey == "c3" and world == 1) else {}
-        march_report = {"kernel": march_k["kernel"], "bound": "latency/issue", "ms_avg": march_k["ms_avg"],
-                        "bytes_by_counters": march_k["traffic"],
-                        "achieved_GBs_by_counters": (march_k["traffic"] / (march_k["ms_avg"] * 1e-3) / 1e9) if march_k["traffic"] and march_k["ms_avg"] > 0 else None,
-                        "frac_of_hbm_peak_by_counters": (march_k["traffic"] / (march_k["ms_avg"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if march_k["traffic"] and march_k["ms_avg"] > 0 else None,
-                        # SQ_INSTS_VALU wave-instructions x 4 issue cycles over (SIMDs x the kernel's cycles; GRBM_GUI_ACTIVE is summed over the 8 XCDs)
-                        "valu_issue_frac": (march_pmc["SQ_INSTS_VALU"] * 4.0 / (4 * info_cus * march_pmc["GRBM_GUI_ACTIVE"] / 8.0))
-                                           if "SQ_INSTS_VALU" in march_pmc and march_pmc.get("GRBM_GUI_ACTIVE") else None,
-                        "wait_frac": (march_pmc["SQ_WAIT_ANY"] / march_pmc["SQ_WAVE_CYCLES"]) if march_pmc.get("SQ_WAVE_CYCLES") else None,
-                        "note": "one lane = one track: the kernel lasts as long as its longest lane's chain of dependent 32-B fetches; "
-                                "it stages 4 B per segment"}
+        if full:  # per-kernel times of the second pass, roofline
+            names = kernel_names(stats)
+            traffic, traffic_src = pmc_traffic()
+            per_kernel = []
+            bps_by_phase = bytes_per_segment(stats)
+            for key in ("march", "compact", "scan"):
+                ms = kern[key] / args.steps
+                bps = bps_by_phase[key]
+                per_kernel.append({"kernel": names[key], "ms_avg": ms, "bytes_per_segment": bps,
+                                   "achieved_GBs": bps * local_total / (ms * 1e-3) / 1e9 if ms > 0 else 0.0,
+                                   "traffic": traffic.get(names[key]) if wkey == "c3" and world == 1 else None})
+            # The roofline's kernel is the one that moves SURVEY §8(d)'s bytes — the record-writing kernel (k_materialise_lin: 4 B read +
+            # 44 B written per segment; k_compact3 for calls that march with exact steps) — priced with its own bytes and its own HIP-event
+            # time.  The march writes 4 B per segment and is bound by its lanes' dependent chains: it is reported as such (`march`: real
+            # bytes and VALU issue by counters when the committed PMC passes belong to this library), never priced with bytes it does not move.
+            rec_k = next(k for k in per_kernel if k["kernel"] == names["compact"])
+            march_k = next(k for k in per_kernel if k["kernel"] == names["march"])
+            # definition_version 3 (round 6): `roofline` is the DOMINANT kernel by HIP-event time again (rounds 1-4; round 5 named the
+            # record kernel whatever its share) — SURVEY §8(d)'s 45 B per segment x the segments of a launch ÷ that kernel's duration when
+            # it is the march (which stages 4 B per segment: `march` says what it is bound by), the record kernel's own 48 B when it is
+            # the record kernel; the record kernel always has its own object, `roofline.record_kernel`.
+            dom_is_march = march_k["ms_avg"] >= rec_k["ms_avg"]
+            dom_k = march_k if dom_is_march else rec_k
+            dom_bps = STEP_BYTES_PER_SEGMENT if dom_is_march else rec_k["bytes_per_segment"]
+            achieved = dom_bps * local_total / (dom_k["ms_avg"] * 1e-3) / 1e9 if dom_k["ms_avg"] > 0 else 0.0
+            step_GBs = STEP_BYTES_PER_SEGMENT * global_segments / (ms_per_step * 1e-3) / 1e9
+            tr_all = [k["traffic"] for k in per_kernel]
+            traffic_ratio = (sum(tr_all) / (STEP_BYTES_PER_SEGMENT * local_total)) if all(t is not None for t in tr_all) else None
+            march_pmc = PMC_KERNELS.get(names["march"], {}) if (wkey == "c3" and world == 1) else {}
+            march_report = {"kernel": march_k["kernel"], "bound": "latency/issue", "ms_avg": march_k["ms_avg"],
+                            "bytes_by_counters": march_k["traffic"],
+                            "achieved_GBs_by_counters": (march_k["traffic"] / (march_k["ms_avg"] * 1e-3) / 1e9) if march_k["traffic"] and march_k["ms_avg"] > 0 else None,
+                            "frac_of_hbm_peak_by_counters": (march_k["traffic"] / (march_k["ms_avg"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if march_k["traffic"] and march_k["ms_avg"] > 0 else None,
+                            # SQ_INSTS_VALU wave-instructions x 4 issue cycles over (SIMDs x the kernel's cycles; GRBM_GUI_ACTIVE is summed over the 8 XCDs)
+                            "valu_issue_frac": (march_pmc["SQ_INSTS_VALU"] * 4.0 / (4 * info_cus * march_pmc["GRBM_GUI_ACTIVE"] / 8.0))
+                                               if "SQ_INSTS_VALU" in march_pmc and march_pmc.get("GRBM_GUI_ACTIVE") else None,
+                            "wait_frac": (march_pmc["SQ_WAIT_ANY"] / march_pmc["SQ_WAVE_CYCLES"]) if march_pmc.get("SQ_WAVE_CYCLES") else None,
+                            "note": "one lane = one track: the kernel lasts as long as its longest lane's chain of dependent 32-B fetches; "
+                                    "it stages 4 B per segment"}
         out = {
             "metric": "segments/sec (whole node)",
             "value": global_segments * args.steps / t_max,
@@ -905,36 +952,39 @@ def _main(real_stdout):
                 "device_GB_held_by_rank0_handle": stats["device_bytes"] / 1e9,
                 "library_sha256": lib_sha256(),
             },
-            "roofline": {
-                "definition_version": 3,
-                "bound": "hbm", "kernel": dom_k["kernel"],
-                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                "traffic": dom_k["traffic"], "traffic_source": traffic_src,
-                "bytes_per_segment": dom_bps, "segments_per_launch": int(local_total),
-                "kernel_ms_avg": dom_k["ms_avg"],
-                "record_kernel": {"kernel": rec_k["kernel"], "bound": "hbm", "achieved": rec_k["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": rec_k["achieved_GBs"] / HBM_PEAK_GBS, "traffic": rec_k["traffic"],
-                                  "bytes_per_segment": rec_k["bytes_per_segment"], "kernel_ms_avg": rec_k["ms_avg"],
-                                  "note": "the kernel that moves SURVEY §8(d)'s bytes: its own 4 B read + 44 B written per segment ÷ its HIP-event time"},
-                "pipeline_frac": step_GBs / (HBM_PEAK_GBS * world),
-                "traffic_over_algorithmic": traffic_ratio,
-                "march": march_report,
-                "pipeline": {"achieved": step_GBs, "frac": step_GBs / (HBM_PEAK_GBS * world), "unit": "GB/s",
-                             "bytes_per_segment": STEP_BYTES_PER_SEGMENT, "ms_per_step": ms_per_step,
-                             "traffic_over_algorithmic": traffic_ratio,
-                             "note": "whole step: algorithmic bytes (45 B/segment) ÷ ms_per_step against the peak of the GPUs in use"},
-                "note": "kernel = the longer of march and record kernel by HIP-event time (definition_version 3); the march is priced with "
-                        "SURVEY §8(d)'s 45 B/segment (it stages 4 B/segment and is bound by its per-track dependent chain: see `march`), the record "
-                        "kernel with its own 48 B (`record_kernel`); pipeline_frac = 45 B/segment ÷ ms_per_step",
-            },
-            "kernels": per_kernel,
-            "kernel_ms": {k: v / args.steps for k, v in kern.items()},
-            "kernel_ms_note": "from a second pass of the same K steps with the library's HIP events on (option \"timing\"); "
-                              "that pass took %.4f ms per step" % (elapsed_with_events / args.steps * 1e3),
-            # what a synchronous call adds around its kernels: completion seen by the host, the return through the caller, the next
-            # call's launches (the kernels of one call run back to back)
-            "host_gap_us": (ms_per_step - (kern["march"] + kern["scan"] + kern["compact"] + kern["volumes"]) / args.steps) * 1e3 if world == 1 else None,
         }
+        if full:
+            out.update({
+                "roofline": {
+                    "definition_version": 3,
+                    "bound": "hbm", "kernel": dom_k["kernel"],
+                    "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                    "traffic": dom_k["traffic"], "traffic_source": traffic_src,
+                    "bytes_per_segment": dom_bps, "segments_per_launch": int(local_total),
+                    "kernel_ms_avg": dom_k["ms_avg"],
+                    "record_kernel": {"kernel": rec_k["kernel"], "bound": "hbm", "achieved": rec_k["achieved_GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                      "frac": rec_k["achieved_GBs"] / HBM_PEAK_GBS, "traffic": rec_k["traffic"],
+                                      "bytes_per_segment": rec_k["bytes_per_segment"], "kernel_ms_avg": rec_k["ms_avg"],
+                                      "note": "the kernel that moves SURVEY §8(d)'s bytes: its own 4 B read + 44 B written per segment ÷ its HIP-event time"},
+                    "pipeline_frac": step_GBs / (HBM_PEAK_GBS * world),
+                    "traffic_over_algorithmic": traffic_ratio,
+                    "march": march_report,
+                    "pipeline": {"achieved": step_GBs, "frac": step_GBs / (HBM_PEAK_GBS * world), "unit": "GB/s",
+                                 "bytes_per_segment": STEP_BYTES_PER_SEGMENT, "ms_per_step": ms_per_step,
+                                 "traffic_over_algorithmic": traffic_ratio,
+                                 "note": "whole step: algorithmic bytes (45 B/segment) ÷ ms_per_step against the peak of the GPUs in use"},
+                    "note": "kernel = the longer of march and record kernel by HIP-event time (definition_version 3); the march is priced with "
+                            "SURVEY §8(d)'s 45 B/segment (it stages 4 B/segment and is bound by its per-track dependent chain: see `march`), the record "
+                            "kernel with its own 48 B (`record_kernel`); pipeline_frac = 45 B/segment ÷ ms_per_step",
+                },
+                "kernels": per_kernel,
+                "kernel_ms": {k: v / args.steps for k, v in kern.items()},
+                "kernel_ms_note": "from a second pass of the same K steps with the library's HIP events on (option \"timing\"); "
+                                  "that pass took %.4f ms per step" % (elapsed_with_events / args.steps * 1e3),
+                # what a synchronous call adds around its kernels: completion seen by the host, the return through the caller, the next
+                # call's launches (the kernels of one call run back to back)
+                "host_gap_us": (ms_per_step - (kern["march"] + kern["scan"] + kern["compact"] + kern["volumes"]) / args.steps) * 1e3 if world == 1 else None,
+            })
         if per_rank is not None:
             out["per_rank"] = per_rank  # load balance of the Σℓ-balanced uid ranges
             for r, v in enumerate(per_rank["segments"]):
@@ -955,7 +1005,7 @@ def _main(real_stdout):
         if same_workload is not None:
             out["single_gpu_same_workload"] = same_workload
             out["speedup_vs_single_gpu"] = same_workload["ms_per_step"] / ms_per_step
-        if dist_on:
+        if dist_on and full:
             # what a sub-linear curve is made of, in the line itself: a rank's shard is a smaller batch, and the march of a batch that
             # no longer fills the chip lasts as long as its longest track's chain whatever the number of waves
             waves = (int(hi - lo) + 63) // 64
@@ -976,11 +1026,11 @@ def _main(real_stdout):
             out["downstream_tau"] = downstream
         if downstream_sweep is not None:
             out["downstream_sweep"] = downstream_sweep
-        if world == 1 and not dist_on and not args.no_concurrent:
+        if full and world == 1 and not dist_on and not args.no_concurrent:
             out["two_batches_in_flight"] = two_in_flight(tg, aq, dmesh, dt, args.steps, local_total)
             out["stream_ordered_calls"] = stream_ordered_calls(rt, tg, aq, dmesh, dt, args.steps, local_total)
             out["completion_order_calls"] = completion_order_calls(rt, tg, aq, dmesh, args.steps, local_total)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(tg)
         with line_lock:
             if not line_printed[0]:

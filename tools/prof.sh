@@ -10,6 +10,7 @@ export TMPDIR=/tmp
 stats() {  # stats <subdir> <program> args...
   local D=$R/gpurun_out/$TAG/$1; shift
   mkdir -p $D
+  LAST=$D
   ( cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $D/stats -- "$@" > $D/stats.log 2>&1 )
   find $D/stats -name "*kernel_stats.csv" -exec cp {} $D/kernel_stats.csv \;
   rm -rf $D/stats
@@ -17,7 +18,7 @@ stats() {  # stats <subdir> <program> args...
 B="--steps 10 --warmup 2 --no-cpu-baseline --no-concurrent --no-extras"
 stats c3 python3 $R/bench.py $B
 bash $R/tools/pmc.sh $TAG/c3 python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-concurrent --no-extras
-( cd $R && python3 bench.py > gpurun_out/$TAG/c3/bench.json 2> gpurun_out/$TAG/c3/bench.log )
+( cd $R && python3 bench.py --full > $LAST/bench.json 2> $LAST/bench.log )  # (LAST: the c3 folder of `stats c3` above)
 stats c5 python3 $R/bench.py --workload c5 $B
 bash $R/tools/pmc.sh $TAG/c5 python3 $R/bench.py --workload c5 --steps 3 --warmup 1 --no-cpu-baseline --no-concurrent --no-extras
 stats sweep python3 $R/tools/ab.py --what sweep
