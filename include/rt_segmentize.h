@@ -436,6 +436,73 @@ void rt_msh_free(rt_msh *msh);
  * listed in DESIGN.md / tools/README.md; "single_pass" and "volumes_mode" exist only in a library built with -DRT_EXPERIMENTAL. */
 int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
 
+/* ---------------------------------------------------------------------------------------
+ * MOC source-iteration solver on the device (power-iteration k_eff and fixed source) over the
+ * records of the last rt_segmentize, built on rt_sweep.  Only a few scalars come back to the
+ * host per iteration.
+ *
+ * Notation: G groups, P polar angles per half space (sin θ_p, weights ω_p, Σ_p ω_p = 1), M
+ * materials (0-based ids) with sigma_t[m][g], sigma_s[m][g'][g] (from g' to g), nu_sigma_f[m][g],
+ * chi[m][g]; cell_material[e] per cell; N2 = n_azim / 2.
+ *
+ * Azimuthal weights α_a (a = 1..N2, Σ_a α_a = 1/2).  The "exact" set: with the first quadrant's
+ * angles φ_1 < ... < φ_n (n = N2 / 2), b_0 = 0, b_i = (φ_i + φ_{i+1}) / 2, b_n = π/2,
+ * α_i = (b_i − b_{i−1}) / 2π, mirrored to the supplementary index N2 − i + 1.  It equals the
+ * reference's ω_a (init_weights!) except at the first angle of each quadrant, where ω_a is
+ * (φ_2 − φ_1) / 4π and makes Σ ω_a = 1/2 − φ_1/π (a biased k).  The library does not know the
+ * angles: the caller passes α (the Python layer computes the exact set); NULL means the equal
+ * set α_a = 1 / (2 N2).
+ *
+ * Volumes      V_e = Σ_u 2 α_a(u) δ_a(u) Σ_{records of u in e} ℓ   (equal α: what rt_fetch_volumes holds)
+ * Components   the sweep runs G·P components c = g·P + p with Σt_g / sin θ_p and source ratio q_g / Σt_g,
+ *              track weights w[u] = 4π α_a(u) δ_a(u); its tally is T[e][c] = Σ w Δψ over both directions
+ * Fold         φ_{e,g} = 4π q_{e,g} / Σt_g + Σ_p ω_p sin θ_p T[e][g·P + p] / (Σt_g V_e)   (V_e = 0: the first term only;
+ *              such cells drop out of every reduction)
+ * Source       q_{e,g} = (Σ_g' Σs[g'→g] φ_{e,g'} + (χ_g / k) Σ_g' νΣf_g' φ_{e,g'} + S_{e,g}) / 4π
+ *              S: external volumetric source (0 in eigenvalue mode); fixed-source mode: k ≡ 1 (fission multiplies)
+ * Iteration    φ⁰ = 1, k⁰ = 1, zero boundary fluxes; each iteration: source update, one sweep with the boundary fluxes
+ *              the previous sweep handed on, fold.  F(φ) = Σ_e V_e Σ_g νΣf_g φ_{e,g}; k^{n+1} = k^n F(φ^{n+1}) / F(φ^n)
+ * Residual     eigenvalue: RMS over the cells with fission (F_e^n > 0) of F_e^{n+1} / F_e^n − 1, F_e = Σ_g νΣf_g φ_{e,g};
+ *              fixed source: ‖φ^{n+1} − φ^n‖₂ / ‖φ^{n+1}‖₂ over all (cell, group) pairs
+ * Stop         |k^{n+1} − k^n| / k^{n+1} < tol_k and residual < tol_flux, or max_iter iterations (converged = 0;
+ *              not an error).  Eigenvalue mode scales the returned φ to F(φ) = 1.
+ * Every Σt must be > 0 (void materials are rejected); all other data finite and >= 0.
+ *
+ * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
+ * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
+ * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
+ * RT_ERR_INVALID.  A solver must not be used after its tracks are destroyed (rt_solver_destroy is still safe).
+ * --------------------------------------------------------------------------------------- */
+typedef struct rt_solver rt_solver;
+
+#define RT_SOLVE_EIGENVALUE 0
+#define RT_SOLVE_FIXED_SOURCE 1
+
+typedef struct rt_solver_result {
+    double k_eff;       /* last k (1 in fixed-source mode)                                          */
+    double residual;    /* last residual (see above)                                                */
+    double dk;          /* last |Δk| / k                                                             */
+    double device_ms;   /* HIP-event time of all iterations (source update, sweep, fold, reductions) */
+    int32_t iterations;
+    int32_t converged;  /* 1: both tolerances met before max_iter                                    */
+} rt_solver_result;
+
+/* Bind a solver to `tracks` (rt_segmentize and rt_sweep_set_links must have run).  All arrays are host
+ * memory and copied: cell_material [n_cells], sigma_t / nu_sigma_f / chi [M][G], sigma_s [M][G][G],
+ * sin_polar / polar_weight [P], azim_weight [N2] (NULL: the equal set).  Computes V_e on the device.
+ * Returns NULL on failure (rt_last_error). */
+rt_solver *rt_solver_create(rt_tracks *tracks, int32_t n_groups, int32_t n_materials, const int32_t *cell_material,
+                            const double *sigma_t, const double *sigma_s, const double *nu_sigma_f, const double *chi,
+                            int32_t n_polar, const double *sin_polar, const double *polar_weight, const double *azim_weight);
+/* External volumetric source S [n_cells][G] for RT_SOLVE_FIXED_SOURCE (NULL: none). */
+int32_t rt_solver_set_source(rt_solver *solver, const double *source);
+/* Run from φ⁰ = 1 (every call starts afresh).  out may be NULL. */
+int32_t rt_solver_run(rt_solver *solver, int32_t mode, int32_t max_iter, double tol_k, double tol_flux, rt_solver_result *out);
+/* After a run: phi [n_cells][G], volumes [n_cells], k_history [iterations] (k after every iteration); any may be NULL.
+ * volumes is available right after rt_solver_create. */
+int32_t rt_solver_fetch(rt_solver *solver, double *phi, double *volumes, double *k_history);
+void rt_solver_destroy(rt_solver *solver);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,8 @@ Host-side mirror of the reference's public surface (``src/RayTracing.jl:32-35``)
 (Python spells the last two ``trace`` and ``segmentize``).  ``segmentize`` runs the
 hand-written HIP kernels in ``csrc/`` through the C ABI declared in
 ``include/rt_segmentize.h``; there is no CPU fallback — without the built library or
-without a GPU it raises.
+without a GPU it raises.  ``solve_eigenvalue`` / ``solve_fixed_source`` run a MOC
+source iteration on the device over the records of the last ``segmentize``.
 """
 from .boundary import BoundaryConditions, BoundaryType, Periodic, Reflective, Vacuum
 from .mesh import DiscreteModel, DiscreteModelFromFile, GmshDiscreteModel, Mesh, data_path
@@ -13,11 +14,15 @@ from .quadrature import AzimuthalQuadrature
 from .trackgenerator import (Backward, Forward, Segment, Track, TrackGenerator, bc_bwd, bc_fwd,
                              dir_next_track_bwd, dir_next_track_fwd, trace)
 from .segmentize import RTOL_DEFAULT, SegmentStore, segmentize
+from .solver import (CrossSections, PolarQuadrature, SolverResult, azimuthal_weights, exact_azimuthal_weights,
+                     solve_eigenvalue, solve_fixed_source)
 
 __all__ = [
     "BoundaryConditions", "BoundaryType", "Vacuum", "Reflective", "Periodic",
     "DiscreteModel", "DiscreteModelFromFile", "GmshDiscreteModel", "Mesh", "data_path",
     "AzimuthalQuadrature", "TrackGenerator", "trace", "segmentize", "SegmentStore", "RTOL_DEFAULT",
     "Track", "Segment",
+    "CrossSections", "PolarQuadrature", "SolverResult", "azimuthal_weights", "exact_azimuthal_weights",
+    "solve_eigenvalue", "solve_fixed_source",
     "Forward", "Backward", "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd",
 ]

@@ -7,6 +7,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import subprocess
+import weakref
 
 import numpy as np
 
@@ -26,6 +27,7 @@ SYMBOLS = (
     "rt_multi_create", "rt_multi_destroy", "rt_multi_set_option", "rt_multi_segmentize", "rt_multi_shards", "rt_multi_shard",
     "rt_multi_failed_tracks", "rt_multi_fetch_offsets", "rt_multi_fetch_segments", "rt_multi_fetch_volumes", "rt_multi_allgather",
     "rt_trace_counts", "rt_trace", "rt_msh_load", "rt_msh_sizes", "rt_msh_fetch", "rt_msh_free",
+    "rt_solver_create", "rt_solver_set_source", "rt_solver_run", "rt_solver_fetch", "rt_solver_destroy",
 )
 
 RT_TRACK_OK = 0
@@ -69,6 +71,12 @@ def _share_hip_runtime_with_torch() -> None:
             C.CDLL(cand, mode=C.RTLD_GLOBAL)
         except OSError:
             pass
+
+
+class SolverResult(C.Structure):
+    """``rt_solver_result``."""
+    _fields_ = [("k_eff", C.c_double), ("residual", C.c_double), ("dk", C.c_double), ("device_ms", C.c_double),
+                ("iterations", C.c_int32), ("converged", C.c_int32)]
 
 
 _lib = None
@@ -204,6 +212,15 @@ def lib():
     L.rt_msh_fetch.restype = C.c_int32
     L.rt_msh_fetch.argtypes = [_vp, _dp, _dp, _ip, _ip, _ip, _dp]
     L.rt_msh_free.argtypes = [_vp]
+    L.rt_solver_create.restype = _vp
+    L.rt_solver_create.argtypes = [_vp, C.c_int32, C.c_int32, _ip, _dp, _dp, _dp, _dp, C.c_int32, _dp, _dp, _dp]
+    L.rt_solver_set_source.restype = C.c_int32
+    L.rt_solver_set_source.argtypes = [_vp, _dp]
+    L.rt_solver_run.restype = C.c_int32
+    L.rt_solver_run.argtypes = [_vp, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(SolverResult)]
+    L.rt_solver_fetch.restype = C.c_int32
+    L.rt_solver_fetch.argtypes = [_vp, _dp, _dp, _dp]
+    L.rt_solver_destroy.argtypes = [_vp]
     if L.rt_abi_version() != 1:
         raise RtError("librt_segmentize.so: ABI version mismatch")
     _lib = L
@@ -585,8 +602,88 @@ class DeviceTracks:
                     volumes=float(ms[5]))
 
     def close(self):
+        for sv in list(getattr(self, "_solvers", ())):  # (a solver must not outlive its tracks)
+            sv.close()
         if getattr(self, "_h", None):
             lib().rt_tracks_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceSolver:
+    """``rt_solver`` handle: MOC source iteration on the device over the records of a ``DeviceTracks`` handle on which
+    ``segmentize`` and ``sweep_set_links`` have run (``include/rt_segmentize.h`` states the definitions).  Arrays:
+    ``cell_material`` [n_cells] (0-based), ``sigma_t`` / ``nu_sigma_f`` / ``chi`` [M, G], ``sigma_s`` [M, G, G] (from g' to g),
+    ``sin_polar`` / ``polar_weight`` [P], ``azim_weight`` [n_azim / 2] (None: the equal set)."""
+
+    EIGENVALUE, FIXED_SOURCE = 0, 1
+
+    def __init__(self, dtracks: DeviceTracks, cell_material, sigma_t, sigma_s, nu_sigma_f, chi, sin_polar, polar_weight, azim_weight=None):
+        L = lib()
+        self.dtracks = dtracks  # keeps the tracks alive
+        st = np.ascontiguousarray(sigma_t, np.float64)
+        if st.ndim != 2:
+            raise ValueError("sigma_t must have shape [M, G]")
+        M, G = st.shape
+        ss = np.ascontiguousarray(sigma_s, np.float64)
+        nf = np.ascontiguousarray(nu_sigma_f, np.float64)
+        ch = np.ascontiguousarray(chi, np.float64)
+        if ss.shape != (M, G, G) or nf.shape != (M, G) or ch.shape != (M, G):
+            raise ValueError("sigma_s must be [M, G, G] and nu_sigma_f, chi [M, G]")
+        cm, cmp_ = _i32(cell_material)
+        if cm.shape != (dtracks.dmesh.n_cells,):
+            raise ValueError("cell_material must have one entry per cell")
+        sp = np.ascontiguousarray(sin_polar, np.float64).reshape(-1)
+        wp = np.ascontiguousarray(polar_weight, np.float64).reshape(-1)
+        if sp.shape != wp.shape:
+            raise ValueError("sin_polar and polar_weight must have equal lengths")
+        aw = None if azim_weight is None else np.ascontiguousarray(azim_weight, np.float64).reshape(-1)
+        self.n_cells, self.G, self.M, self.P = dtracks.dmesh.n_cells, G, M, len(sp)
+        self._h = L.rt_solver_create(dtracks._h, G, M, cmp_, st.ctypes.data_as(_dp), ss.ctypes.data_as(_dp), nf.ctypes.data_as(_dp),
+                                     ch.ctypes.data_as(_dp), len(sp), sp.ctypes.data_as(_dp), wp.ctypes.data_as(_dp),
+                                     None if aw is None else aw.ctypes.data_as(_dp))
+        if not self._h:
+            raise RtError(f"rt_solver_create failed: {last_error()}")
+        if getattr(dtracks, "_solvers", None) is None:
+            dtracks._solvers = weakref.WeakSet()
+        dtracks._solvers.add(self)
+
+    def set_source(self, source):
+        """``rt_solver_set_source``: external volumetric source [n_cells, G] (None: none)."""
+        if source is None:
+            _check(lib().rt_solver_set_source(self._h, None))
+            return
+        q = np.ascontiguousarray(source, np.float64)
+        if q.shape != (self.n_cells, self.G):
+            raise ValueError("source must have shape [n_cells, G]")
+        _check(lib().rt_solver_set_source(self._h, q.ctypes.data_as(_dp)))
+
+    def run(self, mode: int, max_iter: int, tol_k: float, tol_flux: float) -> dict:
+        if not getattr(self, "_h", None):
+            raise RtError("the solver is closed (its tracks were closed or segmentized anew)")
+        r = SolverResult()
+        _check(lib().rt_solver_run(self._h, int(mode), int(max_iter), float(tol_k), float(tol_flux), C.byref(r)))
+        return dict(k_eff=r.k_eff, residual=r.residual, dk=r.dk, device_ms=r.device_ms, iterations=int(r.iterations),
+                    converged=bool(r.converged))
+
+    def fetch(self, iterations: int) -> dict:
+        phi = np.empty((self.n_cells, self.G)); vol = np.empty(self.n_cells); kh = np.empty(int(iterations))
+        _check(lib().rt_solver_fetch(self._h, phi.ctypes.data_as(_dp), vol.ctypes.data_as(_dp), kh.ctypes.data_as(_dp) if len(kh) else None))
+        return dict(phi=phi, volumes=vol, k_history=kh)
+
+    def volumes(self):
+        vol = np.empty(self.n_cells)
+        _check(lib().rt_solver_fetch(self._h, None, vol.ctypes.data_as(_dp), None))
+        return vol
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().rt_solver_destroy(self._h)
             self._h = None
 
     def __del__(self):

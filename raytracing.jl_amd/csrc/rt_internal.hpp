@@ -4,6 +4,7 @@
 //   rt_records.hip     staging -> records: k_compact3, k_materialise, k_finish, the offsets scan, k_volumes, k_fill_tau
 //   rt_materialise.hip k_materialise_lin: a two-phase call's records in output order
 //   rt_sweep.hip       rt_sweep: k_sweep, k_sweep_link, the sweep's host code and entry points
+//   rt_solver.hip      rt_solver: source iteration (k_eff / fixed source) around rt_sweep, fold / source / reduction kernels
 //   rt_segmentize.hip  handles, rt_tracks_create, rt_segmentize (the call's host logic), fetches, statistics
 #pragma once
 #include <hip/hip_runtime.h>
@@ -396,6 +397,7 @@ struct rt_tracks {
     rt::DTracks d{};
     // results
     bool segmentized = false;
+    uint64_t seg_epoch = 0;  // rt_segmentize calls begun on this handle (an rt_solver remembers the one it was built on)
     int64_t total = 0;
     DevBuf<int32_t> counts, status, element;
     DevBuf<int64_t> offsets, tile_sums;
@@ -530,6 +532,8 @@ void launch_scan(hipStream_t s, rt_tracks *t, int64_t n_tiles, unsigned long lon
                  unsigned long long *ctl_next, int32_t first_chunk_next, int32_t side_first_next, unsigned long long seq,
                  double *scale_volumes, double n_azim_2, bool slot_order);
 int launch_volumes_pass(hipStream_t s, rt_tracks *t, const int32_t *overflow, int64_t cap);  // fill_volumes over the compact records
+// ... with the weight w_azim[azim_idx - 1] per track in place of δs, into `volumes` (accumulated: the caller zeroes it)
+int launch_volumes_weighted(hipStream_t s, rt_tracks *t, const double *w_azim, double *volumes, const int32_t *overflow, int64_t cap);
 void launch_scale_volumes(hipStream_t s, double *volumes, int32_t n_cells, double n_azim_2);
 void launch_fill_tau(hipStream_t s, rt_tracks *t, int32_t n_groups);
 void launch_slot_arrays(hipStream_t s, int64_t n, const rt::DTracks &d, double *As, double *Bs, double *Cs, double *Ls, double *Dx, double *Dy,

@@ -917,6 +917,10 @@ void launch_scan(hipStream_t s, rt_tracks *t, int64_t n_tiles, unsigned long lon
 }
 
 int launch_volumes_pass(hipStream_t s, rt_tracks *t, const int32_t *overflow, int64_t cap) {
+    return launch_volumes_weighted(s, t, (const double *)t->delta_s.p, t->volumes.p, overflow, cap);
+}
+
+int launch_volumes_weighted(hipStream_t s, rt_tracks *t, const double *w_azim, double *volumes, const int32_t *overflow, int64_t cap) {
     rt_mesh *m = t->mesh;
     const int64_t n = t->n;
     const int64_t want_blocks = 512;
@@ -930,7 +934,7 @@ int launch_volumes_pass(hipStream_t s, rt_tracks *t, const int32_t *overflow, in
     if (shmem > 48 * 1024)
         RT_HIP(hipFuncSetAttribute((const void *)rt::k_volumes, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     hipLaunchKernelGGL(rt::k_volumes, dim3((unsigned)nb), dim3(1024), shmem, s, (const int64_t *)t->offsets.p, n, (const int32_t *)t->azim.p,
-                       (const double *)t->delta_s.p, (const int32_t *)t->element.p, (const double *)t->sell.p, t->volumes.p, m->n_cells, tpb,
+                       w_azim, (const int32_t *)t->element.p, (const double *)t->sell.p, volumes, m->n_cells, tpb,
                        use_lds, overflow, cap);
     return RT_SUCCESS;
 }

@@ -893,6 +893,7 @@ struct SegmentizeCall {
         s = m->stream;
         n = t->n;
         t->segmentized = false;
+        ++t->seg_epoch;
         t->tau_groups = 0;  // τ of the previous records is void
         for (double &v : t->ms) v = 0.0;
 

@@ -1,0 +1,441 @@
+// rt_solver.hip — rt_solver: MOC source iteration (power-iteration k_eff and fixed source) on the device around rt_sweep.
+// The definitions (azimuthal weights, volumes, components, fold, source, residual) are the contract stated in
+// include/rt_segmentize.h.  One iteration is: k_solver_source (q/Σt of every component into the sweep's xs array, in place),
+// rt_sweep (components c = g·P + p), k_solver_fold (φ from the tallies + block partials), k_solver_reduce (one workgroup:
+// the partials in a fixed order, k and the residual on the device), one 64-B copy to the host.  No FP64 atomics outside the
+// sweep's own tallies: the reductions are deterministic for a given set of tallies.
+#include "rt_internal.hpp"
+
+namespace rt {
+
+constexpr double kFourPi = 12.566370614359172;  // 4π
+constexpr int kSolvePartials = 8;                // doubles per block partial: F, Σ r², cells with fission, Σ Δφ², Σ φ², (pad)
+constexpr int kSolveBlock = 256;
+// scalars on the device (and their host copy): [0] k, [1] F(φ), [2] residual, [3] |Δk| / k
+constexpr int kSolveScalars = 8;
+
+// material table: per material, stride G·(3 + G) doubles — Σt[G], νΣf[G], χ[G], Σs[G][G] (from g' to g)
+__device__ __forceinline__ const double *mat_row(const double *tab, int32_t m, int32_t G) { return tab + (int64_t)m * G * (3 + G); }
+
+// deterministic block sum of NV values (every thread passes its own; thread 0 gets the block's): lanes of a wave by a fixed
+// butterfly, then the waves in order
+template <int NV>
+__device__ __forceinline__ void block_sum(double (&v)[NV], double *red /* [kSolveBlock / 64][NV] LDS */) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        for (int o = 32; o > 0; o >>= 1) v[j] += __shfl_xor(v[j], o, 64);
+    if (lane == 0)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) red[wv * NV + j] = v[j];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int nw = (blockDim.x + 63) >> 6;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            double s = 0.0;
+            for (int w = 0; w < nw; ++w) s += red[w * NV + j];
+            v[j] = s;
+        }
+    }
+}
+
+// q/Σt of every component (one thread per (cell, group)); the scattering matrix and the rest of the material table from LDS
+// when it fits there (the host passes the dynamic LDS size: 0 = read the table where it lies)
+__global__ __launch_bounds__(kSolveBlock) void k_solver_source(const int32_t *__restrict__ mat, const double *__restrict__ tab_g, int32_t tab_len,
+                                                               const double *__restrict__ phi, const double *__restrict__ prod,
+                                                               const double *__restrict__ ext, const double *__restrict__ scal, int32_t eigen,
+                                                               int32_t n_cells, int32_t G, int32_t P, double *__restrict__ xs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char solver_smem[];
+    const double *tab = tab_g;
+    if (tab_len > 0) {
+        double *t = reinterpret_cast<double *>(solver_smem);
+        for (int i = threadIdx.x; i < tab_len; i += blockDim.x) t[i] = tab_g[i];
+        __syncthreads();
+        tab = t;
+    }
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n_cells * G) return;
+    const int64_t e = i / G;
+    const int32_t g = (int32_t)(i - e * G);
+    const double *X = mat_row(tab, mat[e], G);
+    const double *ph = phi + e * G;
+    double s = 0.0;
+    for (int32_t gp = 0; gp < G; ++gp) s += X[3 * G + gp * G + g] * ph[gp];
+    const double k = eigen ? scal[0] : 1.0;
+    s += X[2 * G + g] * prod[e] / k;
+    if (ext) s += ext[i];
+    const double ratio = s / kFourPi / X[g];
+    double *x = xs + (e * G * P + (int64_t)g * P) * 2;
+    for (int32_t p = 0; p < P; ++p) x[2 * p + 1] = ratio;
+}
+
+// INIT: φ = 1, Σt_g / sin θ_p of every component; otherwise the fold of the last sweep's tallies T [n_cells][G·P].  Both: the
+// cell's production F_e = Σ_g νΣf φ into `prod` (the previous one is the residual's reference) and this block's partials.
+// One thread per cell.
+template <bool INIT>
+__global__ __launch_bounds__(kSolveBlock) void k_solver_fold(const int32_t *__restrict__ mat, const double *__restrict__ tab,
+                                                             const double *__restrict__ vol, const double *__restrict__ pol /* [2P]: sin θ_p, ω_p sin θ_p */,
+                                                             const double *__restrict__ T, double *__restrict__ xs, double *__restrict__ phi,
+                                                             double *__restrict__ prod, int32_t n_cells, int32_t G, int32_t P,
+                                                             double *__restrict__ partial) {
+    __shared__ double red[(kSolveBlock / 64) * 5];
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (e < n_cells) {
+        const double V = vol[e];
+        const double *X = mat_row(tab, mat[e], G);
+        const int64_t C = (int64_t)G * P;
+        const double fo = prod[e];
+        double fn = 0.0, d2 = 0.0, n2 = 0.0;
+        for (int32_t g = 0; g < G; ++g) {
+            const double st = X[g];
+            double *x = xs + (e * C + (int64_t)g * P) * 2;
+            double nw;
+            if (INIT) {
+                for (int32_t p = 0; p < P; ++p) x[2 * p] = st / pol[p];
+                nw = 1.0;
+            } else {
+                const double *Tg = T + e * C + (int64_t)g * P;
+                double acc = 0.0;
+                for (int32_t p = 0; p < P; ++p) acc += pol[P + p] * Tg[p];
+                nw = kFourPi * x[1] + (V > 0.0 ? acc / (st * V) : 0.0);
+            }
+            const double old = phi[e * G + g];
+            phi[e * G + g] = nw;
+            fn += X[G + g] * nw;
+            d2 += (nw - old) * (nw - old);
+            n2 += nw * nw;
+        }
+        prod[e] = fn;
+        if (V > 0.0) {
+            v[0] = V * fn;
+            if (fo > 0.0) { const double r = fn / fo - 1.0; v[1] = r * r; v[2] = 1.0; }
+            v[3] = d2; v[4] = n2;
+        }
+    }
+    block_sum<5>(v, red);
+    if (threadIdx.x == 0)
+        for (int j = 0; j < 5; ++j) partial[(int64_t)blockIdx.x * kSolvePartials + j] = v[j];
+}
+
+// one workgroup: the fold's partials in a fixed order -> F, k, residual, |Δk| / k (INIT: F⁰, k⁰ = 1)
+__global__ __launch_bounds__(kSolveBlock) void k_solver_reduce(const double *__restrict__ partial, int32_t n_blocks, int32_t init,
+                                                               int32_t eigen, double *__restrict__ scal) {
+    __shared__ double red[(kSolveBlock / 64) * 5];
+    double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int32_t b = threadIdx.x; b < n_blocks; b += blockDim.x)
+        for (int j = 0; j < 5; ++j) v[j] += partial[(int64_t)b * kSolvePartials + j];
+    block_sum<5>(v, red);
+    if (threadIdx.x != 0) return;
+    const double F = v[0];
+    if (init) {
+        scal[0] = 1.0; scal[1] = F; scal[2] = INFINITY; scal[3] = INFINITY;
+        return;
+    }
+    const double k_old = scal[0], F_old = scal[1];
+    const double k = eigen ? k_old * F / F_old : 1.0;
+    scal[0] = k;
+    scal[1] = F;
+    scal[2] = eigen ? sqrt(v[1] / (v[2] > 0.0 ? v[2] : 1.0)) : (v[4] > 0.0 ? sqrt(v[3] / v[4]) : 0.0);
+    scal[3] = fabs(k - k_old) / k;
+}
+
+__global__ __launch_bounds__(256) void k_solver_scale(double *__restrict__ phi, int64_t n, const double *__restrict__ scal) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) phi[i] = phi[i] / scal[1];
+}
+
+// per-track weights of the sweep (4π α δ) and per-angle weights of the volumes (2 α δ)
+__global__ __launch_bounds__(256) void k_solver_track_weights(const int32_t *__restrict__ azim, int64_t n, const double *__restrict__ w4pi,
+                                                              double *__restrict__ w) {
+    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u < n) w[u] = w4pi[azim[u] - 1];
+}
+
+}  // namespace rt
+
+struct rt_solver {
+    rt_tracks *t = nullptr;
+    int device = 0;
+    uint64_t epoch = 0;
+    int32_t G = 0, M = 0, P = 0, N2 = 0, n_cells = 0;
+    DevBuf<int32_t> mat;
+    DevBuf<double> tab, pol, vol, w_track, phi, prod, ext, partial, scal;
+    bool has_ext = false, ran = false;
+    std::vector<double> k_hist;
+    double *h_scal = nullptr;  // pinned, kSolveScalars
+    hipEvent_t ev[2] = {nullptr, nullptr};
+};
+
+using namespace rtx;
+
+namespace {
+
+bool finite_nonneg(const double *a, size_t n, size_t *bad) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(a[i]) || a[i] < 0.0) { *bad = i; return false; }
+    return true;
+}
+
+void free_solver(rt_solver *s) {
+    if (!s) return;
+    if (s->h_scal) (void)hipHostFree(s->h_scal);
+    for (hipEvent_t &e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete s;
+}
+
+int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_material, const double *sigma_t, const double *sigma_s,
+                       const double *nu_sigma_f, const double *chi, int32_t P, const double *sin_polar, const double *polar_weight,
+                       const double *azim_weight, rt_solver **out) {
+    *out = nullptr;
+    if (!t || !cell_material || !sigma_t || !sigma_s || !nu_sigma_f || !chi || !sin_polar || !polar_weight) {
+        set_error("rt_solver_create: null argument"); return RT_ERR_INVALID;
+    }
+    if (G < 1 || M < 1 || P < 1 || (int64_t)G * P > 4096 || G > 256) { set_error("rt_solver_create: bad sizes (G = %d, M = %d, P = %d)", G, M, P); return RT_ERR_INVALID; }
+    if (!t->segmentized) { set_error("rt_solver_create: rt_segmentize has not run"); return RT_ERR_INVALID; }
+    if (!t->sw_links) { set_error("rt_solver_create: rt_sweep_set_links has not run"); return RT_ERR_INVALID; }
+    rt_mesh *m = t->mesh;
+    const int32_t nc = m->n_cells;
+    const int32_t N2 = (int32_t)t->h_delta_s.size();
+    if (N2 < 1) { set_error("rt_solver_create: the tracks carry no azimuthal spacings"); return RT_ERR_INVALID; }
+    for (int32_t e = 0; e < nc; ++e)
+        if (cell_material[e] < 0 || cell_material[e] >= M) {
+            set_error("rt_solver_create: cell_material[%d] = %d is not a material id in [0, %d)", e, cell_material[e], M);
+            return RT_ERR_INVALID;
+        }
+    const size_t mg = (size_t)M * G;
+    for (size_t i = 0; i < mg; ++i)
+        if (!(sigma_t[i] > 0.0) || !std::isfinite(sigma_t[i])) {
+            set_error("rt_solver_create: sigma_t[%zu][%zu] = %g (every Σt must be finite and > 0; void materials are not supported)", i / G, i % G, sigma_t[i]);
+            return RT_ERR_INVALID;
+        }
+    size_t bad = 0;
+    if (!finite_nonneg(sigma_s, mg * G, &bad)) { set_error("rt_solver_create: sigma_s[%zu] = %g (must be finite and >= 0)", bad, sigma_s[bad]); return RT_ERR_INVALID; }
+    if (!finite_nonneg(nu_sigma_f, mg, &bad)) { set_error("rt_solver_create: nu_sigma_f[%zu] = %g (must be finite and >= 0)", bad, nu_sigma_f[bad]); return RT_ERR_INVALID; }
+    if (!finite_nonneg(chi, mg, &bad)) { set_error("rt_solver_create: chi[%zu] = %g (must be finite and >= 0)", bad, chi[bad]); return RT_ERR_INVALID; }
+    double sp = 0.0;
+    for (int32_t p = 0; p < P; ++p) {
+        if (!(sin_polar[p] > 0.0 && sin_polar[p] <= 1.0) || !(polar_weight[p] > 0.0) || !std::isfinite(polar_weight[p])) {
+            set_error("rt_solver_create: polar angle %d has sin θ = %g, ω = %g (need 0 < sin θ <= 1, ω > 0)", p, sin_polar[p], polar_weight[p]);
+            return RT_ERR_INVALID;
+        }
+        sp += polar_weight[p];
+    }
+    if (std::fabs(sp - 1.0) > 1e-12) { set_error("rt_solver_create: the polar weights sum to %.17g, not 1", sp); return RT_ERR_INVALID; }
+    std::vector<double> alpha((size_t)N2, 1.0 / (2.0 * N2));
+    if (azim_weight) {
+        double sa = 0.0;
+        for (int32_t a = 0; a < N2; ++a) {
+            if (!(azim_weight[a] > 0.0) || !std::isfinite(azim_weight[a])) { set_error("rt_solver_create: azim_weight[%d] = %g (must be > 0)", a, azim_weight[a]); return RT_ERR_INVALID; }
+            sa += azim_weight[a];
+            alpha[(size_t)a] = azim_weight[a];
+        }
+        if (std::fabs(sa - 0.5) > 1e-12) { set_error("rt_solver_create: the azimuthal weights sum to %.17g, not 1/2", sa); return RT_ERR_INVALID; }
+    }
+    if (int rc = finish_call(t)) return rc;
+    RT_HIP(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    if (int rc = ensure_compacted(t)) return rc;  // (the volumes are summed over the compact records)
+
+    rt_solver *S = new rt_solver();
+    struct Guard { rt_solver *&p; ~Guard() { free_solver(p); } } guard{S};
+    S->t = t; S->device = m->device; S->epoch = t->seg_epoch; S->G = G; S->M = M; S->P = P; S->N2 = N2; S->n_cells = nc;
+    // material table (see mat_row)
+    std::vector<double> tab((size_t)M * G * (3 + G));
+    for (int32_t mm = 0; mm < M; ++mm) {
+        double *X = tab.data() + (size_t)mm * G * (3 + G);
+        for (int32_t g = 0; g < G; ++g) {
+            X[g] = sigma_t[(size_t)mm * G + g];
+            X[G + g] = nu_sigma_f[(size_t)mm * G + g];
+            X[2 * G + g] = chi[(size_t)mm * G + g];
+        }
+        for (size_t i = 0; i < (size_t)G * G; ++i) X[3 * G + i] = sigma_s[(size_t)mm * G * G + i];
+    }
+    std::vector<double> pol((size_t)2 * P);
+    for (int32_t p = 0; p < P; ++p) { pol[(size_t)p] = sin_polar[p]; pol[(size_t)(P + p)] = polar_weight[p] * sin_polar[p]; }
+    std::vector<double> w4pi((size_t)N2), wvol((size_t)N2);
+    for (int32_t a = 0; a < N2; ++a) {
+        w4pi[(size_t)a] = rt::kFourPi * alpha[(size_t)a] * t->h_delta_s[(size_t)a];
+        wvol[(size_t)a] = 2.0 * alpha[(size_t)a] * t->h_delta_s[(size_t)a];
+    }
+    DevBuf<double> dw4pi, dwvol;
+    if (int rc = upload(S->mat, cell_material, (size_t)nc, s)) return rc;
+    if (int rc = upload(S->tab, tab.data(), tab.size(), s)) return rc;
+    if (int rc = upload(S->pol, pol.data(), pol.size(), s)) return rc;
+    if (int rc = upload(dw4pi, w4pi.data(), w4pi.size(), s)) return rc;
+    if (int rc = upload(dwvol, wvol.data(), wvol.size(), s)) return rc;
+    const size_t ncg = std::max<size_t>(1, (size_t)nc * G);
+    RT_HIP(S->vol.reserve(std::max<int32_t>(1, nc)));
+    RT_HIP(S->w_track.reserve(std::max<int64_t>(1, t->n)));
+    RT_HIP(S->phi.reserve(ncg)); RT_HIP(S->prod.reserve(std::max<int32_t>(1, nc)));
+    RT_HIP(S->partial.reserve((size_t)((nc + rt::kSolveBlock - 1) / rt::kSolveBlock + 1) * rt::kSolvePartials));
+    RT_HIP(S->scal.reserve(rt::kSolveScalars));
+    RT_HIP(hipHostMalloc((void **)&S->h_scal, rt::kSolveScalars * sizeof(double), hipHostMallocDefault));
+    for (hipEvent_t &e : S->ev) RT_HIP(hipEventCreate(&e));
+    RT_HIP(hipMemsetAsync(S->vol.p, 0, (size_t)nc * sizeof(double), s));
+    if (t->n > 0) {
+        hipLaunchKernelGGL(rt::k_solver_track_weights, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, s, (const int32_t *)t->azim.p, t->n,
+                           (const double *)dw4pi.p, S->w_track.p);
+        if (int rc = launch_volumes_weighted(s, t, dwvol.p, S->vol.p, nullptr, t->total)) return rc;
+    }
+    RT_HIP(hipStreamSynchronize(s));  // (the host vectors and the temporary device buffers die here)
+    RT_HIP(hipGetLastError());
+    *out = S;
+    S = nullptr;  // (the guard lets go)
+    return RT_SUCCESS;
+}
+
+int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, double tol_flux, rt_solver_result *res) {
+    if (!S) { set_error("rt_solver_run: null solver"); return RT_ERR_INVALID; }
+    if ((mode != RT_SOLVE_EIGENVALUE && mode != RT_SOLVE_FIXED_SOURCE) || max_iter < 0 || !(tol_k >= 0.0) || !(tol_flux >= 0.0)) {
+        set_error("rt_solver_run: bad arguments (mode %d, max_iter %d, tol_k %g, tol_flux %g)", mode, max_iter, tol_k, tol_flux);
+        return RT_ERR_INVALID;
+    }
+    rt_tracks *t = S->t;
+    if (!t->segmentized || t->seg_epoch != S->epoch) {
+        set_error("rt_solver_run: the tracks were segmentized again after rt_solver_create (its volumes and weights are stale): create a new solver");
+        return RT_ERR_INVALID;
+    }
+    if (!t->sw_links) { set_error("rt_solver_run: rt_sweep_set_links has not run"); return RT_ERR_INVALID; }
+    const bool eigen = mode == RT_SOLVE_EIGENVALUE;
+    rt_mesh *m = t->mesh;
+    if (int rc = finish_call(t)) return rc;
+    RT_HIP(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    const int32_t G = S->G, P = S->P, nc = S->n_cells, C = G * P;
+    const int64_t n = t->n;
+    // the handle's sweep state: C components, zero boundary fluxes, the solver's track weights
+    const size_t npsi = (size_t)std::max<int64_t>(1, 2 * n * C), nxs = std::max<size_t>(1, (size_t)nc * C);
+    RT_HIP(t->sw_psi_in.reserve(npsi)); RT_HIP(t->sw_psi_out.reserve(npsi)); RT_HIP(t->sw_phi.reserve(nxs));
+    RT_HIP(t->sw_xs.reserve(2 * nxs));
+    RT_HIP(hipMemsetAsync(t->sw_psi_in.p, 0, npsi * sizeof(double), s));
+    RT_HIP(t->sw_w.reserve(std::max<int64_t>(1, n)));
+    if (n > 0) RT_HIP(hipMemcpyAsync(t->sw_w.p, S->w_track.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    t->sw_groups = C; t->sw_has_xs = true; t->sw_has_w = true; t->sw_done = false;
+    struct RestoreWeights { rt_tracks *t; ~RestoreWeights() { t->sw_has_w = false; } } restore{t};  // (the handle's own sweeps weigh by δs again)
+    S->ran = false;
+    S->k_hist.clear();
+    const unsigned cblocks = (unsigned)std::max(1, (nc + rt::kSolveBlock - 1) / rt::kSolveBlock);
+    const int64_t ncg = (int64_t)nc * G;
+    const unsigned sblocks = (unsigned)std::max<int64_t>(1, (ncg + rt::kSolveBlock - 1) / rt::kSolveBlock);
+    const int32_t tab_len = S->M * G * (3 + G);
+    const int32_t lds_len = (size_t)tab_len * sizeof(double) <= 32 * 1024 ? tab_len : 0;  // (else read where it lies: L2-resident)
+    const double *ext = (!eigen && S->has_ext) ? S->ext.p : nullptr;
+    const int32_t eig = eigen ? 1 : 0;
+    // φ⁰ = 1, the components' Σt / sin θ, F⁰
+    RT_HIP(hipMemsetAsync(S->prod.p, 0, (size_t)std::max(1, nc) * sizeof(double), s));
+    hipLaunchKernelGGL(rt::k_solver_fold<true>, dim3(cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
+                       (const double *)S->vol.p, (const double *)S->pol.p, (const double *)nullptr, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P, S->partial.p);
+    hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)cblocks, 1, eig, S->scal.p);
+    RT_HIP(hipGetLastError());
+    RT_HIP(hipEventRecord(S->ev[0], s));
+    double k = 1.0, residual = INFINITY, dk = INFINITY;
+    bool converged = false;
+    int32_t it = 0;
+    while (it < max_iter) {
+        hipLaunchKernelGGL(rt::k_solver_source, dim3(sblocks), dim3(rt::kSolveBlock), (size_t)lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
+                           (const double *)S->tab.p, lds_len, (const double *)S->phi.p, (const double *)S->prod.p, ext, (const double *)S->scal.p, eig,
+                           nc, G, P, t->sw_xs.p);
+        RT_HIP(hipGetLastError());
+        if (int32_t rc = rt_sweep(t, C, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
+        hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P,
+                           S->partial.p);
+        hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)cblocks, 0, eig, S->scal.p);
+        RT_HIP(hipMemcpyAsync(S->h_scal, S->scal.p, rt::kSolveScalars * sizeof(double), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));
+        RT_HIP(hipGetLastError());
+        ++it;
+        k = S->h_scal[0]; residual = S->h_scal[2]; dk = S->h_scal[3];
+        S->k_hist.push_back(k);
+        if (!std::isfinite(k) || !std::isfinite(residual)) {
+            set_error("rt_solver_run: iteration %d produced k = %g, residual = %g", it, k, residual);
+            return RT_ERR_INVALID;
+        }
+        if (dk < tol_k && residual < tol_flux) { converged = true; break; }
+    }
+    RT_HIP(hipEventRecord(S->ev[1], s));
+    if (eigen && nc > 0)
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3(sblocks), dim3(256), 0, s, S->phi.p, ncg, (const double *)S->scal.p);
+    RT_HIP(hipStreamSynchronize(s));
+    RT_HIP(hipGetLastError());
+    float f = 0.0f;
+    RT_HIP(hipEventElapsedTime(&f, S->ev[0], S->ev[1]));
+    t->in_flight = false;
+    S->ran = true;
+    if (res) {
+        res->k_eff = eigen ? k : 1.0; res->residual = residual; res->dk = dk; res->device_ms = f;
+        res->iterations = it; res->converged = converged ? 1 : 0;
+    }
+    return RT_SUCCESS;
+}
+
+}  // namespace
+
+extern "C" {
+
+rt_solver *rt_solver_create(rt_tracks *tracks, int32_t n_groups, int32_t n_materials, const int32_t *cell_material, const double *sigma_t,
+                            const double *sigma_s, const double *nu_sigma_f, const double *chi, int32_t n_polar, const double *sin_polar,
+                            const double *polar_weight, const double *azim_weight) {
+    try {
+        rt_solver *s = nullptr;
+        if (solver_create_impl(tracks, n_groups, n_materials, cell_material, sigma_t, sigma_s, nu_sigma_f, chi, n_polar, sin_polar,
+                               polar_weight, azim_weight, &s))
+            return nullptr;
+        return s;
+    } catch (const std::exception &e) {
+        set_error("rt_solver_create: %s", e.what());
+        return nullptr;
+    }
+}
+
+int32_t rt_solver_set_source(rt_solver *solver, const double *source) {
+    if (!solver) { set_error("rt_solver_set_source: null solver"); return RT_ERR_INVALID; }
+    if (!source) { solver->has_ext = false; return RT_SUCCESS; }
+    const size_t ncg = (size_t)solver->n_cells * solver->G;
+    size_t bad = 0;
+    if (!finite_nonneg(source, ncg, &bad)) { set_error("rt_solver_set_source: source[%zu] = %g (must be finite and >= 0)", bad, source[bad]); return RT_ERR_INVALID; }
+    try {
+        RT_HIP(hipSetDevice(solver->t->mesh->device));
+        if (int rc = upload(solver->ext, source, ncg, solver->t->mesh->stream)) return rc;
+        RT_HIP(hipStreamSynchronize(solver->t->mesh->stream));
+    } catch (const std::exception &e) {
+        set_error("rt_solver_set_source: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+    solver->has_ext = true;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_run(rt_solver *solver, int32_t mode, int32_t max_iter, double tol_k, double tol_flux, rt_solver_result *out) {
+    try {
+        return solver_run_impl(solver, mode, max_iter, tol_k, tol_flux, out);
+    } catch (const std::exception &e) {
+        set_error("rt_solver_run: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+int32_t rt_solver_fetch(rt_solver *solver, double *phi, double *volumes, double *k_history) {
+    if (!solver) { set_error("rt_solver_fetch: null solver"); return RT_ERR_INVALID; }
+    if ((phi || k_history) && !solver->ran) { set_error("rt_solver_fetch: rt_solver_run has not completed"); return RT_ERR_INVALID; }
+    RT_HIP(hipSetDevice(solver->t->mesh->device));
+    hipStream_t s = solver->t->mesh->stream;
+    const size_t nc = (size_t)solver->n_cells;
+    if (phi && nc) RT_HIP(hipMemcpyAsync(phi, solver->phi.p, nc * solver->G * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (volumes && nc) RT_HIP(hipMemcpyAsync(volumes, solver->vol.p, nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    if (k_history && !solver->k_hist.empty()) std::memcpy(k_history, solver->k_hist.data(), solver->k_hist.size() * sizeof(double));
+    return RT_SUCCESS;
+}
+
+void rt_solver_destroy(rt_solver *solver) {
+    if (!solver) return;
+    // (touches neither the tracks nor the mesh, which may be gone already: every entry point has waited for its work)
+    (void)hipSetDevice(solver->device);
+    free_solver(solver);
+}
+
+}  // extern "C"

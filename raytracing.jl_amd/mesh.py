@@ -24,6 +24,7 @@ from __future__ import annotations
 import json
 import os
 from dataclasses import dataclass
+from typing import Optional
 
 import numpy as np
 
@@ -46,11 +47,14 @@ class DiscreteModel:
     """Minimal stand-in for Gridap's ``UnstructuredDiscreteModel`` (triangles only).
 
     ``node_coordinates``: (n_nodes, 2) float64.  ``cell_node_ids``: (n_cells, 3) int32,
-    1-based, in the order ``get_cell_node_ids(grid)`` would return them.
+    1-based, in the order ``get_cell_node_ids(grid)`` would return them.  ``cell_region``:
+    optional (n_cells,) array of the physical-group name of every cell (the loaders fill it
+    from the file's labels; nothing in the segmentize! path reads it).
     """
 
     node_coordinates: np.ndarray
     cell_node_ids: np.ndarray
+    cell_region: Optional[np.ndarray] = None
 
     def __post_init__(self):
         self.node_coordinates = np.ascontiguousarray(self.node_coordinates, dtype=np.float64)
@@ -64,6 +68,10 @@ class DiscreteModel:
         n = self.node_coordinates.shape[0]
         if self.cell_node_ids.size and (self.cell_node_ids.min() < 1 or self.cell_node_ids.max() > n):
             raise ValueError("cell_node_ids must be 1-based ids into node_coordinates")
+        if self.cell_region is not None:
+            self.cell_region = np.asarray(self.cell_region, dtype=str)
+            if self.cell_region.shape != (self.cell_node_ids.shape[0],):
+                raise ValueError("cell_region must hold one name per cell")
 
     @property
     def num_nodes(self) -> int:
@@ -88,7 +96,24 @@ def DiscreteModelFromFile(jsonfile: str) -> DiscreteModel:
     data = np.asarray(grid["cell_node_ids"]["data"], dtype=np.int32)
     if not np.all(np.diff(ptrs) == 3):
         raise ValueError("only triangular cells are supported")
-    return DiscreteModel(xy, data.reshape(-1, 3))
+    return DiscreteModel(xy, data.reshape(-1, 3), _json_cell_regions(d.get("labeling"), len(ptrs) - 1))
+
+
+def _json_cell_regions(lab, n_cells):
+    """Physical-group name per cell from a Gridap labeling: ``entities_2`` gives every cell's entity,
+    ``names[i]`` is the group of the entities ``tags[i]`` (the first group that holds the entity wins)."""
+    if not lab or "entities_2" not in lab or "tags" not in lab or "names" not in lab:
+        return None
+    ent = np.asarray(lab["entities_2"], dtype=np.int64)
+    if ent.shape != (n_cells,):
+        return None
+    name_of = {}
+    for name, tags in zip(lab["names"], lab["tags"]):
+        for t in np.atleast_1d(tags):
+            name_of.setdefault(int(t), str(name))
+    if not all(int(e) in name_of for e in np.unique(ent)):
+        return None
+    return np.asarray([name_of[int(e)] for e in ent], dtype=str)
 
 
 def GmshDiscreteModel(mshfile: str, renumber: bool = True) -> DiscreteModel:
@@ -131,18 +156,50 @@ def GmshDiscreteModel(mshfile: str, renumber: bool = True) -> DiscreteModel:
     n_blocks, _n_el, _mn, _mx = (int(t) for t in lines[i].split())
     i += 1
     tris = []
+    tri_entity = []  # surface entity tag of every triangle
     for _ in range(n_blocks):
-        _dim, _tag, etype, nb = (int(t) for t in lines[i].split())
+        _dim, etag, etype, nb = (int(t) for t in lines[i].split())
         i += 1
         if etype == 2:
             for k in range(nb):
                 t = lines[i + k].split()
                 tris.append((int(t[1]), int(t[2]), int(t[3])))
+            tri_entity += [etag] * nb
         i += nb
     cells = np.asarray(tris, dtype=np.int32).reshape(-1, 3)
     if renumber:
         cells = np.sort(cells, axis=1)
-    return DiscreteModel(xy, cells)
+    regions = None
+    surf_name = _msh_surface_names(lines, pos)
+    if surf_name is not None and all(t in surf_name for t in tri_entity):
+        regions = np.asarray([surf_name[t] for t in tri_entity], dtype=str)
+    return DiscreteModel(xy, cells, regions)
+
+
+def _msh_surface_names(lines, pos):
+    """Surface entity tag -> name of its (first) physical group, through ``$Entities`` and ``$PhysicalNames``
+    (None when the file has neither)."""
+    if "$PhysicalNames" not in pos or "$Entities" not in pos:
+        return None
+    i = pos["$PhysicalNames"] + 1
+    names = {}
+    for k in range(int(lines[i])):
+        dim, tag, rest = lines[i + 1 + k].split(None, 2)
+        if int(dim) == 2:
+            names[int(tag)] = rest.strip().strip('"')
+    i = pos["$Entities"] + 1
+    n_pt, n_cv, n_sf, _n_vol = (int(t) for t in lines[i].split()[:4])
+    i += 1 + n_pt + n_cv
+    out = {}
+    for k in range(n_sf):
+        t = lines[i + k].split()
+        # tag, bounding box (6 numbers), numPhysicalTags, physicalTags..., numBoundingCurves, ...
+        n_phys = int(t[7])
+        phys = [int(v) for v in t[8:8 + n_phys]]
+        named = [names[p] for p in phys if p in names]
+        if named:
+            out[int(t[0])] = named[0]
+    return out
 
 
 class Mesh:

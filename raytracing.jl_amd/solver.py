@@ -1,0 +1,211 @@
+"""MOC transport solver on the device: power-iteration ``k_eff`` and fixed-source source iteration over the
+records of the last ``segmentize`` — what the tracks and segments exist to feed (the reference's README:
+"computes quantities used to solve the transport equation").
+
+The iteration runs in ``librt_segmentize.so`` (``rt_solver_*``, ``csrc/rt_solver.hip``) around ``rt_sweep``:
+per iteration a source-update kernel, one sweep over G x P components (energy groups x polar angles),
+a fold kernel and a fixed-order reduction; only k, the residual and |Δk|/k come back to the host.
+The definitions (azimuthal and polar weights, volumes, fold, source, residual, normalisation) are stated
+in ``include/rt_segmentize.h``.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from . import _capi
+from .trackgenerator import TrackGenerator
+
+__all__ = ["CrossSections", "PolarQuadrature", "SolverResult", "exact_azimuthal_weights", "azimuthal_weights",
+           "solve_eigenvalue", "solve_fixed_source"]
+
+
+class CrossSections:
+    """Macroscopic cross sections of M materials in G groups: ``sigma_t``, ``nu_sigma_f``, ``chi`` [M, G] and
+    ``sigma_s`` [M, G, G] with ``sigma_s[m, g', g]`` the transfer from group g' to g (isotropic scattering).
+    One material may be given without its leading axis."""
+
+    def __init__(self, sigma_t, sigma_s, nu_sigma_f, chi):
+        st = np.asarray(sigma_t, np.float64)
+        st = st.reshape(1, -1) if st.ndim <= 1 else st
+        if st.ndim != 2:
+            raise ValueError("sigma_t must have shape [M, G]")
+        M, G = st.shape
+        ss = np.asarray(sigma_s, np.float64)
+        if ss.size == M * G * G:
+            ss = ss.reshape(M, G, G)
+        nf = np.asarray(nu_sigma_f, np.float64)
+        ch = np.asarray(chi, np.float64)
+        nf = nf.reshape(M, G) if nf.size == M * G else nf
+        ch = ch.reshape(M, G) if ch.size == M * G else ch
+        if ss.shape != (M, G, G):
+            raise ValueError(f"sigma_s must have shape [M, G, G] = {(M, G, G)}, got {np.shape(sigma_s)}")
+        if nf.shape != (M, G) or ch.shape != (M, G):
+            raise ValueError(f"nu_sigma_f and chi must have shape [M, G] = {(M, G)}")
+        self.sigma_t, self.sigma_s, self.nu_sigma_f, self.chi = (np.ascontiguousarray(a) for a in (st, ss, nf, ch))
+
+    @property
+    def n_materials(self) -> int:
+        return int(self.sigma_t.shape[0])
+
+    @property
+    def n_groups(self) -> int:
+        return int(self.sigma_t.shape[1])
+
+
+# Tabuchi-Yamamoto optimal polar sets (sin θ_p, ω_p) for 1-3 angles per half space
+_TY = {
+    1: ((0.798184,), (1.0,)),
+    2: ((0.363900, 0.899900), (0.212854, 0.787146)),
+    3: ((0.166648, 0.537707, 0.932954), (0.046233, 0.283619, 0.670148)),
+}
+
+
+class PolarQuadrature:
+    """Polar angles of one half space: ``sin_theta`` and ``weights`` [P] with Σ weights = 1.  ``spec``:
+    ``"TY1"``, ``"TY2"``, ``"TY3"`` (Tabuchi-Yamamoto), ``"GL<n>"`` (Gauss-Legendre on μ = cos θ in (0, 1)),
+    ``"none"`` (P = 1, sin θ = 1, ω = 1: the plain 2-D sweep), or a pair of arrays (sin θ, ω)."""
+
+    def __init__(self, spec="TY3"):
+        if isinstance(spec, PolarQuadrature):
+            sin_t, w = spec.sin_theta, spec.weights
+        elif isinstance(spec, str):
+            s = spec.strip().upper()
+            if s == "NONE":
+                sin_t, w = [1.0], [1.0]
+            elif s.startswith("TY") and s[2:].isdigit() and int(s[2:]) in _TY:
+                sin_t, w = _TY[int(s[2:])]
+            elif s.startswith("GL") and s[2:].isdigit() and int(s[2:]) >= 1:
+                x, wx = np.polynomial.legendre.leggauss(2 * int(s[2:]))
+                pos = x > 0  # the nodes of (0, 1): half of the symmetric set on (-1, 1)
+                mu, wmu = x[pos], wx[pos]
+                sin_t, w = np.sqrt(1.0 - mu * mu), wmu / wmu.sum()
+            else:
+                raise ValueError(f"unknown polar quadrature {spec!r} (TY1-TY3, GL<n>, none, or (sin_theta, weights))")
+        else:
+            sin_t, w = spec
+        self.sin_theta = np.ascontiguousarray(sin_t, np.float64).reshape(-1)
+        self.weights = np.ascontiguousarray(w, np.float64).reshape(-1)
+        if self.sin_theta.shape != self.weights.shape or not len(self.weights):
+            raise ValueError("sin_theta and weights must be non-empty and of equal length")
+        if np.any(self.sin_theta <= 0) or np.any(self.sin_theta > 1) or np.any(self.weights <= 0):
+            raise ValueError("need 0 < sin θ <= 1 and ω > 0")
+        if abs(float(self.weights.sum()) - 1.0) > 1e-12:
+            raise ValueError(f"polar weights sum to {float(self.weights.sum())!r}, not 1")
+
+    @property
+    def n_polar(self) -> int:
+        return len(self.weights)
+
+
+def exact_azimuthal_weights(aq) -> np.ndarray:
+    """α_a [n_azim/2] with Σ α = 1/2: within the first quadrant (angles φ_1 < ... < φ_n), b_0 = 0,
+    b_i = (φ_i + φ_{i+1}) / 2, b_n = π/2 and α_i = (b_i − b_{i−1}) / 2π, mirrored to the supplementary index.
+    Equal to the reference's ω_a (``init_weights!``) except at the first angle of each quadrant."""
+    n4, n2 = aq.n_azim_4, aq.n_azim_2
+    ph = np.asarray(aq.phis[:n4], np.float64)
+    if np.any(np.isnan(ph)):
+        raise ValueError("the azimuthal angles are not set: call trace first")
+    b = np.empty(n4 + 1)
+    b[0], b[n4] = 0.0, math.pi / 2
+    b[1:n4] = 0.5 * (ph[:-1] + ph[1:])
+    a = np.empty(n2)
+    a[:n4] = np.diff(b) / (2 * math.pi)
+    a[n2 - n4:] = a[:n4][::-1]  # supplementary index N2 − i + 1
+    return a
+
+
+def azimuthal_weights(tg: TrackGenerator, spec="exact") -> np.ndarray:
+    """``"exact"`` (``exact_azimuthal_weights``), ``"equal"`` (α = 1 / n_azim), or an explicit array (positive, sum 1/2)."""
+    aq = tg.azimuthal_quadrature
+    if isinstance(spec, str):
+        if spec == "exact":
+            return exact_azimuthal_weights(aq)
+        if spec == "equal":
+            return np.full(aq.n_azim_2, 1.0 / (2 * aq.n_azim_2))
+        raise ValueError(f"unknown azimuthal weights {spec!r} (exact, equal or an array)")
+    a = np.ascontiguousarray(spec, np.float64).reshape(-1)
+    if a.shape != (aq.n_azim_2,) or np.any(a <= 0) or abs(float(a.sum()) - 0.5) > 1e-12:
+        raise ValueError("azimuthal weights must be n_azim/2 positive numbers that sum to 1/2")
+    return a
+
+
+@dataclass
+class SolverResult:
+    k_eff: Optional[float]        # None in fixed-source mode
+    phi: np.ndarray               # [n_cells, G]; eigenvalue mode: scaled to Σ_e V_e Σ_g νΣf φ = 1
+    volumes: np.ndarray           # [n_cells], with the solver's azimuthal weights
+    iterations: int
+    converged: bool
+    k_history: np.ndarray         # k after every iteration
+    ms_per_iteration: float       # HIP-event time of the iterations / iterations
+    residual: float
+    solver: object = None         # the device solver (rt_solver handle), for a further run
+
+
+def _cell_material(tg, cell_material):
+    if isinstance(cell_material, dict):
+        reg = getattr(tg.mesh.model, "cell_region", None)
+        if reg is None:
+            raise ValueError("cell_material given by region name, but the mesh has no cell regions")
+        missing = sorted(set(np.unique(reg)) - set(cell_material))
+        if missing:
+            raise ValueError(f"no material for regions {missing}")
+        return np.asarray([cell_material[r] for r in reg], np.int32)
+    cm = np.asarray(cell_material)
+    if cm.ndim == 0:
+        return np.full(tg.mesh.num_cells, int(cm), np.int32)
+    return np.ascontiguousarray(cm, np.int32)
+
+
+def _device_tracks(tg, device):
+    """The tracks' device handle after ``segmentize`` (run here with ``fetch=False`` if it has not run), links set."""
+    from .segmentize import segmentize
+
+    dt = getattr(tg, "device_tracks", None)
+    if dt is None or getattr(dt, "_h", None) is None or dt.total is None:
+        segmentize(tg, fetch=False, device=device)
+        dt = tg.device_tracks
+    dt.sweep_set_links(tg)
+    return dt
+
+
+def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device):
+    if not isinstance(xs, CrossSections):
+        raise TypeError("xs must be a CrossSections")
+    pq = PolarQuadrature(polar)
+    alpha = azimuthal_weights(tg, azim_weights)
+    dt = _device_tracks(tg, device)
+    sv = _capi.DeviceSolver(dt, _cell_material(tg, cell_material), xs.sigma_t, xs.sigma_s, xs.nu_sigma_f, xs.chi,
+                            pq.sin_theta, pq.weights, alpha)
+    if source is not None:
+        sv.set_source(source)
+    r = sv.run(mode, int(max_iter), float(tol_k), float(tol_flux))
+    f = sv.fetch(r["iterations"])
+    it = r["iterations"]
+    return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
+                        iterations=it, converged=r["converged"], k_history=f["k_history"],
+                        ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv)
+
+
+def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
+                     tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0) -> SolverResult:
+    """Power iteration for k_eff on the device.  ``cell_material``: material index per cell [n_cells] (or one index for all,
+    or a dict region name -> index over ``tg.mesh.model.cell_region``).  ``polar``: a ``PolarQuadrature`` spec;
+    ``azim_weights``: "exact", "equal" or an array.  Uses ``tg.device_tracks`` when ``segmentize(tg, fetch=False)`` has run,
+    else segmentizes first; the boundary conditions are the ones ``trace`` linked."""
+    return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device)
+
+
+def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
+                       tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0) -> SolverResult:
+    """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
+    the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``."""
+    q = np.asarray(source, np.float64)
+    G = xs.n_groups
+    if q.ndim == 0 or q.shape == (G,):
+        q = np.broadcast_to(q, (tg.mesh.num_cells, G))
+    return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device)

@@ -1,0 +1,101 @@
+"""Timing of the device MOC solver (rt_solver) at the headline configuration: pincell, nφ = 128, δ = 1e-3, 7 groups, TY3.
+
+Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
+around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
+(source update + fold + reductions + the per-iteration readback).  The per-kernel times come from a separate run of this
+script under `rocprofv3 --kernel-trace --stats` (use --no-sweep-probe there so that only the solver's launches are traced):
+
+    rocprofv3 --kernel-trace --stats -d <dir> -o solve -- python tools/solve_timing.py --iters 20 --no-sweep-probe
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def xs_groups(rt, G, seed=1):
+    """Three materials (fuel, clad, moderator) in G groups (as tests/test_gpu_solver.py)."""
+    rng = np.random.default_rng(seed)
+    M = 3
+    st = rng.uniform(0.3, 1.5, (M, G))
+    ss = np.zeros((M, G, G))
+    for m in range(M):
+        for g in range(G):
+            row = np.zeros(G)
+            row[g:min(G, g + 3)] = rng.uniform(0.2, 1.0, min(G, g + 3) - g)
+            if g > 0:
+                row[g - 1] = 0.05 * rng.uniform()
+            ss[m, g] = row / row.sum() * st[m, g] * rng.uniform(0.3, 0.9)
+    nf = np.zeros((M, G))
+    nf[0] = rng.uniform(0.05, 0.5, G) * st[0]
+    chi = np.tile(np.exp(-np.arange(G, dtype=float)), (M, 1))
+    chi /= chi.sum(1, keepdims=True)
+    return rt.CrossSections(st, ss, nf, chi)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mesh", default="pincell.msh")
+    ap.add_argument("--n-azim", type=int, default=128)
+    ap.add_argument("--delta", type=float, default=1e-3)
+    ap.add_argument("--groups", type=int, default=7)
+    ap.add_argument("--polar", default="TY3")
+    ap.add_argument("--iters", type=int, default=30)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
+    a = ap.parse_args()
+
+    import raytracing_jl_amd as rt
+    from raytracing_jl_amd import _capi
+
+    B = rt.BoundaryConditions
+    model = rt.GmshDiscreteModel(rt.data_path(a.mesh)) if a.mesh.endswith(".msh") else rt.DiscreteModelFromFile(rt.data_path(a.mesh))
+    tg = rt.TrackGenerator(model, a.n_azim, a.delta, bcs=B(top=rt.Reflective, bottom=rt.Reflective, left=rt.Reflective, right=rt.Reflective))
+    rt.trace(tg)
+    rt.segmentize(tg, fetch=False)
+    dt = tg.device_tracks
+    dt.sweep_set_links(tg)
+    xs = xs_groups(rt, a.groups)
+    pq = rt.PolarQuadrature(a.polar)
+    cm = {"pin": 0, "cladding": 1, "water": 2} if model.cell_region is not None and "pin" in set(model.cell_region.tolist()) else 0
+    from raytracing_jl_amd.solver import _cell_material
+
+    sv = _capi.DeviceSolver(dt, _cell_material(tg, cm), xs.sigma_t, xs.sigma_s, xs.nu_sigma_f, xs.chi, pq.sin_theta, pq.weights,
+                            rt.exact_azimuthal_weights(tg.azimuthal_quadrature))
+    sv.run(0, 3, 0.0, 0.0)  # warm-up (first launches, LDS attributes, the sweep's ℓ rows)
+    ev_ms, host_ms, ks = [], [], []
+    for _ in range(a.repeats):
+        t0 = time.perf_counter()
+        r = sv.run(0, a.iters, 0.0, 0.0)
+        host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+        ev_ms.append(r["device_ms"] / r["iterations"])
+        ks.append(r["k_eff"])
+    out = dict(config=dict(mesh=a.mesh, n_azim=a.n_azim, delta=a.delta, groups=a.groups, polar=a.polar, components=a.groups * pq.n_polar,
+                           tracks=int(tg.n_total_tracks), records=int(dt.total), cells=int(tg.mesh.num_cells), iters=a.iters),
+               ms_per_iter_events=float(np.median(ev_ms)), ms_per_iter_host=float(np.median(host_ms)), k_eff=ks[-1])
+    if not a.no_sweep_probe:
+        # the same sweep the solver runs: G·P components, the handle's cross sections and boundary fluxes as the solver left them
+        C = a.groups * pq.n_polar
+        sw = []
+        for _ in range(10):
+            ms = _capi.C.c_double(0.0)
+            _capi._check(_capi.lib().rt_sweep(dt._h, C, None, None, None, None, 0, _capi.C.byref(ms)))
+            sw.append(ms.value)
+        s = float(np.median(sw[2:]))
+        out["sweep_ms"] = s
+        out["sweep_share_events"] = s / out["ms_per_iter_events"]
+        out["non_sweep_ms_events"] = out["ms_per_iter_events"] - s
+        out["non_sweep_over_sweep"] = (out["ms_per_iter_events"] - s) / s
+        out["non_sweep_over_sweep_host"] = (out["ms_per_iter_host"] - s) / s
+    print(json.dumps(out))
+    sv.close()
+
+
+if __name__ == "__main__":
+    main()
