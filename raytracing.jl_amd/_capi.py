@@ -308,6 +308,11 @@ class DeviceMesh:
         _check(lib().rt_set_option(self._h, name.encode(), int(value)))
 
     def close(self):
+        # rt_tracks_destroy reads its mesh, and the garbage collector finalizes the objects of a reference cycle in any order:
+        # while tracks on this mesh are open, the last of them to close destroys it
+        if getattr(self, "_n_tracks", 0):
+            self._close_pending = True
+            return
         if getattr(self, "_h", None):
             lib().rt_mesh_destroy(self._h)
             self._h = None
@@ -353,6 +358,7 @@ class DeviceTracks:
         self._h = L.rt_tracks_create(dmesh._h, self.n, *[p for _, p in arrs], azp)
         if not self._h:
             raise RtError(f"rt_tracks_create failed: {last_error()}")
+        dmesh._n_tracks = getattr(dmesh, "_n_tracks", 0) + 1
         self.total = None
 
     def segmentize(self, tiny_step: float, k: int, rtol: float, delta_s, n_azim_2: int) -> int:
@@ -607,6 +613,10 @@ class DeviceTracks:
         if getattr(self, "_h", None):
             lib().rt_tracks_destroy(self._h)
             self._h = None
+            m = self.dmesh
+            m._n_tracks -= 1
+            if not m._n_tracks and getattr(m, "_close_pending", False):
+                m.close()
 
     def __del__(self):
         try:

@@ -1,7 +1,7 @@
 """Numpy twin of the device MOC solver (rt_solver, csrc/rt_solver.hip): the same definitions (include/rt_segmentize.h) step by
 step, with the sweep of tests/sweep_ref.py (`sweep_fast`) over a given set of records — the ORACLE's in the tests.  The checker
-of tests/test_solver_cpu.py (analytic answers) and tests/test_gpu_solver.py (the device against this twin, iteration by
-iteration)."""
+of tests/test_solver_cpu.py (analytic answers), tests/test_gpu_solver.py and tests/test_gpu_solver_shapes.py (the device
+against this twin, iteration by iteration)."""
 import math
 
 import numpy as np
@@ -39,7 +39,7 @@ def solve(rec, links, azim_idx, delta_s, alpha, sigma_t, sigma_s, nu_sigma_f, ch
           mode="eigenvalue", source=None, max_iter=1000, tol_k=1e-8, tol_flux=1e-7):
     """rec: dict with offsets, ell, element (1-based).  links: (next_fwd, next_bwd, dir_fwd, dir_bwd, bc_fwd, bc_bwd).
     Cross sections per material ([M, G], sigma_s [M, G, G] from g' to g).  Returns a dict like the device solver's result plus
-    `psi_out` [2, n, G·P] of the last sweep and `track_weight` [n]."""
+    `psi_out` [2, n, G·P] and the tallies `tally` [n_cells, G·P] of the last sweep (zeros when none ran), and `track_weight` [n]."""
     eigen = mode == "eigenvalue"
     mat = np.asarray(cell_material, np.int64)
     nc = len(mat)
@@ -62,6 +62,7 @@ def solve(rec, links, azim_idx, delta_s, alpha, sigma_t, sigma_s, nu_sigma_f, ch
     k = 1.0
     psi_in = np.zeros((2, n, G * P))
     hist, converged, res, dk, psi_out = [], False, math.inf, math.inf, psi_in
+    T = np.zeros((nc, G * P))
     for _ in range(int(max_iter)):
         scat = np.einsum("eh,ehg->eg", phi, ss)
         q = (scat + ch * prod[:, None] / k + S) / FOUR_PI
@@ -91,7 +92,19 @@ def solve(rec, links, azim_idx, delta_s, alpha, sigma_t, sigma_s, nu_sigma_f, ch
     if eigen:
         phi = phi / F
     return dict(k_eff=k if eigen else None, phi=phi, volumes=V, k_history=np.asarray(hist), iterations=len(hist),
-                converged=converged, residual=res, dk=dk, psi_out=psi_out, track_weight=wtrack)
+                converged=converged, residual=res, dk=dk, psi_out=psi_out, tally=T, track_weight=wtrack)
+
+
+def k_infinity(sigma_t, sigma_s, nu_sigma_f, chi):
+    """Infinite-medium answer of one material ([G], sigma_s [G, G] from g' to g): the largest eigenvalue k∞ of
+    (diag Σt − Σsᵀ)⁻¹ χ νΣfᵀ and its eigenvector φ (positive, scaled to Σ_g φ_g = 1) — what the flat flux of a fully reflective
+    one-material domain converges to."""
+    st, ss, nf, ch = (np.asarray(a, np.float64) for a in (sigma_t, sigma_s, nu_sigma_f, chi))
+    A = np.linalg.solve(np.diag(st) - ss.T, np.outer(ch, nf))
+    w, v = np.linalg.eig(A)
+    i = int(np.argmax(w.real))
+    phi = v[:, i].real
+    return float(w[i].real), phi / phi.sum()
 
 
 def tg_links(tg):

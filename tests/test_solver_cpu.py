@@ -136,3 +136,39 @@ def test_twin_equal_weight_volumes_are_fill_volumes(rt, reflective):
     v = moc_ref.volumes(rec["offsets"], rec["ell"], rec["element"], tg.azim_idx, aq.delta_s, rt.azimuthal_weights(tg, "equal"),
                         tg.mesh.num_cells)
     assert np.allclose(v, ref, rtol=1e-13, atol=0)
+
+
+def dense_xs(rng, G, ratio=(0.3, 0.6)):
+    """One material in G groups with a dense scattering matrix (upscatter into every group), fission in every group."""
+    st = rng.uniform(0.5, 1.5, G)
+    ss = rng.uniform(0.05, 1.0, (G, G))
+    ss *= (st * rng.uniform(*ratio, G) / ss.sum(1))[:, None]
+    nf = rng.uniform(0.05, 0.3, G) * st
+    chi = rng.uniform(0.1, 1.0, G)
+    return st, ss, nf, chi / chi.sum()
+
+
+def test_k_infinity_helper_is_the_balance():
+    st, ss, nf, chi = dense_xs(np.random.default_rng(4), 5)
+    k, v = moc_ref.k_infinity(st, ss, nf, chi)
+    assert np.all(v > 0)
+    # Σt φ = Σsᵀ φ + χ (νΣf · φ) / k
+    assert np.allclose(st * v, ss.T @ v + chi * (nf @ v) / k, rtol=1e-13, atol=0)
+
+
+def test_twin_dense_upscatter_k_infinity(rt, reflective):
+    tg, rec = reflective
+    G = 12
+    st, ss, nf, chi = dense_xs(np.random.default_rng(12), G)
+    assert np.all(ss > 0)  # up- and downscatter between every pair of groups
+    k_inf, v = moc_ref.k_infinity(st, ss, nf, chi)
+    r = _twin(rt, tg, rec, rt.CrossSections(st[None], ss[None], nf[None], chi[None]), polar="TY1", **TIGHT)
+    assert r["converged"] and abs(r["k_eff"] / k_inf - 1) <= 1e-8, (r["k_eff"], k_inf, r["iterations"])
+    V = r["volumes"]
+    live = V > 0
+    assert 0 < (~live).sum() < 20  # (cells no track crosses at this spacing)
+    phi_inf = v / (float(V.sum()) * float(nf @ v))  # F(φ) = Σ_e V_e νΣf·φ = 1
+    assert np.abs(r["phi"][live] - phi_inf).max() <= 1e-8 * phi_inf.max()
+    # a cell no track crosses keeps φ = 4π q / Σt of its own flux: it converges to the spectrum, at its own magnitude
+    dead = r["phi"][~live]
+    assert np.abs(dead / dead.sum(1, keepdims=True) - v).max() <= 1e-8
