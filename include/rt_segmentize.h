@@ -468,6 +468,20 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              not an error).  Eigenvalue mode scales the returned φ to F(φ) = 1.
  * Every Σt must be > 0 (void materials are rejected); all other data finite and >= 0.
  *
+ * Linearly anisotropic (P1) scattering, rt_solver_set_scatter_p1.  sigma_s1[m][g'][g] is the l = 1 Legendre moment of the
+ * transfer from g' to g in the convention Σs(g'→g, μ0) = (1/4π) [Σs0 + 3 Σs1 μ0] (Σs0 = sigma_s).  It may be negative;
+ * every entry must be finite with |Σs1[g'→g]| <= Σs0[g'→g].  In 2-D the z-moment vanishes: the net current has two
+ * components, J_{e,g} = (Jx, Jy).  Fission and the external source stay isotropic.
+ * Direction    track u forward (p → q) travels along Ω = sin θ_p (cos φ_u, sin φ_u), backward along −Ω
+ * Source       q_{e,g}(Ω) = q0_{e,g} + Ωx q1x_{e,g} + Ωy q1y_{e,g}: q0 the isotropic q_{e,g} above,
+ *              q1_{e,g} = (3/4π) Σ_g' Σs1[g'→g] J_{e,g'}
+ * Sweep        the same recurrence with q(Ω) / Σt as that traversal's source ratio; besides T it tallies
+ *              Tx[e][c] = Σ w d cos φ_u Δψ and Ty[e][c] = Σ w d sin φ_u Δψ (d = +1 forward, −1 backward)
+ * Fold         φ as above (the anisotropic part of its first term integrates to zero);
+ *              J_{e,g} = (4π/3) q1_{e,g} / Σt_g + Σ_p ω_p sin²θ_p (Tx, Ty)[e][g·P + p] / (Σt_g V_e)   (V_e = 0: first term only)
+ *              with the continuous value 4π/3 of ∫ Ωx² dΩ, as the scalar term uses 4π
+ * Iteration    J⁰ = 0; k, residual, stopping rule and normalisation are unchanged (eigenvalue mode scales J with φ)
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -501,6 +515,13 @@ int32_t rt_solver_run(rt_solver *solver, int32_t mode, int32_t max_iter, double 
 /* After a run: phi [n_cells][G], volumes [n_cells], k_history [iterations] (k after every iteration); any may be NULL.
  * volumes is available right after rt_solver_create. */
 int32_t rt_solver_fetch(rt_solver *solver, double *phi, double *volumes, double *k_history);
+/* First-moment scattering matrices sigma_s1 [M][G][G] (host memory, copied; see above) for the following runs; NULL: back to
+ * isotropic scattering, which runs exactly the kernels of a solver that never had any.  RT_ERR_INVALID when an entry is not
+ * finite or exceeds Σs0 in magnitude (the solver keeps what it had). */
+int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1);
+/* The net current J [n_cells][G][2] (x, y) of the last run.  RT_ERR_INVALID before a run, or when that run had no
+ * first-moment scattering. */
+int32_t rt_solver_fetch_current(rt_solver *solver, double *J);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

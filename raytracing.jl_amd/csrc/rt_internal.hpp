@@ -299,6 +299,11 @@ struct DSweep {
     int32_t debug;  // development: bit 0 skip the tallies
     RT_G double *ell_rows;  // STAGED: ℓ of every staged row, slot-indexed like the rows — written by the forward waves of a pass that
                             // derives ℓ from the exit points (when non-null), read by the ELLROWS passes instead of the exit points
+    // linearly anisotropic source (k_sweep<..., P1>; rt_solver with rt_solver_set_scatter_p1): the lane's source ratio is
+    // q/Σt + d (cs[u] xs1[..][0] + sn[u] xs1[..][1]), d = +1 forward, -1 backward, and the first-moment tallies go to `cur`
+    const RT_G double *xs1;           // [n_cells * G][2]: q1x sin θ / Σt, q1y sin θ / Σt
+    const RT_G double *cs, *sn;       // [n] cos ϕ, sin ϕ of every track (by uid)
+    RT_G double *cur;                 // [n_cells * G][2] tallies Σ w d cs Δψ, Σ w d sn Δψ
 };
 
 }  // namespace rt
@@ -485,6 +490,8 @@ struct rt_tracks {
     // rt_sweep: the gather map of the cyclic linking, per-track weights, cross sections, boundary fluxes, tallies
     DevBuf<int32_t> sw_src;
     DevBuf<double> sw_w, sw_xs, sw_psi_in, sw_psi_out, sw_phi;
+    DevBuf<double> sw_xs1, sw_cur;  // the anisotropic sweep's first-moment ratios and tallies (DSweep xs1, cur): rt_solver owns their content
+    bool sw_p1 = false;             // ... and switches the mode on for the sweeps of its run
     DevBuf<double> sw_ell;      // ℓ of every staged row (slot-indexed like the staging pool), left by the first staged pass after a call
     bool sw_ell_valid = false;  // ... of the last rt_segmentize
     DevBuf<int32_t> sw_cell;    // codes: cell + 1 of every staged row, beside sw_ell (k_materialise<.., ROWS>)

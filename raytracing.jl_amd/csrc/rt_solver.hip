@@ -4,11 +4,17 @@
 // rt_sweep (components c = g·P + p), k_solver_fold (φ from the tallies + block partials), k_solver_reduce (one workgroup:
 // the partials in a fixed order, k and the residual on the device), one 64-B copy to the host.  No FP64 atomics outside the
 // sweep's own tallies: the reductions are deterministic for a given set of tallies.
+// With first-moment scattering (rt_solver_set_scatter_p1) an iteration has two more kernels, and the sweep runs in its anisotropic
+// mode: k_solver_source_p1 (q1/Σt from the net current J, and its sin θ_p multiple of every component into the sweep's xs1
+// array) after k_solver_source, and k_solver_fold_p1 (J from the first-moment tallies) after k_solver_fold.  Without it the
+// solver launches what it always did.
 #include "rt_internal.hpp"
 
 namespace rt {
 
 constexpr double kFourPi = 12.566370614359172;  // 4π
+constexpr double kThreeOverFourPi = 3.0 / kFourPi;  // the l = 1 source: q1 = (3/4π) Σs1 J
+constexpr double kFourPiOverThree = kFourPi / 3.0;  // ∫ Ωx² dΩ over the sphere
 constexpr int kSolvePartials = 8;                // doubles per block partial: F, Σ r², cells with fission, Σ Δφ², Σ φ², (pad)
 constexpr int kSolveBlock = 256;
 // scalars on the device (and their host copy): [0] k, [1] F(φ), [2] residual, [3] |Δk| / k
@@ -68,6 +74,63 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_source(const int32_t *__
     const double ratio = s / kFourPi / X[g];
     double *x = xs + (e * G * P + (int64_t)g * P) * 2;
     for (int32_t p = 0; p < P; ++p) x[2 * p + 1] = ratio;
+}
+
+// first-moment table: per material, stride G·(1 + G) doubles — Σt[G], Σs1[G][G] (from g' to g)
+__device__ __forceinline__ const double *mat_row_p1(const double *tab, int32_t m, int32_t G) { return tab + (int64_t)m * G * (1 + G); }
+
+// q1/Σt = (3/4π) Σ_g' Σs1[g'→g] J_g' / Σt_g of every (cell, group) (one thread each) into `q1r` [n_cells][G][2], and times
+// sin θ_p into the sweep's first-moment ratios `xs1` [n_cells][G·P][2].  The table from LDS when the host says it fits.
+__global__ __launch_bounds__(kSolveBlock) void k_solver_source_p1(const int32_t *__restrict__ mat, const double *__restrict__ tab_g, int32_t tab_len,
+                                                                  const double *__restrict__ J, const double *__restrict__ pol, int32_t n_cells,
+                                                                  int32_t G, int32_t P, double *__restrict__ q1r, double *__restrict__ xs1) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char solver_smem[];
+    const double *tab = tab_g;
+    if (tab_len > 0) {
+        double *t = reinterpret_cast<double *>(solver_smem);
+        for (int i = threadIdx.x; i < tab_len; i += blockDim.x) t[i] = tab_g[i];
+        __syncthreads();
+        tab = t;
+    }
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n_cells * G) return;
+    const int64_t e = i / G;
+    const int32_t g = (int32_t)(i - e * G);
+    const double *X = mat_row_p1(tab, mat[e], G);
+    const double *Je = J + e * G * 2;
+    double sx = 0.0, sy = 0.0;
+    for (int32_t gp = 0; gp < G; ++gp) {
+        const double s1 = X[G + gp * G + g];
+        sx += s1 * Je[2 * gp];
+        sy += s1 * Je[2 * gp + 1];
+    }
+    const double rx = kThreeOverFourPi * sx / X[g], ry = kThreeOverFourPi * sy / X[g];
+    q1r[2 * i] = rx; q1r[2 * i + 1] = ry;
+    double *x = xs1 + (e * G * P + (int64_t)g * P) * 2;
+    for (int32_t p = 0; p < P; ++p) { x[2 * p] = rx * pol[p]; x[2 * p + 1] = ry * pol[p]; }
+}
+
+// J of every (cell, group) (one thread each) from the sweep's first-moment tallies `cur` [n_cells][G·P][2]:
+// J = (4π/3) q1/Σt + Σ_p ω_p sin²θ_p (Tx, Ty) / (Σt V)
+__global__ __launch_bounds__(kSolveBlock) void k_solver_fold_p1(const int32_t *__restrict__ mat, const double *__restrict__ tab,
+                                                                const double *__restrict__ vol, const double *__restrict__ pol,
+                                                                const double *__restrict__ cur, const double *__restrict__ q1r, int32_t n_cells,
+                                                                int32_t G, int32_t P, double *__restrict__ J) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n_cells * G) return;
+    const int64_t e = i / G;
+    const int32_t g = (int32_t)(i - e * G);
+    const double V = vol[e];
+    const double st = mat_row_p1(tab, mat[e], G)[g];
+    const double *c = cur + (e * G * P + (int64_t)g * P) * 2;
+    double ax = 0.0, ay = 0.0;
+    for (int32_t p = 0; p < P; ++p) {
+        const double wss = pol[P + p] * pol[p];  // ω_p sin²θ_p
+        ax += wss * c[2 * p];
+        ay += wss * c[2 * p + 1];
+    }
+    J[2 * i] = kFourPiOverThree * q1r[2 * i] + (V > 0.0 ? ax / (st * V) : 0.0);
+    J[2 * i + 1] = kFourPiOverThree * q1r[2 * i + 1] + (V > 0.0 ? ay / (st * V) : 0.0);
 }
 
 // INIT: φ = 1, Σt_g / sin θ_p of every component; otherwise the fold of the last sweep's tallies T [n_cells][G·P].  Both: the
@@ -163,6 +226,10 @@ struct rt_solver {
     DevBuf<int32_t> mat;
     DevBuf<double> tab, pol, vol, w_track, phi, prod, ext, partial, scal;
     bool has_ext = false, ran = false;
+    // first-moment scattering (rt_solver_set_scatter_p1)
+    std::vector<double> h_st, h_ss;  // Σt, Σs0 as given (the first moments are checked against them)
+    DevBuf<double> tab1, J, q1r;     // table (see mat_row_p1); net current and q1/Σt [n_cells][G][2]
+    bool p1 = false, ran_p1 = false;
     std::vector<double> k_hist;
     double *h_scal = nullptr;  // pinned, kSolveScalars
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -241,6 +308,7 @@ int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_m
 
     rt_solver *S = new rt_solver();
     struct Guard { rt_solver *&p; ~Guard() { free_solver(p); } } guard{S};
+    S->h_st.assign(sigma_t, sigma_t + mg); S->h_ss.assign(sigma_s, sigma_s + mg * G);
     S->t = t; S->device = m->device; S->epoch = t->seg_epoch; S->G = G; S->M = M; S->P = P; S->N2 = N2; S->n_cells = nc;
     // material table (see mat_row)
     std::vector<double> tab((size_t)M * G * (3 + G));
@@ -314,8 +382,18 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
     RT_HIP(t->sw_w.reserve(std::max<int64_t>(1, n)));
     if (n > 0) RT_HIP(hipMemcpyAsync(t->sw_w.p, S->w_track.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
     t->sw_groups = C; t->sw_has_xs = true; t->sw_has_w = true; t->sw_done = false;
-    struct RestoreWeights { rt_tracks *t; ~RestoreWeights() { t->sw_has_w = false; } } restore{t};  // (the handle's own sweeps weigh by δs again)
-    S->ran = false;
+    struct RestoreWeights { rt_tracks *t; ~RestoreWeights() { t->sw_has_w = false; t->sw_p1 = false; } } restore{t};  // (the handle's own sweeps weigh by δs again, isotropically)
+    S->ran = false; S->ran_p1 = false;
+    const bool p1 = S->p1;
+    const int32_t tab1_len = S->M * G * (1 + G);
+    const int32_t lds1_len = (size_t)tab1_len * sizeof(double) <= 32 * 1024 ? tab1_len : 0;
+    if (p1) {  // J⁰ = 0; the sweep's first-moment arrays
+        const size_t nj = 2 * std::max<size_t>(1, (size_t)nc * G);
+        RT_HIP(S->J.reserve(nj)); RT_HIP(S->q1r.reserve(nj));
+        RT_HIP(t->sw_xs1.reserve(2 * nxs)); RT_HIP(t->sw_cur.reserve(2 * nxs));
+        RT_HIP(hipMemsetAsync(S->J.p, 0, nj * sizeof(double), s));
+        t->sw_p1 = true;
+    }
     S->k_hist.clear();
     const unsigned cblocks = (unsigned)std::max(1, (nc + rt::kSolveBlock - 1) / rt::kSolveBlock);
     const int64_t ncg = (int64_t)nc * G;
@@ -338,11 +416,17 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
         hipLaunchKernelGGL(rt::k_solver_source, dim3(sblocks), dim3(rt::kSolveBlock), (size_t)lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
                            (const double *)S->tab.p, lds_len, (const double *)S->phi.p, (const double *)S->prod.p, ext, (const double *)S->scal.p, eig,
                            nc, G, P, t->sw_xs.p);
+        if (p1)
+            hipLaunchKernelGGL(rt::k_solver_source_p1, dim3(sblocks), dim3(rt::kSolveBlock), (size_t)lds1_len * sizeof(double), s, (const int32_t *)S->mat.p,
+                               (const double *)S->tab1.p, lds1_len, (const double *)S->J.p, (const double *)S->pol.p, nc, G, P, S->q1r.p, t->sw_xs1.p);
         RT_HIP(hipGetLastError());
         if (int32_t rc = rt_sweep(t, C, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
         hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
                            (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P,
                            S->partial.p);
+        if (p1)
+            hipLaunchKernelGGL(rt::k_solver_fold_p1, dim3(sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab1.p,
+                               (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->q1r.p, nc, G, P, S->J.p);
         hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)cblocks, 0, eig, S->scal.p);
         RT_HIP(hipMemcpyAsync(S->h_scal, S->scal.p, rt::kSolveScalars * sizeof(double), hipMemcpyDeviceToHost, s));
         RT_HIP(hipStreamSynchronize(s));
@@ -359,12 +443,14 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
     RT_HIP(hipEventRecord(S->ev[1], s));
     if (eigen && nc > 0)
         hipLaunchKernelGGL(rt::k_solver_scale, dim3(sblocks), dim3(256), 0, s, S->phi.p, ncg, (const double *)S->scal.p);
+    if (eigen && nc > 0 && p1)
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * ncg + 255) / 256)), dim3(256), 0, s, S->J.p, 2 * ncg, (const double *)S->scal.p);
     RT_HIP(hipStreamSynchronize(s));
     RT_HIP(hipGetLastError());
     float f = 0.0f;
     RT_HIP(hipEventElapsedTime(&f, S->ev[0], S->ev[1]));
     t->in_flight = false;
-    S->ran = true;
+    S->ran = true; S->ran_p1 = p1;
     if (res) {
         res->k_eff = eigen ? k : 1.0; res->residual = residual; res->dk = dk; res->device_ms = f;
         res->iterations = it; res->converged = converged ? 1 : 0;
@@ -406,6 +492,53 @@ int32_t rt_solver_set_source(rt_solver *solver, const double *source) {
         return RT_ERR_INVALID;
     }
     solver->has_ext = true;
+    return RT_SUCCESS;
+}
+
+static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) {
+    if (!S) { set_error("rt_solver_set_scatter_p1: null solver"); return RT_ERR_INVALID; }
+    if (!sigma_s1) { S->p1 = false; return RT_SUCCESS; }
+    const int32_t G = S->G, M = S->M;
+    const size_t n1 = (size_t)M * G * G;
+    for (size_t i = 0; i < n1; ++i)
+        if (!std::isfinite(sigma_s1[i]) || !(std::fabs(sigma_s1[i]) <= S->h_ss[i])) {
+            set_error("rt_solver_set_scatter_p1: sigma_s1[%zu] = %g against sigma_s = %g (must be finite with |Σs1| <= Σs0)", i, sigma_s1[i], S->h_ss[i]);
+            return RT_ERR_INVALID;
+        }
+    std::vector<double> tab((size_t)M * G * (1 + G));
+    for (int32_t mm = 0; mm < M; ++mm) {
+        double *X = tab.data() + (size_t)mm * G * (1 + G);
+        for (int32_t g = 0; g < G; ++g) X[g] = S->h_st[(size_t)mm * G + g];
+        for (size_t i = 0; i < (size_t)G * G; ++i) X[G + i] = sigma_s1[(size_t)mm * G * G + i];
+    }
+    if (int rc = finish_call(S->t)) return rc;
+    RT_HIP(hipSetDevice(S->t->mesh->device));
+    if (int rc = upload(S->tab1, tab.data(), tab.size(), S->t->mesh->stream)) return rc;
+    RT_HIP(hipStreamSynchronize(S->t->mesh->stream));
+    S->p1 = true;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1) {
+    try {
+        return solver_set_scatter_p1_impl(solver, sigma_s1);
+    } catch (const std::exception &e) {
+        set_error("rt_solver_set_scatter_p1: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+int32_t rt_solver_fetch_current(rt_solver *solver, double *J) {
+    if (!solver || !J) { set_error("rt_solver_fetch_current: null argument"); return RT_ERR_INVALID; }
+    if (!solver->ran || !solver->ran_p1) {
+        set_error("rt_solver_fetch_current: no completed rt_solver_run with first-moment scattering (rt_solver_set_scatter_p1)");
+        return RT_ERR_INVALID;
+    }
+    RT_HIP(hipSetDevice(solver->t->mesh->device));
+    hipStream_t s = solver->t->mesh->stream;
+    const size_t nj = (size_t)solver->n_cells * solver->G * 2;
+    if (nj) RT_HIP(hipMemcpyAsync(J, solver->J.p, nj * sizeof(double), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
     return RT_SUCCESS;
 }
 

@@ -23,15 +23,22 @@ namespace rt {
 // results masked) so that no wait is forced by a branch, and the one rare load inside a branch — the staged entry point of a
 // marked record — is issued BEFORE the iteration's prefetches: gfx950 returns loads in order, so waiting for it leaves the
 // prefetches in flight.  The wave's chunk ids sit in registers (lane j holds chunk j) and are read with v_readlane.
-template <bool STAGED, int GP, bool LDS, bool ELLROWS>
+// P1 (linearly anisotropic source, rt_solver_set_scatter_p1): the source ratio of a lane is q/Σt + d (cs[u] x1 + sn[u] y1) with the
+// component's first-moment ratios (x1, y1) = DSweep::xs1 and d = +1 forward, −1 backward — two FMAs per component and segment —,
+// and every component tallies three values: w Δψ as before (-> phi) and w d cs Δψ, w d sn Δψ (-> cur).  NT tallies per
+// component: the lane-fold and the LDS copy treat them as NT · GP independent values (wd[g], wd[GP + 2g], wd[GP + 2g + 1]).
+// The isotropic instantiations (P1 = false) compile to what they were.
+template <bool STAGED, int GP, bool LDS, bool ELLROWS, bool P1 = false>
 __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
     static_assert(STAGED || !ELLROWS, "ℓ rows belong to the staging rows");
+    constexpr int NT = P1 ? 3 : 1;       // tallies per component
+    constexpr int NH = P1 ? 2 * GP : 1;  // first-moment ratios of a pass (one unused slot when isotropic)
     extern __shared__ __attribute__((aligned(16))) unsigned char sweep_smem[];
-    double *hist = reinterpret_cast<double *>(sweep_smem);  // [n_cells * GP] when LDS
+    double *hist = reinterpret_cast<double *>(sweep_smem);  // [n_cells * NT * GP] when LDS
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, and known to be
     if (LDS) {
-        for (int c = threadIdx.x; c < a.n_cells * GP; c += blockDim.x) hist[c] = 0.0;
+        for (int c = threadIdx.x; c < a.n_cells * (NT * GP); c += blockDim.x) hist[c] = 0.0;
         __syncthreads();
     }
     // a sweep wave = (march wave, direction).  The march waves are ordered longest first and the sweep is bound by
@@ -53,6 +60,13 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
         }
         const int maxcnt = __builtin_amdgcn_readfirstlane(mc);
         const double w = !have ? 0.0 : (a.w ? a.w[u] : a.delta_s[a.azim[u] - 1]);
+        // P1: the traversal's direction cosines d (cos ϕ, sin ϕ) and the weight times them (0 for a lane without a track)
+        double dcs = 0.0, dsn = 0.0, wcs = 0.0, wsn = 0.0;
+        if constexpr (P1) {
+            const double c0 = have ? a.cs[u] : 0.0, s0 = have ? a.sn[u] : 0.0;
+            dcs = dir ? -c0 : c0; dsn = dir ? -s0 : s0;
+            wcs = w * dcs; wsn = w * dsn;
+        }
         const int64_t off = (!STAGED && have) ? a.offsets[u] : 0;
         const int64_t pbase = ((int64_t)dir * a.n + u) * a.G + a.g0;
         const int ng = a.ng;
@@ -67,12 +81,20 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
             return dir ? maxcnt - 1 - tc : tc;
         };
         // cross sections of GP groups of cell `e` (a padded group repeats the last real one; its result is never used)
-        auto load_xs = [&](const int32_t e, double (&st)[GP], double (&qs)[GP]) {
+        auto load_xs = [&](const int32_t e, double (&st)[GP], double (&qs)[GP], double (&h)[NH]) {
             const RT_G double *x = a.xs + ((int64_t)e * a.G + a.g0) * 2;
 #pragma unroll
             for (int g = 0; g < GP; ++g) {
                 const int gi = g < ng ? g : ng - 1;
                 st[g] = x[2 * gi]; qs[g] = x[2 * gi + 1];
+            }
+            if constexpr (P1) {
+                const RT_G double *x1 = a.xs1 + ((int64_t)e * a.G + a.g0) * 2;
+#pragma unroll
+                for (int g = 0; g < GP; ++g) {
+                    const int gi = g < ng ? g : ng - 1;
+                    h[2 * g] = x1[2 * gi]; h[2 * g + 1] = x1[2 * gi + 1];
+                }
             }
         };
         ExpPoly poly = exp_poly();  // (in vector registers: see one_minus_exp_neg)
@@ -80,14 +102,17 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
         for (int i = 0; i < 6; ++i) asm volatile("" : "+v"(poly.c[i]));
         // one segment: attenuation and tally for the GP groups of this pass.  A lane beyond its track's end evaluates a segment
         // of length 0: τ = 0, 1 − e^{−0} = 0 exactly, Δ = ±0 — its ψ keeps its bits, and one select does for all groups.
-        auto segment = [&](const int32_t e, const double ell_row, const bool act, const double (&st)[GP], const double (&qs)[GP]) {
+        auto segment = [&](const int32_t e, const double ell_row, const bool act, const double (&st)[GP], const double (&qs0)[GP],
+                           const double (&h)[NH]) {
             const double ell = act ? ell_row : 0.0;
-            double wd[GP], tau[GP];
+            double wd[NT * GP], tau[GP], qs[GP];
             bool thin = true;
 #pragma unroll
             for (int g = 0; g < GP; ++g) {
                 tau[g] = st[g] * ell;
                 thin = thin && tau[g] < kThinTau;
+                if constexpr (P1) qs[g] = __builtin_fma(dsn, h[2 * g + 1], __builtin_fma(dcs, h[2 * g], qs0[g]));
+                else qs[g] = qs0[g];
             }
             // −expm1(−τ) to within an ulp (rt_device.hpp): where every lane's segment is optically thin in every group of the pass —
             // a wave-uniform branch — by the series alone (10 instructions per group instead of 24)
@@ -100,6 +125,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                     const double d = (psi[g] - qs[g]) * one_minus_exp_neg_thin(tau[g], poly);
                     psi[g] = psi[g] - d;
                     wd[g] = w * d;
+                    if constexpr (P1) { wd[GP + 2 * g] = wcs * d; wd[GP + 2 * g + 1] = wsn * d; }
                 }
             } else {
 #pragma unroll
@@ -107,6 +133,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                     const double d = (psi[g] - qs[g]) * one_minus_exp_neg(tau[g], poly);
                     psi[g] = psi[g] - d;
                     wd[g] = w * d;
+                    if constexpr (P1) { wd[GP + 2 * g] = wcs * d; wd[GP + 2 * g + 1] = wsn * d; }
                 }
             }
             // Neighbouring lanes are neighbouring parallel tracks: at the same row most of them are in the same cell, and
@@ -127,7 +154,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                     const bool take = ((lane & (2 * NSH - 1)) == 0) && key_up == key;
                     const bool given = ((lane & (2 * NSH - 1)) == NSH) && key_dn == key;
 #pragma unroll
-                    for (int g = 0; g < GP; ++g) {
+                    for (int g = 0; g < NT * GP; ++g) {
                         const uint64_t bits = __builtin_bit_cast(uint64_t, wd[g]);
                         const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)(uint32_t)bits, 0x100 + NSH, 0xf, 0xf, true);
                         const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)(uint32_t)(bits >> 32), 0x100 + NSH, 0xf, 0xf, true);
@@ -142,8 +169,18 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
 #pragma unroll
                 for (int g = 0; g < GP; ++g)
                     if (g < ng) {  // (uniform)
-                        if (LDS) atomicAdd(&hist[e * GP + g], wd[g]);
+                        if (LDS) atomicAdd(&hist[e * (NT * GP) + g], wd[g]);
                         else unsafeAtomicAdd((double *)&a.phi[(int64_t)e * a.G + a.g0 + g], wd[g]);
+                        if constexpr (P1) {
+                            if (LDS) {
+                                atomicAdd(&hist[e * (NT * GP) + GP + 2 * g], wd[GP + 2 * g]);
+                                atomicAdd(&hist[e * (NT * GP) + GP + 2 * g + 1], wd[GP + 2 * g + 1]);
+                            } else {
+                                RT_G double *cu = a.cur + ((int64_t)e * a.G + a.g0 + g) * 2;
+                                unsafeAtomicAdd((double *)cu, wd[GP + 2 * g]);
+                                unsafeAtomicAdd((double *)(cu + 1), wd[GP + 2 * g + 1]);
+                            }
+                        }
                     }
             }
         };
@@ -188,10 +225,10 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                     const int DIR = dir;
                     auto row_d = row_of;
                     Row R0 = load_row(row_d(0)), R1 = load_row(row_d(1)), R2{0.0, 0.0, 0};
-                    double stA[GP], qsA[GP], stB[GP], qsB[GP];
-                    load_xs(cell_of(R0, row_d(0)), stA, qsA);
+                    double stA[GP], qsA[GP], stB[GP], qsB[GP], hA[NH], hB[NH];
+                    load_xs(cell_of(R0, row_d(0)), stA, qsA, hA);
                     auto step = [&](const int t, const Row &Ra, const Row &Rb, Row &Rc, const double (&st0)[GP], const double (&qs0)[GP],
-                                    double (&st1)[GP], double (&qs1)[GP]) {
+                                    const double (&h0)[NH], double (&st1)[GP], double (&qs1)[GP], double (&h1)[NH]) {
                         const int r = row_d(t);
                         const bool act = r < cnt && t < maxcnt;
                         // entry point: the previous record's exit point — forward the row before, backward the NEXT step's row — or,
@@ -203,18 +240,21 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                         if (marked) { px = a.stg.px[sl0]; py = a.stg.py[sl0]; }
                         const int64_t sl2 = slot_cached(row_d(t + 2), cj2, cid2);
                         Rc = Row{a.stg.qx[sl2], a.stg.qy[sl2], a.stg.element[sl2]};
-                        load_xs(cell_of(Rb, row_d(t + 1)), st1, qs1);
+                        load_xs(cell_of(Rb, row_d(t + 1)), st1, qs1, h1);
                         if (marked) { dx = px - Ra.qx; dy = py - Ra.qy; }
                         const double ell = norm2(dx, dy);  // Segment ctor, src/segment.jl:31-33 (as k_compact3)
                         if (a.ell_rows != nullptr && !DIR && act) a.ell_rows[sl0] = ell;  // (uniform && uniform && lane: for the ELLROWS passes)
-                        segment(cell_of(Ra, r), ell, act, st0, qs0);
+                        segment(cell_of(Ra, r), ell, act, st0, qs0, h0);
                     };
                     for (int t = 0; t < maxcnt; t += 3) {
-                        step(t, R0, R1, R2, stA, qsA, stB, qsB);
-                        step(t + 1, R1, R2, R0, stB, qsB, stA, qsA);
-                        step(t + 2, R2, R0, R1, stA, qsA, stB, qsB);
+                        step(t, R0, R1, R2, stA, qsA, hA, stB, qsB, hB);
+                        step(t + 1, R1, R2, R0, stB, qsB, hB, stA, qsA, hA);
+                        step(t + 2, R2, R0, R1, stA, qsA, hA, stB, qsB, hB);
 #pragma unroll
                         for (int g = 0; g < GP; ++g) { stA[g] = stB[g]; qsA[g] = qsB[g]; }
+                        if constexpr (P1)
+#pragma unroll
+                            for (int g = 0; g < NH; ++g) hA[g] = hB[g];
                     }
                 }
                 if constexpr (ELLROWS) {
@@ -224,22 +264,25 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                     auto load_lrow = [&](const int64_t sl) -> LRow { return LRow{a.ell_rows[sl], a.stg.element[sl]}; };
                     auto lcell = [&](const LRow &R, const int r) -> int32_t { return r < cnt ? (R.el < 0 ? -R.el : R.el) - 1 : 0; };
                     LRow L0 = load_lrow(slot_of(row_of(0))), L1 = load_lrow(slot_of(row_of(1))), L2{0.0, 0};
-                    double stA[GP], qsA[GP], stB[GP], qsB[GP];
-                    load_xs(lcell(L0, row_of(0)), stA, qsA);
+                    double stA[GP], qsA[GP], stB[GP], qsB[GP], hA[NH], hB[NH];
+                    load_xs(lcell(L0, row_of(0)), stA, qsA, hA);
                     auto lstep = [&](const int t, const LRow &Ra, const LRow &Rb, LRow &Rc, const double (&st0)[GP], const double (&qs0)[GP],
-                                     double (&st1)[GP], double (&qs1)[GP]) {
+                                     const double (&h0)[NH], double (&st1)[GP], double (&qs1)[GP], double (&h1)[NH]) {
                         const int r = row_of(t);
                         const bool act = r < cnt && t < maxcnt;
                         Rc = load_lrow(slot_cached(row_of(t + 2), cj2, cid2));
-                        load_xs(lcell(Rb, row_of(t + 1)), st1, qs1);
-                        segment(lcell(Ra, r), Ra.ell, act, st0, qs0);
+                        load_xs(lcell(Rb, row_of(t + 1)), st1, qs1, h1);
+                        segment(lcell(Ra, r), Ra.ell, act, st0, qs0, h0);
                     };
                     for (int t = 0; t < maxcnt; t += 3) {
-                        lstep(t, L0, L1, L2, stA, qsA, stB, qsB);
-                        lstep(t + 1, L1, L2, L0, stB, qsB, stA, qsA);
-                        lstep(t + 2, L2, L0, L1, stA, qsA, stB, qsB);
+                        lstep(t, L0, L1, L2, stA, qsA, hA, stB, qsB, hB);
+                        lstep(t + 1, L1, L2, L0, stB, qsB, hB, stA, qsA, hA);
+                        lstep(t + 2, L2, L0, L1, stA, qsA, hA, stB, qsB, hB);
 #pragma unroll
                         for (int g = 0; g < GP; ++g) { stA[g] = stB[g]; qsA[g] = qsB[g]; }
+                        if constexpr (P1)
+#pragma unroll
+                            for (int g = 0; g < NH; ++g) hA[g] = hB[g];
                     }
                 }
             } else {
@@ -251,17 +294,20 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                 };
                 auto cell_of = [&](const Rec &R, const int r) -> int32_t { return r < cnt ? R.el - 1 : 0; };
                 Rec R0 = load_rec(row_of(0)), R1 = load_rec(row_of(1));
-                double st0[GP], qs0[GP];
-                load_xs(cell_of(R0, row_of(0)), st0, qs0);
+                double st0[GP], qs0[GP], h0[NH];
+                load_xs(cell_of(R0, row_of(0)), st0, qs0, h0);
                 for (int t = 0; t < maxcnt; ++t) {
                     const int r = row_of(t);
                     const Rec R2 = load_rec(row_of(t + 2));
-                    double st1[GP], qs1[GP];
-                    load_xs(cell_of(R1, row_of(t + 1)), st1, qs1);
-                    segment(cell_of(R0, r), R0.ell, r < cnt, st0, qs0);
+                    double st1[GP], qs1[GP], h1[NH];
+                    load_xs(cell_of(R1, row_of(t + 1)), st1, qs1, h1);
+                    segment(cell_of(R0, r), R0.ell, r < cnt, st0, qs0, h0);
                     R0 = R1; R1 = R2;
 #pragma unroll
                     for (int g = 0; g < GP; ++g) { st0[g] = st1[g]; qs0[g] = qs1[g]; }
+                    if constexpr (P1)
+#pragma unroll
+                        for (int g = 0; g < NH; ++g) h0[g] = h1[g];
                 }
             }
         }
@@ -272,10 +318,15 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
     }
     if (LDS) {
         __syncthreads();
-        for (int c = threadIdx.x; c < a.n_cells * GP; c += blockDim.x) {
+        for (int c = threadIdx.x; c < a.n_cells * (NT * GP); c += blockDim.x) {
             const double v = hist[c];
-            const int cell = c / GP, g = c - cell * GP;
-            if (v != 0.0 && g < a.ng) unsafeAtomicAdd((double *)&a.phi[(int64_t)cell * a.G + a.g0 + g], v);
+            const int cell = c / (NT * GP), i = c - cell * (NT * GP);
+            if (!P1 || i < GP) {
+                if (v != 0.0 && i < a.ng) unsafeAtomicAdd((double *)&a.phi[(int64_t)cell * a.G + a.g0 + i], v);
+            } else {
+                const int g = (i - GP) >> 1;
+                if (v != 0.0 && g < a.ng) unsafeAtomicAdd((double *)&a.cur[((int64_t)cell * a.G + a.g0 + g) * 2 + ((i - GP) & 1)], v);
+            }
         }
     }
 }
@@ -360,6 +411,8 @@ __global__ __launch_bounds__(256) void k_rows_fill(const int32_t *__restrict__ c
         }
     }
 }
+
+constexpr int kSweepGpP1 = 2;  // components per pass of the anisotropic sweep, at most
 
 }  // namespace rt
 
@@ -496,18 +549,30 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     a.xs = as_global((const double *)t->sw_xs.p);
     a.psi_in = as_global((const double *)t->sw_psi_in.p); a.psi_out = as_global(t->sw_psi_out.p); a.phi = as_global(t->sw_phi.p);
     a.n = n; a.n_waves = (int32_t)((n + 63) / 64); a.n_cells = m->n_cells; a.G = G; a.debug = m->sweep_debug;
+    // the anisotropic mode (an rt_solver with first-moment scattering has filled sw_xs1 for these G components)
+    const bool p1 = t->sw_p1;
+    const int nt = p1 ? 3 : 1;  // tallies per component
+    if (p1) {
+        if (!t->sw_xs1.p || !t->sw_cur.p) { set_error("rt_sweep: the anisotropic mode has no first-moment arrays"); return RT_ERR_INVALID; }
+        a.xs1 = as_global((const double *)t->sw_xs1.p); a.cur = as_global(t->sw_cur.p);
+        a.cs = as_global((const double *)t->cs.p); a.sn = as_global((const double *)t->sn.p);
+    }
     // groups per pass: as many as an LDS-private copy of their tallies allows (up to 4); none fits: global atomics.  The last pass
     // takes what is left with the kernel compiled for that many groups (7 groups = 4 + 3: a padded fourth group was an eighth
     // of the sweep's arithmetic).
+    // Anisotropic: three tallies per component, so a mesh that fits 4 components fits 1; at most kSweepGpP1 per pass (the kernel
+    // carries two more ratios per pipeline stage and two more deltas per component: see DESIGN.md for the registers).
     const size_t lds_cap = (size_t)std::min(m->lds_per_block, 160 * 1024) - 1024;
-    int gp = std::min(G, 4);
+    const int gp_max = p1 ? rt::kSweepGpP1 : 4;
+    int gp = std::min(G, gp_max);
     if (m->sweep_gp >= 1 && m->sweep_gp <= 4) gp = std::min(gp, m->sweep_gp);
-    while (gp > 1 && (size_t)m->n_cells * gp * sizeof(double) > lds_cap) --gp;
-    a.use_lds = (size_t)m->n_cells * gp * sizeof(double) <= lds_cap ? 1 : 0;
-    if (!a.use_lds) gp = std::min(G, 4);
+    while (gp > 1 && (size_t)m->n_cells * gp * nt * sizeof(double) > lds_cap) --gp;
+    a.use_lds = (size_t)m->n_cells * gp * nt * sizeof(double) <= lds_cap ? 1 : 0;
+    if (!a.use_lds) gp = std::min(G, gp_max);
     if (m->sweep_gp >= 8) a.use_lds = 0;  // experiment: tallies straight to HBM (measured 4x slower at C3: 2.1 ms against 0.48)
     if (!async_sweep) RT_HIP(hipEventRecord(t->ev[0], s));
     RT_HIP(hipMemsetAsync(t->sw_phi.p, 0, nphi * sizeof(double), s));
+    if (p1 && nphi) RT_HIP(hipMemsetAsync(t->sw_cur.p, 0, 2 * nphi * sizeof(double), s));
     int passes = 0;
     // Staged rows: the first pass after an rt_segmentize derives ℓ from the exit points and leaves it in `sw_ell`, slot-indexed
     // like the rows; every later pass — of this sweep and of all following sweeps over the same segmentation — reads (ℓ, cell)
@@ -529,8 +594,8 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         else (void)hipGetLastError();  // (no memory for it: every pass derives ℓ itself)
     }
     a.ell_rows = ell_rows ? as_global(t->sw_ell.p) : nullptr;
-    auto launch = [&]<bool STAGED, int GP, bool LDS>(int g0) -> int {
-        size_t smem = a.use_lds ? (size_t)m->n_cells * GP * sizeof(double) : 0;
+    auto launch = [&]<bool STAGED, int GP, bool LDS, bool P1>(int g0) -> int {
+        size_t smem = a.use_lds ? (size_t)m->n_cells * GP * (P1 ? 3 : 1) * sizeof(double) : 0;
         // (compact records: more than one eight-wave workgroup per CU thrashes its L1 — a pass of few groups asks for LDS it
         //  does not use, so that it still gets a CU to itself: 5 groups = 4 + 1 took 0.88 ms against 0.58 for 7 = 4 + 3)
         if (!STAGED && a.use_lds) smem = std::max(smem, std::min(lds_cap, (size_t)81 * 1024));
@@ -544,13 +609,13 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         if (STAGED && ell_rows && (t->sw_ell_valid || rows_compact)) {
             if constexpr (STAGED) {
                 if (smem > 48 * 1024)
-                    RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<true, GP, LDS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                hipLaunchKernelGGL((rt::k_sweep<true, GP, LDS, true>), dim3(blocks), dim3(64 * W), smem, s, a);
+                    RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<true, GP, LDS, true, P1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+                hipLaunchKernelGGL((rt::k_sweep<true, GP, LDS, true, P1>), dim3(blocks), dim3(64 * W), smem, s, a);
             }
         } else {
             if (smem > 48 * 1024)
-                RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<STAGED, GP, LDS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            hipLaunchKernelGGL((rt::k_sweep<STAGED, GP, LDS, false>), dim3(blocks), dim3(64 * W), smem, s, a);
+                RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<STAGED, GP, LDS, false, P1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            hipLaunchKernelGGL((rt::k_sweep<STAGED, GP, LDS, false, P1>), dim3(blocks), dim3(64 * W), smem, s, a);
             if (STAGED && ell_rows) { t->sw_ell_valid = true; t->sw_rowsc_valid = false; }  // (the forward waves of this pass have written every row's ℓ)
         }
         ++passes;
@@ -560,10 +625,14 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         for (int g0 = 0; g0 < G;) {
             const int take = std::min(gp, G - g0);
             int rc;
-            if (take == 4) rc = launch.template operator()<STAGED, 4, LDS>(g0);
-            else if (take == 3) rc = launch.template operator()<STAGED, 3, LDS>(g0);
-            else if (take == 2) rc = launch.template operator()<STAGED, 2, LDS>(g0);
-            else rc = launch.template operator()<STAGED, 1, LDS>(g0);
+            if (p1) {
+                static_assert(rt::kSweepGpP1 == 2, "the anisotropic passes below");
+                if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, true>(g0);
+                else rc = launch.template operator()<STAGED, 1, LDS, true>(g0);
+            } else if (take == 4) rc = launch.template operator()<STAGED, 4, LDS, false>(g0);
+            else if (take == 3) rc = launch.template operator()<STAGED, 3, LDS, false>(g0);
+            else if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, false>(g0);
+            else rc = launch.template operator()<STAGED, 1, LDS, false>(g0);
             if (rc) return rc;
             g0 += take;
         }

@@ -6,7 +6,9 @@ The iteration runs in ``librt_segmentize.so`` (``rt_solver_*``, ``csrc/rt_solver
 per iteration a source-update kernel, one sweep over G x P components (energy groups x polar angles),
 a fold kernel and a fixed-order reduction; only k, the residual and |Δk|/k come back to the host.
 The definitions (azimuthal and polar weights, volumes, fold, source, residual, normalisation) are stated
-in ``include/rt_segmentize.h``.
+in ``include/rt_segmentize.h``.  With ``CrossSections(..., sigma_s1=...)`` scattering is linearly anisotropic (P1): the
+sweep's source depends on the direction of travel, first angular moments are tallied and ``SolverResult.current`` is the
+net current.
 """
 from __future__ import annotations
 
@@ -26,9 +28,11 @@ __all__ = ["CrossSections", "PolarQuadrature", "SolverResult", "exact_azimuthal_
 class CrossSections:
     """Macroscopic cross sections of M materials in G groups: ``sigma_t``, ``nu_sigma_f``, ``chi`` [M, G] and
     ``sigma_s`` [M, G, G] with ``sigma_s[m, g', g]`` the transfer from group g' to g (isotropic scattering).
-    One material may be given without its leading axis."""
+    One material may be given without its leading axis.  ``sigma_s1`` [M, G, G] (optional): the l = 1 Legendre moment of the
+    same transfer, Σs(g'→g, μ0) = (1/4π) [Σs0 + 3 Σs1 μ0] — linearly anisotropic scattering; entries may be negative but
+    must be finite with |Σs1| <= Σs0."""
 
-    def __init__(self, sigma_t, sigma_s, nu_sigma_f, chi):
+    def __init__(self, sigma_t, sigma_s, nu_sigma_f, chi, sigma_s1=None):
         st = np.asarray(sigma_t, np.float64)
         st = st.reshape(1, -1) if st.ndim <= 1 else st
         if st.ndim != 2:
@@ -46,6 +50,16 @@ class CrossSections:
         if nf.shape != (M, G) or ch.shape != (M, G):
             raise ValueError(f"nu_sigma_f and chi must have shape [M, G] = {(M, G)}")
         self.sigma_t, self.sigma_s, self.nu_sigma_f, self.chi = (np.ascontiguousarray(a) for a in (st, ss, nf, ch))
+        self.sigma_s1 = None
+        if sigma_s1 is not None:
+            s1 = np.asarray(sigma_s1, np.float64)
+            if s1.size == M * G * G and s1.ndim <= 3:
+                s1 = s1.reshape(M, G, G)
+            if s1.shape != (M, G, G):
+                raise ValueError(f"sigma_s1 must have shape [M, G, G] = {(M, G, G)}, got {np.shape(sigma_s1)}")
+            if not np.all(np.isfinite(s1)) or not np.all(np.abs(s1) <= self.sigma_s):
+                raise ValueError("every sigma_s1 must be finite with |sigma_s1| <= sigma_s")
+            self.sigma_s1 = np.ascontiguousarray(s1)
 
     @property
     def n_materials(self) -> int:
@@ -144,6 +158,7 @@ class SolverResult:
     ms_per_iteration: float       # HIP-event time of the iterations / iterations
     residual: float
     solver: object = None         # the device solver (rt_solver handle), for a further run
+    current: Optional[np.ndarray] = None  # net current (Jx, Jy) [n_cells, G, 2] with sigma_s1; None when isotropic
 
 
 def _cell_material(tg, cell_material):
@@ -183,12 +198,15 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
                             pq.sin_theta, pq.weights, alpha)
     if source is not None:
         sv.set_source(source)
+    if xs.sigma_s1 is not None:
+        sv.set_scatter_p1(xs.sigma_s1)
     r = sv.run(mode, int(max_iter), float(tol_k), float(tol_flux))
     f = sv.fetch(r["iterations"])
+    current = sv.fetch_current() if xs.sigma_s1 is not None else None
     it = r["iterations"]
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
-                        ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv)
+                        ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current)
 
 
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
