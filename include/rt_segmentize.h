@@ -482,6 +482,32 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              with the continuous value 4π/3 of ∫ Ωx² dΩ, as the scalar term uses 4π
  * Iteration    J⁰ = 0; k, residual, stopping rule and normalisation are unchanged (eigenvalue mode scales J with φ)
  *
+ * Linear source (LS-MOC), rt_solver_set_linear_source.  The source of cell e is Q(r) = q_{e,g} + q⃗_{e,g}·(r − r_c,e) instead of
+ * the flat q_{e,g}, and the characteristic equation is still solved exactly along every segment.  A traversal is
+ * (track u, d = ±1) and moves along d (cs, sn) = d (cos φ_u, sin φ_u); lengths ℓ are 2-D, Σ_c = Σt_g / sin θ_p.
+ * Geometry     once per solver, from the records and α.  m = ((px + qx)/2, (py + qy)/2) is a record's midpoint (the sweep forms
+ *              it from the track's end point and the running sum of ℓ: the two differ by rounding, and behind a record that does
+ *              not start where the previous one ended — the march stepped over a sliver narrower than its tiny step — by that gap)
+ *              r_c,e = (X_e, Y_e) = (1/V_e) Σ_u 2αδ Σ_rec ℓ m;   with ξ = m_x − X_e, η = m_y − Y_e:
+ *              Cxx_e = (1/V_e) Σ_u 2αδ Σ_rec (ℓ ξ² + cs² ℓ³/12),  Cxy_e with (ℓ ξη + cs sn ℓ³/12),  Cyy_e with (ℓ η² + sn² ℓ³/12)
+ *              — the track-based value of (1/V) ∫ (r − r_c)(r − r_c)ᵀ dV
+ * Degenerate   V_e = 0, or det C_e <= 1e-10 (Cxx + Cyy)² (a cell seen from one direction only): the cell keeps a flat source
+ *              (q⃗ = 0, φ⃗ = 0).  A guard, not a tuning knob; rt_solver_fetch_geometry returns how many cells it caught
+ * Source       s⃗_{e,g} = (1/4π) [Σ_g' Σs[g'→g] φ⃗_{e,g'} + (χ_g / k) Σ_g' νΣf_g' φ⃗_{e,g'}],   q⃗_{e,g} = C_e⁻¹ s⃗_{e,g}
+ *              with the flux moments φ⃗ = (φx, φy) of the fold below.  The external source S stays flat.  There is no
+ *              negative-source fix-up: Q, and with it ψ, may dip below zero near steep gradients, as in other LS codes
+ * Segment      t the path length from the entry point, τ = Σ_c ℓ, E = e^{−τ};  source ratio r(t) = r_m + ρ (t − ℓ/2) with
+ *              r_m = (q + q⃗·(m − r_c)) / Σt_g,  ρ = d (cs q_x + sn q_y) / Σt_g
+ *              F1(τ) = 1 − E,   F2(τ) = τ (1 + E) − 2 (1 − E) = τ³/6 − τ⁴/12 + …  (evaluated without cancellation)
+ *              Δψ = ψ_in − ψ_out = (ψ_in − r_m) F1 − (ρ / 2Σ_c) F2
+ *              K = ψ_in − r_m + ρ (ℓ/2 + 1/Σ_c),   H = K F2 / (2 Σ_c)
+ *              (from dψ/dt + Σ_c ψ = Σ_c r(t): ∫ψ dt = ℓ r_m + Δψ/Σ_c and ∫(t − ℓ/2) ψ dt = ρ ℓ³/12 − K F2 / (2 Σ_c²))
+ * Tallies      T += w Δψ as before,   Tx += w (ξ Δψ − d cs H),   Ty += w (η Δψ − d sn H)
+ * Fold         φ as above (the linear part of its first term integrates to zero by the definition of r_c);
+ *              φ⃗_{e,g} = (4π / Σt_g) C_e q⃗_{e,g} + Σ_p ω_p sin θ_p (Tx, Ty)[e][g·P + p] / (Σt_g V_e);  degenerate cells: 0
+ * Iteration    φ⃗⁰ = 0; k, residual, stopping rule and normalisation are unchanged and use φ only (eigenvalue mode scales φ⃗
+ *              with φ).  Together with first-moment scattering it is not supported: whichever is switched on second fails
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -522,6 +548,17 @@ int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1);
 /* The net current J [n_cells][G][2] (x, y) of the last run.  RT_ERR_INVALID before a run, or when that run had no
  * first-moment scattering. */
 int32_t rt_solver_fetch_current(rt_solver *solver, double *J);
+/* Linear source (see above) on (non-zero) or off for the following runs.  Off runs exactly the kernels of a solver that never
+ * had it on.  The first switching-on computes the cells' geometry on the device.  RT_ERR_INVALID while first-moment scattering
+ * is set (and rt_solver_set_scatter_p1 fails while the linear source is on). */
+int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on);
+/* Geometry of the linear source: centroid [n_cells][2], cmat [n_cells][3] (Cxx, Cxy, Cyy), the number of degenerate cells; any
+ * may be NULL.  RT_ERR_INVALID when the linear source has never been switched on. */
+int32_t rt_solver_fetch_geometry(rt_solver *solver, double *centroid, double *cmat, int32_t *n_degenerate);
+/* After a run with the linear source: the flux moments phi_xy [n_cells][G][2] and grad = C⁻¹ φ⃗ [n_cells][G][2], the flux gradient
+ * (for plots, or to reconstruct the flux at r as φ + grad·(r − r_c)); either may be NULL.  RT_ERR_INVALID before a run, or when
+ * that run had a flat source. */
+int32_t rt_solver_fetch_moments(rt_solver *solver, double *phi_xy, double *grad);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

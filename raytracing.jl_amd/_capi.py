@@ -28,6 +28,7 @@ SYMBOLS = (
     "rt_multi_failed_tracks", "rt_multi_fetch_offsets", "rt_multi_fetch_segments", "rt_multi_fetch_volumes", "rt_multi_allgather",
     "rt_trace_counts", "rt_trace", "rt_msh_load", "rt_msh_sizes", "rt_msh_fetch", "rt_msh_free",
     "rt_solver_create", "rt_solver_set_source", "rt_solver_run", "rt_solver_fetch", "rt_solver_destroy",
+    "rt_solver_set_linear_source", "rt_solver_fetch_geometry", "rt_solver_fetch_moments",
     "rt_solver_fetch_current",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
@@ -230,6 +231,12 @@ def lib():
     L.rt_solver_set_scatter_p1.argtypes = [_vp, _dp]
     L.rt_solver_fetch_current.restype = C.c_int32
     L.rt_solver_fetch_current.argtypes = [_vp, _dp]
+    L.rt_solver_set_linear_source.restype = C.c_int32
+    L.rt_solver_set_linear_source.argtypes = [_vp, C.c_int32]
+    L.rt_solver_fetch_geometry.restype = C.c_int32
+    L.rt_solver_fetch_geometry.argtypes = [_vp, _dp, _dp, C.POINTER(C.c_int32)]
+    L.rt_solver_fetch_moments.restype = C.c_int32
+    L.rt_solver_fetch_moments.argtypes = [_vp, _dp, _dp]
     if L.rt_abi_version() != 1:
         raise RtError("librt_segmentize.so: ABI version mismatch")
     _lib = L
@@ -698,6 +705,22 @@ class DeviceSolver:
         J = np.empty((self.n_cells, self.G, 2))
         _check(lib().rt_solver_fetch_current(self._h, J.ctypes.data_as(_dp)))
         return J
+
+    def set_linear_source(self, on=True):
+        """``rt_solver_set_linear_source``: the linear-source approximation for the following runs (False: flat again)."""
+        _check(lib().rt_solver_set_linear_source(self._h, 1 if on else 0))
+
+    def fetch_geometry(self) -> dict:
+        """``rt_solver_fetch_geometry``: ``centroids`` [n_cells, 2], ``cmat`` [n_cells, 3] (Cxx, Cxy, Cyy), ``n_degenerate``."""
+        cen = np.empty((self.n_cells, 2)); cm = np.empty((self.n_cells, 3)); nd = C.c_int32(0)
+        _check(lib().rt_solver_fetch_geometry(self._h, cen.ctypes.data_as(_dp), cm.ctypes.data_as(_dp), C.byref(nd)))
+        return dict(centroids=cen, cmat=cm, n_degenerate=int(nd.value))
+
+    def fetch_moments(self) -> dict:
+        """``rt_solver_fetch_moments``: ``flux_moments`` (φx, φy) and ``flux_gradient`` = C⁻¹ φ⃗, both [n_cells, G, 2]."""
+        m = np.empty((self.n_cells, self.G, 2)); g = np.empty((self.n_cells, self.G, 2))
+        _check(lib().rt_solver_fetch_moments(self._h, m.ctypes.data_as(_dp), g.ctypes.data_as(_dp)))
+        return dict(flux_moments=m, flux_gradient=g)
 
     def run(self, mode: int, max_iter: int, tol_k: float, tol_flux: float) -> dict:
         if not getattr(self, "_h", None):

@@ -1065,4 +1065,82 @@ RT_HD __forceinline__ double one_minus_exp_neg_thin(double tau, const ExpPoly &h
     return tau * q;
 }
 
+// ---- linear source (k_sweep<..., LS>) ------------------------------------------------------------------------------------
+// one_minus_exp_neg that also hands out e^{−τ} = 2^n (1 + expm1(r)), itself to an ulp (1 − F1 would lose what F1 cancels).
+RT_HD __forceinline__ double one_minus_exp_neg_both(double tau, double &E, const ExpPoly &hi = exp_poly()) {
+    const double x = -__builtin_fmin(tau, 41.5);
+    const double kMagic = 6755399441055744.0;
+    const double t = __builtin_fma(x, 1.4426950408889634074, kMagic);
+    const double n = t - kMagic;
+    const int32_t ni = (int32_t)(uint32_t)__builtin_bit_cast(uint64_t, t);
+    double r = __builtin_fma(n, -6.93147180369123816490e-01, x);
+    r = __builtin_fma(n, -1.90821492927058770002e-10, r);
+    double q = hi.c[0];
+    q = __builtin_fma(q, r, hi.c[1]);
+    q = __builtin_fma(q, r, hi.c[2]);
+    q = __builtin_fma(q, r, hi.c[3]);
+    q = __builtin_fma(q, r, hi.c[4]);
+    q = __builtin_fma(q, r, hi.c[5]);
+    q = __builtin_fma(q, r, 1.984126984126984e-04);
+    q = __builtin_fma(q, r, 1.3888888888888889e-03);
+    q = __builtin_fma(q, r, 8.333333333333333e-03);
+    q = __builtin_fma(q, r, 4.1666666666666664e-02);
+    q = __builtin_fma(q, r, 1.6666666666666666e-01);
+    q = __builtin_fma(q, r, 0.5);
+    const double p = __builtin_fma(r * r, q, r);
+    const double s2 = __builtin_bit_cast(double, (uint64_t)(uint32_t)(ni + 1023) << 52);
+    E = __builtin_fma(s2, p, s2);
+    return -__builtin_fma(s2, p, s2 - 1.0);
+}
+// F2(τ) = τ (1 + e^{−τ}) − 2 (1 − e^{−τ}) = τ³/6 − τ⁴/12 + …, τ >= 0, to a few ulp.  Written out it cancels (at τ = 0.1 all but
+// 1e-4 of its terms), so: below τ = 1.5, F2 = e^{−τ} G(τ) with G(τ) = e^{τ} F2 = Σ_{n>=3} (n − 2) τ^n / n!, whose terms are all
+// positive — n to 24, the next term is below 2e-17 of the sum —; from 1.5 on, (τ − 2) + (τ + 2) e^{−τ}, where an ulp of e^{−τ}
+// is at most 2.6 ulp of the result (1 at τ = 2, less beyond).  E = e^{−τ} as one_minus_exp_neg_both gives it.
+constexpr double kLsSeriesTau = 1.5;
+RT_HD __forceinline__ double ls_f2(double tau, double E) {
+    if (tau < kLsSeriesTau) {
+        double q = 22.0 / 620448401733239439360000.0;          // (n − 2)/n!, n = 24
+        q = __builtin_fma(q, tau, 21.0 / 25852016738884976640000.0);
+        q = __builtin_fma(q, tau, 20.0 / 1124000727777607680000.0);
+        q = __builtin_fma(q, tau, 19.0 / 51090942171709440000.0);
+        q = __builtin_fma(q, tau, 18.0 / 2432902008176640000.0);
+        q = __builtin_fma(q, tau, 17.0 / 121645100408832000.0);
+        q = __builtin_fma(q, tau, 16.0 / 6402373705728000.0);
+        q = __builtin_fma(q, tau, 15.0 / 355687428096000.0);
+        q = __builtin_fma(q, tau, 14.0 / 20922789888000.0);
+        q = __builtin_fma(q, tau, 13.0 / 1307674368000.0);
+        q = __builtin_fma(q, tau, 12.0 / 87178291200.0);
+        q = __builtin_fma(q, tau, 11.0 / 6227020800.0);
+        q = __builtin_fma(q, tau, 10.0 / 479001600.0);
+        q = __builtin_fma(q, tau, 9.0 / 39916800.0);
+        q = __builtin_fma(q, tau, 8.0 / 3628800.0);
+        q = __builtin_fma(q, tau, 7.0 / 362880.0);
+        q = __builtin_fma(q, tau, 6.0 / 40320.0);
+        q = __builtin_fma(q, tau, 5.0 / 5040.0);
+        q = __builtin_fma(q, tau, 4.0 / 720.0);
+        q = __builtin_fma(q, tau, 3.0 / 120.0);
+        q = __builtin_fma(q, tau, 2.0 / 24.0);
+        q = __builtin_fma(q, tau, 1.0 / 6.0);
+        return E * (tau * tau * tau) * q;
+    }
+    return __builtin_fma(tau + 2.0, E, tau - 2.0);
+}
+// The same for an optically THIN segment, 0 <= τ < 1/8 (kThinTau): the series itself, F2 = τ³ Σ_{n>=3} (−1)^{n+1} (n − 2) τ^{n−3} / n!
+// to n = 13 (the next term is below 1e-19 of the sum; the alternating terms cancel less than 5 % of it at 1/8).  No exponential.
+RT_HD __forceinline__ double ls_f2_thin(double tau) {
+    const double x = -tau;
+    double q = 11.0 / 6227020800.0;                // n = 13, the sign of τ^{n−3} rides on x
+    q = __builtin_fma(q, x, 10.0 / 479001600.0);
+    q = __builtin_fma(q, x, 9.0 / 39916800.0);
+    q = __builtin_fma(q, x, 8.0 / 3628800.0);
+    q = __builtin_fma(q, x, 7.0 / 362880.0);
+    q = __builtin_fma(q, x, 6.0 / 40320.0);
+    q = __builtin_fma(q, x, 5.0 / 5040.0);
+    q = __builtin_fma(q, x, 4.0 / 720.0);
+    q = __builtin_fma(q, x, 3.0 / 120.0);
+    q = __builtin_fma(q, x, 2.0 / 24.0);
+    q = __builtin_fma(q, x, 1.0 / 6.0);
+    return (tau * tau * tau) * q;
+}
+
 }  // namespace rt

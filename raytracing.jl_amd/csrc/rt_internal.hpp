@@ -304,6 +304,10 @@ struct DSweep {
     const RT_G double *xs1;           // [n_cells * G][2]: q1x sin θ / Σt, q1y sin θ / Σt
     const RT_G double *cs, *sn;       // [n] cos ϕ, sin ϕ of every track (by uid)
     RT_G double *cur;                 // [n_cells * G][2] tallies Σ w d cs Δψ, Σ w d sn Δψ
+    // linear source (k_sweep<..., LS>; rt_solver with rt_solver_set_linear_source): xs1 holds the gradient ratios q⃗ / (Σt_g Σ_c) of
+    // every component, `cur` receives Σ_c times the moment tallies (Tx, Ty)
+    const RT_G double *cen;           // [n_cells][2] track-based centroids
+    const RT_G double *ends;          // [n][4] by uid: the first record's entry point, the last record's exit point
 };
 
 }  // namespace rt
@@ -492,6 +496,8 @@ struct rt_tracks {
     DevBuf<double> sw_w, sw_xs, sw_psi_in, sw_psi_out, sw_phi;
     DevBuf<double> sw_xs1, sw_cur;  // the anisotropic sweep's first-moment ratios and tallies (DSweep xs1, cur): rt_solver owns their content
     bool sw_p1 = false;             // ... and switches the mode on for the sweeps of its run
+    bool sw_ls = false;             // the linear-source mode, switched on by an rt_solver for the sweeps of its run (sw_xs1: gradient
+    const double *sw_ls_cen = nullptr, *sw_ls_ends = nullptr;  // ratios, sw_cur: moment tallies); the solver's centroids and track ends
     DevBuf<double> sw_ell;      // ℓ of every staged row (slot-indexed like the staging pool), left by the first staged pass after a call
     bool sw_ell_valid = false;  // ... of the last rt_segmentize
     DevBuf<int32_t> sw_cell;    // codes: cell + 1 of every staged row, beside sw_ell (k_materialise<.., ROWS>)

@@ -8,6 +8,11 @@
 // mode: k_solver_source_p1 (q1/Σt from the net current J, and its sin θ_p multiple of every component into the sweep's xs1
 // array) after k_solver_source, and k_solver_fold_p1 (J from the first-moment tallies) after k_solver_fold.  Without it the
 // solver launches what it always did.
+// With the linear source (rt_solver_set_linear_source) likewise two more kernels, and the sweep runs in its linear-source mode:
+// k_solver_source_ls (q⃗ = C⁻¹ s⃗ from the flux moments φ⃗, and q⃗ / (Σt_g Σ_c) of every component into the sweep's xs1 array) and
+// k_solver_fold_ls (φ⃗ from the moment tallies).  The cells' geometry (centroids, C, C⁻¹, the tracks' end points) is computed once,
+// when the option is first switched on: k_solver_ls_moments over the compact records, twice (first moments, then second moments
+// about the centroid), and k_solver_ls_centroid / k_solver_ls_cmat per cell.
 #include "rt_internal.hpp"
 
 namespace rt {
@@ -133,6 +138,132 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_fold_p1(const int32_t *_
     J[2 * i + 1] = kFourPiOverThree * q1r[2 * i + 1] + (V > 0.0 ? ay / (st * V) : 0.0);
 }
 
+// ---- linear source ---------------------------------------------------------------------------------------------------------
+// One thread per track over its compact records.  SECOND = false: acc[e][0..1] += 2αδ ℓ (m_x, m_y) and the track's end points
+// (first record's p, last record's q) into ends[u][4]; SECOND = true: acc[e][0..2] += 2αδ (ℓ ξ² + cs² ℓ³/12), (ℓ ξη + cs sn ℓ³/12),
+// (ℓ η² + sn² ℓ³/12) about the centroids `cen`.  Once per solver: plain global atomics.
+template <bool SECOND>
+__global__ __launch_bounds__(256) void k_solver_ls_moments(const int64_t *__restrict__ offsets, const int32_t *__restrict__ counts, int64_t n, const int32_t *__restrict__ azim,
+                                                           const double *__restrict__ wvol, const double *__restrict__ cs, const double *__restrict__ sn,
+                                                           const int32_t *__restrict__ element, const double *__restrict__ px, const double *__restrict__ py,
+                                                           const double *__restrict__ qx, const double *__restrict__ qy, const double *__restrict__ ell,
+                                                           const double *__restrict__ cen, int32_t n_cells, double *__restrict__ acc,
+                                                           double *__restrict__ ends) {
+    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (u >= n) return;
+    const int64_t b = offsets[u], e1 = b + counts[u];
+    const double w = wvol[azim[u] - 1];
+    if (!SECOND) {
+        double *E = ends + u * 4;
+        E[0] = e1 > b ? px[b] : 0.0; E[1] = e1 > b ? py[b] : 0.0;
+        E[2] = e1 > b ? qx[e1 - 1] : 0.0; E[3] = e1 > b ? qy[e1 - 1] : 0.0;
+    }
+    const double c = cs[u], sv = sn[u];
+    for (int64_t i = b; i < e1; ++i) {
+        const int32_t e = element[i] - 1;
+        if (e < 0 || e >= n_cells) continue;
+        const double l = ell[i], mx = 0.5 * (px[i] + qx[i]), my = 0.5 * (py[i] + qy[i]);
+        if (!SECOND) {
+            unsafeAtomicAdd(&acc[(int64_t)e * 3], w * l * mx);
+            unsafeAtomicAdd(&acc[(int64_t)e * 3 + 1], w * l * my);
+        } else {
+            const double xi = mx - cen[2 * (int64_t)e], eta = my - cen[2 * (int64_t)e + 1], l3 = l * l * l / 12.0;
+            unsafeAtomicAdd(&acc[(int64_t)e * 3], w * (l * xi * xi + c * c * l3));
+            unsafeAtomicAdd(&acc[(int64_t)e * 3 + 1], w * (l * xi * eta + c * sv * l3));
+            unsafeAtomicAdd(&acc[(int64_t)e * 3 + 2], w * (l * eta * eta + sv * sv * l3));
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_solver_ls_centroid(const double *__restrict__ acc, const double *__restrict__ vol, int32_t n_cells,
+                                                            double *__restrict__ cen) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_cells) return;
+    const double V = vol[e];
+    cen[2 * e] = V > 0.0 ? acc[3 * e] / V : 0.0;
+    cen[2 * e + 1] = V > 0.0 ? acc[3 * e + 1] / V : 0.0;
+}
+// C = acc / V [n_cells][3] (xx, xy, yy); cinv [n_cells][4]: C⁻¹ (xx, xy, yy) and 1.0 for a live cell — all 0 for a degenerate one
+// (V = 0 or det C <= 1e-10 (Cxx + Cyy)²), which is counted
+__global__ __launch_bounds__(256) void k_solver_ls_cmat(const double *__restrict__ acc, const double *__restrict__ vol, int32_t n_cells,
+                                                        double *__restrict__ cmat, double *__restrict__ cinv, int32_t *__restrict__ n_deg) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_cells) return;
+    const double V = vol[e];
+    const double xx = V > 0.0 ? acc[3 * e] / V : 0.0, xy = V > 0.0 ? acc[3 * e + 1] / V : 0.0, yy = V > 0.0 ? acc[3 * e + 2] / V : 0.0;
+    cmat[3 * e] = xx; cmat[3 * e + 1] = xy; cmat[3 * e + 2] = yy;
+    const double det = xx * yy - xy * xy, tr = xx + yy;
+    const bool ok = V > 0.0 && det > 1e-10 * tr * tr;
+    cinv[4 * e] = ok ? yy / det : 0.0; cinv[4 * e + 1] = ok ? -xy / det : 0.0; cinv[4 * e + 2] = ok ? xx / det : 0.0;
+    cinv[4 * e + 3] = ok ? 1.0 : 0.0;
+    if (!ok) atomicAdd(n_deg, 1);
+}
+
+// q⃗/Σt_g = C⁻¹ s⃗ / Σt_g of every (cell, group) (one thread each) into `gr` [n_cells][G][2], with
+// s⃗ = (1/4π) [Σ_g' Σs[g'→g] φ⃗_g' + (χ_g/k) Σ_g' νΣf_g' φ⃗_g'], and divided by Σ_c = Σt_g / sin θ_p into the sweep's ratios `xs1`
+// [n_cells][G·P][2].  The table from LDS when the host says it fits.
+__global__ __launch_bounds__(kSolveBlock) void k_solver_source_ls(const int32_t *__restrict__ mat, const double *__restrict__ tab_g, int32_t tab_len,
+                                                                  const double *__restrict__ mom, const double *__restrict__ cinv,
+                                                                  const double *__restrict__ pol, const double *__restrict__ scal, int32_t eigen,
+                                                                  int32_t n_cells, int32_t G, int32_t P, double *__restrict__ gr,
+                                                                  double *__restrict__ xs1) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char solver_smem[];
+    const double *tab = tab_g;
+    if (tab_len > 0) {
+        double *t = reinterpret_cast<double *>(solver_smem);
+        for (int i = threadIdx.x; i < tab_len; i += blockDim.x) t[i] = tab_g[i];
+        __syncthreads();
+        tab = t;
+    }
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n_cells * G) return;
+    const int64_t e = i / G;
+    const int32_t g = (int32_t)(i - e * G);
+    const double *X = mat_row(tab, mat[e], G);
+    const double *m = mom + e * G * 2;
+    double sx = 0.0, sy = 0.0, fx = 0.0, fy = 0.0;
+    for (int32_t gp = 0; gp < G; ++gp) {
+        const double s0 = X[3 * G + gp * G + g], nf = X[G + gp];
+        sx += s0 * m[2 * gp]; sy += s0 * m[2 * gp + 1];
+        fx += nf * m[2 * gp]; fy += nf * m[2 * gp + 1];
+    }
+    const double k = eigen ? scal[0] : 1.0;
+    sx = (sx + X[2 * G + g] * fx / k) / kFourPi;
+    sy = (sy + X[2 * G + g] * fy / k) / kFourPi;
+    const double *ci = cinv + e * 4;
+    const double st = X[g];
+    const double gx = (ci[0] * sx + ci[1] * sy) / st, gy = (ci[1] * sx + ci[2] * sy) / st;
+    gr[2 * i] = gx; gr[2 * i + 1] = gy;
+    double *x = xs1 + (e * G * P + (int64_t)g * P) * 2;
+    for (int32_t p = 0; p < P; ++p) { const double f = pol[p] / st; x[2 * p] = gx * f; x[2 * p + 1] = gy * f; }
+}
+
+// φ⃗ of every (cell, group) (one thread each) from the sweep's moment tallies `cur` [n_cells][G·P][2], which hold Σ_c (Tx, Ty):
+// φ⃗ = 4π C q⃗/Σt_g + Σ_p ω_p sin θ_p (Tx, Ty) / (Σt_g V); 0 in a degenerate cell
+__global__ __launch_bounds__(kSolveBlock) void k_solver_fold_ls(const int32_t *__restrict__ mat, const double *__restrict__ tab,
+                                                                const double *__restrict__ vol, const double *__restrict__ pol,
+                                                                const double *__restrict__ cur, const double *__restrict__ gr,
+                                                                const double *__restrict__ cmat, const double *__restrict__ cinv, int32_t n_cells,
+                                                                int32_t G, int32_t P, double *__restrict__ mom) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n_cells * G) return;
+    const int64_t e = i / G;
+    const int32_t g = (int32_t)(i - e * G);
+    if (cinv[4 * e + 3] == 0.0) { mom[2 * i] = 0.0; mom[2 * i + 1] = 0.0; return; }
+    const double V = vol[e];
+    const double st = mat_row(tab, mat[e], G)[g];
+    const double *c = cur + (e * G * P + (int64_t)g * P) * 2;
+    double ax = 0.0, ay = 0.0;
+    for (int32_t p = 0; p < P; ++p) {
+        const double f = pol[P + p] * (pol[p] / st);  // ω_p sin θ_p / Σ_c
+        ax += f * c[2 * p];
+        ay += f * c[2 * p + 1];
+    }
+    const double *Cm = cmat + 3 * e;
+    const double gx = gr[2 * i], gy = gr[2 * i + 1];
+    mom[2 * i] = kFourPi * (Cm[0] * gx + Cm[1] * gy) + ax / (st * V);
+    mom[2 * i + 1] = kFourPi * (Cm[1] * gx + Cm[2] * gy) + ay / (st * V);
+}
+
 // INIT: φ = 1, Σt_g / sin θ_p of every component; otherwise the fold of the last sweep's tallies T [n_cells][G·P].  Both: the
 // cell's production F_e = Σ_g νΣf φ into `prod` (the previous one is the residual's reference) and this block's partials.
 // One thread per cell.
@@ -230,6 +361,12 @@ struct rt_solver {
     std::vector<double> h_st, h_ss;  // Σt, Σs0 as given (the first moments are checked against them)
     DevBuf<double> tab1, J, q1r;     // table (see mat_row_p1); net current and q1/Σt [n_cells][G][2]
     bool p1 = false, ran_p1 = false;
+    // linear source (rt_solver_set_linear_source)
+    std::vector<double> h_wvol;              // 2 α δ per azimuthal index (the volumes' weights)
+    DevBuf<double> cen, cmat, cinv, ends;    // geometry: [n_cells][2], [n_cells][3], [n_cells][4] (see k_solver_ls_cmat), [n][4]
+    DevBuf<double> mom, gr;                  // flux moments φ⃗ and q⃗/Σt_g [n_cells][G][2]
+    bool ls = false, ran_ls = false, has_geom = false;
+    int32_t n_degenerate = 0;
     std::vector<double> k_hist;
     double *h_scal = nullptr;  // pinned, kSolveScalars
     hipEvent_t ev[2] = {nullptr, nullptr};
@@ -329,6 +466,7 @@ int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_m
         wvol[(size_t)a] = 2.0 * alpha[(size_t)a] * t->h_delta_s[(size_t)a];
     }
     DevBuf<double> dw4pi, dwvol;
+    S->h_wvol = wvol;
     if (int rc = upload(S->mat, cell_material, (size_t)nc, s)) return rc;
     if (int rc = upload(S->tab, tab.data(), tab.size(), s)) return rc;
     if (int rc = upload(S->pol, pol.data(), pol.size(), s)) return rc;
@@ -382,9 +520,11 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
     RT_HIP(t->sw_w.reserve(std::max<int64_t>(1, n)));
     if (n > 0) RT_HIP(hipMemcpyAsync(t->sw_w.p, S->w_track.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
     t->sw_groups = C; t->sw_has_xs = true; t->sw_has_w = true; t->sw_done = false;
-    struct RestoreWeights { rt_tracks *t; ~RestoreWeights() { t->sw_has_w = false; t->sw_p1 = false; } } restore{t};  // (the handle's own sweeps weigh by δs again, isotropically)
-    S->ran = false; S->ran_p1 = false;
-    const bool p1 = S->p1;
+    struct RestoreWeights { rt_tracks *t; ~RestoreWeights() { t->sw_has_w = false; t->sw_p1 = false; t->sw_ls = false; t->sw_ls_cen = t->sw_ls_ends = nullptr; } } restore{t};  // (the handle's own sweeps weigh by δs again, isotropically)
+    S->ran = false; S->ran_p1 = false; S->ran_ls = false;
+    const bool p1 = S->p1, ls = S->ls;
+    if (p1 && ls) { set_error("rt_solver_run: linear source together with first-moment scattering is not supported"); return RT_ERR_INVALID; }
+    if (ls && !S->has_geom) { set_error("rt_solver_run: the linear source has no geometry"); return RT_ERR_INVALID; }
     const int32_t tab1_len = S->M * G * (1 + G);
     const int32_t lds1_len = (size_t)tab1_len * sizeof(double) <= 32 * 1024 ? tab1_len : 0;
     if (p1) {  // J⁰ = 0; the sweep's first-moment arrays
@@ -393,6 +533,13 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
         RT_HIP(t->sw_xs1.reserve(2 * nxs)); RT_HIP(t->sw_cur.reserve(2 * nxs));
         RT_HIP(hipMemsetAsync(S->J.p, 0, nj * sizeof(double), s));
         t->sw_p1 = true;
+    }
+    if (ls) {  // φ⃗⁰ = 0; the sweep's gradient ratios and moment tallies (the buffers of the anisotropic mode)
+        const size_t nj = 2 * std::max<size_t>(1, (size_t)nc * G);
+        RT_HIP(S->mom.reserve(nj)); RT_HIP(S->gr.reserve(nj));
+        RT_HIP(t->sw_xs1.reserve(2 * nxs)); RT_HIP(t->sw_cur.reserve(2 * nxs));
+        RT_HIP(hipMemsetAsync(S->mom.p, 0, nj * sizeof(double), s));
+        t->sw_ls = true; t->sw_ls_cen = S->cen.p; t->sw_ls_ends = S->ends.p;
     }
     S->k_hist.clear();
     const unsigned cblocks = (unsigned)std::max(1, (nc + rt::kSolveBlock - 1) / rt::kSolveBlock);
@@ -419,6 +566,10 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
         if (p1)
             hipLaunchKernelGGL(rt::k_solver_source_p1, dim3(sblocks), dim3(rt::kSolveBlock), (size_t)lds1_len * sizeof(double), s, (const int32_t *)S->mat.p,
                                (const double *)S->tab1.p, lds1_len, (const double *)S->J.p, (const double *)S->pol.p, nc, G, P, S->q1r.p, t->sw_xs1.p);
+        if (ls)
+            hipLaunchKernelGGL(rt::k_solver_source_ls, dim3(sblocks), dim3(rt::kSolveBlock), (size_t)lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
+                               (const double *)S->tab.p, lds_len, (const double *)S->mom.p, (const double *)S->cinv.p, (const double *)S->pol.p,
+                               (const double *)S->scal.p, eig, nc, G, P, S->gr.p, t->sw_xs1.p);
         RT_HIP(hipGetLastError());
         if (int32_t rc = rt_sweep(t, C, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
         hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
@@ -427,6 +578,10 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
         if (p1)
             hipLaunchKernelGGL(rt::k_solver_fold_p1, dim3(sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab1.p,
                                (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->q1r.p, nc, G, P, S->J.p);
+        if (ls)
+            hipLaunchKernelGGL(rt::k_solver_fold_ls, dim3(sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
+                               (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->gr.p,
+                               (const double *)S->cmat.p, (const double *)S->cinv.p, nc, G, P, S->mom.p);
         hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)cblocks, 0, eig, S->scal.p);
         RT_HIP(hipMemcpyAsync(S->h_scal, S->scal.p, rt::kSolveScalars * sizeof(double), hipMemcpyDeviceToHost, s));
         RT_HIP(hipStreamSynchronize(s));
@@ -445,12 +600,14 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
         hipLaunchKernelGGL(rt::k_solver_scale, dim3(sblocks), dim3(256), 0, s, S->phi.p, ncg, (const double *)S->scal.p);
     if (eigen && nc > 0 && p1)
         hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * ncg + 255) / 256)), dim3(256), 0, s, S->J.p, 2 * ncg, (const double *)S->scal.p);
+    if (eigen && nc > 0 && ls)
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * ncg + 255) / 256)), dim3(256), 0, s, S->mom.p, 2 * ncg, (const double *)S->scal.p);
     RT_HIP(hipStreamSynchronize(s));
     RT_HIP(hipGetLastError());
     float f = 0.0f;
     RT_HIP(hipEventElapsedTime(&f, S->ev[0], S->ev[1]));
     t->in_flight = false;
-    S->ran = true; S->ran_p1 = p1;
+    S->ran = true; S->ran_p1 = p1; S->ran_ls = ls;
     if (res) {
         res->k_eff = eigen ? k : 1.0; res->residual = residual; res->dk = dk; res->device_ms = f;
         res->iterations = it; res->converged = converged ? 1 : 0;
@@ -498,6 +655,7 @@ int32_t rt_solver_set_source(rt_solver *solver, const double *source) {
 static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) {
     if (!S) { set_error("rt_solver_set_scatter_p1: null solver"); return RT_ERR_INVALID; }
     if (!sigma_s1) { S->p1 = false; return RT_SUCCESS; }
+    if (S->ls) { set_error("rt_solver_set_scatter_p1: the linear source is on, and the two together are not supported"); return RT_ERR_INVALID; }
     const int32_t G = S->G, M = S->M;
     const size_t n1 = (size_t)M * G * G;
     for (size_t i = 0; i < n1; ++i)
@@ -539,6 +697,108 @@ int32_t rt_solver_fetch_current(rt_solver *solver, double *J) {
     const size_t nj = (size_t)solver->n_cells * solver->G * 2;
     if (nj) RT_HIP(hipMemcpyAsync(J, solver->J.p, nj * sizeof(double), hipMemcpyDeviceToHost, s));
     RT_HIP(hipStreamSynchronize(s));
+    return RT_SUCCESS;
+}
+
+// the cells' geometry for the linear source, once per solver (records and α only)
+static int32_t solver_ls_geometry(rt_solver *S) {
+    rt_tracks *t = S->t;
+    if (!t->segmentized || t->seg_epoch != S->epoch) {
+        set_error("rt_solver_set_linear_source: the tracks were segmentized again after rt_solver_create: create a new solver");
+        return RT_ERR_INVALID;
+    }
+    if (int rc = finish_call(t)) return rc;
+    RT_HIP(hipSetDevice(t->mesh->device));
+    hipStream_t s = t->mesh->stream;
+    if (int rc = ensure_compacted(t)) return rc;
+    const int32_t nc = S->n_cells;
+    const int64_t n = t->n;
+    const size_t ncs = (size_t)std::max<int32_t>(1, nc);
+    DevBuf<double> dwvol, acc;
+    DevBuf<int32_t> ndeg;
+    if (int rc = upload(dwvol, S->h_wvol.data(), S->h_wvol.size(), s)) return rc;
+    RT_HIP(acc.reserve(3 * ncs)); RT_HIP(ndeg.reserve(1));
+    RT_HIP(S->cen.reserve(2 * ncs)); RT_HIP(S->cmat.reserve(3 * ncs)); RT_HIP(S->cinv.reserve(4 * ncs));
+    RT_HIP(S->ends.reserve((size_t)std::max<int64_t>(1, 4 * n)));
+    RT_HIP(hipMemsetAsync(ndeg.p, 0, sizeof(int32_t), s));
+    const unsigned tb = (unsigned)std::max<int64_t>(1, (n + 255) / 256), cb = (unsigned)((ncs + 255) / 256);
+    auto moments = [&]<bool SECOND>() {
+        hipLaunchKernelGGL(rt::k_solver_ls_moments<SECOND>, dim3(tb), dim3(256), 0, s, (const int64_t *)t->offsets.p, (const int32_t *)t->counts.p, n,
+                           (const int32_t *)t->azim.p, (const double *)dwvol.p, (const double *)t->cs.p, (const double *)t->sn.p, (const int32_t *)t->element.p,
+                           (const double *)t->spx.p, (const double *)t->spy.p, (const double *)t->sqx.p, (const double *)t->sqy.p,
+                           (const double *)t->sell.p, (const double *)S->cen.p, nc, acc.p, S->ends.p);
+    };
+    RT_HIP(hipMemsetAsync(acc.p, 0, 3 * ncs * sizeof(double), s));
+    if (n > 0) moments.template operator()<false>();
+    hipLaunchKernelGGL(rt::k_solver_ls_centroid, dim3(cb), dim3(256), 0, s, (const double *)acc.p, (const double *)S->vol.p, nc, S->cen.p);
+    RT_HIP(hipMemsetAsync(acc.p, 0, 3 * ncs * sizeof(double), s));
+    if (n > 0) moments.template operator()<true>();
+    hipLaunchKernelGGL(rt::k_solver_ls_cmat, dim3(cb), dim3(256), 0, s, (const double *)acc.p, (const double *)S->vol.p, nc, S->cmat.p, S->cinv.p, ndeg.p);
+    int32_t h = 0;
+    RT_HIP(hipMemcpyAsync(&h, ndeg.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));  // (the temporary buffers die here)
+    RT_HIP(hipGetLastError());
+    S->n_degenerate = h;
+    S->has_geom = true;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
+    if (!solver) { set_error("rt_solver_set_linear_source: null solver"); return RT_ERR_INVALID; }
+    if (!on) { solver->ls = false; return RT_SUCCESS; }
+    if (solver->p1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
+    try {
+        if (!solver->has_geom)
+            if (int32_t rc = solver_ls_geometry(solver)) return rc;
+    } catch (const std::exception &e) {
+        set_error("rt_solver_set_linear_source: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+    solver->ls = true;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_fetch_geometry(rt_solver *solver, double *centroid, double *cmat, int32_t *n_degenerate) {
+    if (!solver) { set_error("rt_solver_fetch_geometry: null solver"); return RT_ERR_INVALID; }
+    if (!solver->has_geom) { set_error("rt_solver_fetch_geometry: the linear source has never been switched on (rt_solver_set_linear_source)"); return RT_ERR_INVALID; }
+    RT_HIP(hipSetDevice(solver->t->mesh->device));
+    hipStream_t s = solver->t->mesh->stream;
+    const size_t nc = (size_t)solver->n_cells;
+    if (centroid && nc) RT_HIP(hipMemcpyAsync(centroid, solver->cen.p, 2 * nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (cmat && nc) RT_HIP(hipMemcpyAsync(cmat, solver->cmat.p, 3 * nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    if (n_degenerate) *n_degenerate = solver->n_degenerate;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_fetch_moments(rt_solver *solver, double *phi_xy, double *grad) {
+    if (!solver) { set_error("rt_solver_fetch_moments: null solver"); return RT_ERR_INVALID; }
+    if (!solver->ran || !solver->ran_ls) {
+        set_error("rt_solver_fetch_moments: no completed rt_solver_run with the linear source (rt_solver_set_linear_source)");
+        return RT_ERR_INVALID;
+    }
+    try {
+        RT_HIP(hipSetDevice(solver->t->mesh->device));
+        hipStream_t s = solver->t->mesh->stream;
+        const size_t nc = (size_t)solver->n_cells, G = (size_t)solver->G, nj = nc * G * 2;
+        std::vector<double> m(nj), ci(4 * nc);
+        if (nj) {
+            RT_HIP(hipMemcpyAsync(m.data(), solver->mom.p, nj * sizeof(double), hipMemcpyDeviceToHost, s));
+            RT_HIP(hipMemcpyAsync(ci.data(), solver->cinv.p, 4 * nc * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        RT_HIP(hipStreamSynchronize(s));
+        if (phi_xy && nj) std::memcpy(phi_xy, m.data(), nj * sizeof(double));
+        if (grad)
+            for (size_t e = 0; e < nc; ++e)
+                for (size_t g = 0; g < G; ++g) {
+                    const double mx = m[(e * G + g) * 2], my = m[(e * G + g) * 2 + 1];
+                    grad[(e * G + g) * 2] = ci[4 * e] * mx + ci[4 * e + 1] * my;
+                    grad[(e * G + g) * 2 + 1] = ci[4 * e + 1] * mx + ci[4 * e + 2] * my;
+                }
+    } catch (const std::exception &e) {
+        set_error("rt_solver_fetch_moments: %s", e.what());
+        return RT_ERR_INVALID;
+    }
     return RT_SUCCESS;
 }
 

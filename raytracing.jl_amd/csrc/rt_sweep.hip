@@ -28,11 +28,26 @@ namespace rt {
 // and every component tallies three values: w Δψ as before (-> phi) and w d cs Δψ, w d sn Δψ (-> cur).  NT tallies per
 // component: the lane-fold and the LDS copy treat them as NT · GP independent values (wd[g], wd[GP + 2g], wd[GP + 2g + 1]).
 // The isotropic instantiations (P1 = false) compile to what they were.
-template <bool STAGED, int GP, bool LDS, bool ELLROWS, bool P1 = false>
-__global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
+// LS (linear source, rt_solver_set_linear_source; include/rt_segmentize.h states the formulas): a further flag of this kernel and not
+// a sibling, because everything but the body of `segment` is shared — the row pipeline of the three row variants, the lane fold, the
+// LDS copy with three tallies per component and its flush — and the P1 mode had already made the number of tallies and of per-cell
+// ratios a compile-time quantity.  The lane keeps the traversal's entry point and the running sum s of ℓ, so the midpoint of a
+// segment is entry + d (cs, sn)(s + ℓ/2) — the rows hold no coordinates once they are (ℓ, cell) rows — and loads the cell's
+// centroid (16 B per row, with the cross sections, one stage ahead).  The per-component ratios (gx, gy) = DSweep::xs1 are
+// q⃗ / (Σt_g Σ_c), i.e. already divided by Σ_c, and the moment tallies are accumulated TIMES Σ_c (the fold divides): with
+// u = ξ gx + η gy, ρ' = d (cs gx + sn gy) = ρ/Σ_c, r_m = q/Σt + Σ_c u,
+//     Δψ = (ψ − r_m) F1 − ρ' F2/2,   K = ψ − r_m + ρ' (τ/2 + 1),   H' = K F2/2 = Σ_c H,   Σ_c Tx += w (ξ Σ_c Δψ − d cs H')
+// — no reciprocal of Σ_c in the loop and no third per-component load.  F1 and e^{−τ} come from one evaluation
+// (one_minus_exp_neg_both), F2 from ls_f2 / ls_f2_thin (rt_device.hpp).
+// LS instantiations are bounded to eight waves per workgroup: with the series' coefficients and the lane's geometry they need up to
+// ~190 VGPRs, and under the sixteen-wave bound (128 VGPRs) they spilled to scratch.
+template <bool STAGED, int GP, bool LDS, bool ELLROWS, bool P1 = false, bool LS = false>
+__global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep(DSweep a) {
     static_assert(STAGED || !ELLROWS, "ℓ rows belong to the staging rows");
-    constexpr int NT = P1 ? 3 : 1;       // tallies per component
-    constexpr int NH = P1 ? 2 * GP : 1;  // first-moment ratios of a pass (one unused slot when isotropic)
+    static_assert(!(P1 && LS), "linear source with first-moment scattering is not built");
+    constexpr bool AN = P1 || LS;        // three tallies and two ratios per component
+    constexpr int NT = AN ? 3 : 1;       // tallies per component
+    constexpr int NH = LS ? 2 * GP + 2 : (P1 ? 2 * GP : 1);  // ratios of a pass (one unused slot when isotropic); LS: + the cell's centroid
     extern __shared__ __attribute__((aligned(16))) unsigned char sweep_smem[];
     double *hist = reinterpret_cast<double *>(sweep_smem);  // [n_cells * NT * GP] when LDS
     const int lane = threadIdx.x & 63;
@@ -62,10 +77,15 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
         const double w = !have ? 0.0 : (a.w ? a.w[u] : a.delta_s[a.azim[u] - 1]);
         // P1: the traversal's direction cosines d (cos ϕ, sin ϕ) and the weight times them (0 for a lane without a track)
         double dcs = 0.0, dsn = 0.0, wcs = 0.0, wsn = 0.0;
-        if constexpr (P1) {
+        if constexpr (AN) {
             const double c0 = have ? a.cs[u] : 0.0, s0 = have ? a.sn[u] : 0.0;
             dcs = dir ? -c0 : c0; dsn = dir ? -s0 : s0;
             wcs = w * dcs; wsn = w * dsn;
+        }
+        // LS: the traversal's entry point (first record's p forward, last record's q backward) and the path length behind the lane
+        double ex = 0.0, ey = 0.0, srun = 0.0;
+        if constexpr (LS) {
+            if (have) { ex = a.ends[(int64_t)u * 4 + 2 * dir]; ey = a.ends[(int64_t)u * 4 + 2 * dir + 1]; }
         }
         const int64_t off = (!STAGED && have) ? a.offsets[u] : 0;
         const int64_t pbase = ((int64_t)dir * a.n + u) * a.G + a.g0;
@@ -88,7 +108,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                 const int gi = g < ng ? g : ng - 1;
                 st[g] = x[2 * gi]; qs[g] = x[2 * gi + 1];
             }
-            if constexpr (P1) {
+            if constexpr (AN) {
                 const RT_G double *x1 = a.xs1 + ((int64_t)e * a.G + a.g0) * 2;
 #pragma unroll
                 for (int g = 0; g < GP; ++g) {
@@ -96,6 +116,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                     h[2 * g] = x1[2 * gi]; h[2 * g + 1] = x1[2 * gi + 1];
                 }
             }
+            if constexpr (LS) { h[2 * GP] = a.cen[(int64_t)e * 2]; h[2 * GP + 1] = a.cen[(int64_t)e * 2 + 1]; }
         };
         ExpPoly poly = exp_poly();  // (in vector registers: see one_minus_exp_neg)
 #pragma unroll
@@ -107,19 +128,52 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
             const double ell = act ? ell_row : 0.0;
             double wd[NT * GP], tau[GP], qs[GP];
             bool thin = true;
+            // LS: the midpoint relative to the cell's centroid; s moves on by ℓ (0 for a lane beyond its track's end)
+            double xi = 0.0, eta = 0.0;
+            if constexpr (LS) {
+                const double sm = __builtin_fma(0.5, ell, srun);
+                xi = __builtin_fma(dcs, sm, ex - h[2 * GP]);
+                eta = __builtin_fma(dsn, sm, ey - h[2 * GP + 1]);
+                srun += ell;
+            }
 #pragma unroll
             for (int g = 0; g < GP; ++g) {
                 tau[g] = st[g] * ell;
                 thin = thin && tau[g] < kThinTau;
                 if constexpr (P1) qs[g] = __builtin_fma(dsn, h[2 * g + 1], __builtin_fma(dcs, h[2 * g], qs0[g]));
+                else if constexpr (LS) qs[g] = __builtin_fma(st[g], __builtin_fma(eta, h[2 * g + 1], xi * h[2 * g]), qs0[g]);  // r_m
                 else qs[g] = qs0[g];
             }
+            // LS: one component from F1 = 1 − e^{−τ} and hF2 = F2/2 (see the head of the kernel)
+            [[maybe_unused]] auto ls_component = [&](const int g, const double F1, const double hF2) {
+                const double rho = __builtin_fma(dsn, h[2 * g + 1], dcs * h[2 * g]);  // ρ / Σ_c
+                const double am = psi[g] - qs[g];
+                const double d = __builtin_fma(am, F1, -(rho * hF2));
+                const double Hs = __builtin_fma(rho, __builtin_fma(0.5, tau[g], 1.0), am) * hF2;  // Σ_c H
+                psi[g] = psi[g] - d;
+                wd[g] = w * d;
+                const double ws = wd[g] * st[g];
+                wd[GP + 2 * g] = __builtin_fma(xi, ws, -(wcs * Hs));
+                wd[GP + 2 * g + 1] = __builtin_fma(eta, ws, -(wsn * Hs));
+            };
             // −expm1(−τ) to within an ulp (rt_device.hpp): where every lane's segment is optically thin in every group of the pass —
             // a wave-uniform branch — by the series alone (10 instructions per group instead of 24)
             // (The choice is per WAVE-row: a segment takes the series when the other 63 lanes' segments are thin too, else the general
             //  form — the two agree to 2 ulp, so ψ_out is NOT bitwise invariant across march orders, sort modes or shardings of the
             //  same problem; the tests compare at 1e-12.  "sweep_debug" 4 = the general form everywhere: the reproducible mode.)
-            if (__ballot(!thin) == 0 && !(a.debug & 4)) {
+            if constexpr (LS) {
+                if (__ballot(!thin) == 0 && !(a.debug & 4)) {
+#pragma unroll
+                    for (int g = 0; g < GP; ++g) ls_component(g, one_minus_exp_neg_thin(tau[g], poly), 0.5 * ls_f2_thin(tau[g]));
+                } else {
+#pragma unroll
+                    for (int g = 0; g < GP; ++g) {
+                        double E;
+                        const double F1 = one_minus_exp_neg_both(tau[g], E, poly);
+                        ls_component(g, F1, 0.5 * ls_f2(tau[g], E));
+                    }
+                }
+            } else if (__ballot(!thin) == 0 && !(a.debug & 4)) {
 #pragma unroll
                 for (int g = 0; g < GP; ++g) {
                     const double d = (psi[g] - qs[g]) * one_minus_exp_neg_thin(tau[g], poly);
@@ -171,7 +225,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                     if (g < ng) {  // (uniform)
                         if (LDS) atomicAdd(&hist[e * (NT * GP) + g], wd[g]);
                         else unsafeAtomicAdd((double *)&a.phi[(int64_t)e * a.G + a.g0 + g], wd[g]);
-                        if constexpr (P1) {
+                        if constexpr (AN) {
                             if (LDS) {
                                 atomicAdd(&hist[e * (NT * GP) + GP + 2 * g], wd[GP + 2 * g]);
                                 atomicAdd(&hist[e * (NT * GP) + GP + 2 * g + 1], wd[GP + 2 * g + 1]);
@@ -252,7 +306,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                         step(t + 2, R2, R0, R1, stA, qsA, hA, stB, qsB, hB);
 #pragma unroll
                         for (int g = 0; g < GP; ++g) { stA[g] = stB[g]; qsA[g] = qsB[g]; }
-                        if constexpr (P1)
+                        if constexpr (AN)
 #pragma unroll
                             for (int g = 0; g < NH; ++g) hA[g] = hB[g];
                     }
@@ -280,7 +334,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                         lstep(t + 2, L2, L0, L1, stA, qsA, hA, stB, qsB, hB);
 #pragma unroll
                         for (int g = 0; g < GP; ++g) { stA[g] = stB[g]; qsA[g] = qsB[g]; }
-                        if constexpr (P1)
+                        if constexpr (AN)
 #pragma unroll
                             for (int g = 0; g < NH; ++g) hA[g] = hB[g];
                     }
@@ -305,7 +359,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
                     R0 = R1; R1 = R2;
 #pragma unroll
                     for (int g = 0; g < GP; ++g) { st0[g] = st1[g]; qs0[g] = qs1[g]; }
-                    if constexpr (P1)
+                    if constexpr (AN)
 #pragma unroll
                         for (int g = 0; g < NH; ++g) h0[g] = h1[g];
                 }
@@ -321,7 +375,7 @@ __global__ __launch_bounds__(1024) void k_sweep(DSweep a) {
         for (int c = threadIdx.x; c < a.n_cells * (NT * GP); c += blockDim.x) {
             const double v = hist[c];
             const int cell = c / (NT * GP), i = c - cell * (NT * GP);
-            if (!P1 || i < GP) {
+            if (!AN || i < GP) {
                 if (v != 0.0 && i < a.ng) unsafeAtomicAdd((double *)&a.phi[(int64_t)cell * a.G + a.g0 + i], v);
             } else {
                 const int g = (i - GP) >> 1;
@@ -550,8 +604,15 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     a.psi_in = as_global((const double *)t->sw_psi_in.p); a.psi_out = as_global(t->sw_psi_out.p); a.phi = as_global(t->sw_phi.p);
     a.n = n; a.n_waves = (int32_t)((n + 63) / 64); a.n_cells = m->n_cells; a.G = G; a.debug = m->sweep_debug;
     // the anisotropic mode (an rt_solver with first-moment scattering has filled sw_xs1 for these G components)
-    const bool p1 = t->sw_p1;
-    const int nt = p1 ? 3 : 1;  // tallies per component
+    const bool p1 = t->sw_p1, ls = t->sw_ls;
+    const int nt = (p1 || ls) ? 3 : 1;  // tallies per component
+    if (p1 && ls) { set_error("rt_sweep: linear source together with first-moment scattering"); return RT_ERR_INVALID; }
+    if (ls) {  // the linear-source mode (an rt_solver with rt_solver_set_linear_source has filled sw_xs1 with the gradient ratios)
+        if (!t->sw_xs1.p || !t->sw_cur.p || !t->sw_ls_cen || !t->sw_ls_ends) { set_error("rt_sweep: the linear-source mode has no geometry arrays"); return RT_ERR_INVALID; }
+        a.xs1 = as_global((const double *)t->sw_xs1.p); a.cur = as_global(t->sw_cur.p);
+        a.cs = as_global((const double *)t->cs.p); a.sn = as_global((const double *)t->sn.p);
+        a.cen = as_global(t->sw_ls_cen); a.ends = as_global(t->sw_ls_ends);
+    }
     if (p1) {
         if (!t->sw_xs1.p || !t->sw_cur.p) { set_error("rt_sweep: the anisotropic mode has no first-moment arrays"); return RT_ERR_INVALID; }
         a.xs1 = as_global((const double *)t->sw_xs1.p); a.cur = as_global(t->sw_cur.p);
@@ -563,7 +624,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     // Anisotropic: three tallies per component, so a mesh that fits 4 components fits 1; at most kSweepGpP1 per pass (the kernel
     // carries two more ratios per pipeline stage and two more deltas per component: see DESIGN.md for the registers).
     const size_t lds_cap = (size_t)std::min(m->lds_per_block, 160 * 1024) - 1024;
-    const int gp_max = p1 ? rt::kSweepGpP1 : 4;
+    const int gp_max = (p1 || ls) ? rt::kSweepGpP1 : 4;  // (linear source: the same three tallies per component, the same limit)
     int gp = std::min(G, gp_max);
     if (m->sweep_gp >= 1 && m->sweep_gp <= 4) gp = std::min(gp, m->sweep_gp);
     while (gp > 1 && (size_t)m->n_cells * gp * nt * sizeof(double) > lds_cap) --gp;
@@ -572,7 +633,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     if (m->sweep_gp >= 8) a.use_lds = 0;  // experiment: tallies straight to HBM (measured 4x slower at C3: 2.1 ms against 0.48)
     if (!async_sweep) RT_HIP(hipEventRecord(t->ev[0], s));
     RT_HIP(hipMemsetAsync(t->sw_phi.p, 0, nphi * sizeof(double), s));
-    if (p1 && nphi) RT_HIP(hipMemsetAsync(t->sw_cur.p, 0, 2 * nphi * sizeof(double), s));
+    if ((p1 || ls) && nphi) RT_HIP(hipMemsetAsync(t->sw_cur.p, 0, 2 * nphi * sizeof(double), s));
     int passes = 0;
     // Staged rows: the first pass after an rt_segmentize derives ℓ from the exit points and leaves it in `sw_ell`, slot-indexed
     // like the rows; every later pass — of this sweep and of all following sweeps over the same segmentation — reads (ℓ, cell)
@@ -594,8 +655,8 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         else (void)hipGetLastError();  // (no memory for it: every pass derives ℓ itself)
     }
     a.ell_rows = ell_rows ? as_global(t->sw_ell.p) : nullptr;
-    auto launch = [&]<bool STAGED, int GP, bool LDS, bool P1>(int g0) -> int {
-        size_t smem = a.use_lds ? (size_t)m->n_cells * GP * (P1 ? 3 : 1) * sizeof(double) : 0;
+    auto launch = [&]<bool STAGED, int GP, bool LDS, bool P1, bool LS = false>(int g0) -> int {
+        size_t smem = a.use_lds ? (size_t)m->n_cells * GP * ((P1 || LS) ? 3 : 1) * sizeof(double) : 0;
         // (compact records: more than one eight-wave workgroup per CU thrashes its L1 — a pass of few groups asks for LDS it
         //  does not use, so that it still gets a CU to itself: 5 groups = 4 + 1 took 0.88 ms against 0.58 for 7 = 4 + 3)
         if (!STAGED && a.use_lds) smem = std::max(smem, std::min(lds_cap, (size_t)81 * 1024));
@@ -604,18 +665,19 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         // thrash the CU's L1 — 1.04 against 0.62 ms at C3); two or more workgroups per CU: eight waves each
         int W = (smem > 79 * 1024 && STAGED) ? 16 : 8;
         if (m->sweep_waves == 4 || m->sweep_waves == 8 || m->sweep_waves == 16) W = m->sweep_waves;
+        if (LS && W > 8) W = 8;  // (the linear-source kernels are compiled for eight waves at most)
         const unsigned blocks = (unsigned)((2 * (int64_t)a.n_waves + W - 1) / W);
         a.g0 = g0; a.ng = GP;
         if (STAGED && ell_rows && (t->sw_ell_valid || rows_compact)) {
             if constexpr (STAGED) {
                 if (smem > 48 * 1024)
-                    RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<true, GP, LDS, true, P1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                hipLaunchKernelGGL((rt::k_sweep<true, GP, LDS, true, P1>), dim3(blocks), dim3(64 * W), smem, s, a);
+                    RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<true, GP, LDS, true, P1, LS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+                hipLaunchKernelGGL((rt::k_sweep<true, GP, LDS, true, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
             }
         } else {
             if (smem > 48 * 1024)
-                RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<STAGED, GP, LDS, false, P1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            hipLaunchKernelGGL((rt::k_sweep<STAGED, GP, LDS, false, P1>), dim3(blocks), dim3(64 * W), smem, s, a);
+                RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<STAGED, GP, LDS, false, P1, LS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            hipLaunchKernelGGL((rt::k_sweep<STAGED, GP, LDS, false, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
             if (STAGED && ell_rows) { t->sw_ell_valid = true; t->sw_rowsc_valid = false; }  // (the forward waves of this pass have written every row's ℓ)
         }
         ++passes;
@@ -625,7 +687,10 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         for (int g0 = 0; g0 < G;) {
             const int take = std::min(gp, G - g0);
             int rc;
-            if (p1) {
+            if (ls) {
+                if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, false, true>(g0);
+                else rc = launch.template operator()<STAGED, 1, LDS, false, true>(g0);
+            } else if (p1) {
                 static_assert(rt::kSweepGpP1 == 2, "the anisotropic passes below");
                 if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, true>(g0);
                 else rc = launch.template operator()<STAGED, 1, LDS, true>(g0);

@@ -8,7 +8,8 @@ a fold kernel and a fixed-order reduction; only k, the residual and |Δk|/k come
 The definitions (azimuthal and polar weights, volumes, fold, source, residual, normalisation) are stated
 in ``include/rt_segmentize.h``.  With ``CrossSections(..., sigma_s1=...)`` scattering is linearly anisotropic (P1): the
 sweep's source depends on the direction of travel, first angular moments are tallied and ``SolverResult.current`` is the
-net current.
+net current.  With ``scheme="linear"`` the source of a cell is linear in space (LS-MOC: a coarser mesh resolves the same flux
+gradient); ``SolverResult.flux_moments``, ``flux_gradient`` and ``centroids`` describe the flux inside the cells.
 """
 from __future__ import annotations
 
@@ -159,6 +160,9 @@ class SolverResult:
     residual: float
     solver: object = None         # the device solver (rt_solver handle), for a further run
     current: Optional[np.ndarray] = None  # net current (Jx, Jy) [n_cells, G, 2] with sigma_s1; None when isotropic
+    flux_moments: Optional[np.ndarray] = None   # scheme="linear": (φx, φy) [n_cells, G, 2], the moments of φ about the centroid
+    flux_gradient: Optional[np.ndarray] = None  # ... C⁻¹ φ⃗ [n_cells, G, 2]: φ(r) ≈ phi + flux_gradient·(r − centroid)
+    centroids: Optional[np.ndarray] = None      # ... track-based cell centroids [n_cells, 2]; all three None when flat
 
 
 def _cell_material(tg, cell_material):
@@ -188,9 +192,14 @@ def _device_tracks(tg, device):
     return dt
 
 
-def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device):
+def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat"):
     if not isinstance(xs, CrossSections):
         raise TypeError("xs must be a CrossSections")
+    if scheme not in ("flat", "linear"):
+        raise ValueError(f"unknown scheme {scheme!r} (flat or linear)")
+    linear = scheme == "linear"
+    if linear and xs.sigma_s1 is not None:
+        raise ValueError('scheme="linear" together with sigma_s1 (P1 scattering) is not supported')
     pq = PolarQuadrature(polar)
     alpha = azimuthal_weights(tg, azim_weights)
     dt = _device_tracks(tg, device)
@@ -200,30 +209,36 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         sv.set_source(source)
     if xs.sigma_s1 is not None:
         sv.set_scatter_p1(xs.sigma_s1)
+    if linear:
+        sv.set_linear_source(True)
     r = sv.run(mode, int(max_iter), float(tol_k), float(tol_flux))
     f = sv.fetch(r["iterations"])
+    mom = sv.fetch_moments() if linear else dict(flux_moments=None, flux_gradient=None)
+    centroids = sv.fetch_geometry()["centroids"] if linear else None
     current = sv.fetch_current() if xs.sigma_s1 is not None else None
     it = r["iterations"]
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
-                        ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current)
+                        ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
+                        flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids)
 
 
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
-                     tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0) -> SolverResult:
+                     tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat") -> SolverResult:
     """Power iteration for k_eff on the device.  ``cell_material``: material index per cell [n_cells] (or one index for all,
     or a dict region name -> index over ``tg.mesh.model.cell_region``).  ``polar``: a ``PolarQuadrature`` spec;
     ``azim_weights``: "exact", "equal" or an array.  Uses ``tg.device_tracks`` when ``segmentize(tg, fetch=False)`` has run,
-    else segmentizes first; the boundary conditions are the ones ``trace`` linked."""
-    return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device)
+    else segmentizes first; the boundary conditions are the ones ``trace`` linked.  ``scheme``: "flat" (a constant source per cell)
+    or "linear" (a source linear in space per cell; not together with ``sigma_s1``)."""
+    return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme)
 
 
 def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
-                       tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0) -> SolverResult:
+                       tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat") -> SolverResult:
     """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
     the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``."""
     q = np.asarray(source, np.float64)
     G = xs.n_groups
     if q.ndim == 0 or q.shape == (G,):
         q = np.broadcast_to(q, (tg.mesh.num_cells, G))
-    return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device)
+    return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme)

@@ -1,5 +1,5 @@
 """Timing of the device MOC solver (rt_solver) at the headline configuration: pincell, nφ = 128, δ = 1e-3, 7 groups, TY3
-(`--p1`: with linearly anisotropic scattering, Σs1 = 0.3 Σs0).
+(`--p1`: with linearly anisotropic scattering, Σs1 = 0.3 Σs0; `--linear`: with the linear source).
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
@@ -50,6 +50,7 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--p1", action="store_true", help="linearly anisotropic scattering: a synthetic Σs1 = 0.3 Σs0 (rt_solver_set_scatter_p1)")
+    ap.add_argument("--linear", action="store_true", help="the linear source (rt_solver_set_linear_source); not together with --p1")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
 
@@ -72,6 +73,8 @@ def main():
                             rt.exact_azimuthal_weights(tg.azimuthal_quadrature))
     if a.p1:
         sv.set_scatter_p1(0.3 * xs.sigma_s)
+    if a.linear:
+        sv.set_linear_source(True)
     sv.run(0, 3, 0.0, 0.0)  # warm-up (first launches, LDS attributes, the sweep's ℓ rows)
     ev_ms, host_ms, ks = [], [], []
     for _ in range(a.repeats):
@@ -81,9 +84,11 @@ def main():
         ev_ms.append(r["device_ms"] / r["iterations"])
         ks.append(r["k_eff"])
     out = dict(config=dict(mesh=a.mesh, n_azim=a.n_azim, delta=a.delta, groups=a.groups, polar=a.polar, components=a.groups * pq.n_polar,
-                           p1=bool(a.p1), tracks=int(tg.n_total_tracks), records=int(dt.total), cells=int(tg.mesh.num_cells), iters=a.iters),
+                           p1=bool(a.p1), linear=bool(a.linear), tracks=int(tg.n_total_tracks), records=int(dt.total), cells=int(tg.mesh.num_cells), iters=a.iters),
                ms_per_iter_events=float(np.median(ev_ms)), ms_per_iter_host=float(np.median(host_ms)), k_eff=ks[-1])
-    if not a.no_sweep_probe and not a.p1:  # (the handle's own rt_sweep is the isotropic one)
+    if a.linear:
+        out["n_degenerate"] = sv.fetch_geometry()["n_degenerate"]
+    if not a.no_sweep_probe and not a.p1 and not a.linear:  # (the handle's own rt_sweep is the isotropic one)
         # the same sweep the solver runs: G·P components, the handle's cross sections and boundary fluxes as the solver left them
         C = a.groups * pq.n_polar
         sw = []
