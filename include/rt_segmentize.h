@@ -512,6 +512,35 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
  * RT_ERR_INVALID.  A solver must not be used after its tracks are destroyed (rt_solver_destroy is still safe).
+ *
+ * Stepwise iteration and sharded runs.  rt_solver_run is a loop over four calls that a caller may make itself:
+ *     rt_solver_begin (φ⁰ = 1, F⁰, zero boundary fluxes; the solver takes the handle's sweep state)
+ *     { rt_solver_step_sweep (source update + one sweep, queued);  rt_solver_step_fold (fold, k, residual) } as often as wanted
+ *     rt_solver_end (normalisation, device_ms from begin to end; the handle gets its sweep state back, the fetches work)
+ * — to continue a run, to watch it, to stop it by a rule of its own, or to put work between the sweep and the fold.
+ * State machine: step_sweep, step_fold and end need an open run (a begin without its end); step_sweep and step_fold
+ *              alternate, sweep first; end may follow a begin or a step_fold directly, and also an unfolded sweep (whose tallies
+ *              are then dropped).  Every other order returns RT_ERR_INVALID with a message that names the entry point and changes
+ *              nothing.  A second begin starts afresh; a begin (or rt_solver_run) of ANOTHER solver on the same tracks ends
+ *              this solver's run, as do rt_solver_destroy and rt_tracks_destroy: in every case the handle's sweep state is
+ *              handed back.  rt_segmentize of the tracks ends the run too, at once (the handle's own sweeps weigh by δs again
+ *              whether or not the solver is called once more), and every later call of the stale solver returns the
+ *              "segmentized again" error.  A step that fails for another reason (a non-finite k) ends the run as well.
+ *              While a run is open, the handle's own rt_sweep with explicit cross sections, weights or another group count
+ *              is the caller's error: it overwrites what the solver iterates on, and is not detected.
+ * Pointers     rt_solver_pointers returns device addresses that the fold reads where they lie.  Between step_sweep and
+ *              step_fold a caller may ADD to the scalar tally T [n_cells][G·P] and to the first-moment tallies
+ *              [n_cells][G·P][2] (Tx, Ty; only with first-moment scattering or the linear source); between
+ *              rt_solver_create and rt_solver_begin it may OVERWRITE volumes [n_cells].  Nothing the flat and the
+ *              first-moment iteration use is derived from the volumes ahead of time: V_e is read by the fold of every
+ *              iteration (and by begin for F⁰).  All such writes must be ordered against rt_mesh_get_stream: after the
+ *              library's queued work (rt_wait, or an event on that stream) and finished before the next call.
+ * Sharded      a solver on a uid shard of the tracks (links restricted to the shard, the GLOBAL α) computes partial volumes
+ *              and partial tallies: sum the volumes over the shards once, before begin; per iteration, between step_sweep and
+ *              step_fold, hand the boundary fluxes that leave the shard to their owners (rt_sweep_info: psi_out, psi_in) and
+ *              sum T (and Tx, Ty) over the shards.  Every shard then folds the same whole-mesh arrays and gets the same k
+ *              and residual.  The linear source is excluded: its geometry (centroids, C) is a sum over tracks taken when
+ *              the option is switched on, from this handle's tracks alone, and would need its own reduction.
  * --------------------------------------------------------------------------------------- */
 typedef struct rt_solver rt_solver;
 
@@ -559,6 +588,22 @@ int32_t rt_solver_fetch_geometry(rt_solver *solver, double *centroid, double *cm
  * (for plots, or to reconstruct the flux at r as φ + grad·(r − r_c)); either may be NULL.  RT_ERR_INVALID before a run, or when
  * that run had a flat source. */
 int32_t rt_solver_fetch_moments(rt_solver *solver, double *phi_xy, double *grad);
+/* The iteration in steps (see "Stepwise iteration and sharded runs" above).  rt_solver_begin: everything rt_solver_run does
+ * before its first iteration, for `mode`.  rt_solver_step_sweep: queues the source update and one rt_sweep and returns (it waits
+ * no longer than rt_sweep does: not at all under the mesh option "async").  rt_solver_step_fold: fold and reductions; waits, then
+ * fills out (may be NULL) with k_eff, residual, dk and iterations so far — converged stays 0 (stopping is the caller's decision)
+ * and device_ms 0; RT_ERR_INVALID on a non-finite k or residual.  rt_solver_end: normalisation; fills out (may be NULL) with
+ * the last k_eff, residual, dk, the iterations and device_ms (begin to end, whatever the caller did in between included);
+ * afterwards rt_solver_fetch* behave as after rt_solver_run. */
+int32_t rt_solver_begin(rt_solver *solver, int32_t mode);
+int32_t rt_solver_step_sweep(rt_solver *solver);
+int32_t rt_solver_step_fold(rt_solver *solver, rt_solver_result *out);
+int32_t rt_solver_end(rt_solver *solver, rt_solver_result *out);
+/* Device addresses ptrs_dev[4] and element counts lens[4] (doubles; either may be NULL): [0] volumes [n_cells], valid from
+ * rt_solver_create on; [1] the scalar tally T [n_cells·G·P] and [2] the first-moment tallies [2·n_cells·G·P], valid between
+ * rt_solver_begin and rt_solver_end (NULL / 0 outside, and [2] in a flat isotropic run); [3] phi [n_cells·G], the iterate
+ * (unnormalised until rt_solver_end).  What may be written through them, and when: see above.  Does not wait. */
+int32_t rt_solver_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

@@ -16,6 +16,7 @@ from .trackgenerator import (Backward, Forward, Segment, Track, TrackGenerator, 
 from .segmentize import RTOL_DEFAULT, SegmentStore, segmentize
 from .solver import (CrossSections, PolarQuadrature, SolverResult, azimuthal_weights, exact_azimuthal_weights,
                      solve_eigenvalue, solve_fixed_source)
+from .distributed import ShardedSolver
 
 __all__ = [
     "BoundaryConditions", "BoundaryType", "Vacuum", "Reflective", "Periodic",
@@ -23,6 +24,6 @@ __all__ = [
     "AzimuthalQuadrature", "TrackGenerator", "trace", "segmentize", "SegmentStore", "RTOL_DEFAULT",
     "Track", "Segment",
     "CrossSections", "PolarQuadrature", "SolverResult", "azimuthal_weights", "exact_azimuthal_weights",
-    "solve_eigenvalue", "solve_fixed_source",
+    "solve_eigenvalue", "solve_fixed_source", "ShardedSolver",
     "Forward", "Backward", "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd",
 ]

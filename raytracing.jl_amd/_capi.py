@@ -30,6 +30,7 @@ SYMBOLS = (
     "rt_solver_create", "rt_solver_set_source", "rt_solver_run", "rt_solver_fetch", "rt_solver_destroy",
     "rt_solver_set_linear_source", "rt_solver_fetch_geometry", "rt_solver_fetch_moments",
     "rt_solver_fetch_current",
+    "rt_solver_begin", "rt_solver_step_sweep", "rt_solver_step_fold", "rt_solver_end", "rt_solver_pointers",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -237,6 +238,16 @@ def lib():
     L.rt_solver_fetch_geometry.argtypes = [_vp, _dp, _dp, C.POINTER(C.c_int32)]
     L.rt_solver_fetch_moments.restype = C.c_int32
     L.rt_solver_fetch_moments.argtypes = [_vp, _dp, _dp]
+    L.rt_solver_begin.restype = C.c_int32
+    L.rt_solver_begin.argtypes = [_vp, C.c_int32]
+    L.rt_solver_step_sweep.restype = C.c_int32
+    L.rt_solver_step_sweep.argtypes = [_vp]
+    L.rt_solver_step_fold.restype = C.c_int32
+    L.rt_solver_step_fold.argtypes = [_vp, C.POINTER(SolverResult)]
+    L.rt_solver_end.restype = C.c_int32
+    L.rt_solver_end.argtypes = [_vp, C.POINTER(SolverResult)]
+    L.rt_solver_pointers.restype = C.c_int32
+    L.rt_solver_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
     if L.rt_abi_version() != 1:
         raise RtError("librt_segmentize.so: ABI version mismatch")
     _lib = L
@@ -727,8 +738,50 @@ class DeviceSolver:
             raise RtError("the solver is closed (its tracks were closed or segmentized anew)")
         r = SolverResult()
         _check(lib().rt_solver_run(self._h, int(mode), int(max_iter), float(tol_k), float(tol_flux), C.byref(r)))
+        return self._result(r)
+
+    # ---- the iteration in steps (what ``run`` loops over inside the library): begin, (step_sweep, step_fold) as often as
+    # wanted, end — see "Stepwise iteration and sharded runs" in include/rt_segmentize.h
+    def _open(self):
+        if not getattr(self, "_h", None):
+            raise RtError("the solver is closed (its tracks were closed or segmentized anew)")
+        return self._h
+
+    @staticmethod
+    def _result(r) -> dict:
         return dict(k_eff=r.k_eff, residual=r.residual, dk=r.dk, device_ms=r.device_ms, iterations=int(r.iterations),
                     converged=bool(r.converged))
+
+    def begin(self, mode: int):
+        """``rt_solver_begin``: φ⁰ = 1, zero boundary fluxes; the solver takes the handle's sweep state until ``end``."""
+        _check(lib().rt_solver_begin(self._open(), int(mode)))
+
+    def step_sweep(self):
+        """``rt_solver_step_sweep``: the source update and one sweep, queued on the mesh's stream."""
+        _check(lib().rt_solver_step_sweep(self._open()))
+
+    def step_fold(self) -> dict:
+        """``rt_solver_step_fold``: the fold and the reductions; ``k_eff``, ``residual``, ``dk`` and ``iterations`` so far."""
+        r = SolverResult()
+        _check(lib().rt_solver_step_fold(self._open(), C.byref(r)))
+        return self._result(r)
+
+    def end(self) -> dict:
+        """``rt_solver_end``: the normalisation; the result as ``run`` returns it (``converged`` False: the caller stopped)."""
+        r = SolverResult()
+        _check(lib().rt_solver_end(self._open(), C.byref(r)))
+        return self._result(r)
+
+    def pointers(self) -> dict:
+        """``rt_solver_pointers``: device addresses (0: none) of ``volumes`` [n_cells], ``tally`` [n_cells, G·P], ``tally1``
+        [n_cells, G·P, 2] and ``phi`` [n_cells, G], and their element counts under ``lens``."""
+        ptrs = (_vp * 4)()
+        lens = (C.c_int64 * 4)()
+        _check(lib().rt_solver_pointers(self._open(), ptrs, lens))
+        names = ("volumes", "tally", "tally1", "phi")
+        out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
+        out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
+        return out
 
     def fetch(self, iterations: int) -> dict:
         phi = np.empty((self.n_cells, self.G)); vol = np.empty(self.n_cells); kh = np.empty(int(iterations))

@@ -504,6 +504,7 @@ struct rt_tracks {
     DevBuf<int32_t> sw_ctab, sw_plan;  // rows made from the COMPACT records (rt_sweep.hip ensure_rows_from_compact): their own chunk table
     bool sw_rowsc_valid = false;       // ... sw_ell / sw_cell hold those rows for the last rt_segmentize
     bool sw_links = false, sw_has_w = false, sw_has_xs = false, sw_done = false;
+    rt_solver *sw_borrower = nullptr;  // the rt_solver between rt_solver_begin and rt_solver_end that holds this sweep state
     int32_t sw_groups = 0, sw_last_input = 0, sw_last_gp = 0, sw_last_passes = 0, sw_last_rows = 0;
     int64_t refusals[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // cheap-step refusals of the last call by certificate term
     int64_t n_near_rtol = 0, n_restarts = 0, n_exact_tally = 0;
@@ -517,6 +518,7 @@ namespace rtx {
 // rt_segmentize.hip
 hipError_t wait_stream(hipStream_t s);
 hipError_t wait_seq(const unsigned long long *h_res, unsigned long long seq, hipStream_t s);
+void solver_release(rt_solver *s);  // rt_solver.hip: ends a solver's run in progress and hands the handle's sweep state back
 int finish_call(rt_tracks *t);  // every entry point that reads a call's results first waits for a call still on the stream
 template <typename T>
 int upload(DevBuf<T> &b, const T *src, size_t n, hipStream_t s) {

@@ -368,10 +368,28 @@ struct rt_solver {
     bool ls = false, ran_ls = false, has_geom = false;
     int32_t n_degenerate = 0;
     std::vector<double> k_hist;
+    // the run in progress (rt_solver_begin ... rt_solver_end): `open` while this solver holds the handle's sweep state
+    // (rt_tracks::sw_borrower points back here), `swept` between rt_solver_step_sweep and rt_solver_step_fold
+    bool open = false, swept = false, run_eigen = false, run_p1 = false, run_ls = false;
+    int32_t it = 0;
+    double last_k = 1.0, last_res = INFINITY, last_dk = INFINITY;
     double *h_scal = nullptr;  // pinned, kSolveScalars
     hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
+namespace rtx {
+
+// The end of a run's hold on its handle, whichever way the run ends: the handle's own sweeps weigh by δs again, isotropically.
+// Called with the tracks alive (rt_tracks_destroy calls it before it frees them).
+void solver_release(rt_solver *S) {
+    if (!S || !S->open) return;
+    rt_tracks *t = S->t;
+    t->sw_has_w = false; t->sw_p1 = false; t->sw_ls = false; t->sw_ls_cen = t->sw_ls_ends = nullptr;
+    if (t->sw_borrower == S) t->sw_borrower = nullptr;
+    S->open = false; S->swept = false;
+}
+
+}  // namespace rtx
 using namespace rtx;
 
 namespace {
@@ -493,24 +511,63 @@ int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_m
     return RT_SUCCESS;
 }
 
-int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, double tol_flux, rt_solver_result *res) {
-    if (!S) { set_error("rt_solver_run: null solver"); return RT_ERR_INVALID; }
-    if ((mode != RT_SOLVE_EIGENVALUE && mode != RT_SOLVE_FIXED_SOURCE) || max_iter < 0 || !(tol_k >= 0.0) || !(tol_flux >= 0.0)) {
-        set_error("rt_solver_run: bad arguments (mode %d, max_iter %d, tol_k %g, tol_flux %g)", mode, max_iter, tol_k, tol_flux);
-        return RT_ERR_INVALID;
+// ---- one run, in steps (rt_solver_begin / _step_sweep / _step_fold / _end; rt_solver_run is a loop over them) --------------------
+// launch shapes and table sizes of a solver's kernels
+struct SolverDims {
+    int32_t G, P, nc, C, tab_len, lds_len, tab1_len, lds1_len;
+    int64_t ncg;
+    unsigned cblocks, sblocks;
+    explicit SolverDims(const rt_solver *S) : G(S->G), P(S->P), nc(S->n_cells), C(S->G * S->P) {
+        ncg = (int64_t)nc * G;
+        cblocks = (unsigned)std::max(1, (nc + rt::kSolveBlock - 1) / rt::kSolveBlock);
+        sblocks = (unsigned)std::max<int64_t>(1, (ncg + rt::kSolveBlock - 1) / rt::kSolveBlock);
+        tab_len = S->M * G * (3 + G);
+        lds_len = (size_t)tab_len * sizeof(double) <= 32 * 1024 ? tab_len : 0;  // (else read where it lies: L2-resident)
+        tab1_len = S->M * G * (1 + G);
+        lds1_len = (size_t)tab1_len * sizeof(double) <= 32 * 1024 ? tab1_len : 0;
     }
-    rt_tracks *t = S->t;
+};
+
+// a failure past the state checks ends the run: the handle gets its sweep state back
+struct AbortRun { rt_solver *S; bool ok = false; ~AbortRun() { if (!ok) solver_release(S); } };
+
+int solver_check_epoch(const rt_solver *S, const char *who) {
+    const rt_tracks *t = S->t;
     if (!t->segmentized || t->seg_epoch != S->epoch) {
-        set_error("rt_solver_run: the tracks were segmentized again after rt_solver_create (its volumes and weights are stale): create a new solver");
+        set_error("%s: the tracks were segmentized again after rt_solver_create (its volumes and weights are stale): create a new solver", who);
         return RT_ERR_INVALID;
     }
-    if (!t->sw_links) { set_error("rt_solver_run: rt_sweep_set_links has not run"); return RT_ERR_INVALID; }
+    return RT_SUCCESS;
+}
+
+int solver_check_tracks(const rt_solver *S, const char *who) {
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (!S->t->sw_links) { set_error("%s: rt_sweep_set_links has not run", who); return RT_ERR_INVALID; }
+    return RT_SUCCESS;
+}
+
+// what every step call checks before it queues anything (rt_solver_run checks once, in its begin): the tracks' epoch first --
+// rt_segmentize ends an open run, and the stale solver is the error to report -- then the order of the calls
+int solver_step_enter(const rt_solver *S, bool want_swept, const char *who) {
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (!S->open) { set_error("%s: no run is open (rt_solver_begin has not run, or the run has ended)", who); return RT_ERR_INVALID; }
+    if (want_swept && !S->swept) { set_error("%s: there is no sweep to fold (rt_solver_step_sweep comes first)", who); return RT_ERR_INVALID; }
+    if (!want_swept && S->swept) { set_error("%s: the last sweep has not been folded yet (rt_solver_step_fold comes between two sweeps)", who); return RT_ERR_INVALID; }
+    return RT_SUCCESS;
+}
+
+int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
+    if (S->open) solver_release(S);  // (a second begin starts afresh)
+    rt_tracks *t = S->t;
+    if (int rc = solver_check_tracks(S, who)) return rc;
+    if (t->sw_borrower) solver_release(t->sw_borrower);  // (another solver's unfinished run on this handle ends here)
     const bool eigen = mode == RT_SOLVE_EIGENVALUE;
     rt_mesh *m = t->mesh;
     if (int rc = finish_call(t)) return rc;
     RT_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    const int32_t G = S->G, P = S->P, nc = S->n_cells, C = G * P;
+    const SolverDims d(S);
+    const int32_t G = d.G, P = d.P, nc = d.nc, C = d.C;
     const int64_t n = t->n;
     // the handle's sweep state: C components, zero boundary fluxes, the solver's track weights
     const size_t npsi = (size_t)std::max<int64_t>(1, 2 * n * C), nxs = std::max<size_t>(1, (size_t)nc * C);
@@ -520,13 +577,12 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
     RT_HIP(t->sw_w.reserve(std::max<int64_t>(1, n)));
     if (n > 0) RT_HIP(hipMemcpyAsync(t->sw_w.p, S->w_track.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
     t->sw_groups = C; t->sw_has_xs = true; t->sw_has_w = true; t->sw_done = false;
-    struct RestoreWeights { rt_tracks *t; ~RestoreWeights() { t->sw_has_w = false; t->sw_p1 = false; t->sw_ls = false; t->sw_ls_cen = t->sw_ls_ends = nullptr; } } restore{t};  // (the handle's own sweeps weigh by δs again, isotropically)
+    t->sw_borrower = S; S->open = true; S->swept = false;  // (solver_release hands the state back: the handle's own sweeps weigh by δs again, isotropically)
+    AbortRun abort_run{S};
     S->ran = false; S->ran_p1 = false; S->ran_ls = false;
     const bool p1 = S->p1, ls = S->ls;
-    if (p1 && ls) { set_error("rt_solver_run: linear source together with first-moment scattering is not supported"); return RT_ERR_INVALID; }
-    if (ls && !S->has_geom) { set_error("rt_solver_run: the linear source has no geometry"); return RT_ERR_INVALID; }
-    const int32_t tab1_len = S->M * G * (1 + G);
-    const int32_t lds1_len = (size_t)tab1_len * sizeof(double) <= 32 * 1024 ? tab1_len : 0;
+    if (p1 && ls) { set_error("%s: linear source together with first-moment scattering is not supported", who); return RT_ERR_INVALID; }
+    if (ls && !S->has_geom) { set_error("%s: the linear source has no geometry", who); return RT_ERR_INVALID; }
     if (p1) {  // J⁰ = 0; the sweep's first-moment arrays
         const size_t nj = 2 * std::max<size_t>(1, (size_t)nc * G);
         RT_HIP(S->J.reserve(nj)); RT_HIP(S->q1r.reserve(nj));
@@ -542,76 +598,146 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
         t->sw_ls = true; t->sw_ls_cen = S->cen.p; t->sw_ls_ends = S->ends.p;
     }
     S->k_hist.clear();
-    const unsigned cblocks = (unsigned)std::max(1, (nc + rt::kSolveBlock - 1) / rt::kSolveBlock);
-    const int64_t ncg = (int64_t)nc * G;
-    const unsigned sblocks = (unsigned)std::max<int64_t>(1, (ncg + rt::kSolveBlock - 1) / rt::kSolveBlock);
-    const int32_t tab_len = S->M * G * (3 + G);
-    const int32_t lds_len = (size_t)tab_len * sizeof(double) <= 32 * 1024 ? tab_len : 0;  // (else read where it lies: L2-resident)
-    const double *ext = (!eigen && S->has_ext) ? S->ext.p : nullptr;
-    const int32_t eig = eigen ? 1 : 0;
+    S->run_eigen = eigen; S->run_p1 = p1; S->run_ls = ls;
+    S->it = 0; S->last_k = 1.0; S->last_res = INFINITY; S->last_dk = INFINITY;
     // φ⁰ = 1, the components' Σt / sin θ, F⁰
     RT_HIP(hipMemsetAsync(S->prod.p, 0, (size_t)std::max(1, nc) * sizeof(double), s));
-    hipLaunchKernelGGL(rt::k_solver_fold<true>, dim3(cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
+    hipLaunchKernelGGL(rt::k_solver_fold<true>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
                        (const double *)S->vol.p, (const double *)S->pol.p, (const double *)nullptr, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P, S->partial.p);
-    hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)cblocks, 1, eig, S->scal.p);
+    hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)d.cblocks, 1, eigen ? 1 : 0, S->scal.p);
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(S->ev[0], s));
-    double k = 1.0, residual = INFINITY, dk = INFINITY;
-    bool converged = false;
-    int32_t it = 0;
-    while (it < max_iter) {
-        hipLaunchKernelGGL(rt::k_solver_source, dim3(sblocks), dim3(rt::kSolveBlock), (size_t)lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
-                           (const double *)S->tab.p, lds_len, (const double *)S->phi.p, (const double *)S->prod.p, ext, (const double *)S->scal.p, eig,
-                           nc, G, P, t->sw_xs.p);
-        if (p1)
-            hipLaunchKernelGGL(rt::k_solver_source_p1, dim3(sblocks), dim3(rt::kSolveBlock), (size_t)lds1_len * sizeof(double), s, (const int32_t *)S->mat.p,
-                               (const double *)S->tab1.p, lds1_len, (const double *)S->J.p, (const double *)S->pol.p, nc, G, P, S->q1r.p, t->sw_xs1.p);
-        if (ls)
-            hipLaunchKernelGGL(rt::k_solver_source_ls, dim3(sblocks), dim3(rt::kSolveBlock), (size_t)lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
-                               (const double *)S->tab.p, lds_len, (const double *)S->mom.p, (const double *)S->cinv.p, (const double *)S->pol.p,
-                               (const double *)S->scal.p, eig, nc, G, P, S->gr.p, t->sw_xs1.p);
-        RT_HIP(hipGetLastError());
-        if (int32_t rc = rt_sweep(t, C, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
-        hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
-                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P,
-                           S->partial.p);
-        if (p1)
-            hipLaunchKernelGGL(rt::k_solver_fold_p1, dim3(sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab1.p,
-                               (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->q1r.p, nc, G, P, S->J.p);
-        if (ls)
-            hipLaunchKernelGGL(rt::k_solver_fold_ls, dim3(sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
-                               (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->gr.p,
-                               (const double *)S->cmat.p, (const double *)S->cinv.p, nc, G, P, S->mom.p);
-        hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)cblocks, 0, eig, S->scal.p);
-        RT_HIP(hipMemcpyAsync(S->h_scal, S->scal.p, rt::kSolveScalars * sizeof(double), hipMemcpyDeviceToHost, s));
-        RT_HIP(hipStreamSynchronize(s));
-        RT_HIP(hipGetLastError());
-        ++it;
-        k = S->h_scal[0]; residual = S->h_scal[2]; dk = S->h_scal[3];
-        S->k_hist.push_back(k);
-        if (!std::isfinite(k) || !std::isfinite(residual)) {
-            set_error("rt_solver_run: iteration %d produced k = %g, residual = %g", it, k, residual);
-            return RT_ERR_INVALID;
-        }
-        if (dk < tol_k && residual < tol_flux) { converged = true; break; }
+    abort_run.ok = true;
+    return RT_SUCCESS;
+}
+
+// the two halves of an iteration of an open run, on the device and with the shapes the caller has set and made
+int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
+    rt_tracks *t = S->t;
+    hipStream_t s = t->mesh->stream;
+    const int32_t G = d.G, P = d.P, nc = d.nc, eig = S->run_eigen ? 1 : 0;
+    const double *ext = (!S->run_eigen && S->has_ext) ? S->ext.p : nullptr;
+    hipLaunchKernelGGL(rt::k_solver_source, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
+                       (const double *)S->tab.p, d.lds_len, (const double *)S->phi.p, (const double *)S->prod.p, ext, (const double *)S->scal.p, eig,
+                       nc, G, P, t->sw_xs.p);
+    if (S->run_p1)
+        hipLaunchKernelGGL(rt::k_solver_source_p1, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds1_len * sizeof(double), s, (const int32_t *)S->mat.p,
+                           (const double *)S->tab1.p, d.lds1_len, (const double *)S->J.p, (const double *)S->pol.p, nc, G, P, S->q1r.p, t->sw_xs1.p);
+    if (S->run_ls)
+        hipLaunchKernelGGL(rt::k_solver_source_ls, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
+                           (const double *)S->tab.p, d.lds_len, (const double *)S->mom.p, (const double *)S->cinv.p, (const double *)S->pol.p,
+                           (const double *)S->scal.p, eig, nc, G, P, S->gr.p, t->sw_xs1.p);
+    RT_HIP(hipGetLastError());
+    if (int32_t rc = rt_sweep(t, d.C, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
+    S->swept = true;
+    return RT_SUCCESS;
+}
+
+int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, const char *who) {
+    rt_tracks *t = S->t;
+    hipStream_t s = t->mesh->stream;
+    const int32_t G = d.G, P = d.P, nc = d.nc;
+    hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
+                       (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P,
+                       S->partial.p);
+    if (S->run_p1)
+        hipLaunchKernelGGL(rt::k_solver_fold_p1, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab1.p,
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->q1r.p, nc, G, P, S->J.p);
+    if (S->run_ls)
+        hipLaunchKernelGGL(rt::k_solver_fold_ls, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->gr.p,
+                           (const double *)S->cmat.p, (const double *)S->cinv.p, nc, G, P, S->mom.p);
+    hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)d.cblocks, 0, S->run_eigen ? 1 : 0, S->scal.p);
+    RT_HIP(hipMemcpyAsync(S->h_scal, S->scal.p, rt::kSolveScalars * sizeof(double), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    RT_HIP(hipGetLastError());
+    S->swept = false;
+    ++S->it;
+    S->last_k = S->h_scal[0]; S->last_res = S->h_scal[2]; S->last_dk = S->h_scal[3];
+    S->k_hist.push_back(S->last_k);
+    if (!std::isfinite(S->last_k) || !std::isfinite(S->last_res)) {
+        set_error("%s: iteration %d produced k = %g, residual = %g", who, S->it, S->last_k, S->last_res);
+        return RT_ERR_INVALID;
     }
+    if (res) {
+        res->k_eff = S->run_eigen ? S->last_k : 1.0; res->residual = S->last_res; res->dk = S->last_dk; res->device_ms = 0.0;
+        res->iterations = S->it; res->converged = 0;
+    }
+    return RT_SUCCESS;
+}
+
+int solver_step_sweep_impl(rt_solver *S, const char *who) {
+    if (int rc = solver_step_enter(S, false, who)) return rc;
+    AbortRun abort_run{S};
+    RT_HIP(hipSetDevice(S->t->mesh->device));
+    if (int rc = solver_queue_sweep(S, SolverDims(S))) return rc;
+    abort_run.ok = true;
+    return RT_SUCCESS;
+}
+
+int solver_step_fold_impl(rt_solver *S, rt_solver_result *res, const char *who) {
+    if (int rc = solver_step_enter(S, true, who)) return rc;
+    AbortRun abort_run{S};
+    RT_HIP(hipSetDevice(S->t->mesh->device));
+    if (int rc = solver_queue_fold(S, SolverDims(S), res, who)) return rc;
+    abort_run.ok = true;
+    return RT_SUCCESS;
+}
+
+int solver_end_impl(rt_solver *S, rt_solver_result *res, const char *who) {
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (!S->open) { set_error("%s: no run is open (rt_solver_begin has not run, or the run has ended)", who); return RT_ERR_INVALID; }
+    AbortRun abort_run{S};
+    rt_tracks *t = S->t;
+    RT_HIP(hipSetDevice(t->mesh->device));
+    hipStream_t s = t->mesh->stream;
+    const SolverDims d(S);
+    const bool eigen = S->run_eigen;
     RT_HIP(hipEventRecord(S->ev[1], s));
-    if (eigen && nc > 0)
-        hipLaunchKernelGGL(rt::k_solver_scale, dim3(sblocks), dim3(256), 0, s, S->phi.p, ncg, (const double *)S->scal.p);
-    if (eigen && nc > 0 && p1)
-        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * ncg + 255) / 256)), dim3(256), 0, s, S->J.p, 2 * ncg, (const double *)S->scal.p);
-    if (eigen && nc > 0 && ls)
-        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * ncg + 255) / 256)), dim3(256), 0, s, S->mom.p, 2 * ncg, (const double *)S->scal.p);
+    if (eigen && d.nc > 0)
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3(d.sblocks), dim3(256), 0, s, S->phi.p, d.ncg, (const double *)S->scal.p);
+    if (eigen && d.nc > 0 && S->run_p1)
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * d.ncg + 255) / 256)), dim3(256), 0, s, S->J.p, 2 * d.ncg, (const double *)S->scal.p);
+    if (eigen && d.nc > 0 && S->run_ls)
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * d.ncg + 255) / 256)), dim3(256), 0, s, S->mom.p, 2 * d.ncg, (const double *)S->scal.p);
     RT_HIP(hipStreamSynchronize(s));
     RT_HIP(hipGetLastError());
     float f = 0.0f;
     RT_HIP(hipEventElapsedTime(&f, S->ev[0], S->ev[1]));
     t->in_flight = false;
-    S->ran = true; S->ran_p1 = p1; S->ran_ls = ls;
+    S->ran = true; S->ran_p1 = S->run_p1; S->ran_ls = S->run_ls;
     if (res) {
-        res->k_eff = eigen ? k : 1.0; res->residual = residual; res->dk = dk; res->device_ms = f;
-        res->iterations = it; res->converged = converged ? 1 : 0;
+        res->k_eff = eigen ? S->last_k : 1.0; res->residual = S->last_res; res->dk = S->last_dk; res->device_ms = f;
+        res->iterations = S->it; res->converged = 0;
     }
+    solver_release(S);  // (the run is over: the handle has its sweep state back)
+    abort_run.ok = true;
+    return RT_SUCCESS;
+}
+
+bool solver_mode_ok(int32_t mode) { return mode == RT_SOLVE_EIGENVALUE || mode == RT_SOLVE_FIXED_SOURCE; }
+
+int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, double tol_flux, rt_solver_result *res) {
+    const char *who = "rt_solver_run";
+    if (!S) { set_error("rt_solver_run: null solver"); return RT_ERR_INVALID; }
+    if (!solver_mode_ok(mode) || max_iter < 0 || !(tol_k >= 0.0) || !(tol_flux >= 0.0)) {
+        set_error("rt_solver_run: bad arguments (mode %d, max_iter %d, tol_k %g, tol_flux %g)", mode, max_iter, tol_k, tol_flux);
+        return RT_ERR_INVALID;
+    }
+    if (int rc = solver_begin_impl(S, mode, who)) return rc;
+    bool converged = false;
+    {   // (begin has checked the tracks and set the device, and nothing comes between the steps here)
+        AbortRun abort_run{S};
+        const SolverDims d(S);
+        while (S->it < max_iter) {
+            if (int rc = solver_queue_sweep(S, d)) return rc;
+            if (int rc = solver_queue_fold(S, d, nullptr, who)) return rc;
+            if (S->last_dk < tol_k && S->last_res < tol_flux) { converged = true; break; }
+        }
+        abort_run.ok = true;
+    }
+    if (int rc = solver_end_impl(S, res, who)) return rc;
+    if (res) res->converged = converged ? 1 : 0;
     return RT_SUCCESS;
 }
 
@@ -811,6 +937,61 @@ int32_t rt_solver_run(rt_solver *solver, int32_t mode, int32_t max_iter, double 
     }
 }
 
+int32_t rt_solver_begin(rt_solver *solver, int32_t mode) {
+    if (!solver) { set_error("rt_solver_begin: null solver"); return RT_ERR_INVALID; }
+    if (!solver_mode_ok(mode)) { set_error("rt_solver_begin: bad arguments (mode %d)", mode); return RT_ERR_INVALID; }
+    try {
+        return solver_begin_impl(solver, mode, "rt_solver_begin");
+    } catch (const std::exception &e) {
+        set_error("rt_solver_begin: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+int32_t rt_solver_step_sweep(rt_solver *solver) {
+    if (!solver) { set_error("rt_solver_step_sweep: null solver"); return RT_ERR_INVALID; }
+    try {
+        return solver_step_sweep_impl(solver, "rt_solver_step_sweep");
+    } catch (const std::exception &e) {
+        set_error("rt_solver_step_sweep: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+int32_t rt_solver_step_fold(rt_solver *solver, rt_solver_result *out) {
+    if (!solver) { set_error("rt_solver_step_fold: null solver"); return RT_ERR_INVALID; }
+    try {
+        return solver_step_fold_impl(solver, out, "rt_solver_step_fold");
+    } catch (const std::exception &e) {
+        set_error("rt_solver_step_fold: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+int32_t rt_solver_end(rt_solver *solver, rt_solver_result *out) {
+    if (!solver) { set_error("rt_solver_end: null solver"); return RT_ERR_INVALID; }
+    try {
+        return solver_end_impl(solver, out, "rt_solver_end");
+    } catch (const std::exception &e) {
+        set_error("rt_solver_end: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+int32_t rt_solver_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
+    if (!solver) { set_error("rt_solver_pointers: null solver"); return RT_ERR_INVALID; }
+    // (no wait here: addresses and counts only)
+    const int64_t nc = solver->n_cells, C = (int64_t)solver->G * solver->P;
+    const bool open = solver->open, mom = open && (solver->run_p1 || solver->run_ls);
+    void *p[4] = {solver->vol.p, open ? solver->t->sw_phi.p : nullptr, mom ? solver->t->sw_cur.p : nullptr, solver->phi.p};
+    const int64_t l[4] = {nc, open ? nc * C : 0, mom ? 2 * nc * C : 0, nc * solver->G};
+    for (int i = 0; i < 4; ++i) {
+        if (ptrs_dev) ptrs_dev[i] = p[i];
+        if (lens) lens[i] = l[i];
+    }
+    return RT_SUCCESS;
+}
+
 int32_t rt_solver_fetch(rt_solver *solver, double *phi, double *volumes, double *k_history) {
     if (!solver) { set_error("rt_solver_fetch: null solver"); return RT_ERR_INVALID; }
     if ((phi || k_history) && !solver->ran) { set_error("rt_solver_fetch: rt_solver_run has not completed"); return RT_ERR_INVALID; }
@@ -826,7 +1007,9 @@ int32_t rt_solver_fetch(rt_solver *solver, double *phi, double *volumes, double 
 
 void rt_solver_destroy(rt_solver *solver) {
     if (!solver) return;
-    // (touches neither the tracks nor the mesh, which may be gone already: every entry point has waited for its work)
+    // (touches neither the tracks nor the mesh, which may be gone already: every entry point has waited for its work — except
+    //  in the middle of a run, where the tracks are alive (rt_tracks_destroy ends the run) and get their sweep state back)
+    solver_release(solver);
     (void)hipSetDevice(solver->device);
     free_solver(solver);
 }

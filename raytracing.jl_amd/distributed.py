@@ -20,7 +20,7 @@ import numpy as np
 
 __all__ = ["shard_ranges", "shard_arrays", "segmentize_shard", "allreduce_volumes",
            "allgather_segments", "SegmentGather", "DevArray", "TRACK_FIELDS", "PipelinedVolumesAllReduce",
-           "SweepExchangePlan", "ShardedSweep"]
+           "SweepExchangePlan", "ShardedSweep", "ShardedSolver"]
 
 TRACK_FIELDS = ("px", "py", "phi", "cos_phi", "sin_phi", "A", "B", "C", "ell", "azim_idx")
 
@@ -347,3 +347,152 @@ class ShardedSweep:
         r = self.dt.sweep(G, sigma_t, source, track_weight, psi_in, input=input, fetch=False)
         r["phi"], r["psi_out"], r["psi_next"] = self.exchange(G)
         return r
+
+
+class ShardedSolver:
+    """The device MOC solver (``rt_solver``) on a uid shard: one rank's part of a source iteration over the GLOBAL problem, every
+    other stage of which already shards by uid range.  ``dt`` is this rank's shard handle as ``segmentize_shard``
+    returns it, after ``segmentize``; ``tg`` the GLOBAL traced ``TrackGenerator``; ``xs`` a ``CrossSections`` (with ``sigma_s1``:
+    P1 scattering); ``cell_material`` as for ``solve_eigenvalue``.  Construction sets the links restricted to the shard
+    (``ShardedSweep``), creates the solver over the shard's tracks with the global azimuthal weights and sums the ranks' partial
+    ``volumes`` in place, once.  ``run`` then drives the library's iteration in steps (``rt_solver_begin / _step_sweep / _step_fold /
+    _end``) and puts between every sweep and its fold
+
+    * ``ShardedSweep.exchange``: the boundary fluxes that leave the shard go to their owners, the entering ones come in, and the
+      scalar tallies T [n_cells, G·P] are summed over the ranks;
+    * with P1 scattering the all-reduce of the first-moment tallies [n_cells, G·P, 2].
+
+    Every rank then folds the same whole-mesh arrays: k, the residual and with them the stopping decision agree on all ranks, and
+    every rank returns the full result.  With the ``nccl`` backend all of this acts on the library's device buffers through
+    ``DevArray`` views; no host copy is made.  ``tensors`` (for ``gloo``): a callable that receives the dict of those views
+    (``volumes``, ``tally``, ``tally1``, ``psi_out``, ``psi_in``) and returns the tensors the collectives are to act on instead,
+    e.g. ``lambda v: {k: t.cpu() for k, t in v.items()}``; what the collectives changed is copied back.
+
+    ``scheme="linear"`` raises ``ValueError``: the linear source's geometry (centroids, C) is a sum over tracks which the library
+    takes from the handle's own tracks when the option is switched on, and which would need its own all-reduce before the centroids
+    are formed.  ``solver``: a ready object with the step interface instead of a ``DeviceSolver`` (the CPU tests' numpy stand-in;
+    ``xs`` and ``dt`` may then be None, and its ``pointers()`` returns torch tensors, ``psi_out`` / ``psi_in`` among them)."""
+
+    def __init__(self, tg, dt, xs, cell_material, rank, world, *, ranges=None, polar="TY3", azim_weights="exact", scheme="flat",
+                 group=None, device=None, tensors=None, solver=None):
+        if scheme == "linear":
+            raise ValueError('scheme="linear" is not supported on a shard: the linear source\'s geometry is a track sum that would need its own all-reduce')
+        if scheme != "flat":
+            raise ValueError(f"unknown scheme {scheme!r} (flat)")
+        self.dt, self.rank, self.world, self.group, self.device = dt, rank, world, group, device
+        self._tensors = tensors
+        self._coll = None
+        self.sweep = ShardedSweep(tg, dt, rank, world, ranges=ranges, group=group, device=device, tensors=lambda: self._coll)
+        self.plan, self.ranges = self.sweep.plan, self.sweep.ranges
+        self.p1 = xs is not None and getattr(xs, "sigma_s1", None) is not None
+        if solver is None:
+            from . import _capi
+            from .solver import CrossSections, PolarQuadrature, _cell_material, azimuthal_weights
+
+            if not isinstance(xs, CrossSections):
+                raise TypeError("xs must be a CrossSections")
+            pq = PolarQuadrature(polar)
+            solver = _capi.DeviceSolver(dt, _cell_material(tg, cell_material), xs.sigma_t, xs.sigma_s, xs.nu_sigma_f, xs.chi,
+                                        pq.sin_theta, pq.weights, azimuthal_weights(tg, azim_weights))
+            if self.p1:
+                solver.set_scatter_p1(xs.sigma_s1)
+        else:
+            self.p1 = bool(getattr(solver, "p1", self.p1))
+        self.solver = solver
+        self.n_cells, self.C = solver.n_cells, solver.G * solver.P
+        # the volumes: every rank has summed its own tracks' chords; the fold needs the whole sums (once: they do not change)
+        lib = self._views(("volumes",))
+        coll = self._tensors(lib) if self._tensors is not None else lib
+        allreduce_volumes(coll["volumes"], group=self.group)
+        self._commit(lib, coll, ("volumes",))
+
+    def _views(self, names):
+        """The library's buffers as torch tensors (zero-copy), by name."""
+        import torch
+
+        p = self.solver.pointers()
+        nc, C, n2 = self.n_cells, self.C, 2 * self.plan.n_local
+        shapes = dict(volumes=(nc,), tally=(nc, C), tally1=(nc, 2 * C), psi_out=(n2, C), psi_in=(n2, C))
+        sp = None
+        out = {}
+        for k in names:
+            v = p.get(k)
+            if v is None and k in ("psi_out", "psi_in"):
+                sp = sp if sp is not None else self.dt.sweep_pointers()
+                v = sp[k]
+            if isinstance(v, torch.Tensor):
+                out[k] = v.view(shapes[k])
+                continue
+            if not v:
+                raise RuntimeError(f"the solver has no {k} buffer now")
+            n = int(np.prod(shapes[k]))
+            out[k] = torch.as_tensor(DevArray(v, n, "<f8", self.solver), device=self.device).view(shapes[k])
+        return out
+
+    def _commit(self, lib, coll, names):
+        """Copy back what the collectives changed where they acted on copies; drain torch's stream: the library's next kernels
+        (the mesh's stream) must see it."""
+        import torch
+
+        for k in names:
+            if coll[k] is not lib[k]:
+                lib[k].copy_(coll[k])
+        for k in names:
+            if lib[k].is_cuda:
+                torch.cuda.current_stream(lib[k].device).synchronize()
+                break
+
+    def _exchange(self):
+        """Between a sweep and its fold: boundary fluxes to their owners, tallies summed over the ranks."""
+        import torch.distributed as dist
+
+        if self.dt is not None:
+            self.dt.wait()  # (the sweep is on the mesh's stream, and under the option "async" only queued)
+        names = ("tally", "psi_out", "psi_in") + (("tally1",) if self.p1 else ())
+        lib = self._views(names)
+        coll = self._tensors(lib) if self._tensors is not None else lib
+        if self.p1 and self.world > 1:
+            dist.all_reduce(coll["tally1"], op=dist.ReduceOp.SUM, group=self.group)
+        self._coll = (coll["tally"], coll["psi_out"], coll["psi_in"])
+        try:
+            self.sweep.exchange(self.C)
+        finally:
+            self._coll = None
+        self._commit(lib, coll, ("tally", "psi_in") + (("tally1",) if self.p1 else ()))
+
+    def _iterate(self) -> dict:
+        """One iteration of the global problem: sweep, exchange, fold — in this order (a fold before the exchange would use this
+        rank's partial tallies alone)."""
+        self.solver.step_sweep()
+        self._exchange()
+        return self.solver.step_fold()
+
+    def run(self, mode, max_iter, tol_k, tol_flux, source=None):
+        """``max_iter`` iterations at most of the global problem, stopped by the rule of ``rt_solver_run`` (|Δk| / k < ``tol_k`` and
+        residual < ``tol_flux``), which every rank evaluates on the same numbers.  ``mode``: 0 / "eigenvalue" or 1 / "fixed";
+        ``source`` [n_cells, G]: the external source of a fixed-source run.  Returns a ``solver.SolverResult``."""
+        from .solver import SolverResult
+
+        mode = {"eigenvalue": 0, "fixed": 1}.get(mode, mode)
+        if mode not in (0, 1):
+            raise ValueError(f"unknown mode {mode!r}")
+        sv = self.solver
+        if source is not None:
+            q = np.asarray(source, np.float64)
+            if q.ndim == 0 or q.shape == (sv.G,):
+                q = np.broadcast_to(q, (self.n_cells, sv.G))
+            sv.set_source(q)
+        sv.begin(mode)
+        it, converged = 0, False
+        while it < int(max_iter):
+            r = self._iterate()
+            it = r["iterations"]
+            if r["dk"] < tol_k and r["residual"] < tol_flux:
+                converged = True
+                break
+        r = sv.end()
+        f = sv.fetch(r["iterations"])
+        it = r["iterations"]
+        return SolverResult(k_eff=r["k_eff"] if mode == 0 else None, phi=f["phi"], volumes=f["volumes"], iterations=it,
+                            converged=converged, k_history=f["k_history"], ms_per_iteration=r["device_ms"] / it if it else 0.0,
+                            residual=r["residual"], solver=sv, current=sv.fetch_current() if self.p1 else None)

@@ -3,7 +3,9 @@
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
-(source update + fold + reductions + the per-iteration readback).  The per-kernel times come from a separate run of this
+(source update + fold + reductions + the per-iteration readback).  `--steps`: the same iterations driven from Python one half at a
+time (rt_solver_begin / _step_sweep / _step_fold / _end) beside the library's own loop: what the host turnaround of the stepwise
+interface costs per iteration.  The per-kernel times come from a separate run of this
 script under `rocprofv3 --kernel-trace --stats` (use --no-sweep-probe there so that only the solver's launches are traced):
 
     rocprofv3 --kernel-trace --stats -d <dir> -o solve -- python tools/solve_timing.py --iters 20 --no-sweep-probe
@@ -51,6 +53,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--p1", action="store_true", help="linearly anisotropic scattering: a synthetic Σs1 = 0.3 Σs0 (rt_solver_set_scatter_p1)")
     ap.add_argument("--linear", action="store_true", help="the linear source (rt_solver_set_linear_source); not together with --p1")
+    ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
 
@@ -86,6 +89,20 @@ def main():
     out = dict(config=dict(mesh=a.mesh, n_azim=a.n_azim, delta=a.delta, groups=a.groups, polar=a.polar, components=a.groups * pq.n_polar,
                            p1=bool(a.p1), linear=bool(a.linear), tracks=int(tg.n_total_tracks), records=int(dt.total), cells=int(tg.mesh.num_cells), iters=a.iters),
                ms_per_iter_events=float(np.median(ev_ms)), ms_per_iter_host=float(np.median(host_ms)), k_eff=ks[-1])
+    if a.steps:
+        ev_ms, host_ms = [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            sv.begin(0)
+            for _ in range(a.iters):
+                sv.step_sweep()
+                sv.step_fold()
+            r = sv.end()
+            host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+            ev_ms.append(r["device_ms"] / r["iterations"])
+        out["steps_ms_per_iter_events"] = float(np.median(ev_ms))
+        out["steps_ms_per_iter_host"] = float(np.median(host_ms))
+        out["steps_k_eff"] = r["k_eff"]
     if a.linear:
         out["n_degenerate"] = sv.fetch_geometry()["n_degenerate"]
     if not a.no_sweep_probe and not a.p1 and not a.linear:  # (the handle's own rt_sweep is the isotropic one)
