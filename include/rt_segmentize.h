@@ -539,8 +539,23 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              and partial tallies: sum the volumes over the shards once, before begin; per iteration, between step_sweep and
  *              step_fold, hand the boundary fluxes that leave the shard to their owners (rt_sweep_info: psi_out, psi_in) and
  *              sum T (and Tx, Ty) over the shards.  Every shard then folds the same whole-mesh arrays and gets the same k
- *              and residual.  The linear source is excluded: its geometry (centroids, C) is a sum over tracks taken when
- *              the option is switched on, from this handle's tracks alone, and would need its own reduction.
+ *              and residual.
+ * Sharded LS   the linear source's geometry (centroids, C) is a sum over tracks as well, with a division in its middle, so
+ *              rt_solver_set_linear_source on a shard would take it from the shard's tracks alone.  rt_solver_ls_geometry runs
+ *              it in three stages instead, once per solver, after the volumes have been summed and with no run open:
+ *                  stage 0 (first moments Σ 2αδ ℓ m of the shard's tracks into an accumulator; the tracks' end points)
+ *                  stage 1 (centroids = accumulator / volumes; second moments about them into the zeroed accumulator)
+ *                  stage 2 (C, C⁻¹, the degenerate count from accumulator / volumes; frees it and switches the linear source on)
+ *              After stage 0 and again after stage 1 the caller sums the accumulator (rt_solver_ls_geometry_pointer: one
+ *              address, valid from stage 0 to stage 2) over the shards, ordered against rt_mesh_get_stream as above (rt_wait
+ *              first: stages 0 and 1 only queue their kernels) — and does nothing else to it.  volumes must already hold the
+ *              whole-mesh sums before stage 1: the centroids and C divide by them.  Every shard then holds the same centroids,
+ *              C and degenerate count (a cell none of a shard's tracks cross is live if another shard's cross it), and a run
+ *              needs per iteration what first-moment scattering needs: the sum of Tx, Ty over the shards.  The tracks' end
+ *              points and the sweep's running path length are per track, hence local.  Stages run in order; stage 0 may
+ *              always follow (it starts the geometry afresh, the linear source off until stage 2).  A stage out of order, with a
+ *              run open, with first-moment scattering set or after the tracks were segmentized again returns RT_ERR_INVALID
+ *              and changes nothing.  With no summing in between, stages 0, 1, 2 are rt_solver_set_linear_source(solver, 1).
  * --------------------------------------------------------------------------------------- */
 typedef struct rt_solver rt_solver;
 
@@ -581,6 +596,13 @@ int32_t rt_solver_fetch_current(rt_solver *solver, double *J);
  * had it on.  The first switching-on computes the cells' geometry on the device.  RT_ERR_INVALID while first-moment scattering
  * is set (and rt_solver_set_scatter_p1 fails while the linear source is on). */
 int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on);
+/* The geometry of the linear source in stages 0, 1, 2 (see "Sharded LS" above), for a caller that sums the accumulator over
+ * shards between them; stage 2 switches the linear source on.  Stages 0 and 1 queue their kernels and return; stage 2 waits. */
+int32_t rt_solver_ls_geometry(rt_solver *solver, int32_t stage);
+/* The accumulator of the staged geometry: its device address and length in doubles (3 per cell: first moments x, y and one unused
+ * after stage 0; second moments xx, xy, yy after stage 1) from stage 0 until stage 2, NULL / 0 outside; either may be NULL.
+ * Does not wait. */
+int32_t rt_solver_ls_geometry_pointer(rt_solver *solver, void **acc_dev, int64_t *len);
 /* Geometry of the linear source: centroid [n_cells][2], cmat [n_cells][3] (Cxx, Cxy, Cyy), the number of degenerate cells; any
  * may be NULL.  RT_ERR_INVALID when the linear source has never been switched on. */
 int32_t rt_solver_fetch_geometry(rt_solver *solver, double *centroid, double *cmat, int32_t *n_degenerate);

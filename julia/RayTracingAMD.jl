@@ -300,6 +300,23 @@ function segmentize_amd_multi!(t::TrackGenerator{Float64}; devices::Vector{Int}=
     return t
 end
 
+# The linear source's geometry in stages, for an `rt_solver` handle `hs` on a uid shard (include/rt_segmentize.h, "Sharded LS"):
+# stage 0, sum the accumulator over the ranks, stage 1, sum it again, stage 2.  Nothing else may touch the accumulator, and the
+# solver's volumes must hold the whole-mesh sums before stage 1.
+function solver_ls_geometry!(hs::Ptr{Cvoid}, stage::Integer)
+    rc = ccall((:rt_solver_ls_geometry, LIB), Int32, (Ptr{Cvoid}, Int32), hs, stage)
+    rc == 0 || error("rt_solver_ls_geometry failed: " * lasterror())
+    return nothing
+end
+
+# (device address, length in doubles) of that accumulator between stage 0 and stage 2; (C_NULL, 0) outside
+function solver_ls_geometry_pointer(hs::Ptr{Cvoid})
+    p = Ref{Ptr{Cvoid}}(C_NULL); n = Ref{Int64}(0)
+    rc = ccall((:rt_solver_ls_geometry_pointer, LIB), Int32, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Int64}), hs, p, n)
+    rc == 0 || error("rt_solver_ls_geometry_pointer failed: " * lasterror())
+    return p[], n[]
+end
+
 # rt_multi_create for the generator's mesh and tracks (flattened as in segmentize_amd!)
 function multi_create(t::TrackGenerator{Float64}, devices::Vector{Int})
     tracks = t.tracks_by_uid

@@ -29,6 +29,7 @@ SYMBOLS = (
     "rt_trace_counts", "rt_trace", "rt_msh_load", "rt_msh_sizes", "rt_msh_fetch", "rt_msh_free",
     "rt_solver_create", "rt_solver_set_source", "rt_solver_run", "rt_solver_fetch", "rt_solver_destroy",
     "rt_solver_set_linear_source", "rt_solver_fetch_geometry", "rt_solver_fetch_moments",
+    "rt_solver_ls_geometry", "rt_solver_ls_geometry_pointer",
     "rt_solver_fetch_current",
     "rt_solver_begin", "rt_solver_step_sweep", "rt_solver_step_fold", "rt_solver_end", "rt_solver_pointers",
 )
@@ -234,6 +235,10 @@ def lib():
     L.rt_solver_fetch_current.argtypes = [_vp, _dp]
     L.rt_solver_set_linear_source.restype = C.c_int32
     L.rt_solver_set_linear_source.argtypes = [_vp, C.c_int32]
+    L.rt_solver_ls_geometry.restype = C.c_int32
+    L.rt_solver_ls_geometry.argtypes = [_vp, C.c_int32]
+    L.rt_solver_ls_geometry_pointer.restype = C.c_int32
+    L.rt_solver_ls_geometry_pointer.argtypes = [_vp, C.POINTER(_vp), _lp]
     L.rt_solver_fetch_geometry.restype = C.c_int32
     L.rt_solver_fetch_geometry.argtypes = [_vp, _dp, _dp, C.POINTER(C.c_int32)]
     L.rt_solver_fetch_moments.restype = C.c_int32
@@ -720,6 +725,18 @@ class DeviceSolver:
     def set_linear_source(self, on=True):
         """``rt_solver_set_linear_source``: the linear-source approximation for the following runs (False: flat again)."""
         _check(lib().rt_solver_set_linear_source(self._h, 1 if on else 0))
+
+    def ls_geometry(self, stage: int):
+        """``rt_solver_ls_geometry``: stage 0, 1 or 2 of the linear source's geometry, for a caller that sums the accumulator
+        (``ls_geometry_pointer``) over shards after stage 0 and after stage 1; stage 2 switches the linear source on."""
+        _check(lib().rt_solver_ls_geometry(self._open(), int(stage)))
+
+    def ls_geometry_pointer(self):
+        """``rt_solver_ls_geometry_pointer``: ``(address, doubles)`` of the staged geometry's accumulator; ``(0, 0)`` outside
+        stage 0 .. stage 2."""
+        ptr, n = _vp(), C.c_int64(0)
+        _check(lib().rt_solver_ls_geometry_pointer(self._open(), C.byref(ptr), C.byref(n)))
+        return ptr.value or 0, int(n.value)
 
     def fetch_geometry(self) -> dict:
         """``rt_solver_fetch_geometry``: ``centroids`` [n_cells, 2], ``cmat`` [n_cells, 3] (Cxx, Cxy, Cyy), ``n_degenerate``."""

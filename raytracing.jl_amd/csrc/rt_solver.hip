@@ -366,6 +366,11 @@ struct rt_solver {
     DevBuf<double> cen, cmat, cinv, ends;    // geometry: [n_cells][2], [n_cells][3], [n_cells][4] (see k_solver_ls_cmat), [n][4]
     DevBuf<double> mom, gr;                  // flux moments φ⃗ and q⃗/Σt_g [n_cells][G][2]
     bool ls = false, ran_ls = false, has_geom = false;
+    // the geometry in stages (rt_solver_ls_geometry): the stage that comes next, 0 outside; the accumulator [n_cells][3] lives
+    // from stage 0 to stage 2
+    int32_t ls_stage = 0;
+    DevBuf<double> ls_acc, ls_wvol;
+    DevBuf<int32_t> ls_ndeg;
     int32_t n_degenerate = 0;
     std::vector<double> k_hist;
     // the run in progress (rt_solver_begin ... rt_solver_end): `open` while this solver holds the handle's sweep state
@@ -826,61 +831,115 @@ int32_t rt_solver_fetch_current(rt_solver *solver, double *J) {
     return RT_SUCCESS;
 }
 
-// the cells' geometry for the linear source, once per solver (records and α only)
-static int32_t solver_ls_geometry(rt_solver *S) {
+// The cells' geometry for the linear source, once per solver (records and α only), in three stages cut where a sharded caller sums
+// the accumulator over the ranks (rt_solver_ls_geometry); rt_solver_set_linear_source runs them back to back.
+//   0: acc = 0; first moments of the handle's tracks into acc [n_cells][3] (third entry unused), the tracks' end points into `ends`
+//   1: centroids = acc / volumes; acc = 0; second moments about them into acc
+//   2: C, C⁻¹ and the degenerate count from acc / volumes; the accumulator is freed and the linear source switched on
+// `staged`: the caller is rt_solver_ls_geometry: an open run is refused, and stages 0 and 1 return with their kernels queued (the
+// handle is marked in flight, so that rt_wait and every accessor wait for them).
+static void solver_ls_geometry_drop(rt_solver *S) {
+    S->ls_acc.release(); S->ls_stage = 0;
+}
+
+static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged, const char *who) {
     rt_tracks *t = S->t;
     if (!t->segmentized || t->seg_epoch != S->epoch) {
-        set_error("rt_solver_set_linear_source: the tracks were segmentized again after rt_solver_create: create a new solver");
+        set_error("%s: the tracks were segmentized again after rt_solver_create: create a new solver", who);
+        return RT_ERR_INVALID;
+    }
+    if (S->p1) { set_error("%s: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported", who); return RT_ERR_INVALID; }
+    if (staged && S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the geometry cannot change under it", who); return RT_ERR_INVALID; }
+    if (stage != 0 && stage != S->ls_stage) {
+        set_error("%s: stage %d out of order (%s)", who, stage,
+                  S->ls_stage == 0 ? "stage 0 has not run, or the geometry is complete" : S->ls_stage == 1 ? "stage 1 comes next" : "stage 2 comes next");
         return RT_ERR_INVALID;
     }
     if (int rc = finish_call(t)) return rc;
     RT_HIP(hipSetDevice(t->mesh->device));
     hipStream_t s = t->mesh->stream;
-    if (int rc = ensure_compacted(t)) return rc;
     const int32_t nc = S->n_cells;
     const int64_t n = t->n;
     const size_t ncs = (size_t)std::max<int32_t>(1, nc);
-    DevBuf<double> dwvol, acc;
-    DevBuf<int32_t> ndeg;
-    if (int rc = upload(dwvol, S->h_wvol.data(), S->h_wvol.size(), s)) return rc;
-    RT_HIP(acc.reserve(3 * ncs)); RT_HIP(ndeg.reserve(1));
-    RT_HIP(S->cen.reserve(2 * ncs)); RT_HIP(S->cmat.reserve(3 * ncs)); RT_HIP(S->cinv.reserve(4 * ncs));
-    RT_HIP(S->ends.reserve((size_t)std::max<int64_t>(1, 4 * n)));
-    RT_HIP(hipMemsetAsync(ndeg.p, 0, sizeof(int32_t), s));
     const unsigned tb = (unsigned)std::max<int64_t>(1, (n + 255) / 256), cb = (unsigned)((ncs + 255) / 256);
+    struct Drop { rt_solver *S; bool ok = false; ~Drop() { if (!ok) solver_ls_geometry_drop(S); } } drop{S};  // (a failure ends the geometry)
     auto moments = [&]<bool SECOND>() {
         hipLaunchKernelGGL(rt::k_solver_ls_moments<SECOND>, dim3(tb), dim3(256), 0, s, (const int64_t *)t->offsets.p, (const int32_t *)t->counts.p, n,
-                           (const int32_t *)t->azim.p, (const double *)dwvol.p, (const double *)t->cs.p, (const double *)t->sn.p, (const int32_t *)t->element.p,
+                           (const int32_t *)t->azim.p, (const double *)S->ls_wvol.p, (const double *)t->cs.p, (const double *)t->sn.p, (const int32_t *)t->element.p,
                            (const double *)t->spx.p, (const double *)t->spy.p, (const double *)t->sqx.p, (const double *)t->sqy.p,
-                           (const double *)t->sell.p, (const double *)S->cen.p, nc, acc.p, S->ends.p);
+                           (const double *)t->sell.p, (const double *)S->cen.p, nc, S->ls_acc.p, S->ends.p);
     };
-    RT_HIP(hipMemsetAsync(acc.p, 0, 3 * ncs * sizeof(double), s));
-    if (n > 0) moments.template operator()<false>();
-    hipLaunchKernelGGL(rt::k_solver_ls_centroid, dim3(cb), dim3(256), 0, s, (const double *)acc.p, (const double *)S->vol.p, nc, S->cen.p);
-    RT_HIP(hipMemsetAsync(acc.p, 0, 3 * ncs * sizeof(double), s));
-    if (n > 0) moments.template operator()<true>();
-    hipLaunchKernelGGL(rt::k_solver_ls_cmat, dim3(cb), dim3(256), 0, s, (const double *)acc.p, (const double *)S->vol.p, nc, S->cmat.p, S->cinv.p, ndeg.p);
-    int32_t h = 0;
-    RT_HIP(hipMemcpyAsync(&h, ndeg.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    RT_HIP(hipStreamSynchronize(s));  // (the temporary buffers die here)
+    if (stage == 0) {
+        S->ls = false; S->has_geom = false; S->ran_ls = false; S->ls_stage = 0;  // (afresh, whatever there was)
+        if (int rc = ensure_compacted(t)) return rc;
+        if (int rc = upload(S->ls_wvol, S->h_wvol.data(), S->h_wvol.size(), s)) return rc;
+        RT_HIP(S->ls_acc.reserve(3 * ncs)); RT_HIP(S->ls_ndeg.reserve(1));
+        RT_HIP(S->cen.reserve(2 * ncs)); RT_HIP(S->cmat.reserve(3 * ncs)); RT_HIP(S->cinv.reserve(4 * ncs));
+        RT_HIP(S->ends.reserve((size_t)std::max<int64_t>(1, 4 * n)));
+        RT_HIP(hipMemsetAsync(S->ls_ndeg.p, 0, sizeof(int32_t), s));
+        RT_HIP(hipMemsetAsync(S->ls_acc.p, 0, 3 * ncs * sizeof(double), s));
+        if (n > 0) moments.template operator()<false>();
+    } else if (stage == 1) {
+        hipLaunchKernelGGL(rt::k_solver_ls_centroid, dim3(cb), dim3(256), 0, s, (const double *)S->ls_acc.p, (const double *)S->vol.p, nc, S->cen.p);
+        RT_HIP(hipMemsetAsync(S->ls_acc.p, 0, 3 * ncs * sizeof(double), s));
+        if (n > 0) moments.template operator()<true>();
+    } else {
+        hipLaunchKernelGGL(rt::k_solver_ls_cmat, dim3(cb), dim3(256), 0, s, (const double *)S->ls_acc.p, (const double *)S->vol.p, nc, S->cmat.p, S->cinv.p,
+                           S->ls_ndeg.p);
+        int32_t h = 0;
+        RT_HIP(hipMemcpyAsync(&h, S->ls_ndeg.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));  // (the accumulator dies here)
+        RT_HIP(hipGetLastError());
+        solver_ls_geometry_drop(S);
+        S->n_degenerate = h;
+        S->has_geom = true; S->ls = true;
+        drop.ok = true;
+        return RT_SUCCESS;
+    }
     RT_HIP(hipGetLastError());
-    S->n_degenerate = h;
-    S->has_geom = true;
+    if (staged) t->in_flight = true;  // (queued only: rt_wait, or the next call of the library, waits)
+    S->ls_stage = stage + 1;
+    drop.ok = true;
     return RT_SUCCESS;
 }
 
 int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
+    const char *who = "rt_solver_set_linear_source";
     if (!solver) { set_error("rt_solver_set_linear_source: null solver"); return RT_ERR_INVALID; }
     if (!on) { solver->ls = false; return RT_SUCCESS; }
     if (solver->p1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
     try {
         if (!solver->has_geom)
-            if (int32_t rc = solver_ls_geometry(solver)) return rc;
+            for (int32_t stage = 0; stage < 3; ++stage)
+                if (int32_t rc = solver_ls_geometry_stage(solver, stage, false, who)) return rc;
     } catch (const std::exception &e) {
+        solver_ls_geometry_drop(solver);
         set_error("rt_solver_set_linear_source: %s", e.what());
         return RT_ERR_INVALID;
     }
     solver->ls = true;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_ls_geometry(rt_solver *solver, int32_t stage) {
+    const char *who = "rt_solver_ls_geometry";
+    if (!solver) { set_error("rt_solver_ls_geometry: null solver"); return RT_ERR_INVALID; }
+    if (stage < 0 || stage > 2) { set_error("rt_solver_ls_geometry: bad arguments (stage %d)", stage); return RT_ERR_INVALID; }
+    try {
+        return solver_ls_geometry_stage(solver, stage, true, who);
+    } catch (const std::exception &e) {
+        solver_ls_geometry_drop(solver);
+        set_error("rt_solver_ls_geometry: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+int32_t rt_solver_ls_geometry_pointer(rt_solver *solver, void **acc_dev, int64_t *len) {
+    if (!solver) { set_error("rt_solver_ls_geometry_pointer: null solver"); return RT_ERR_INVALID; }
+    // (no wait here: an address and a count only)
+    const bool on = solver->ls_stage != 0;
+    if (acc_dev) *acc_dev = on ? solver->ls_acc.p : nullptr;
+    if (len) *len = on ? 3 * (int64_t)std::max<int32_t>(1, solver->n_cells) : 0;
     return RT_SUCCESS;
 }
 

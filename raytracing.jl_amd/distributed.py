@@ -360,25 +360,45 @@ class ShardedSolver:
 
     * ``ShardedSweep.exchange``: the boundary fluxes that leave the shard go to their owners, the entering ones come in, and the
       scalar tallies T [n_cells, G·P] are summed over the ranks;
-    * with P1 scattering the all-reduce of the first-moment tallies [n_cells, G·P, 2].
+    * with P1 scattering or the linear source the all-reduce of the first-moment tallies [n_cells, G·P, 2].
 
     Every rank then folds the same whole-mesh arrays: k, the residual and with them the stopping decision agree on all ranks, and
     every rank returns the full result.  With the ``nccl`` backend all of this acts on the library's device buffers through
     ``DevArray`` views; no host copy is made.  ``tensors`` (for ``gloo``): a callable that receives the dict of those views
-    (``volumes``, ``tally``, ``tally1``, ``psi_out``, ``psi_in``) and returns the tensors the collectives are to act on instead,
-    e.g. ``lambda v: {k: t.cpu() for k, t in v.items()}``; what the collectives changed is copied back.
+    (``volumes``, ``tally``, ``tally1``, ``psi_out``, ``psi_in``; ``ls_acc`` during the linear source's geometry) and returns the
+    tensors the collectives are to act on instead, e.g. ``lambda v: {k: t.cpu() for k, t in v.items()}``; what the collectives
+    changed is copied back.
 
-    ``scheme="linear"`` raises ``ValueError``: the linear source's geometry (centroids, C) is a sum over tracks which the library
-    takes from the handle's own tracks when the option is switched on, and which would need its own all-reduce before the centroids
-    are formed.  ``solver``: a ready object with the step interface instead of a ``DeviceSolver`` (the CPU tests' numpy stand-in;
-    ``xs`` and ``dt`` may then be None, and its ``pointers()`` returns torch tensors, ``psi_out`` / ``psi_in`` among them)."""
+    ``scheme="linear", staged_geometry=True``: the linear source (not together with ``xs.sigma_s1``).  Without
+    ``staged_geometry=True`` the scheme raises ``ValueError`` as it always did on a shard, so that no caller gets the two extra
+    collectives of the constructor unasked.  Its geometry (centroids, C) is a sum over tracks
+    with a division in its middle, so the constructor runs it in the library's stages (``rt_solver_ls_geometry``), once, after the
+    volumes: stage 0, all-reduce of the accumulator (``rt_solver_ls_geometry_pointer``: first moments), stage 1, all-reduce of the
+    accumulator (second moments), stage 2 — every rank then holds the same centroids, C and degenerate count, also for a cell that
+    none of its own tracks cross.  Per iteration the moment tallies (the ``tally1`` buffer) are summed as with P1 scattering.  The
+    result carries ``flux_moments``, ``flux_gradient`` and ``centroids`` as ``solve_eigenvalue(scheme="linear")`` does.
+
+    ``solver``: a ready object with the step interface instead of a ``DeviceSolver`` (the CPU tests' numpy stand-in; ``xs`` and
+    ``dt`` may then be None, and its ``pointers()`` returns torch tensors, ``psi_out`` / ``psi_in`` among them): ``n_cells``, ``G``,
+    ``P``, ``set_source``, ``begin``, ``step_sweep``, ``step_fold``, ``end``, ``pointers``, ``fetch`` (and ``p1`` / ``fetch_current``
+    with first-moment tallies).  For ``scheme="linear"`` it has the two geometry calls as well — ``ls_geometry(stage)`` and
+    ``ls_geometry_pointer()`` returning ``(tensor or address, doubles)`` — and ``fetch_moments`` / ``fetch_geometry``; without
+    them ``scheme="linear"`` raises ``ValueError``."""
 
     def __init__(self, tg, dt, xs, cell_material, rank, world, *, ranges=None, polar="TY3", azim_weights="exact", scheme="flat",
-                 group=None, device=None, tensors=None, solver=None):
-        if scheme == "linear":
-            raise ValueError('scheme="linear" is not supported on a shard: the linear source\'s geometry is a track sum that would need its own all-reduce')
-        if scheme != "flat":
-            raise ValueError(f"unknown scheme {scheme!r} (flat)")
+                 group=None, device=None, tensors=None, solver=None, staged_geometry=False):
+        if scheme not in ("flat", "linear"):
+            raise ValueError(f"unknown scheme {scheme!r} (flat or linear)")
+        self.linear = scheme == "linear"
+        if self.linear and not staged_geometry:
+            raise ValueError('scheme="linear" on a shard needs staged_geometry=True: the linear source\'s geometry is a track sum that the '
+                             'constructor then builds in stages with two all-reduces of its own (rt_solver_ls_geometry)')
+        if staged_geometry and not self.linear:
+            raise ValueError('staged_geometry=True goes with scheme="linear" only')
+        if self.linear and (getattr(xs, "sigma_s1", None) is not None or getattr(solver, "p1", False)):
+            raise ValueError('scheme="linear" together with sigma_s1 (P1 scattering) is not supported')
+        if self.linear and solver is not None and not (hasattr(solver, "ls_geometry") and hasattr(solver, "ls_geometry_pointer")):
+            raise ValueError('scheme="linear" needs a solver with the geometry calls ls_geometry(stage) and ls_geometry_pointer()')
         self.dt, self.rank, self.world, self.group, self.device = dt, rank, world, group, device
         self._tensors = tensors
         self._coll = None
@@ -405,6 +425,28 @@ class ShardedSolver:
         coll = self._tensors(lib) if self._tensors is not None else lib
         allreduce_volumes(coll["volumes"], group=self.group)
         self._commit(lib, coll, ("volumes",))
+        if self.linear:
+            self._ls_geometry()
+        self.moments = self.p1 or self.linear  # the run has first-moment tallies (tally1) to sum
+
+    def _ls_geometry(self):
+        """The linear source's geometry over the whole track set: the library's stages with the accumulator summed over the ranks
+        after the first-moment pass and after the second-moment pass (the volumes are whole already)."""
+        for stage in (0, 1):
+            self.solver.ls_geometry(stage)
+            self._reduce_ls_accumulator()
+        self.solver.ls_geometry(2)
+
+    def _reduce_ls_accumulator(self):
+        import torch.distributed as dist
+
+        if self.dt is not None:
+            self.dt.wait()  # (stages 0 and 1 only queue their kernels, on the mesh's stream)
+        lib = self._views(("ls_acc",))
+        coll = self._tensors(lib) if self._tensors is not None else lib
+        if self.world > 1:
+            dist.all_reduce(coll["ls_acc"], op=dist.ReduceOp.SUM, group=self.group)
+        self._commit(lib, coll, ("ls_acc",))
 
     def _views(self, names):
         """The library's buffers as torch tensors (zero-copy), by name."""
@@ -416,7 +458,11 @@ class ShardedSolver:
         sp = None
         out = {}
         for k in names:
-            v = p.get(k)
+            if k == "ls_acc":  # (not among rt_solver_pointers: it lives from stage 0 to stage 2 of the geometry only)
+                v, n_acc = self.solver.ls_geometry_pointer()
+                shapes[k] = (int(n_acc),)
+            else:
+                v = p.get(k)
             if v is None and k in ("psi_out", "psi_in"):
                 sp = sp if sp is not None else self.dt.sweep_pointers()
                 v = sp[k]
@@ -448,17 +494,17 @@ class ShardedSolver:
 
         if self.dt is not None:
             self.dt.wait()  # (the sweep is on the mesh's stream, and under the option "async" only queued)
-        names = ("tally", "psi_out", "psi_in") + (("tally1",) if self.p1 else ())
+        names = ("tally", "psi_out", "psi_in") + (("tally1",) if self.moments else ())
         lib = self._views(names)
         coll = self._tensors(lib) if self._tensors is not None else lib
-        if self.p1 and self.world > 1:
+        if self.moments and self.world > 1:
             dist.all_reduce(coll["tally1"], op=dist.ReduceOp.SUM, group=self.group)
         self._coll = (coll["tally"], coll["psi_out"], coll["psi_in"])
         try:
             self.sweep.exchange(self.C)
         finally:
             self._coll = None
-        self._commit(lib, coll, ("tally", "psi_in") + (("tally1",) if self.p1 else ()))
+        self._commit(lib, coll, ("tally", "psi_in") + (("tally1",) if self.moments else ()))
 
     def _iterate(self) -> dict:
         """One iteration of the global problem: sweep, exchange, fold — in this order (a fold before the exchange would use this
@@ -493,6 +539,9 @@ class ShardedSolver:
         r = sv.end()
         f = sv.fetch(r["iterations"])
         it = r["iterations"]
+        mom = sv.fetch_moments() if self.linear else dict(flux_moments=None, flux_gradient=None)
+        centroids = sv.fetch_geometry()["centroids"] if self.linear else None
         return SolverResult(k_eff=r["k_eff"] if mode == 0 else None, phi=f["phi"], volumes=f["volumes"], iterations=it,
                             converged=converged, k_history=f["k_history"], ms_per_iteration=r["device_ms"] / it if it else 0.0,
-                            residual=r["residual"], solver=sv, current=sv.fetch_current() if self.p1 else None)
+                            residual=r["residual"], solver=sv, current=sv.fetch_current() if self.p1 else None,
+                            flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids)
