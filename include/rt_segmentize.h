@@ -508,6 +508,32 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  * Iteration    φ⃗⁰ = 0; k, residual, stopping rule and normalisation are unchanged and use φ only (eigenvalue mode scales φ⃗
  *              with φ).  Together with first-moment scattering it is not supported: whichever is switched on second fails
  *
+ * Adjoint mode, rt_solver_set_adjoint.  The one-collision operator K_g of a group satisfies D K_g = (D K_g)ᵀ with D = diag(V_e) in
+ * this discretisation (along a track the weight w (1 − e^{−τ'}) e^{−τ_between} (1 − e^{−τ}) is the same for the reversed traversal,
+ * and every track is swept in both directions with one weight), so the adjoint iteration is the forward one on transposed data:
+ * the same kernels on a material table with Σs[g'→g] := Σs[g→g'], χ_g in the νΣf slot (zero in a material without fission,
+ * Σ_g νΣf_g = 0: a stray χ in a moderator does not enter F†) and νΣf_g in the χ slot; with first-moment scattering Σs1 is
+ * transposed likewise (in either order of the two calls).
+ * Iterate      φ† of the transposed problem: φ†_{e,g} = 4π q†_{e,g} / Σt_g + (fold of the sweep, as above) with
+ *              q†_{e,g} = (Σ_g' Σs[g→g'] φ†_{e,g'} + (νΣf_g / k) Σ_g' χ_g' φ†_{e,g'} + S†_{e,g}) / 4π
+ * Production   F†(φ†) = Σ_e V_e Σ_g χ_g φ†_{e,g} over the cells of fissile materials drives k, the residual and the normalisation
+ *              (eigenvalue mode scales the returned φ† to F† = 1).  The discrete spectra are equal: k† = k up to iteration error
+ * Source       the external source of a fixed-source run is the adjoint source S† (for instance a detector cross section);
+ *              reciprocity: Σ_e V_e Σ_g S†_{e,g} φ_{e,g} = Σ_e V_e Σ_g S_{e,g} φ†_{e,g}
+ * Current      with Σs1 the returned current is that of the transposed problem, J*.  The adjoint angular flux is
+ *              ψ†(Ω) = ψ*(−Ω), so J† = −J*
+ * Linear       with the linear source, the moments φ⃗ and the gradient are those of φ†.  Behind records that do not start where the
+ *              previous one ended (see "Geometry") the running midpoints of the two directions differ and the LS discretisation
+ *              is self-adjoint only up to those gaps
+ * The stepwise calls, rt_solver_pointers, the fetches and the sharded contract hold also in adjoint mode.
+ *
+ * Adjoint-weighted bilinear forms, rt_solver_bilinear.  For matrices A_f[m][g'][g] ("from g' to g", as sigma_s)
+ *              B_f = Σ_e V_e Σ_g Σ_g' φ†_{e,g} A_f[m(e)][g'→g] φ_{e,g'}
+ * with φ† the last run's flux of `adjoint`, φ that of `forward`, V and cell_material those of `forward`; cells with V_e = 0 drop
+ * out.  One thread per cell, block sums, one workgroup over the block partials in a fixed order: no FP64 atomics, two calls on the
+ * same data return the same bits.  First-order perturbation theory (flat source, isotropic scattering), X = S + F/k:
+ *              δ(1/k) = − ⟨φ†, (δS + δF/k) φ⟩ / ⟨φ†, F φ⟩,   F[g'→g] = χ_g νΣf_g',  S[g'→g] = Σs[g'→g]
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -589,6 +615,16 @@ int32_t rt_solver_fetch(rt_solver *solver, double *phi, double *volumes, double 
  * isotropic scattering, which runs exactly the kernels of a solver that never had any.  RT_ERR_INVALID when an entry is not
  * finite or exceeds Σs0 in magnitude (the solver keeps what it had). */
 int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1);
+/* Adjoint mode (see above) on (non-zero) or off for the following runs: rebuilds the device material table, and the first-moment
+ * table when first-moment scattering is set, from host copies.  Off restores the forward tables; a solver that never had it on
+ * launches exactly what it always did.  RT_ERR_INVALID with a run open (rt_solver_begin without rt_solver_end) or after the
+ * tracks were segmentized again; the solver then keeps the tables it had. */
+int32_t rt_solver_set_adjoint(rt_solver *solver, int32_t on);
+/* Bilinear forms B_f (see above) of n_forms (1 .. 8) matrix sets A [n_forms][M][G][G] (host memory, A[f][m][g'][g]) into
+ * out [n_forms]; out_cell [n_forms][n_cells] (may be NULL) receives each cell's V_e-weighted contribution.  Both solvers must have
+ * completed a run and have none open, be bound to the same tracks at the same segmentation and agree in G, M and the number of
+ * cells; `adjoint == forward` is allowed (plain ⟨φ, Aφ⟩).  RT_ERR_INVALID otherwise, or when an entry of A is not finite. */
+int32_t rt_solver_bilinear(rt_solver *adjoint, rt_solver *forward, int32_t n_forms, const double *A, double *out, double *out_cell);
 /* The net current J [n_cells][G][2] (x, y) of the last run.  RT_ERR_INVALID before a run, or when that run had no
  * first-moment scattering. */
 int32_t rt_solver_fetch_current(rt_solver *solver, double *J);

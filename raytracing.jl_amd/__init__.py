@@ -6,7 +6,8 @@ Host-side mirror of the reference's public surface (``src/RayTracing.jl:32-35``)
 hand-written HIP kernels in ``csrc/`` through the C ABI declared in
 ``include/rt_segmentize.h``; there is no CPU fallback — without the built library or
 without a GPU it raises.  ``solve_eigenvalue`` / ``solve_fixed_source`` run a MOC
-source iteration on the device over the records of the last ``segmentize``.
+source iteration on the device over the records of the last ``segmentize``, forward or
+adjoint; ``perturbation_reactivity`` / ``kinetics_parameters`` weigh with the adjoint flux.
 """
 from .boundary import BoundaryConditions, BoundaryType, Periodic, Reflective, Vacuum
 from .mesh import DiscreteModel, DiscreteModelFromFile, GmshDiscreteModel, Mesh, data_path
@@ -15,7 +16,7 @@ from .trackgenerator import (Backward, Forward, Segment, Track, TrackGenerator, 
                              dir_next_track_bwd, dir_next_track_fwd, trace)
 from .segmentize import RTOL_DEFAULT, SegmentStore, segmentize
 from .solver import (CrossSections, PolarQuadrature, SolverResult, azimuthal_weights, exact_azimuthal_weights,
-                     solve_eigenvalue, solve_fixed_source)
+                     kinetics_parameters, perturbation_reactivity, solve_eigenvalue, solve_fixed_source)
 from .distributed import ShardedSolver
 
 __all__ = [
@@ -24,6 +25,6 @@ __all__ = [
     "AzimuthalQuadrature", "TrackGenerator", "trace", "segmentize", "SegmentStore", "RTOL_DEFAULT",
     "Track", "Segment",
     "CrossSections", "PolarQuadrature", "SolverResult", "azimuthal_weights", "exact_azimuthal_weights",
-    "solve_eigenvalue", "solve_fixed_source", "ShardedSolver",
+    "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "ShardedSolver",
     "Forward", "Backward", "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd",
 ]

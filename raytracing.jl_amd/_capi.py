@@ -32,6 +32,7 @@ SYMBOLS = (
     "rt_solver_ls_geometry", "rt_solver_ls_geometry_pointer",
     "rt_solver_fetch_current",
     "rt_solver_begin", "rt_solver_step_sweep", "rt_solver_step_fold", "rt_solver_end", "rt_solver_pointers",
+    "rt_solver_set_adjoint", "rt_solver_bilinear",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -231,6 +232,10 @@ def lib():
     L.rt_solver_destroy.argtypes = [_vp]
     L.rt_solver_set_scatter_p1.restype = C.c_int32
     L.rt_solver_set_scatter_p1.argtypes = [_vp, _dp]
+    L.rt_solver_set_adjoint.restype = C.c_int32
+    L.rt_solver_set_adjoint.argtypes = [_vp, C.c_int32]
+    L.rt_solver_bilinear.restype = C.c_int32
+    L.rt_solver_bilinear.argtypes = [_vp, _vp, C.c_int32, _dp, _dp, _dp]
     L.rt_solver_fetch_current.restype = C.c_int32
     L.rt_solver_fetch_current.argtypes = [_vp, _dp]
     L.rt_solver_set_linear_source.restype = C.c_int32
@@ -715,6 +720,39 @@ class DeviceSolver:
         if s1.shape != (self.M, self.G, self.G):
             raise ValueError("sigma_s1 must have shape [M, G, G]")
         _check(lib().rt_solver_set_scatter_p1(self._h, s1.ctypes.data_as(_dp)))
+
+    def set_adjoint(self, on=True):
+        """``rt_solver_set_adjoint``: the adjoint (transposed) problem for the following runs (False: the forward one again)."""
+        _check(lib().rt_solver_set_adjoint(self._open(), 1 if on else 0))
+
+    def bilinear(self, forward, A, per_cell=False):
+        """``rt_solver_bilinear`` with this solver's flux as φ† and ``forward``'s as φ: B_f = Σ_e V_e Σ_g Σ_g' φ†[e, g] A[f, m(e), g', g]
+        φ[e, g'] for ``A`` [n_forms, M, G, G] (or [M, G, G]: one form, a scalar returned); any number of forms (the library takes
+        8 per call).  ``per_cell=True``: ``(B, cells)`` with ``cells`` [n_forms, n_cells] the cells' V-weighted contributions."""
+        a = np.ascontiguousarray(A, np.float64)
+        single = a.ndim == 3
+        a = a[None] if single else a
+        if a.ndim != 4 or a.shape[1:] != (self.M, self.G, self.G) or a.shape[0] < 1:
+            raise ValueError("A must have shape [n_forms, M, G, G] (or [M, G, G])")
+        if not isinstance(forward, DeviceSolver):
+            raise TypeError("forward must be a DeviceSolver")
+        nf = a.shape[0]
+        out = np.empty(nf)
+        cells = np.empty((nf, self.n_cells)) if per_cell else None
+        for lo in range(0, nf, 8):
+            hi = min(nf, lo + 8)
+            blk = np.ascontiguousarray(a[lo:hi])
+            o = np.empty(hi - lo)
+            c = np.empty((hi - lo, self.n_cells)) if per_cell else None
+            _check(lib().rt_solver_bilinear(self._open(), forward._open(), hi - lo, blk.ctypes.data_as(_dp), o.ctypes.data_as(_dp),
+                                            None if c is None else c.ctypes.data_as(_dp)))
+            out[lo:hi] = o
+            if per_cell:
+                cells[lo:hi] = c
+        res = float(out[0]) if single else out
+        if per_cell:
+            return res, (cells[0] if single else cells)
+        return res
 
     def fetch_current(self) -> np.ndarray:
         """``rt_solver_fetch_current``: the net current [n_cells, G, 2] of the last run (with first-moment scattering)."""

@@ -340,6 +340,75 @@ __global__ __launch_bounds__(256) void k_solver_scale(double *__restrict__ phi, 
     if (i < n) phi[i] = phi[i] / scal[1];
 }
 
+// ---- adjoint-weighted bilinear forms (rt_solver_bilinear) ---------------------------------------------------------------------
+constexpr int kMaxForms = 8;
+
+// B_f = Σ_e V_e Σ_g Σ_g' φ†[e][g] A_f[m(e)][g'][g] φ[e][g'] for n_forms <= kMaxForms forms, one thread per cell: the cell's V-weighted
+// terms into `cell` [n_forms][n_cells] (when given) and this block's sums into partial[block][kMaxForms].  The matrices A
+// [n_forms][M][G][G] from LDS when the host says they fit (a_len doubles; 0 = read them where they lie).  Cells with V_e = 0
+// contribute 0.
+__global__ __launch_bounds__(kSolveBlock) void k_solver_bilinear(const int32_t *__restrict__ mat, const double *__restrict__ A_g, int32_t a_len,
+                                                                 const double *__restrict__ vol, const double *__restrict__ phi_adj,
+                                                                 const double *__restrict__ phi, int32_t n_cells, int32_t G, int32_t M,
+                                                                 int32_t n_forms, double *__restrict__ cell, double *__restrict__ partial) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char solver_smem[];
+    __shared__ double red[(kSolveBlock / 64) * kMaxForms];
+    const double *A = A_g;
+    if (a_len > 0) {
+        double *t = reinterpret_cast<double *>(solver_smem);
+        for (int i = threadIdx.x; i < a_len; i += blockDim.x) t[i] = A_g[i];
+        __syncthreads();
+        A = t;
+    }
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    double v[kMaxForms];
+#pragma unroll
+    for (int f = 0; f < kMaxForms; ++f) v[f] = 0.0;
+    if (e < n_cells) {
+        const double V = vol[e];
+        if (V > 0.0) {
+            const int64_t GG = (int64_t)G * G, MGG = (int64_t)M * GG;
+            const double *Am = A + (int64_t)mat[e] * GG;
+            const double *pa = phi_adj + e * G, *pf = phi + e * G;
+            for (int32_t gp = 0; gp < G; ++gp) {
+                const double x = pf[gp];
+                for (int32_t g = 0; g < G; ++g) {
+                    const double w = pa[g] * x;
+                    const double *a = Am + gp * G + g;
+#pragma unroll
+                    for (int f = 0; f < kMaxForms; ++f)
+                        if (f < n_forms) v[f] += a[f * MGG] * w;
+                }
+            }
+#pragma unroll
+            for (int f = 0; f < kMaxForms; ++f) v[f] *= V;
+        }
+        if (cell)
+#pragma unroll
+            for (int f = 0; f < kMaxForms; ++f)
+                if (f < n_forms) cell[(int64_t)f * n_cells + e] = v[f];
+    }
+    block_sum<kMaxForms>(v, red);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int f = 0; f < kMaxForms; ++f) partial[(int64_t)blockIdx.x * kMaxForms + f] = v[f];
+}
+
+// one workgroup: the block partials of k_solver_bilinear in a fixed order -> out[kMaxForms]
+__global__ __launch_bounds__(kSolveBlock) void k_solver_bilinear_reduce(const double *__restrict__ partial, int32_t n_blocks, double *__restrict__ out) {
+    __shared__ double red[(kSolveBlock / 64) * kMaxForms];
+    double v[kMaxForms];
+#pragma unroll
+    for (int f = 0; f < kMaxForms; ++f) v[f] = 0.0;
+    for (int32_t b = threadIdx.x; b < n_blocks; b += blockDim.x)
+#pragma unroll
+        for (int f = 0; f < kMaxForms; ++f) v[f] += partial[(int64_t)b * kMaxForms + f];
+    block_sum<kMaxForms>(v, red);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int f = 0; f < kMaxForms; ++f) out[f] = v[f];
+}
+
 // per-track weights of the sweep (4π α δ) and per-angle weights of the volumes (2 α δ)
 __global__ __launch_bounds__(256) void k_solver_track_weights(const int32_t *__restrict__ azim, int64_t n, const double *__restrict__ w4pi,
                                                               double *__restrict__ w) {
@@ -359,6 +428,9 @@ struct rt_solver {
     bool has_ext = false, ran = false;
     // first-moment scattering (rt_solver_set_scatter_p1)
     std::vector<double> h_st, h_ss;  // Σt, Σs0 as given (the first moments are checked against them)
+    // adjoint mode (rt_solver_set_adjoint): the tables are rebuilt from the host copies, νΣf, χ and Σs1 (when set) among them
+    std::vector<double> h_nf, h_chi, h_s1;
+    bool adjoint = false;
     DevBuf<double> tab1, J, q1r;     // table (see mat_row_p1); net current and q1/Σt [n_cells][G][2]
     bool p1 = false, ran_p1 = false;
     // linear source (rt_solver_set_linear_source)
@@ -411,6 +483,41 @@ void free_solver(rt_solver *s) {
     for (hipEvent_t &e : s->ev)
         if (e) (void)hipEventDestroy(e);
     delete s;
+}
+
+// The material table (see mat_row) from the solver's host copies.  Adjoint: Σs transposed, χ in the νΣf slot — zero for a material
+// without fission (Σ_g νΣf = 0), so that a stray χ there does not enter F† — and νΣf in the χ slot.
+std::vector<double> solver_table(const rt_solver *S, bool adjoint) {
+    const int32_t G = S->G, M = S->M;
+    std::vector<double> tab((size_t)M * G * (3 + G));
+    for (int32_t mm = 0; mm < M; ++mm) {
+        double *X = tab.data() + (size_t)mm * G * (3 + G);
+        const double *nf = S->h_nf.data() + (size_t)mm * G, *ch = S->h_chi.data() + (size_t)mm * G, *ss = S->h_ss.data() + (size_t)mm * G * G;
+        double fis = 0.0;
+        for (int32_t g = 0; g < G; ++g) fis += nf[g];
+        for (int32_t g = 0; g < G; ++g) {
+            X[g] = S->h_st[(size_t)mm * G + g];
+            X[G + g] = adjoint ? (fis > 0.0 ? ch[g] : 0.0) : nf[g];
+            X[2 * G + g] = adjoint ? nf[g] : ch[g];
+        }
+        for (int32_t a = 0; a < G; ++a)
+            for (int32_t b = 0; b < G; ++b) X[3 * G + a * G + b] = adjoint ? ss[b * G + a] : ss[a * G + b];
+    }
+    return tab;
+}
+
+// The first-moment table (see mat_row_p1) from the host copies; adjoint: Σs1 transposed.
+std::vector<double> solver_table_p1(const rt_solver *S, const double *sigma_s1, bool adjoint) {
+    const int32_t G = S->G, M = S->M;
+    std::vector<double> tab((size_t)M * G * (1 + G));
+    for (int32_t mm = 0; mm < M; ++mm) {
+        double *X = tab.data() + (size_t)mm * G * (1 + G);
+        const double *s1 = sigma_s1 + (size_t)mm * G * G;
+        for (int32_t g = 0; g < G; ++g) X[g] = S->h_st[(size_t)mm * G + g];
+        for (int32_t a = 0; a < G; ++a)
+            for (int32_t b = 0; b < G; ++b) X[G + a * G + b] = adjoint ? s1[b * G + a] : s1[a * G + b];
+    }
+    return tab;
 }
 
 int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_material, const double *sigma_t, const double *sigma_s,
@@ -470,17 +577,8 @@ int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_m
     struct Guard { rt_solver *&p; ~Guard() { free_solver(p); } } guard{S};
     S->h_st.assign(sigma_t, sigma_t + mg); S->h_ss.assign(sigma_s, sigma_s + mg * G);
     S->t = t; S->device = m->device; S->epoch = t->seg_epoch; S->G = G; S->M = M; S->P = P; S->N2 = N2; S->n_cells = nc;
-    // material table (see mat_row)
-    std::vector<double> tab((size_t)M * G * (3 + G));
-    for (int32_t mm = 0; mm < M; ++mm) {
-        double *X = tab.data() + (size_t)mm * G * (3 + G);
-        for (int32_t g = 0; g < G; ++g) {
-            X[g] = sigma_t[(size_t)mm * G + g];
-            X[G + g] = nu_sigma_f[(size_t)mm * G + g];
-            X[2 * G + g] = chi[(size_t)mm * G + g];
-        }
-        for (size_t i = 0; i < (size_t)G * G; ++i) X[3 * G + i] = sigma_s[(size_t)mm * G * G + i];
-    }
+    S->h_nf.assign(nu_sigma_f, nu_sigma_f + mg); S->h_chi.assign(chi, chi + mg);
+    const std::vector<double> tab = solver_table(S, false);
     std::vector<double> pol((size_t)2 * P);
     for (int32_t p = 0; p < P; ++p) { pol[(size_t)p] = sin_polar[p]; pol[(size_t)(P + p)] = polar_weight[p] * sin_polar[p]; }
     std::vector<double> w4pi((size_t)N2), wvol((size_t)N2);
@@ -794,16 +892,13 @@ static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) 
             set_error("rt_solver_set_scatter_p1: sigma_s1[%zu] = %g against sigma_s = %g (must be finite with |Σs1| <= Σs0)", i, sigma_s1[i], S->h_ss[i]);
             return RT_ERR_INVALID;
         }
-    std::vector<double> tab((size_t)M * G * (1 + G));
-    for (int32_t mm = 0; mm < M; ++mm) {
-        double *X = tab.data() + (size_t)mm * G * (1 + G);
-        for (int32_t g = 0; g < G; ++g) X[g] = S->h_st[(size_t)mm * G + g];
-        for (size_t i = 0; i < (size_t)G * G; ++i) X[G + i] = sigma_s1[(size_t)mm * G * G + i];
-    }
+    const std::vector<double> tab = solver_table_p1(S, sigma_s1, S->adjoint);
+    std::vector<double> keep(sigma_s1, sigma_s1 + n1);  // (rt_solver_set_adjoint rebuilds the table from it)
     if (int rc = finish_call(S->t)) return rc;
     RT_HIP(hipSetDevice(S->t->mesh->device));
     if (int rc = upload(S->tab1, tab.data(), tab.size(), S->t->mesh->stream)) return rc;
     RT_HIP(hipStreamSynchronize(S->t->mesh->stream));
+    S->h_s1.swap(keep);
     S->p1 = true;
     return RT_SUCCESS;
 }
@@ -813,6 +908,90 @@ int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1) {
         return solver_set_scatter_p1_impl(solver, sigma_s1);
     } catch (const std::exception &e) {
         set_error("rt_solver_set_scatter_p1: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+// Adjoint mode: the device tables of the transposed problem (solver_table, solver_table_p1), or the forward ones again.  The
+// kernels of the iteration read the tables they always read.
+static int32_t solver_set_adjoint_impl(rt_solver *S, int32_t on) {
+    const char *who = "rt_solver_set_adjoint";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the tables cannot change under it", who); return RT_ERR_INVALID; }
+    const bool adj = on != 0;
+    if (adj == S->adjoint) return RT_SUCCESS;
+    const std::vector<double> tab = solver_table(S, adj);
+    std::vector<double> tab1;
+    if (S->p1) tab1 = solver_table_p1(S, S->h_s1.data(), adj);
+    if (int rc = finish_call(S->t)) return rc;
+    RT_HIP(hipSetDevice(S->t->mesh->device));
+    hipStream_t s = S->t->mesh->stream;
+    if (int rc = upload(S->tab, tab.data(), tab.size(), s)) return rc;
+    if (S->p1)
+        if (int rc = upload(S->tab1, tab1.data(), tab1.size(), s)) return rc;
+    RT_HIP(hipStreamSynchronize(s));  // (the host vectors die here)
+    S->adjoint = adj;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_adjoint(rt_solver *solver, int32_t on) {
+    try {
+        return solver_set_adjoint_impl(solver, on);
+    } catch (const std::exception &e) {
+        set_error("rt_solver_set_adjoint: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+static int32_t solver_bilinear_impl(rt_solver *Sa, rt_solver *Sf, int32_t n_forms, const double *A, double *out, double *out_cell) {
+    const char *who = "rt_solver_bilinear";
+    if (!Sa || !Sf || !A || !out) { set_error("%s: null argument", who); return RT_ERR_INVALID; }
+    if (n_forms < 1 || n_forms > rt::kMaxForms) { set_error("%s: bad arguments (n_forms %d, need 1 .. %d)", who, n_forms, rt::kMaxForms); return RT_ERR_INVALID; }
+    if (Sa->t != Sf->t) { set_error("%s: the two solvers are bound to different tracks", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(Sf, who)) return rc;
+    if (Sa->epoch != Sf->epoch) { set_error("%s: the two solvers were created at different segmentations of the tracks", who); return RT_ERR_INVALID; }
+    if (Sa->G != Sf->G || Sa->M != Sf->M || Sa->n_cells != Sf->n_cells) {
+        set_error("%s: the two solvers differ in shape (G %d / %d, M %d / %d, cells %d / %d)", who, Sa->G, Sf->G, Sa->M, Sf->M, Sa->n_cells, Sf->n_cells);
+        return RT_ERR_INVALID;
+    }
+    for (const rt_solver *S : {Sa, Sf}) {
+        const char *which = S == Sf ? "forward" : "adjoint";
+        if (S->open) { set_error("%s: the %s solver has a run open (rt_solver_end comes first)", who, which); return RT_ERR_INVALID; }
+        if (!S->ran) { set_error("%s: the %s solver has no completed run", who, which); return RT_ERR_INVALID; }
+    }
+    const int32_t G = Sf->G, M = Sf->M, nc = Sf->n_cells;
+    const size_t a_len = (size_t)n_forms * M * G * G;
+    for (size_t i = 0; i < a_len; ++i)
+        if (!std::isfinite(A[i])) { set_error("%s: A[%zu] = %g (must be finite)", who, i, A[i]); return RT_ERR_INVALID; }
+    rt_tracks *t = Sf->t;
+    if (int rc = finish_call(t)) return rc;
+    RT_HIP(hipSetDevice(t->mesh->device));
+    hipStream_t s = t->mesh->stream;
+    const unsigned blocks = (unsigned)std::max(1, (nc + rt::kSolveBlock - 1) / rt::kSolveBlock);
+    DevBuf<double> dA, partial, dout, dcell;
+    if (int rc = upload(dA, A, a_len, s)) return rc;
+    RT_HIP(partial.reserve((size_t)blocks * rt::kMaxForms)); RT_HIP(dout.reserve(rt::kMaxForms));
+    if (out_cell) RT_HIP(dcell.reserve(std::max<size_t>(1, (size_t)n_forms * nc)));
+    const int32_t lds_len = a_len * sizeof(double) <= 32 * 1024 ? (int32_t)a_len : 0;  // (else read where they lie: L2-resident)
+    hipLaunchKernelGGL(rt::k_solver_bilinear, dim3(blocks), dim3(rt::kSolveBlock), (size_t)lds_len * sizeof(double), s, (const int32_t *)Sf->mat.p,
+                       (const double *)dA.p, lds_len, (const double *)Sf->vol.p, (const double *)Sa->phi.p, (const double *)Sf->phi.p, nc, G, M, n_forms,
+                       out_cell ? dcell.p : (double *)nullptr, partial.p);
+    hipLaunchKernelGGL(rt::k_solver_bilinear_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)partial.p, (int32_t)blocks, dout.p);
+    RT_HIP(hipGetLastError());
+    double h[rt::kMaxForms];
+    RT_HIP(hipMemcpyAsync(h, dout.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    if (out_cell && nc > 0) RT_HIP(hipMemcpyAsync(out_cell, dcell.p, (size_t)n_forms * nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));  // (the temporary device buffers die here)
+    for (int32_t f = 0; f < n_forms; ++f) out[f] = h[f];
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_bilinear(rt_solver *adjoint, rt_solver *forward, int32_t n_forms, const double *A, double *out, double *out_cell) {
+    try {
+        return solver_bilinear_impl(adjoint, forward, n_forms, A, out, out_cell);
+    } catch (const std::exception &e) {
+        set_error("rt_solver_bilinear: %s", e.what());
         return RT_ERR_INVALID;
     }
 }

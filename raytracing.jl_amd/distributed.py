@@ -383,10 +383,13 @@ class ShardedSolver:
     ``P``, ``set_source``, ``begin``, ``step_sweep``, ``step_fold``, ``end``, ``pointers``, ``fetch`` (and ``p1`` / ``fetch_current``
     with first-moment tallies).  For ``scheme="linear"`` it has the two geometry calls as well — ``ls_geometry(stage)`` and
     ``ls_geometry_pointer()`` returning ``(tensor or address, doubles)`` — and ``fetch_moments`` / ``fetch_geometry``; without
-    them ``scheme="linear"`` raises ``ValueError``."""
+    them ``scheme="linear"`` raises ``ValueError``.
+
+    ``adjoint=True``: the adjoint problem (``rt_solver_set_adjoint`` on the rank's solver, before the first ``begin``).  Nothing in
+    the exchange changes: the links already carry both directions.  A ``solver`` given ready needs ``set_adjoint`` for it."""
 
     def __init__(self, tg, dt, xs, cell_material, rank, world, *, ranges=None, polar="TY3", azim_weights="exact", scheme="flat",
-                 group=None, device=None, tensors=None, solver=None, staged_geometry=False):
+                 group=None, device=None, tensors=None, solver=None, staged_geometry=False, adjoint=False):
         if scheme not in ("flat", "linear"):
             raise ValueError(f"unknown scheme {scheme!r} (flat or linear)")
         self.linear = scheme == "linear"
@@ -418,6 +421,11 @@ class ShardedSolver:
                 solver.set_scatter_p1(xs.sigma_s1)
         else:
             self.p1 = bool(getattr(solver, "p1", self.p1))
+        self.adjoint = bool(adjoint)
+        if self.adjoint:
+            if not hasattr(solver, "set_adjoint"):
+                raise ValueError("adjoint=True needs a solver with set_adjoint(on)")
+            solver.set_adjoint(True)
         self.solver = solver
         self.n_cells, self.C = solver.n_cells, solver.G * solver.P
         # the volumes: every rank has summed its own tracks' chords; the fold needs the whole sums (once: they do not change)
@@ -544,4 +552,5 @@ class ShardedSolver:
         return SolverResult(k_eff=r["k_eff"] if mode == 0 else None, phi=f["phi"], volumes=f["volumes"], iterations=it,
                             converged=converged, k_history=f["k_history"], ms_per_iteration=r["device_ms"] / it if it else 0.0,
                             residual=r["residual"], solver=sv, current=sv.fetch_current() if self.p1 else None,
-                            flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids)
+                            flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids,
+                            adjoint=self.adjoint)

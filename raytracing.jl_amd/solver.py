@@ -10,6 +10,9 @@ in ``include/rt_segmentize.h``.  With ``CrossSections(..., sigma_s1=...)`` scatt
 sweep's source depends on the direction of travel, first angular moments are tallied and ``SolverResult.current`` is the
 net current.  With ``scheme="linear"`` the source of a cell is linear in space (LS-MOC: a coarser mesh resolves the same flux
 gradient); ``SolverResult.flux_moments``, ``flux_gradient`` and ``centroids`` describe the flux inside the cells.
+With ``adjoint=True`` the same iteration runs on the transposed problem (``rt_solver_set_adjoint``) and returns the adjoint flux φ†;
+``perturbation_reactivity`` and ``kinetics_parameters`` weigh cross-section changes and kinetics data with it
+(``rt_solver_bilinear``).
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ from . import _capi
 from .trackgenerator import TrackGenerator
 
 __all__ = ["CrossSections", "PolarQuadrature", "SolverResult", "exact_azimuthal_weights", "azimuthal_weights",
-           "solve_eigenvalue", "solve_fixed_source"]
+           "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters"]
 
 
 class CrossSections:
@@ -163,6 +166,7 @@ class SolverResult:
     flux_moments: Optional[np.ndarray] = None   # scheme="linear": (φx, φy) [n_cells, G, 2], the moments of φ about the centroid
     flux_gradient: Optional[np.ndarray] = None  # ... C⁻¹ φ⃗ [n_cells, G, 2]: φ(r) ≈ phi + flux_gradient·(r − centroid)
     centroids: Optional[np.ndarray] = None      # ... track-based cell centroids [n_cells, 2]; all three None when flat
+    adjoint: bool = False         # True: phi (current, flux_moments, ...) are the adjoint quantities of include/rt_segmentize.h
 
 
 def _cell_material(tg, cell_material):
@@ -192,7 +196,7 @@ def _device_tracks(tg, device):
     return dt
 
 
-def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat"):
+def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat", adjoint=False):
     if not isinstance(xs, CrossSections):
         raise TypeError("xs must be a CrossSections")
     if scheme not in ("flat", "linear"):
@@ -211,6 +215,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         sv.set_scatter_p1(xs.sigma_s1)
     if linear:
         sv.set_linear_source(True)
+    if adjoint:
+        sv.set_adjoint(True)
     r = sv.run(mode, int(max_iter), float(tol_k), float(tol_flux))
     f = sv.fetch(r["iterations"])
     mom = sv.fetch_moments() if linear else dict(flux_moments=None, flux_gradient=None)
@@ -220,25 +226,111 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
-                        flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids)
+                        flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids, adjoint=bool(adjoint))
 
 
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
-                     tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat") -> SolverResult:
+                     tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False) -> SolverResult:
     """Power iteration for k_eff on the device.  ``cell_material``: material index per cell [n_cells] (or one index for all,
     or a dict region name -> index over ``tg.mesh.model.cell_region``).  ``polar``: a ``PolarQuadrature`` spec;
     ``azim_weights``: "exact", "equal" or an array.  Uses ``tg.device_tracks`` when ``segmentize(tg, fetch=False)`` has run,
     else segmentizes first; the boundary conditions are the ones ``trace`` linked.  ``scheme``: "flat" (a constant source per cell)
-    or "linear" (a source linear in space per cell; not together with ``sigma_s1``)."""
-    return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme)
+    or "linear" (a source linear in space per cell; not together with ``sigma_s1``).  ``adjoint=True``: the adjoint problem — the
+    same k_eff, ``phi`` the adjoint flux φ† scaled to Σ_e V_e Σ_g χ_g φ† = 1 over the fissile cells (``current``: that of the
+    transposed problem, J† = −J*; ``flux_moments``: those of φ†)."""
+    return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
+                  adjoint)
 
 
 def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
-                       tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat") -> SolverResult:
+                       tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False) -> SolverResult:
     """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
-    the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``."""
+    the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``; with ``adjoint=True`` ``source`` is the
+    adjoint source S† (for instance a detector cross section) and ``phi`` the importance φ†: Σ V S† φ = Σ V S φ†."""
     q = np.asarray(source, np.float64)
     G = xs.n_groups
     if q.ndim == 0 or q.shape == (G,):
         q = np.broadcast_to(q, (tg.mesh.num_cells, G))
-    return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme)
+    return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
+                  adjoint)
+
+
+# ---- adjoint-weighted integrals ------------------------------------------------------------------------------------------------
+def _bilinear(forward, adjoint, A, cell_material):
+    """B_f = Σ_e V_e Σ_g Σ_g' φ†[e, g] A[f, m(e), g', g] φ[e, g'] for A [n_forms, M, G, G]: on the device (``rt_solver_bilinear``)
+    when the two results carry their device solvers; for host results (``solver`` None: the numpy twins of the tests) by
+    ``numpy.einsum`` with ``cell_material`` [n_cells], which they do not carry."""
+    sa, sf = getattr(adjoint, "solver", None), getattr(forward, "solver", None)
+    if sa is not None and sf is not None:
+        return np.asarray(sa.bilinear(sf, A))
+    if sa is not None or sf is not None:
+        raise ValueError("one result carries a device solver and the other does not")
+    if cell_material is None:
+        raise ValueError("host results carry no materials: cell_material [n_cells] is needed")
+    mat = np.asarray(cell_material, np.int64)
+    V = np.asarray(forward.volumes, np.float64)
+    live = V > 0
+    return np.einsum("e,eg,fehg,eh->f", V[live], np.asarray(adjoint.phi)[live], np.asarray(A)[:, mat[live]], np.asarray(forward.phi)[live])
+
+
+def _fission_form(xs):
+    """F[m, g', g] = χ_g νΣf_g'."""
+    return xs.nu_sigma_f[:, :, None] * xs.chi[:, None, :]
+
+
+def _check_pair(forward, adjoint):
+    if getattr(forward, "adjoint", False) or not getattr(adjoint, "adjoint", True):
+        raise ValueError("forward must be a forward result and adjoint an adjoint one (solve_eigenvalue(..., adjoint=True))")
+    if forward.k_eff is None:
+        raise ValueError("forward must be an eigenvalue result")
+
+
+def perturbation_reactivity(forward, adjoint, xs: CrossSections, xs_perturbed: CrossSections, cell_material=None) -> dict:
+    """First-order estimate of the reactivity change Δρ = ρ' − ρ (ρ = 1 − 1/k) when ``xs`` becomes ``xs_perturbed`` (same materials
+    and groups), from the forward and the adjoint eigenvalue results of the unperturbed problem:
+
+        Δρ = ((1/k) B(ΔF) − B(ΔΣt) + B(ΔS)) / B(F),    B(A) = Σ_e V_e Σ_g Σ_g' φ†_{e,g} A[m(e)][g'→g] φ_{e,g'}
+
+    with F = χ ⊗ νΣf, ΔF the difference of the two outer products, ΔS = ΔΣs0 and ΔΣt on the diagonal.  The S and F terms
+    (changes of Σs0, νΣf and χ) are exact to first order for a flat source with isotropic scattering: the error is O(Δ²).  The ΔΣt
+    term uses the scalar fluxes only — the isotropic-angular-flux approximation, exact in an infinite medium and approximate where
+    the angular flux is anisotropic.  With ``sigma_s1`` or ``scheme="linear"`` the whole estimate is of that approximate kind (the
+    first moments and the flux moments carry weight that the scalar integrals do not see; a change of ``sigma_s1`` is ignored).
+    ``cell_material`` [n_cells]: only for host results without a device solver.  Returns ``delta_rho`` and the four integrals
+    ``B_F``, ``B_dF``, ``B_dS``, ``B_dT``."""
+    _check_pair(forward, adjoint)
+    if xs_perturbed.sigma_t.shape != xs.sigma_t.shape:
+        raise ValueError("xs and xs_perturbed must have the same materials and groups")
+    M, G = xs.sigma_t.shape
+    F = _fission_form(xs)
+    dT = np.zeros((M, G, G))
+    dT[:, np.arange(G), np.arange(G)] = xs_perturbed.sigma_t - xs.sigma_t
+    A = np.stack([F, _fission_form(xs_perturbed) - F, xs_perturbed.sigma_s - xs.sigma_s, dT])
+    bF, bdF, bdS, bdT = (float(b) for b in _bilinear(forward, adjoint, A, cell_material))
+    return dict(delta_rho=(bdF / forward.k_eff - bdT + bdS) / bF, B_F=bF, B_dF=bdF, B_dS=bdS, B_dT=bdT)
+
+
+def kinetics_parameters(forward, adjoint, xs: CrossSections, inv_velocity, beta, chi_delayed, cell_material=None) -> dict:
+    """Adjoint-weighted kinetics parameters from the forward and the adjoint eigenvalue results: the generation time
+    ``Lambda`` = B(diag 1/v) / B(F) and ``beta_eff`` [D] with β_eff,d = B(χ_d ⊗ β_d νΣf) / B(F), F = χ ⊗ νΣf and B as in
+    ``perturbation_reactivity``.  ``inv_velocity`` [G] or [M, G]; ``beta`` [M, D] (delayed fractions per material and family);
+    ``chi_delayed`` [M, D, G] (delayed spectra).  Returns ``Lambda``, ``beta_eff`` and ``B_F``."""
+    _check_pair(forward, adjoint)
+    M, G = xs.sigma_t.shape
+    iv = np.asarray(inv_velocity, np.float64)
+    iv = np.broadcast_to(iv, (M, G)) if iv.shape == (G,) else iv
+    be = np.asarray(beta, np.float64)
+    be = be.reshape(1, -1) if be.ndim == 1 and M == 1 else be
+    if iv.shape != (M, G) or be.ndim != 2 or be.shape[0] != M:
+        raise ValueError("inv_velocity must have shape [G] or [M, G] and beta [M, D]")
+    D = be.shape[1]
+    cd = np.asarray(chi_delayed, np.float64)
+    cd = cd.reshape(M, D, G) if cd.size == M * D * G else cd
+    if cd.shape != (M, D, G):
+        raise ValueError(f"chi_delayed must have shape [M, D, G] = {(M, D, G)}")
+    V = np.zeros((M, G, G))
+    V[:, np.arange(G), np.arange(G)] = iv
+    Ad = (be[:, :, None] * xs.nu_sigma_f[:, None, :])[:, :, :, None] * cd[:, :, None, :]  # [M, D, g', g]
+    A = np.concatenate([np.stack([_fission_form(xs), V]), Ad.transpose(1, 0, 2, 3)])
+    b = _bilinear(forward, adjoint, A, cell_material)
+    return dict(Lambda=float(b[1] / b[0]), beta_eff=np.asarray(b[2:] / b[0]), B_F=float(b[0]))

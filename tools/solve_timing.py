@@ -1,5 +1,6 @@
 """Timing of the device MOC solver (rt_solver) at the headline configuration: pincell, nφ = 128, δ = 1e-3, 7 groups, TY3
-(`--p1`: with linearly anisotropic scattering, Σs1 = 0.3 Σs0; `--linear`: with the linear source).
+(`--p1`: with linearly anisotropic scattering, Σs1 = 0.3 Σs0; `--linear`: with the linear source; `--adjoint`: the forward
+figures first, then the same runs in adjoint mode (rt_solver_set_adjoint) on the same solver, under "adjoint_*").
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
@@ -53,6 +54,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--p1", action="store_true", help="linearly anisotropic scattering: a synthetic Σs1 = 0.3 Σs0 (rt_solver_set_scatter_p1)")
     ap.add_argument("--linear", action="store_true", help="the linear source (rt_solver_set_linear_source); not together with --p1")
+    ap.add_argument("--adjoint", action="store_true", help="after the forward runs, the same runs in adjoint mode (rt_solver_set_adjoint)")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -89,6 +91,19 @@ def main():
     out = dict(config=dict(mesh=a.mesh, n_azim=a.n_azim, delta=a.delta, groups=a.groups, polar=a.polar, components=a.groups * pq.n_polar,
                            p1=bool(a.p1), linear=bool(a.linear), tracks=int(tg.n_total_tracks), records=int(dt.total), cells=int(tg.mesh.num_cells), iters=a.iters),
                ms_per_iter_events=float(np.median(ev_ms)), ms_per_iter_host=float(np.median(host_ms)), k_eff=ks[-1])
+    if a.adjoint:  # (the same kernels on the transposed tables: the time per iteration is expected to equal the forward one)
+        sv.set_adjoint(True)
+        sv.run(0, 3, 0.0, 0.0)
+        ev_ms, host_ms = [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            r = sv.run(0, a.iters, 0.0, 0.0)
+            host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+            ev_ms.append(r["device_ms"] / r["iterations"])
+        out["adjoint_ms_per_iter_events"] = float(np.median(ev_ms))
+        out["adjoint_ms_per_iter_host"] = float(np.median(host_ms))
+        out["adjoint_k_eff"] = r["k_eff"]
+        sv.set_adjoint(False)
     if a.steps:
         ev_ms, host_ms = [], []
         for _ in range(a.repeats):
