@@ -1,10 +1,11 @@
 """Numpy twin of the device MOC solver with the linear-source option (rt_solver_set_linear_source, scheme="linear"): the
-definitions of include/rt_segmentize.h step by step, on top of tests/moc_ref.py (volumes, link) and in the manner of
-tests/moc_ref_p1.py.  `geometry` gives the track-based centroids and second moments of the cells; `f2` the function
+definitions of include/rt_segmentize.h for the sweep and its helpers, in the manner of tests/moc_ref_p1.py; the iteration and the
+cell geometry in stages are tests/moc_ref.py's `Twin`.  `geometry` gives the track-based centroids and second moments of the cells
+(the twin's three stages back to back); `f2` the function
 F2(τ) = τ(1 + e^{−τ}) − 2(1 − e^{−τ}) without cancellation; `sweep_ls` the sweep (source ratio linear along every segment, three
 tallies per component); `sweep_ls_loop` the same from the definitions by a plain loop over tracks and segments
-(tests/test_solver_ls_cpu.py pins one against the other); `solve` the iteration, equal to moc_ref.solve step for step when the
-gradients are forced to zero (`force_flat`)."""
+(tests/test_solver_ls_cpu.py pins one against the other); `solve` the stepwise twin with the linear source run by moc_ref.run,
+equal to moc_ref.solve step for step when the gradients are forced to zero (`force_flat`)."""
 import math
 
 import numpy as np
@@ -31,29 +32,13 @@ def f2(tau):
 
 
 def geometry(rec, azim_idx, delta_s, alpha, cos_phi, sin_phi, n_cells):
-    """Track-based cell geometry: V [nc], centroid [nc, 2], C = (Cxx, Cxy, Cyy) [nc, 3], degenerate [nc] (bool)."""
-    offsets = np.asarray(rec["offsets"], np.int64)
-    cnt = np.diff(offsets)
-    a = np.asarray(azim_idx) - 1
-    w = np.repeat(2.0 * alpha[a] * delta_s[a], cnt)
-    cs, sn = np.repeat(np.asarray(cos_phi, np.float64), cnt), np.repeat(np.asarray(sin_phi, np.float64), cnt)
-    e = np.asarray(rec["element"]) - 1
-    ell = np.asarray(rec["ell"], np.float64)
-    mx, my = 0.5 * (rec["px"] + rec["qx"]), 0.5 * (rec["py"] + rec["qy"])
-    V = np.bincount(e, weights=w * ell, minlength=n_cells)
-    live = V > 0
-    Vs = np.where(live, V, 1.0)
-    X = np.bincount(e, weights=w * ell * mx, minlength=n_cells) / Vs
-    Y = np.bincount(e, weights=w * ell * my, minlength=n_cells) / Vs
-    xi, eta = mx - X[e], my - Y[e]
-    l3 = ell ** 3 / 12.0
-    cxx = np.bincount(e, weights=w * (ell * xi * xi + cs * cs * l3), minlength=n_cells) / Vs
-    cxy = np.bincount(e, weights=w * (ell * xi * eta + cs * sn * l3), minlength=n_cells) / Vs
-    cyy = np.bincount(e, weights=w * (ell * eta * eta + sn * sn * l3), minlength=n_cells) / Vs
-    det = cxx * cyy - cxy * cxy
-    deg = ~live | ~(det > DEGENERATE * (cxx + cyy) ** 2)
-    cen = np.stack([np.where(live, X, 0.0), np.where(live, Y, 0.0)], 1)
-    return V, cen, np.stack([cxx, cxy, cyy], 1) * live[:, None], deg
+    """Track-based cell geometry: V [nc], centroid [nc, 2], C = (Cxx, Cxy, Cyy) [nc, 3], degenerate [nc] (bool): the three stages
+    of moc_ref.Twin.ls_geometry back to back (the twin's one material in one group and one polar angle plays no part in them)."""
+    one = np.ones((1, 1))
+    twin = moc_ref.Twin(rec, None, azim_idx, delta_s, alpha, one, np.ones((1, 1, 1)), one, one, np.zeros(n_cells, np.int64), [1.0], [1.0],
+                        linear=True, cos_phi=cos_phi, sin_phi=sin_phi)
+    twin.set_linear_source()
+    return twin.vol, twin.cen, twin.cmat, twin.deg
 
 
 def c_inverse_apply(cmat, deg, s):
@@ -176,69 +161,7 @@ def solve(rec, links, azim_idx, delta_s, alpha, cos_phi, sin_phi, sigma_t, sigma
     `moments` (φx, φy) and `gradient` = C⁻¹ φ⃗ [nc, G, 2], `centroids` [nc, 2], `cmat` [nc, 3], `n_degenerate` and the moment
     tallies `tally_x`, `tally_y` [nc, G·P].  force_flat: q⃗ = 0 in every iteration (the flat solver, step for step).
     midpoints: ((mx, my) forward, (mx, my) backward) for the sweep instead of the records' own (`running_midpoints`)."""
-    eigen = mode == "eigenvalue"
-    mat = np.asarray(cell_material, np.int64)
-    nc = len(mat)
-    st, ss, nf, ch = (np.asarray(a, np.float64)[mat] for a in (sigma_t, sigma_s, nu_sigma_f, chi))
-    G = st.shape[1]
-    sp = np.asarray(sin_polar, np.float64)
-    wsp = np.asarray(polar_weight, np.float64) * sp
-    P = len(sp)
-    offsets = rec["offsets"]
-    V, cen, cmat, deg = geometry(rec, azim_idx, delta_s, alpha, cos_phi, sin_phi, nc)
-    a = np.asarray(azim_idx) - 1
-    wtrack = FOUR_PI * alpha[a] * delta_s[a]
-    sig_c = (st[:, :, None] / sp[None, None, :]).reshape(nc, G * P)
-    S = np.zeros((nc, G)) if (eigen or source is None) else np.asarray(source, np.float64).reshape(nc, G)
-    live = V > 0
-    n = len(offsets) - 1
-    phi = np.ones((nc, G))
-    mom = np.zeros((nc, G, 2))
-    prod = (nf * phi).sum(1)
-    F = float((V[live] * prod[live]).sum())
-    k = 1.0
-    psi_in = np.zeros((2, n, G * P))
-    hist, converged, res, dk, psi_out = [], False, math.inf, math.inf, psi_in
-    T = Tx = Ty = np.zeros((nc, G * P))
-    Vs = np.where(live, V, 1.0)
-    for _ in range(int(max_iter)):
-        scat = np.einsum("eh,ehg->eg", phi, ss)
-        q = (scat + ch * prod[:, None] / k + S) / FOUR_PI
-        ratio = q / st
-        pm = (nf[:, :, None] * mom).sum(1)  # [nc, 2]: Σ_g' νΣf φ⃗
-        sv = (np.einsum("ehx,ehg->egx", mom, ss) + ch[:, :, None] * pm[:, None, :] / k) / FOUR_PI
-        qv = c_inverse_apply(cmat, deg, sv)
-        if force_flat:
-            qv = np.zeros_like(qv)
-        gr = qv / st[:, :, None]
-        rep = lambda x: np.repeat(x, P, axis=1)
-        T, Tx, Ty, psi_out = sweep_ls(rec, sig_c, rep(ratio), rep(gr[:, :, 0]), rep(gr[:, :, 1]), cen, cos_phi, sin_phi, wtrack, psi_in,
-                                         midpoints=midpoints)
-        psi_in = moc_ref.link(psi_out, *links)
-        acc = (T.reshape(nc, G, P) * wsp[None, None, :]).sum(2)
-        new = FOUR_PI * ratio + np.where(live[:, None], acc / (st * Vs[:, None]), 0.0)
-        accm = np.stack([(Tx.reshape(nc, G, P) * wsp[None, None, :]).sum(2), (Ty.reshape(nc, G, P) * wsp[None, None, :]).sum(2)], 2)
-        mom = FOUR_PI * c_apply(cmat, gr) + accm / (st * Vs[:, None])[:, :, None]
-        mom = np.where(deg[:, None, None], 0.0, mom)
-        prod_new = (nf * new).sum(1)
-        F_new = float((V[live] * prod_new[live]).sum())
-        if eigen:
-            k_new = k * F_new / F
-            fis = live & (prod > 0)
-            res = math.sqrt(float(((prod_new[fis] / prod[fis] - 1.0) ** 2).sum()) / max(int(fis.sum()), 1))
-        else:
-            k_new = 1.0
-            n2 = float((new[live] ** 2).sum())
-            res = math.sqrt(float(((new[live] - phi[live]) ** 2).sum()) / n2) if n2 > 0 else 0.0
-        dk = abs(k_new - k) / k_new
-        phi, prod, F, k = new, prod_new, F_new, k_new
-        hist.append(k)
-        if dk < tol_k and res < tol_flux:
-            converged = True
-            break
-    if eigen:
-        phi = phi / F
-        mom = mom / F
-    return dict(k_eff=k if eigen else None, phi=phi, moments=mom, gradient=c_inverse_apply(cmat, deg, mom), centroids=cen, cmat=cmat,
-                n_degenerate=int(deg.sum()), volumes=V, k_history=np.asarray(hist), iterations=len(hist), converged=converged,
-                residual=res, dk=dk, psi_out=psi_out, tally=T, tally_x=Tx, tally_y=Ty, track_weight=wtrack)
+    twin = moc_ref.Twin(rec, links, azim_idx, delta_s, alpha, sigma_t, sigma_s, nu_sigma_f, chi, cell_material, sin_polar, polar_weight,
+                        linear=True, cos_phi=cos_phi, sin_phi=sin_phi, force_flat=force_flat, midpoints=midpoints)
+    twin.set_linear_source()
+    return moc_ref.run(twin, mode, source, max_iter, tol_k, tol_flux)

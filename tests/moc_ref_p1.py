@@ -1,8 +1,9 @@
 """Numpy twin of the device MOC solver with linearly anisotropic (P1) scattering (rt_solver_set_scatter_p1): the definitions of
-include/rt_segmentize.h step by step, on top of tests/moc_ref.py (volumes, link) and in the manner of sweep_ref.sweep_fast.
+include/rt_segmentize.h for the sweep, in the manner of sweep_ref.sweep_fast; the iteration around it is tests/moc_ref.py's `Twin`.
 `sweep_p1` is the direction-aware sweep (source ratio q0/Σt + d (cos φ_u x1 + sin φ_u y1) per traversal, three tallies);
 `sweep_p1_loop` the same from the definitions by a plain loop over tracks and segments (tests/test_solver_p1_cpu.py pins one
-against the other); `solve` the iteration, equal to moc_ref.solve step for step when sigma_s1 = 0."""
+against the other); `solve` the stepwise twin with sigma_s1 run by moc_ref.run, equal to moc_ref.solve step for step when
+sigma_s1 = 0."""
 import math
 
 import numpy as np
@@ -75,66 +76,6 @@ def solve(rec, links, azim_idx, delta_s, alpha, cos_phi, sin_phi, sigma_t, sigma
           sin_polar, polar_weight, mode="eigenvalue", source=None, max_iter=1000, tol_k=1e-8, tol_flux=1e-7):
     """moc_ref.solve with first-moment scattering sigma_s1 [M, G, G] (from g' to g) and the tracks' cos φ, sin φ [n].  Returns
     its dict plus `current` [n_cells, G, 2] and the first-moment tallies `tally_x`, `tally_y` [n_cells, G·P]."""
-    eigen = mode == "eigenvalue"
-    mat = np.asarray(cell_material, np.int64)
-    nc = len(mat)
-    st, ss, s1, nf, ch = (np.asarray(a, np.float64)[mat] for a in (sigma_t, sigma_s, sigma_s1, nu_sigma_f, chi))
-    G = st.shape[1]
-    sp = np.asarray(sin_polar, np.float64)
-    wp = np.asarray(polar_weight, np.float64)
-    wsp = wp * sp
-    P = len(sp)
-    offsets, ell, element = rec["offsets"], rec["ell"], rec["element"]
-    V = moc_ref.volumes(offsets, ell, element, azim_idx, delta_s, alpha, nc)
-    a = np.asarray(azim_idx) - 1
-    wtrack = FOUR_PI * alpha[a] * delta_s[a]
-    sig_c = (st[:, :, None] / sp[None, None, :]).reshape(nc, G * P)
-    S = np.zeros((nc, G)) if (eigen or source is None) else np.asarray(source, np.float64).reshape(nc, G)
-    live = V > 0
-    n = len(offsets) - 1
-    phi = np.ones((nc, G))
-    J = np.zeros((nc, G, 2))
-    prod = (nf * phi).sum(1)
-    F = float((V[live] * prod[live]).sum())
-    k = 1.0
-    psi_in = np.zeros((2, n, G * P))
-    hist, converged, res, dk, psi_out = [], False, math.inf, math.inf, psi_in
-    T = Tx = Ty = np.zeros((nc, G * P))
-    Vs = np.where(live, V, 1.0)
-    for _ in range(int(max_iter)):
-        scat = np.einsum("eh,ehg->eg", phi, ss)
-        q = (scat + ch * prod[:, None] / k + S) / FOUR_PI
-        ratio = q / st
-        q1 = (3.0 / FOUR_PI) * np.einsum("ehx,ehg->egx", J, s1)   # [nc, G, 2]
-        r1 = q1 / st[:, :, None]
-        src_c = sig_c * np.repeat(ratio, P, axis=1)
-        x1 = (r1[:, :, None, 0] * sp[None, None, :]).reshape(nc, G * P)
-        y1 = (r1[:, :, None, 1] * sp[None, None, :]).reshape(nc, G * P)
-        T, Tx, Ty, psi_out = sweep_p1(offsets, ell, element, sig_c, src_c, x1, y1, cos_phi, sin_phi, wtrack, psi_in)
-        psi_in = moc_ref.link(psi_out, *links)
-        acc = (T.reshape(nc, G, P) * wsp[None, None, :]).sum(2)
-        new = FOUR_PI * ratio + np.where(live[:, None], acc / (st * Vs[:, None]), 0.0)
-        accj = np.stack([(Tx.reshape(nc, G, P) * (wp * sp * sp)[None, None, :]).sum(2),
-                         (Ty.reshape(nc, G, P) * (wp * sp * sp)[None, None, :]).sum(2)], 2)
-        J = (FOUR_PI / 3.0) * r1 + np.where(live[:, None, None], accj / (st * Vs[:, None])[:, :, None], 0.0)
-        prod_new = (nf * new).sum(1)
-        F_new = float((V[live] * prod_new[live]).sum())
-        if eigen:
-            k_new = k * F_new / F
-            fis = live & (prod > 0)
-            res = math.sqrt(float(((prod_new[fis] / prod[fis] - 1.0) ** 2).sum()) / max(int(fis.sum()), 1))
-        else:
-            k_new = 1.0
-            n2 = float((new[live] ** 2).sum())
-            res = math.sqrt(float(((new[live] - phi[live]) ** 2).sum()) / n2) if n2 > 0 else 0.0
-        dk = abs(k_new - k) / k_new
-        phi, prod, F, k = new, prod_new, F_new, k_new
-        hist.append(k)
-        if dk < tol_k and res < tol_flux:
-            converged = True
-            break
-    if eigen:
-        phi = phi / F
-        J = J / F
-    return dict(k_eff=k if eigen else None, phi=phi, current=J, volumes=V, k_history=np.asarray(hist), iterations=len(hist),
-                converged=converged, residual=res, dk=dk, psi_out=psi_out, tally=T, tally_x=Tx, tally_y=Ty, track_weight=wtrack)
+    twin = moc_ref.Twin(rec, links, azim_idx, delta_s, alpha, sigma_t, sigma_s, nu_sigma_f, chi, cell_material, sin_polar, polar_weight,
+                        sigma_s1=sigma_s1, cos_phi=cos_phi, sin_phi=sin_phi)
+    return moc_ref.run(twin, mode, source, max_iter, tol_k, tol_flux)

@@ -23,12 +23,20 @@ def _bcs(rt, kind):
     return B(top=rt.Vacuum, bottom=rt.Reflective, left=rt.Periodic, right=rt.Periodic)  # mixed
 
 
+_KEPT = []  # conftest's oracle_run caches by id(tg) for the session: a TrackGenerator it has seen must not die, or a later one
+# at the same address gets the dead one's records (conftest's `traced` keeps its own alive in the same way)
+
+
+def _traced(tg, rt):
+    rt.trace(tg)
+    _KEPT.append(tg)
+    return tg
+
+
 def _tg(rt, mesh, n_azim, delta, bc):
     path = rt.data_path(mesh)
     model = rt.GmshDiscreteModel(path) if mesh.endswith(".msh") else rt.DiscreteModelFromFile(path)
-    tg = rt.TrackGenerator(model, n_azim, delta, bcs=_bcs(rt, bc))
-    rt.trace(tg)
-    return tg
+    return _traced(rt.TrackGenerator(model, n_azim, delta, bcs=_bcs(rt, bc)), rt)
 
 
 def _device(rt, tg, links=True, **opts):
@@ -86,10 +94,7 @@ def _cell_material_array(tg, cm):
 
 
 def _twin(rt, tg, rec, xs, cm, mode="eigenvalue", source=None, polar="TY3", alpha="exact", **kw):
-    pq = rt.PolarQuadrature(polar)
-    aq = tg.azimuthal_quadrature
-    return moc_ref.solve(rec, moc_ref.tg_links(tg), tg.azim_idx, aq.delta_s, rt.azimuthal_weights(tg, alpha), xs.sigma_t, xs.sigma_s,
-                         xs.nu_sigma_f, xs.chi, _cell_material_array(tg, cm), pq.sin_theta, pq.weights, mode=mode, source=source, **kw)
+    return moc_ref.solve_tg(rt, tg, rec, xs, _cell_material_array(tg, cm), polar, alpha, mode=mode, source=source, **kw)
 
 
 # ---- 1. analytic answers on the fully reflective pincell (one material) -----------------------------------------------

@@ -11,7 +11,7 @@ import pytest
 
 import meshgen
 import moc_ref
-from test_gpu_solver import N_ITER, _cell_material_array, _device, _materials, _xs
+from test_gpu_solver import N_ITER, _cell_material_array, _device, _materials, _traced, _xs
 from test_gpu_solver_shapes import _bands, _dense_materials, _handle, _solver, _tg_model
 from test_solver_adjoint_cpu import (EPS, K_PAIR_MEASURED, adjoint_xs, perturbed, quarter_sources, ratio_check, twin_flat,
                                      two_group_problem)
@@ -33,10 +33,8 @@ def _size(tg):
 
 def _pin_tg(rt, n_azim=32, delta=5e-3):
     B = rt.BoundaryConditions
-    tg = rt.TrackGenerator(rt.DiscreteModelFromFile(rt.data_path("pincell.json")), n_azim, delta,
-                           bcs=B(top=rt.Vacuum, bottom=rt.Reflective, left=rt.Reflective, right=rt.Reflective))
-    rt.trace(tg)
-    return tg
+    return _traced(rt.TrackGenerator(rt.DiscreteModelFromFile(rt.data_path("pincell.json")), n_azim, delta,
+                                     bcs=B(top=rt.Vacuum, bottom=rt.Reflective, left=rt.Reflective, right=rt.Reflective)), rt)
 
 
 @pytest.fixture(scope="module")

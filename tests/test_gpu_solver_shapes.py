@@ -22,7 +22,7 @@ import pytest
 
 import meshgen
 import moc_ref
-from test_gpu_solver import _bcs, _cell_material_array, _device, _materials, _tg, _twin, _xs
+from test_gpu_solver import _bcs, _cell_material_array, _device, _materials, _tg, _traced, _twin, _xs
 from test_solver_cpu import dense_xs
 
 pytestmark = pytest.mark.gpu
@@ -33,9 +33,7 @@ EXACT = dict(tol_k=0, tol_flux=0)
 
 # ---- helpers --------------------------------------------------------------------------------------------------------
 def _tg_model(rt, model, n_azim, delta, bc):
-    tg = rt.TrackGenerator(model, n_azim, delta, bcs=_bcs(rt, bc))
-    rt.trace(tg)
-    return tg
+    return _traced(rt.TrackGenerator(model, n_azim, delta, bcs=_bcs(rt, bc)), rt)
 
 
 def _handle(rt, tg, device=0):

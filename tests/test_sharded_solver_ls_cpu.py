@@ -1,7 +1,7 @@
 """distributed.ShardedSolver(scheme="linear", staged_geometry=True) without a GPU: `gloo` worlds of 2 and 3 ranks, each driving the
-numpy stand-in of tests/sharded_ls_standin.py (the step interface with the linear source and its geometry in stages, from the formulas of
-tests/moc_ref_ls.py) over ITS uid range of the oracle's records.  Two fixtures, both jittered meshgen lattices under tracks so coarse
-that the ranks see different parts of the mesh:
+stand-in of tests/shard_standin.py (the stepwise twin of tests/moc_ref.py with the linear source and its geometry in stages, the
+same code moc_ref_ls.solve and moc_ref_ls.geometry run over the whole track set) over ITS uid range of the oracle's records.  Two
+fixtures, both jittered meshgen lattices under tracks so coarse that the ranks see different parts of the mesh:
 
 * "covered" (6 x 6, 8 angles, spacing 0.15: 72 cells, 40 tracks): every cell is crossed, none is degenerate, and in a world of 3
   every rank has cells that only OTHER ranks' tracks cross — its own first moments and volume there are 0, and only the reduced
@@ -40,18 +40,6 @@ def _free_port():
     return p
 
 
-def _stand_in_class():
-    import torch
-
-    import moc_ref
-    import moc_ref_p1
-    import sharded_ls_standin
-    import sweep_ref
-    from test_sharded_solver_cpu import _stand_in
-
-    return sharded_ls_standin.make(torch, _stand_in(torch, moc_ref, sweep_ref, moc_ref_p1))
-
-
 def _problem(rt, fixture):
     import meshgen
     from oracle import oracle as orc
@@ -79,6 +67,7 @@ def _worker(rank, world, port, q, fixture):
 
         import raytracing_jl_amd as rt
         from raytracing_jl_amd import distributed as rtd
+        from shard_standin import ShardTwin
         from test_solver_ls_cpu import twin_ls
 
         dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -89,12 +78,12 @@ def _worker(rank, world, port, q, fixture):
         alpha = rt.azimuthal_weights(tg, "exact")
         ranges = rtd.shard_ranges(tg.ell, world)
         lo, hi = ranges[rank]
-        Solver = _stand_in_class()
         size = float(tg.mesh.width())
 
         def sharded(cls):
             plan = rtd.SweepExchangePlan(tg.next_fwd_uid, tg.next_bwd_uid, tg.dir_next_fwd, tg.dir_next_bwd, tg.bc_fwd, tg.bc_bwd, ranges, rank)
-            sv = Solver(rec, lo, hi, plan.local_links, tg.azim_idx, aq.delta_s, alpha, xs, mat, pq.sin_theta, pq.weights, tg.cos_phi, tg.sin_phi)
+            sv = ShardTwin(rec, lo, hi, plan.local_links, tg.azim_idx, aq.delta_s, alpha, xs, mat, pq.sin_theta, pq.weights, tg.cos_phi, tg.sin_phi,
+                           linear=True)
             return cls(tg, None, None, None, rank, world, ranges=ranges, scheme="linear", staged_geometry=True, solver=sv)
 
         class NoGeometryReduce(rtd.ShardedSolver):  # the geometry from this rank's tracks alone (over the whole volumes)
@@ -182,23 +171,23 @@ def test_gloo_sharded_linear_source_equals_unsharded(world, fixture):
 def one_rank(rt):
     """The stand-in over the whole track set of the small fixture (a world of one: no process group)."""
     from raytracing_jl_amd import distributed as rtd
+    from shard_standin import ShardTwin
 
     tg, rec, xs, mat, S = _problem(rt, "covered")
     pq = rt.PolarQuadrature("TY2")
     aq = tg.azimuthal_quadrature
     ranges = rtd.shard_ranges(tg.ell, 1)
     plan = rtd.SweepExchangePlan(tg.next_fwd_uid, tg.next_bwd_uid, tg.dir_next_fwd, tg.dir_next_bwd, tg.bc_fwd, tg.bc_bwd, ranges, 0)
-    Solver = _stand_in_class()
 
     def make(xs_=xs):
-        return Solver(rec, 0, len(tg.ell), plan.local_links, tg.azim_idx, aq.delta_s, rt.azimuthal_weights(tg, "exact"), xs_, mat,
-                      pq.sin_theta, pq.weights, tg.cos_phi, tg.sin_phi)
+        return ShardTwin(rec, 0, len(tg.ell), plan.local_links, tg.azim_idx, aq.delta_s, rt.azimuthal_weights(tg, "exact"), xs_, mat,
+                         pq.sin_theta, pq.weights, tg.cos_phi, tg.sin_phi, linear=True)
 
     return tg, rec, xs, mat, ranges, make
 
 
 def test_stages_out_of_order_change_nothing(rt, one_rank):
-    from sharded_ls_standin import StageError
+    from moc_ref import StageError
 
     tg, rec, xs, mat, ranges, make = one_rank
     sv = make()

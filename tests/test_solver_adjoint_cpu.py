@@ -27,10 +27,7 @@ def adjoint_xs(rt, xs):
 
 
 def twin_flat(rt, tg, rec, xs, cm, polar="TY3", **kw):
-    pq = rt.PolarQuadrature(polar)
-    aq = tg.azimuthal_quadrature
-    return moc_ref.solve(rec, moc_ref.tg_links(tg), tg.azim_idx, aq.delta_s, rt.azimuthal_weights(tg, "exact"), xs.sigma_t, xs.sigma_s,
-                         xs.nu_sigma_f, xs.chi, np.asarray(cm, np.int64), pq.sin_theta, pq.weights, **kw)
+    return moc_ref.solve_tg(rt, tg, rec, xs, cm, polar, **kw)
 
 
 def host_result(r, adjoint=False):

@@ -95,11 +95,7 @@ def reflective(rt, orc):
 
 
 def _twin(rt, tg, rec, xs, mode="eigenvalue", source=None, polar="TY3", alpha="exact", **kw):
-    pq = rt.PolarQuadrature(polar)
-    aq = tg.azimuthal_quadrature
-    return moc_ref.solve(rec, moc_ref.tg_links(tg), tg.azim_idx, aq.delta_s, rt.azimuthal_weights(tg, alpha), xs.sigma_t, xs.sigma_s,
-                         xs.nu_sigma_f, xs.chi, np.zeros(tg.mesh.num_cells, np.int64), pq.sin_theta, pq.weights, mode=mode, source=source,
-                         **kw)
+    return moc_ref.solve_tg(rt, tg, rec, xs, np.zeros(tg.mesh.num_cells, np.int64), polar, alpha, mode=mode, source=source, **kw)
 
 
 TIGHT = dict(tol_k=1e-12, tol_flux=1e-11, max_iter=3000)

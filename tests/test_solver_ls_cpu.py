@@ -22,17 +22,11 @@ import decimal
 
 
 def twin_ls(rt, tg, rec, xs, cm, polar="TY3", alpha="exact", **kw):
-    pq = rt.PolarQuadrature(polar)
-    aq = tg.azimuthal_quadrature
-    return moc_ref_ls.solve(rec, moc_ref.tg_links(tg), tg.azim_idx, aq.delta_s, rt.azimuthal_weights(tg, alpha), tg.cos_phi, tg.sin_phi,
-                            xs.sigma_t, xs.sigma_s, xs.nu_sigma_f, xs.chi, np.asarray(cm, np.int64), pq.sin_theta, pq.weights, **kw)
+    return moc_ref.solve_tg(rt, tg, rec, xs, cm, polar, alpha, scheme="linear", **kw)
 
 
 def twin_flat(rt, tg, rec, xs, cm, polar="TY3", alpha="exact", **kw):
-    pq = rt.PolarQuadrature(polar)
-    aq = tg.azimuthal_quadrature
-    return moc_ref.solve(rec, moc_ref.tg_links(tg), tg.azim_idx, aq.delta_s, rt.azimuthal_weights(tg, alpha), xs.sigma_t, xs.sigma_s,
-                         xs.nu_sigma_f, xs.chi, np.asarray(cm, np.int64), pq.sin_theta, pq.weights, **kw)
+    return moc_ref.solve_tg(rt, tg, rec, xs, cm, polar, alpha, **kw)
 
 
 TAUS = [1e-12, 1e-9, 1e-6, 1e-4, 1e-3, 0.01, 0.05, 0.124, 0.126, 0.3, 0.7, 1.0, 1.49, 1.5, 1.51, 2.0, 3.0, 5.0, 10.0, 25.0, 41.5, 50.0]

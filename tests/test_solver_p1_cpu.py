@@ -28,12 +28,8 @@ def oracle_records(rt, orc, model, n_azim, delta, bc):
 
 
 def twin_p1(rt, tg, rec, xs, cm, sigma_s1=None, polar="TY3", alpha="exact", **kw):
-    """moc_ref_p1.solve for a CrossSections (its sigma_s1 unless one is given)."""
-    pq = rt.PolarQuadrature(polar)
-    aq = tg.azimuthal_quadrature
-    s1 = xs.sigma_s1 if sigma_s1 is None else np.asarray(sigma_s1, np.float64).reshape(xs.sigma_s.shape)
-    return moc_ref_p1.solve(rec, moc_ref.tg_links(tg), tg.azim_idx, aq.delta_s, rt.azimuthal_weights(tg, alpha), tg.cos_phi, tg.sin_phi,
-                            xs.sigma_t, xs.sigma_s, s1, xs.nu_sigma_f, xs.chi, np.asarray(cm, np.int64), pq.sin_theta, pq.weights, **kw)
+    """The P1 twin for a CrossSections (its sigma_s1 unless one is given)."""
+    return moc_ref.solve_tg(rt, tg, rec, xs, cm, polar, alpha, scheme="p1", sigma_s1=sigma_s1, **kw)
 
 
 # ---- the reference problems shared with tests/test_gpu_solver_p1.py ------------------------------------------------------
