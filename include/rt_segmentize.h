@@ -327,7 +327,8 @@ int32_t rt_last_timing(rt_tracks *tracks, double *ms, int32_t n);
  * length by the second kernel of the two-phase march (a short chord or a shallow crossing: the chord from the vertices' distances
  * would not be within 4e-11 of it — DESIGN.md §2).
  * stats[21] the lean plan of the call's march (option "lean"; 0: one kernel), stats[22] the lanes its k_serve finished; stats[23] the
- * kernel that wrote the call's records (1 k_compact3, 2 k_materialise, 3 k_materialise_lin, 4 k_materialise writing (ℓ, cell) rows);
+ * kernel that wrote the call's records (1 k_compact3, 2 k_materialise, 3 k_materialise_lin, 4 k_materialise writing (ℓ, cell) rows,
+ * 5 k_materialise_lin with 32-track units — option "lin_unit");
  * stats[24] 1 if the call wrote its records beside the march, in completion order (option "record_order"); stats[25] side-list entries
  * the call used beyond the one reserved per track, stats[26] side-list entries allocated, stats[27] attempts the call took (> 1: a staging
  * pool, side list or result array that was too small on the first one, or a fall-back to another plan).
@@ -429,6 +430,8 @@ void rt_msh_free(rt_msh *msh);
  *   "topo"     0: exact walk steps only, 1: cheap steps where >= 90 % of the walkable records carry a cheap certificate
  *                 (default), 2: forced — wherever a record carries one, and waves never hand back to exact steps
  *   "walk"     0: literal step only (find_element + intersections every iteration)
+ *   "lin_unit" tracks per workgroup of the record kernel of the two-phase march (k_materialise_lin): 16, 32, or 0 (default):
+ *                 32 for calls with few records per track, 16 otherwise; the records are the same bit for bit
  *   "iter_cap" guard on the reference's unbounded `continue` paths (default 4,000,000 iterations per track)
  *   "split"    (read by rt_tracks_create) 0: never march track pieces; L > 0: pieces of about L records; default −1: pieces for
  *                 batches far below the chip's capacity (< 160 march waves; above that the two-phase march of whole tracks is faster)

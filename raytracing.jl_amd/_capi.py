@@ -628,7 +628,7 @@ class DeviceTracks:
                     tracks_near_rtol=int(v[18]), tracks_restarted=int(v[19]), records_tallied_from_lengths=int(v[20]),
                     lean=int(v[21]), lean_queued=int(v[22]), completion_order=int(v[24]), side_entries_used=int(v[25]), side_entries_allocated=int(v[26]), attempts=int(v[27]),
                     record_kernel={0: None, 1: "rt::k_compact3", 2: "rt::k_materialise<true, false>", 3: "rt::k_materialise_lin<true>" if int(v[24]) else "rt::k_materialise_lin<false>",
-                                   4: "rt::k_materialise<false, true>"}.get(int(v[23])))
+                                   4: "rt::k_materialise<false, true>", 5: "rt::k_materialise_lin<false, 32>"}.get(int(v[23])))
 
     # the nine terms of the cheap step's certificate (rt_device.hpp, topo_certified), in rt_last_stats' order
     REFUSAL_TERMS = ("no_record", "scan_window", "vertex_clearance", "entry_not_crossed", "isolation_margin", "entry_rounding",

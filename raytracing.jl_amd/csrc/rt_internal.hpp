@@ -256,7 +256,7 @@ struct DMat {
     const RT_G EdgeABC *etab;
     int32_t etab_bytes;           // 3 n_cells entries of 32 B (k_materialise_lin's buffer resource; < 2^32)
     const RT_G int32_t *corder;   // large batches: march waves in the order of their output addresses (as k_compact3)
-    int64_t n_units;              // 4 per march wave
+    int64_t n_units;              // 4 per march wave (k_materialise_lin with 32-track units: 2)
     double rtol;
     double coord_max;             // largest |coordinate| of the mesh's bounding box (the Σℓ chain's absolute band)
     int32_t tally;                // 1: Σℓ + status (the call's first pass over the codes); 0: records / rows only
@@ -344,6 +344,7 @@ struct rt_mesh {
     int sweep_ell = 1;  // rt_sweep over staged rows: keep ℓ of every row from the first pass for the later ones (0: every pass derives it)
     int sweep_debug = 0, compact_debug = 0;
     int mat_kernel = 0;      // records of a two-phase call: 0 k_materialise_lin (output order, 16-B stores), 1 k_materialise (chunk tiles; A/B)
+    int lin_unit = 0;        // tracks per workgroup of k_materialise_lin: 16, 32, or 0 — by the call's records per track (choose_lin_unit)
     int march_waves = 0;     // 4 / 6: waves per workgroup of the fused march (0: automatic)
     int topo = 1;          // 1: cheap steps (k_march<..., TOPO>) for whole-track batches when the mesh allows it; 2: forced — also on
                            // meshes where fewer than 90 % of the walkable records carry a cheap certificate, and a wave that is
@@ -451,7 +452,8 @@ struct rt_tracks {
     bool force_unsplit = false;  // a track reached MAX_ITER segments in split mode: this track set marches whole from now on
     int32_t last_topo = 0;  // 1: the last call marched with cheap steps
     int32_t last_lean = 0;  // ... in three kernels (the option's value)
-    int32_t last_record_kernel = 0;  // which kernel wrote the last call's records: 0 none yet, 1 k_compact3, 2 k_materialise, 3 k_materialise_lin, 4 k_materialise (rows only)
+    int32_t last_record_kernel = 0;  // which kernel wrote the last call's records: 0 none yet, 1 k_compact3, 2 k_materialise, 3 k_materialise_lin, 4 k_materialise (rows only), 5 k_materialise_lin with 32-track units
+    int32_t last_lin_unit = 0;       // the unit width of the call's first (tallying) record launch: a later launch over the same codes takes it again
     bool lean_gave_up = false, lean_q_clean = false;
     int64_t n_lean_queued = 0;
     DevBuf<int32_t> lean_i;   // DLean: the lanes' state (8 int arrays), the queue, the dump row
@@ -532,7 +534,7 @@ int launch_materialise(rt_tracks *t, const rt::DOut &out, hipStream_t s, bool re
 bool lin_kernel_serves(const rt_tracks *t, const rt::DOut &out);  // k_materialise_lin can write this call's records
 // rt_materialise.hip
 void launch_materialise_lin(const rt::DTracks &d, int32_t *status, const rt::DStage &stg, const rt::DOut &out, const rt::DMat &a, hipStream_t s,
-                            int n_cus, bool queue = false);
+                            int n_cus, bool queue = false, int unit = 16);
 void launch_finish(rt_tracks *t, const rt::DOut &out, hipStream_t s, bool from_rows, bool scale_volumes, double n_azim_2,
                    unsigned long long *d_ctl, unsigned long long *h_res_dev, unsigned long long seq, bool completion_order = false);
 void launch_compaction(rt_tracks *t, const rt::DOut &out, hipStream_t s);

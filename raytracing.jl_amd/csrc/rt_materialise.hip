@@ -1,7 +1,7 @@
 // rt_materialise.hip — codes -> records in OUTPUT ORDER (gfx950): the record-writing half of the two-phase march, round 5.
 //
 // k_march<..., TOPO> leaves one word per record (DStage); this kernel turns the words of a unit — the 16 tracks of a quarter of a
-// march wave — into the reference's records:
+// march wave, or the 32 of a half (LinShape, round 7) — into the reference's records:
 //   q = intersection(track.ABC, general_form of the exit edge)   src/intersection.jl:127-138 (edge_exit_point; `etab` holds the
 //       host's general forms, evaluated with the reference's operations — bit-identical),
 //   p = the previous record's q (bit-identical to the reference's own intersection with the shared edge), or the side list's p,
@@ -48,9 +48,24 @@
 
 namespace rt {
 
-constexpr int kLinRows = 256;                      // rows of a track per round (a unit of longer tracks takes several rounds)
-constexpr int kLinCap = 16 * kLinRows + 16 * 32;   // linear slots of a round: records + per run group < 16 pads in front, < 16 behind
-static_assert(kLinRows % kChunkRows == 0 && kLinRows / kChunkRows == 8, "a wave takes two of a round's eight chunks");
+constexpr int kLinRows = 256;                      // rows of a track per round of a 16-track unit (a unit of longer tracks takes several rounds)
+// A unit is UNIT = 16 or 32 tracks of a march wave (a quarter or a half of it).  Both widths hold the same 4,096 records per round —
+// 256 or 128 rows of every track —, so the loop, the stores and the words a wave fetches per round are the same; a 32-track unit
+// pays the header, the priming of the loop and the epilogue once for twice as many records as long as its tracks fit one round.
+template <int UNIT>
+struct LinShape {
+    static_assert(UNIT == 16 || UNIT == 32, "a unit is a quarter or a half of a march wave");
+    static constexpr int kRows = kLinRows * 16 / UNIT;          // rows of a track per round
+    static constexpr int kCap = UNIT * kRows + UNIT * 32;       // linear slots of a round: records + per run group < 16 pads in front, < 16 behind
+    static constexpr int kRoundChunks = kRows / kChunkRows;     // 8 / 4 chunks per round ...
+    static constexpr int kWaveChunks = kRoundChunks / 4;        // ... two / one of them per wave
+    static constexpr int kRowLog2 = UNIT == 16 ? 2 : 1;         // a wave-load of words covers 4 / 2 rows of the unit's tracks
+    static constexpr int kRowStep = 1 << kRowLog2;
+    static constexpr int kLoads = kChunkRows / kRowStep;        // 8 / 16 wave-loads per chunk (16 words per lane and round either way)
+    static constexpr int kFieldLoads = UNIT / 16;               // table: a wave-load covers 4 / 2 fields of the unit's tracks
+    static constexpr int kShr = UNIT == 16 ? 0x111 : 0x138;     // DPP "the track before": row_shr:1; 32 tracks span two rows — wave_shr:1
+    static_assert(kRows % kChunkRows == 0 && kRoundChunks % 4 == 0, "every wave takes whole chunks of a round");
+};
 
 // What the linear phase needs per track (LDS).  16-B aligned pieces: one ds_read_b128 each.
 struct __attribute__((aligned(16))) LinTrack {
@@ -160,18 +175,21 @@ constexpr int kWaitVm0 = 0x0F70;  // s_waitcnt vmcnt(0) (gfx9 encoding: expcnt a
 // its XCD's queue holds no further unit; one that waits far beyond any march (~0.3 s), or sees another one's give-up flag, sets
 // the flag in the control block and leaves: the attempt is void, the host marches again in CSR order.  The host also counts: a
 // call whose units were not all served (no record workgroup on some XCD: never observed) writes its records again, in CSR order.
-template <bool QUEUE>
+template <bool QUEUE, int UNIT>
 __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, int32_t *__restrict__ status, DStage stg, DOut out, DMat a) {
-    __shared__ __attribute__((aligned(16))) int32_t s_meta[kLinCap];   // the round's words in output order (0: no record)
-    __shared__ __attribute__((aligned(16))) uint8_t s_tmap[kLinCap];   // ... and which of the 16 tracks each belongs to
-    __shared__ LinTrack s_trk[16];
+    using SH = LinShape<UNIT>;
+    static_assert(!QUEUE || UNIT == 16, "the completion queue deals 16-track units");
+    constexpr int kRows = SH::kRows, kTrackMask = UNIT - 1, kUnitsPerWave = 64 / UNIT;
+    __shared__ __attribute__((aligned(16))) int32_t s_meta[SH::kCap];   // the round's words in output order (0: no record)
+    __shared__ __attribute__((aligned(16))) uint8_t s_tmap[SH::kCap];   // ... and which of the unit's tracks each belongs to
+    __shared__ LinTrack s_trk[UNIT];
     // Σℓ of a track (src/track.jl:171) without adding up its records: the records of a track lie head to tail on its line (p of a
     // record IS the q before it, bit for bit), so Σ‖p_i − q_i‖ = ‖p_first − q_last‖ up to the roundings of the n norms and of their
     // sum — n·2⁻⁵³·Σ, the margin the check already leaves to a sum in another order; only where a record keeps its own p (a
     // generic step's, behind tiny steps) the gap ‖p_i − q_(i−1)‖ is missing from the chain: those are added up here.  What the
     // margin cannot decide, k_finish sums left to right as before.
-    __shared__ lin_d2 s_qlast[16];   // exit point of the track's last record
-    __shared__ double s_gap[16];     // what the chain misses: Σ gaps in front of records that keep their own p (signed: an overlap counts
+    __shared__ lin_d2 s_qlast[UNIT];   // exit point of the track's last record
+    __shared__ double s_gap[UNIT];   // what the chain misses: Σ gaps in front of records that keep their own p (signed: an overlap counts
                                      // negative), minus twice the length of such a record if it walks backwards
     __shared__ LinHalf s_half[4][kLinHalfCap];   // per wave: half pairs for the epilogue
     __shared__ double s_fval[4][kLinFlagCap];    // per wave: fill_volumes terms of marked records (value, cell) for the epilogue
@@ -245,7 +263,7 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
     }
     if (hprio) __builtin_amdgcn_s_setprio(3);
     const int kw = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;  // (kw in a scalar register: uniform loops)
-    const int tl = lane & 15, rr = lane >> 4;  // transposition: track tl, rows 4 i + rr of a chunk
+    const int tl = lane & kTrackMask, rr = lane / UNIT;  // transposition: track tl, rows kRowStep i + rr of a chunk
 #ifdef RT_LIN_TIMING
     unsigned long long stamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     LIN_STAMP(0);
@@ -266,12 +284,12 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
     const bool nostore = (out.dbg & 1) != 0;
     // the exit edges' general forms: gathered through a buffer resource too (32-bit offsets: 3 n_cells < 2^27 entries of 32 B)
     const __amdgpu_buffer_rsrc_t r_etab = __builtin_amdgcn_make_buffer_rsrc((void *)a.etab, 0, a.etab_bytes, kBufWord3);
-    const int32_t w = __builtin_amdgcn_readfirstlane((int32_t)((!QUEUE && a.corder) ? a.corder[unit >> 2] : (int32_t)(unit >> 2)));
-    const int q = (int)(unit & 3);
-    const int64_t slot0 = (int64_t)w * 64 + 16 * q;
+    const int32_t w = __builtin_amdgcn_readfirstlane((int32_t)((!QUEUE && a.corder) ? a.corder[unit / kUnitsPerWave] : (int32_t)(unit / kUnitsPerWave)));
+    const int q = (int)(unit & (kUnitsPerWave - 1));
+    const int64_t slot0 = (int64_t)w * 64 + UNIT * q;
     const int64_t slot = slot0 + tl;
     const bool have = slot < t.n;
-    const int lane_q = 16 * q + tl;
+    const int lane_q = UNIT * q + tl;
     const RT_G int32_t *ctab = stg.ctab + (int64_t)w * kMaxChunks;
     // reserved chunks follow from (w, j) and kernel arguments (DStage): scalar loads.  A chunk from the cursor is looked up, and
     // waited for where it is looked up (a wait at the join would also wait for the other chunk's words)
@@ -287,19 +305,19 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
     int32_t cnt = 0;
     int64_t off = 0;
     if (have) { cnt = ld_handoff<QUEUE>(&t.cnt_slot[slot]); off = ld_handoff<QUEUE>(&t.off_slot[slot]); }
-    int32_t ve[2][8];
-    bool spec[2];
+    int32_t ve[SH::kWaveChunks][SH::kLoads];
+    bool spec[SH::kWaveChunks];
 #pragma unroll
-    for (int c2 = 0; c2 < 2; ++c2) {
+    for (int c2 = 0; c2 < SH::kWaveChunks; ++c2) {
         const int j = kw + 4 * c2;
         spec[c2] = j < stg.n_regions && w < stg.reg_cap[j];
         if (spec[c2]) {
             const int32_t c = stg.reg_base[j] + w;
 #pragma unroll
-            for (int i = 0; i < 8; ++i) ve[c2][i] = __builtin_nontemporal_load(&stg.element[stage_slot(c, 4 * i + rr, lane_q)]);
+            for (int i = 0; i < SH::kLoads; ++i) ve[c2][i] = __builtin_nontemporal_load(&stg.element[stage_slot(c, SH::kRowStep * i + rr, lane_q)]);
         } else {
 #pragma unroll
-            for (int i = 0; i < 8; ++i) ve[c2][i] = 0;
+            for (int i = 0; i < SH::kLoads; ++i) ve[c2][i] = 0;
         }
     }
     {
@@ -308,68 +326,103 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
         const int64_t sc = have ? slot : t.n - 1;
         const int64_t side_last = stg.side_cap > 0 ? stg.side_cap - 1 : 0;
         const int64_t ss = sc < side_last ? sc : side_last;
+        // (a 32-track unit: two wave-loads per table, fields rr and rr + 2 — issued together, the same single trip)
+        constexpr int NF = SH::kFieldLoads;
+        double fv[NF];
         if (kw == 0) {
-            const RT_G double *pg0 = rr == 0 ? t.As : (rr == 1 ? t.Bs : (rr == 2 ? t.Cs : t.Ls));
-            s_trk[tl].g0[rr] = pg0[sc];
+#pragma unroll
+            for (int h = 0; h < NF; ++h) {
+                const int f = rr + (4 / NF) * h;
+                const RT_G double *pg0 = f == 0 ? t.As : (f == 1 ? t.Bs : (f == 2 ? t.Cs : t.Ls));
+                fv[h] = pg0[sc];
+            }
+#pragma unroll
+            for (int h = 0; h < NF; ++h) s_trk[tl].g0[rr + (4 / NF) * h] = fv[h];
         } else if (kw == 1) {
-            const RT_G double *pg1 = rr == 0 ? (const RT_G double *)t.w_slot : (rr == 1 ? (const RT_G double *)stg.s_px : (rr == 2 ? (const RT_G double *)stg.s_py : (const RT_G double *)stg.s_qx));
-            s_trk[tl].g1[rr] = ld_handoff<QUEUE>(&pg1[rr == 0 ? sc : ss]);
+#pragma unroll
+            for (int h = 0; h < NF; ++h) {
+                const int f = rr + (4 / NF) * h;
+                const RT_G double *pg1 = f == 0 ? (const RT_G double *)t.w_slot : (f == 1 ? (const RT_G double *)stg.s_px : (f == 2 ? (const RT_G double *)stg.s_py : (const RT_G double *)stg.s_qx));
+                fv[h] = ld_handoff<QUEUE>(&pg1[f == 0 ? sc : ss]);
+            }
+#pragma unroll
+            for (int h = 0; h < NF; ++h) s_trk[tl].g1[rr + (4 / NF) * h] = fv[h];
         } else if (kw == 2) {
-            const RT_G double *pg2 = rr == 0 ? (const RT_G double *)stg.s_qy : (rr == 1 ? t.Dxs : t.Dys);
-            s_trk[tl].g2[rr] = ld_handoff<QUEUE>(&pg2[rr == 0 ? ss : sc]);
-        } else if (lane < 16) {
+#pragma unroll
+            for (int h = 0; h < NF; ++h) {
+                const int f = rr + (4 / NF) * h;
+                const RT_G double *pg2 = f == 0 ? (const RT_G double *)stg.s_qy : (f == 1 ? t.Dxs : t.Dys);
+                fv[h] = ld_handoff<QUEUE>(&pg2[f == 0 ? ss : sc]);
+            }
+#pragma unroll
+            for (int h = 0; h < NF; ++h) s_trk[tl].g2[rr + (4 / NF) * h] = fv[h];
+        } else if (lane < UNIT) {
             s_trk[tl].el0 = ld_handoff<QUEUE>(&stg.s_el[ss]); s_gap[tl] = 0.0;
         }
     }
     int32_t gmax = cnt;
-    for (int o = 8; o > 0; o >>= 1) {
+    for (int o = UNIT / 2; o > 0; o >>= 1) {
         const int32_t v = __shfl_xor(gmax, o, 64);
         gmax = v > gmax ? v : gmax;
     }
     gmax = __builtin_amdgcn_readfirstlane(gmax);
     LIN_STAMP(1);
-    const int nrounds = (gmax + kLinRows - 1) / kLinRows;
+    const int nrounds = (gmax + kRows - 1) / kRows;
     const bool many_rounds = nrounds > 1;
     for (int s = 0; s < nrounds; ++s) {
-        const int r0 = s * kLinRows;
+        const int r0 = s * kRows;
         if (s > 0) {
             __syncthreads();  // the previous round's linear phase has read its slots
             if (hprio) __builtin_amdgcn_s_setprio(3);
         }
-        // ---- the round's words: wave kw takes chunks 8 s + kw and 8 s + kw + 4 (lane = track tl, rows 4 i + rr)
+        // ---- the round's words: wave kw takes chunks 8 s + kw and 8 s + kw + 4 (lane = track tl, rows 4 i + rr) — of a 32-track
+        //      unit's rounds of four chunks: chunk 4 s + kw (rows 2 i + rr)
 #pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2) {
-            const int j = 8 * s + kw + 4 * c2;
+        for (int c2 = 0; c2 < SH::kWaveChunks; ++c2) {
+            const int j = SH::kRoundChunks * s + kw + 4 * c2;
             if (__builtin_expect((j << kChunkLog2) < gmax && !(s == 0 && spec[c2]), 0)) {  // a later round's chunk, or one from the pool's cursor: looked up, fetched now
                 const int32_t c = chunk_id(j);
+                // (32 tracks: the lane's part of the address is formed HERE — hoisted in front of the rounds as loop-invariant, it is
+                //  one 64-bit register pair too many across the store loop and spills)
+                if constexpr (UNIT == 32) {
+                    int lq = lane_q;
+                    asm volatile("" : "+v"(lq));
 #pragma unroll
-                for (int i = 0; i < 8; ++i) ve[c2][i] = __builtin_nontemporal_load(&stg.element[stage_slot(c, 4 * i + rr, lane_q)]);
+                    for (int i = 0; i < SH::kLoads; ++i) ve[c2][i] = __builtin_nontemporal_load(&stg.element[stage_slot(c, SH::kRowStep * i + rr, lq)]);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < SH::kLoads; ++i) ve[c2][i] = __builtin_nontemporal_load(&stg.element[stage_slot(c, SH::kRowStep * i + rr, lane_q)]);
+                }
             }
         }
         // ---- linear slots.  Track k's rows of this round follow track k - 1's when their records are adjacent in memory; else a
         // new run group starts, on the next multiple of 16 slots + (record index mod 16): slot ≡ record index (mod 16) everywhere.
         int32_t cr = cnt - r0;
-        cr = cr < 0 ? 0 : (cr > kLinRows ? kLinRows : cr);
+        cr = cr < 0 ? 0 : (cr > kRows ? kRows : cr);
         const int64_t o = off + r0;
         int32_t end = 0, my_lb = 0, my_gap = 0;
         // The usual unit is ONE run group — sixteen tracks with records whose runs follow one another in memory: every track starts
         // where the one before it ends (one DPP shift), and its first slot is its distance from the first track's.  (The general
         // recurrence below is a chain of sixteen dependent scalar steps: 4,000 cycles of a workgroup's 30,000, in-kernel stamps.)
         const uint32_t o_lo = (uint32_t)(uint64_t)o, o_hi = (uint32_t)((uint64_t)o >> 32);
-        const uint32_t po_lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)o_lo, 0x111, 0xf, 0xf, false);  // row_shr:1 — track tl − 1's
-        const uint32_t po_hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)o_hi, 0x111, 0xf, 0xf, false);
-        const int32_t pcr = __builtin_amdgcn_update_dpp(0, cr, 0x111, 0xf, 0xf, false);
+        // (row_shr:1 — track tl − 1's; a 32-track unit spans two DPP rows, which a row shift does not cross: wave_shr:1, as the
+        //  loop's hand-over of q — lanes 0 and 32 are track 0 and do not look)
+        const uint32_t po_lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)o_lo, SH::kShr, 0xf, 0xf, false);
+        const uint32_t po_hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)o_hi, SH::kShr, 0xf, 0xf, false);
+        const int32_t pcr = __builtin_amdgcn_update_dpp(0, cr, SH::kShr, 0xf, 0xf, false);
         const int64_t po = (int64_t)(((uint64_t)po_hi << 32) | po_lo);
         const bool one_group = __ballot(cr > 0 && (tl == 0 || o == po + pcr)) == ~0ull;
         if (one_group) {
             const uint32_t o0 = (uint32_t)__builtin_amdgcn_readlane((int)o_lo, 0);
             my_lb = (int32_t)(o0 & 15u) + (int32_t)(o_lo - o0);
             my_gap = tl == 0 ? 0 : my_lb;
-            end = __builtin_amdgcn_readlane(my_lb + cr, 15);
+            end = __builtin_amdgcn_readlane(my_lb + cr, UNIT - 1);
         } else {
             int64_t next_o = -1;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {
+            constexpr int kGroupUnroll = UNIT == 16 ? 16 : 1;
+            // (32 tracks: a rolled loop — unrolled, its 32 lane compares are hoisted out of the rounds into scalar registers that spill)
+#pragma unroll kGroupUnroll
+            for (int k = 0; k < UNIT; ++k) {
                 const int32_t crk = __builtin_amdgcn_readlane(cr, k);
                 const uint32_t olo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(uint64_t)o, k);
                 const uint32_t ohi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)o >> 32), k);
@@ -386,10 +439,10 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
         }
         const int Lp = (end + 1) & ~1;
         LIN_STAMP(2);
-        if (kw == 3 && lane < 16) {
+        if (kw == 3 && lane < UNIT) {
             const int lr = cnt - 1 - r0;
             s_trk[tl].goff = (int32_t)(o - my_lb);
-            s_trk[tl].last = (lr >= 0 && lr < kLinRows) ? my_lb + lr : -1;
+            s_trk[tl].last = (lr >= 0 && lr < kRows) ? my_lb + lr : -1;
             s_trk[tl].lb = my_lb;
             for (int k = my_gap; k < my_lb; ++k) s_meta[k] = 0;  // pads in front of a run group
             if (tl == 0 && end < Lp) s_meta[end] = 0;           // ... and behind the last one (pairs)
@@ -398,19 +451,24 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
         //      the rows beyond its track's end are those from index nv on (round 5: 14 vector instructions per word -> 2; the
         //      track's last record is no longer marked in the word: its slot is in the table)
 #pragma unroll
-        for (int c2 = 0; c2 < 2; ++c2) {
-            const int j = 8 * s + kw + 4 * c2;
+        for (int c2 = 0; c2 < SH::kWaveChunks; ++c2) {
+            const int j = SH::kRoundChunks * s + kw + 4 * c2;
             const int rb = (j << kChunkLog2) + rr;  // the lane's first row of the chunk
-            const int nv = (cnt - rb + 3) >> 2;     // its rows below the track's end (<= 0: none, >= 8: all)
+            const int nv = (cnt - rb + SH::kRowStep - 1) >> SH::kRowLog2;  // its rows below the track's end (<= 0: none, >= kLoads: all)
             int32_t *pm = &s_meta[my_lb + (rb - r0)];
             uint8_t *pt = &s_tmap[my_lb + (rb - r0)];
 #pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (__builtin_expect(i < nv, 1)) { pm[4 * i] = ve[c2][i]; pt[4 * i] = (uint8_t)tl; }
+            for (int i = 0; i < SH::kLoads; ++i)
+                if (__builtin_expect(i < nv, 1)) { pm[SH::kRowStep * i] = ve[c2][i]; pt[SH::kRowStep * i] = (uint8_t)tl; }
         }
         LIN_STAMP(3);
         __syncthreads();
         LIN_STAMP(4);
+#ifdef RT_EXPERIMENTAL
+        // (A/B probe, option "compact_debug" 32: the unit ends behind its header and transposition — what the fixed phases of a
+        //  launch cost without the loop; nothing is written, the call's results are void.  profiles/r07/exp_unit_width.log)
+        if (out.dbg & 32) return;
+#endif
         if (hprio) __builtin_amdgcn_s_setprio(0);
         // ---- the linear phase: wave kw takes pairs [m0, m1) (a multiple of 8 pairs = whole cache lines of the f64 arrays)
         const int P = Lp >> 1;
@@ -427,8 +485,8 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
                 const lin_i2 ww = *(const lin_i2 *)&s_meta[2 * m];
                 const uint32_t tt = *(const uint16_t *)&s_tmap[2 * m];
                 p.w0 = ww.x; p.w1 = ww.y;
-                p.t0 = p.w0 != 0 ? (int32_t)(tt & 15u) : 0;
-                p.t1 = p.w1 != 0 ? (int32_t)((tt >> 8) & 15u) : 0;
+                p.t0 = p.w0 != 0 ? (int32_t)(tt & (uint32_t)kTrackMask) : 0;
+                p.t1 = p.w1 != 0 ? (int32_t)((tt >> 8) & (uint32_t)kTrackMask) : 0;
             }
             const uint32_t o0 = (uint32_t)(p.w0 > 0 ? (p.w0 & kWordCode) - 1 : 0) << 5, o1 = (uint32_t)(p.w1 > 0 ? (p.w1 & kWordCode) - 1 : 0) << 5;
             const lin_d2 ab0 = __builtin_bit_cast(lin_d2, __builtin_amdgcn_raw_buffer_load_b128(r_etab, o0, 0, 0));
@@ -440,7 +498,7 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
         // the exit point of the record in front of the wave's first pair (another wave's record: computed once more, by every lane alike)
         double carry_x = 0.0, carry_y = 0.0;
         int32_t wp = 0, tp = 0;
-        if (m0 > 0) { wp = s_meta[2 * m0 - 1]; tp = wp != 0 ? (s_tmap[2 * m0 - 1] & 15) : 0; }
+        if (m0 > 0) { wp = s_meta[2 * m0 - 1]; tp = wp != 0 ? (s_tmap[2 * m0 - 1] & kTrackMask) : 0; }
         const RT_G EdgeABC *ep = a.etab + (wp > 0 ? (wp & kWordCode) - 1 : 0);
         const double epA = ep->A, epB = ep->B, epC = ep->C;
         Pre cur = prefetch(m0 + lane);
@@ -528,8 +586,8 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
                     if (w0 > 0 && 2 * m == s_trk[t0].lb) { own0 = true; o0x = s_trk[t0].cx[s & 1]; o0y = s_trk[t0].cy[s & 1]; }
                     if (w1 > 0 && 2 * m + 1 == s_trk[t1].lb) { own1 = true; o1x = s_trk[t1].cx[s & 1]; o1y = s_trk[t1].cy[s & 1]; }
                 }
-                if (w0 != 0 && 2 * m == s_trk[t0].lb + kLinRows - 1) { s_trk[t0].cx[(s + 1) & 1] = q0x; s_trk[t0].cy[(s + 1) & 1] = q0y; }
-                if (w1 != 0 && 2 * m + 1 == s_trk[t1].lb + kLinRows - 1) { s_trk[t1].cx[(s + 1) & 1] = q1x; s_trk[t1].cy[(s + 1) & 1] = q1y; }
+                if (w0 != 0 && 2 * m == s_trk[t0].lb + kRows - 1) { s_trk[t0].cx[(s + 1) & 1] = q0x; s_trk[t0].cy[(s + 1) & 1] = q0y; }
+                if (w1 != 0 && 2 * m + 1 == s_trk[t1].lb + kRows - 1) { s_trk[t1].cx[(s + 1) & 1] = q1x; s_trk[t1].cy[(s + 1) & 1] = q1y; }
             }
             // p = the exit point of the slot before: the neighbouring lane's second record (lane 0: the carry)
             const double prev_x = dpp_f64<0x138, 0xf>(carry_x, q1x), prev_y = dpp_f64<0x138, 0xf>(carry_y, q1y);
@@ -691,7 +749,7 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
 #endif
     if (a.tally) {
         __syncthreads();
-        if (threadIdx.x < 16 && have) {
+        if (threadIdx.x < UNIT && have) {
             // Σℓ = first record + chain from its q to the last record's q − gaps (a track of one record: the first record alone)
             const double fx = s_trk[tl].g1[1], fy = s_trk[tl].g1[2], gx = s_trk[tl].g1[3], gy = s_trk[tl].g2[0];
             const lin_d2 ql = s_qlast[tl];
@@ -723,8 +781,9 @@ __global__ __launch_bounds__(256, RT_LIN_OCC) void k_materialise_lin(DTracks t, 
 namespace rtx {
 
 // The launch of k_materialise_lin for the plan of the last two-phase call (records only; rows for rt_sweep: k_materialise).
+// unit: tracks per workgroup, 16 or 32 (a.n_units counts units of that width); the completion queue deals 16-track units.
 void launch_materialise_lin(const rt::DTracks &d, int32_t *status, const rt::DStage &stg, const rt::DOut &out, const rt::DMat &a_in, hipStream_t s,
-                            int n_cus, bool queue) {
+                            int n_cus, bool queue, int unit) {
     rt::DMat a = a_in;
     const unsigned blocks = (unsigned)a.n_units;
 #ifdef RT_LIN_TIMING
@@ -739,9 +798,11 @@ void launch_materialise_lin(const rt::DTracks &d, int32_t *status, const rt::DSt
     if (queue) {
         // persistent workgroups: as many as fit on the chip at once (four per CU), never more than there are units
         const unsigned qblocks = (unsigned)std::min<int64_t>((int64_t)std::max(1, n_cus) * RT_LIN_OCC, a.n_units);
-        hipLaunchKernelGGL(rt::k_materialise_lin<true>, dim3(qblocks), dim3(256), 0, s, d, status, stg, out, a);
+        hipLaunchKernelGGL((rt::k_materialise_lin<true, 16>), dim3(qblocks), dim3(256), 0, s, d, status, stg, out, a);
+    } else if (unit == 32) {
+        hipLaunchKernelGGL((rt::k_materialise_lin<false, 32>), dim3(blocks), dim3(256), 0, s, d, status, stg, out, a);
     } else {
-        hipLaunchKernelGGL(rt::k_materialise_lin<false>, dim3(blocks), dim3(256), 0, s, d, status, stg, out, a);
+        hipLaunchKernelGGL((rt::k_materialise_lin<false, 16>), dim3(blocks), dim3(256), 0, s, d, status, stg, out, a);
     }
 #ifdef RT_LIN_TIMING
     static int calls = 0;

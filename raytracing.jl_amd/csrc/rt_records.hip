@@ -787,6 +787,20 @@ bool lin_kernel_serves(const rt_tracks *t, const rt::DOut &out) {
     return t->mesh->mat_kernel != 1 && out.cap < ((int64_t)1 << 29) - 64 && t->cplan.stg.side_cap > 0;
 }
 
+// Tracks per workgroup of k_materialise_lin (option "lin_unit"; 0: chosen here).  A 32-track unit pays a unit's fixed phases — the
+// header's trip to memory, two barriers, the priming of the loop, the epilogue — once for twice as many records, as long as its
+// tracks fit one round of 128 rows; longer tracks take two rounds where a 16-track unit takes one, and the gain is gone.  Decided
+// from what the call knows before it runs: the records per track of the previous call on this handle, or the estimate the pools are
+// sized from.  The threshold is measured (profiles/r07/exp_unit_width.log).  The completion queue deals 16-track units.
+constexpr int64_t kLinUnit32MaxMean = 100;
+static int choose_lin_unit(const rt_tracks *t, bool queue) {
+    const rt_mesh *m = t->mesh;
+    if (queue) return 16;
+    if (m->lin_unit == 16 || m->lin_unit == 32) return m->lin_unit;
+    const int64_t est = t->total_last > 0 ? t->total_last : (int64_t)(1.08 * m->kappa * t->sum_ell) + 2 * t->n;
+    return est <= kLinUnit32MaxMean * t->n ? 32 : 16;
+}
+
 // Codes -> records and / or (ℓ, cell) rows (k_materialise) for the plan of the last two-phase call.  tally: the call's first
 // pass over the codes — Σℓ and status (k_finish completes them).
 int launch_materialise(rt_tracks *t, const rt::DOut &out, hipStream_t s, bool records, bool rows, bool tally, unsigned long long *d_ctl, bool queue) {
@@ -813,8 +827,11 @@ int launch_materialise(rt_tracks *t, const rt::DOut &out, hipStream_t s, bool re
     }
     const unsigned blocks = (unsigned)a.n_units;
     if (records && !rows && lin_kernel_serves(t, out)) {
-        launch_materialise_lin(c.d_whole, t->status.p, c.stg, out, a, s, m->n_cus, queue);
-        if (tally) t->last_record_kernel = 3;
+        // (a launch that does not tally writes the records of a call that has tallied — arrays that were too small: the same width)
+        const int unit = tally || t->last_lin_unit == 0 ? choose_lin_unit(t, queue) : t->last_lin_unit;
+        a.n_units = (64 / unit) * c.n_whole_waves;
+        launch_materialise_lin(c.d_whole, t->status.p, c.stg, out, a, s, m->n_cus, queue, unit);
+        if (tally) { t->last_record_kernel = unit == 32 ? 5 : 3; t->last_lin_unit = unit; }
         return RT_SUCCESS;
     }
     if (queue) { set_error("records in completion order need k_materialise_lin"); return RT_ERR_INVALID; }

@@ -570,6 +570,11 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value) {
     if (!strcmp(name, "sweep_debug")) { mesh->sweep_debug = (int)value; return RT_SUCCESS; }
     if (!strcmp(name, "compact_debug")) { mesh->compact_debug = (int)value; return RT_SUCCESS; }
     if (!strcmp(name, "mat_kernel")) { mesh->mat_kernel = (int)value; return RT_SUCCESS; }
+    if (!strcmp(name, "lin_unit")) {
+        if (value != 0 && value != 16 && value != 32) { set_error("option 'lin_unit' is 0 (automatic), 16 or 32"); return RT_ERR_INVALID; }
+        mesh->lin_unit = (int)value;
+        return RT_SUCCESS;
+    }
     if (!strcmp(name, "march_waves")) { mesh->march_waves = (int)value; return RT_SUCCESS; }
     if (!strcmp(name, "topo")) { mesh->topo = value < 0 ? 0 : (value > 2 ? 2 : (int)value); return RT_SUCCESS; }
     if (!strcmp(name, "record_order")) { mesh->record_order = value < 0 ? 0 : (value > 2 ? 2 : (int)value); return RT_SUCCESS; }
@@ -1883,7 +1888,7 @@ int32_t rt_last_stats(rt_tracks *t, int64_t *stats, int32_t n) {
     if (n > 26) stats[26] = t->side_cap;        // side-list entries allocated (one reserved per march slot + the dynamic part)
     if (n > 25) stats[25] = t->side_needed_last;  // ... and used beyond the reserved ones
     if (n > 24) stats[24] = t->last_completion;  // 1: the call wrote its records beside the march, in completion order (option "record_order")
-    if (n > 23) stats[23] = t->last_record_kernel;  // 1 k_compact3, 2 k_materialise, 3 k_materialise_lin, 4 k_materialise writing (ℓ, cell) rows only
+    if (n > 23) stats[23] = t->last_record_kernel;  // 1 k_compact3, 2 k_materialise, 3 k_materialise_lin, 4 k_materialise writing (ℓ, cell) rows only, 5 k_materialise_lin with 32-track units
     if (n > 7) {  // device memory held by this handle: inputs, staging pools, tables, results
         auto b = [](const auto &d) { return (int64_t)(d.cap * sizeof(*d.p)); };
         stats[7] = b(t->in_arena) + b(t->cnt_slot) + b(t->off_slot) + b(t->w_slot) +
