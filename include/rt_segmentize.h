@@ -537,6 +537,33 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  * same data return the same bits.  First-order perturbation theory (flat source, isotropic scattering), X = S + F/k:
  *              δ(1/k) = − ⟨φ†, (δS + δF/k) φ⟩ / ⟨φ†, F φ⟩,   F[g'→g] = χ_g νΣf_g',  S[g'→g] = Σs[g'→g]
  *
+ * Boundary, rt_solver_set_boundary: albedos, a prescribed incoming flux, and the partial currents per side.  A traversal is
+ * (d, u), d = 0 forward and d = 1 backward along track u; the caller names S <= 16 sides and says for every traversal which side
+ * it ENDS on, end_side[d][u] in 0 .. S − 1, or −1 for "no side".  It STARTS on side end_side[1 − d][u].
+ * Hand-over    let (d, u) end on side s >= 0 and its link name the entry (d', v) in this track set.  For the next sweep
+ *                  ψ_in[(d', v)][g·P + p] = β[s][g] · ψ_out[(d, u)][g·P + p] + ψ_inc[s][g]          (one fused multiply-add)
+ *              whatever bc the link carries: β = 1, ψ_inc = 0 is the reflective hand-over with the same bits, β = 0, ψ_inc = 0 the
+ *              vacuum one.  ψ_inc is an isotropic angular flux, the same for every p.  Ends with side −1 keep what their bc
+ *              decides.  Where two links name one entry the last one in rt_sweep_set_links' order decides, sided or not.  The
+ *              first sweep of a run enters with ψ_in = ψ_inc behind the sided ends (0 elsewhere)
+ * Currents     per sweep, side and group, with the fold's weights (a track end stands for the boundary length δ_a / |cos| and
+ *              Ω·n = sin θ_p |cos|, so w[u] ω_p sin θ_p is |Ω·n| ψ integrated over the side):
+ *                  J⁺[s][g] = Σ_{(d,u) ends on s}   w[u] Σ_p ω_p sin θ_p ψ_out[(d, u)][g·P + p]
+ *                  J⁻[s][g] = Σ_{(d,u) starts on s} w[u] Σ_p ω_p sin θ_p ψ_in[(d, u)][g·P + p]       (ψ_in: what ENTERED that sweep)
+ * Identity     T[e] sums w (ψ_in − ψ_out) over segments and the sum along a track telescopes: when every end has a side >= 0,
+ *                  Σ_e Σ_p ω_p sin θ_p T[e][g·P + p] = Σ_s (J⁻[s][g] − J⁺[s][g])
+ *              for every sweep and group, up to the rounding of the sums (no convergence needed)
+ * Balance      with the fold, per group: Σ_e V_e (Σt_g φ_{e,g} − 4π q_{e,g}) = Σ_s (J⁻ − J⁺)[s][g]; summed over the groups with a
+ *              converged source: production / k = absorption + net leakage.  rt_solver_fetch_boundary returns the LAST sweep's
+ *              J⁺ and J⁻ (eigenvalue mode: rt_solver_end scales them with φ), so a balance formed with the last φ has a defect of
+ *              the size of the iteration error
+ * Reductions   block partials per (side, group) in LDS columns owned by one thread each, then one workgroup over the partials in a
+ *              fixed order: no FP64 atomics, the same ψ gives the same bits
+ * Restrictions β finite in [0, 1]; ψ_inc finite and >= 0, and a ψ_inc > 0 makes rt_solver_begin refuse RT_SOLVE_EIGENVALUE; a track
+ *              set with a next uid of 0 (a shard) is refused.  The hand-over acts on ψ only: first-moment scattering, the linear
+ *              source, adjoint mode (β is diagonal in the groups and the same for a traversal and its reverse: k† = k) and the
+ *              stepwise calls work unchanged.  A solver without a boundary launches exactly what it always did
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -665,6 +692,19 @@ int32_t rt_solver_end(rt_solver *solver, rt_solver_result *out);
  * rt_solver_begin and rt_solver_end (NULL / 0 outside, and [2] in a flat isotropic run); [3] phi [n_cells·G], the iterate
  * (unnormalised until rt_solver_end).  What may be written through them, and when: see above.  Does not wait. */
 int32_t rt_solver_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
+/* Boundary (see above) for the following runs.  end_side [2][n_tracks] (forward ends, then backward ends; −1 .. n_sides − 1),
+ * albedo [n_sides][G], incoming [n_sides][G] or NULL (zero); host memory, copied.  n_sides = 0 switches it off (the arrays are
+ * not read): the solver then launches exactly what one that never had a boundary does.  Builds its gather map from the links
+ * rt_sweep_set_links got last; if that runs again, set the boundary again (rt_solver_begin refuses until then).  RT_ERR_INVALID for
+ * n_sides > 16, a side id outside −1 .. n_sides − 1, a β outside [0, 1], a negative ψ_inc, a non-finite entry, a shard's track set,
+ * with a run open or after the tracks were segmentized again; the solver then keeps what it had. */
+int32_t rt_solver_set_boundary(rt_solver *solver, int32_t n_sides, const int32_t *end_side, const double *albedo, const double *incoming);
+/* The partial currents of the last sweep, j_out = J⁺ and j_in = J⁻ [n_sides][G] (either may be NULL): after a run, and in an open
+ * run after an rt_solver_step_sweep (waits for it).  RT_ERR_INVALID without a boundary, or before the first sweep with it. */
+int32_t rt_solver_fetch_boundary(rt_solver *solver, double *j_out, double *j_in);
+/* Device addresses ptrs_dev[2] and element counts lens[2] (either may be NULL) of J⁺ and J⁻ [n_sides·G], valid while a boundary is
+ * set (NULL / 0 without one); the content is that of rt_solver_fetch_boundary.  Does not wait. */
+int32_t rt_solver_boundary_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

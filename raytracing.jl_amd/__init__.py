@@ -8,14 +8,16 @@ hand-written HIP kernels in ``csrc/`` through the C ABI declared in
 without a GPU it raises.  ``solve_eigenvalue`` / ``solve_fixed_source`` run a MOC
 source iteration on the device over the records of the last ``segmentize``, forward or
 adjoint; ``perturbation_reactivity`` / ``kinetics_parameters`` weigh with the adjoint flux.
+``SolverBoundary`` puts albedos and an incoming flux on the four sides and makes a run
+return the partial currents per side and the neutron balance.
 """
 from .boundary import BoundaryConditions, BoundaryType, Periodic, Reflective, Vacuum
 from .mesh import DiscreteModel, DiscreteModelFromFile, GmshDiscreteModel, Mesh, data_path
 from .quadrature import AzimuthalQuadrature
 from .trackgenerator import (Backward, Forward, Segment, Track, TrackGenerator, bc_bwd, bc_fwd,
-                             dir_next_track_bwd, dir_next_track_fwd, trace)
+                             dir_next_track_bwd, dir_next_track_fwd, trace, track_end_sides)
 from .segmentize import RTOL_DEFAULT, SegmentStore, segmentize
-from .solver import (CrossSections, PolarQuadrature, SolverResult, azimuthal_weights, exact_azimuthal_weights,
+from .solver import (CrossSections, PolarQuadrature, SolverBoundary, SolverResult, azimuthal_weights, exact_azimuthal_weights,
                      kinetics_parameters, perturbation_reactivity, solve_eigenvalue, solve_fixed_source)
 from .distributed import ShardedSolver
 
@@ -26,5 +28,6 @@ __all__ = [
     "Track", "Segment",
     "CrossSections", "PolarQuadrature", "SolverResult", "azimuthal_weights", "exact_azimuthal_weights",
     "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "ShardedSolver",
+    "SolverBoundary", "track_end_sides",
     "Forward", "Backward", "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd",
 ]

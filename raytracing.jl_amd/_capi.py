@@ -33,6 +33,7 @@ SYMBOLS = (
     "rt_solver_fetch_current",
     "rt_solver_begin", "rt_solver_step_sweep", "rt_solver_step_fold", "rt_solver_end", "rt_solver_pointers",
     "rt_solver_set_adjoint", "rt_solver_bilinear",
+    "rt_solver_set_boundary", "rt_solver_fetch_boundary", "rt_solver_boundary_pointers",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -256,6 +257,12 @@ def lib():
     L.rt_solver_step_fold.argtypes = [_vp, C.POINTER(SolverResult)]
     L.rt_solver_end.restype = C.c_int32
     L.rt_solver_end.argtypes = [_vp, C.POINTER(SolverResult)]
+    L.rt_solver_set_boundary.restype = C.c_int32
+    L.rt_solver_set_boundary.argtypes = [_vp, C.c_int32, _ip, _dp, _dp]
+    L.rt_solver_fetch_boundary.restype = C.c_int32
+    L.rt_solver_fetch_boundary.argtypes = [_vp, _dp, _dp]
+    L.rt_solver_boundary_pointers.restype = C.c_int32
+    L.rt_solver_boundary_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
     L.rt_solver_pointers.restype = C.c_int32
     L.rt_solver_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
     if L.rt_abi_version() != 1:
@@ -753,6 +760,51 @@ class DeviceSolver:
         if per_cell:
             return res, (cells[0] if single else cells)
         return res
+
+    def set_boundary(self, boundary=None, end_side=None, albedo=None, incoming=None):
+        """``rt_solver_set_boundary`` for the following runs.  ``boundary``: a ``solver.SolverBoundary`` (four sides; ``end_side`` =
+        ``track_end_sides(tg)``), or None with ``albedo`` [S, G] and ``incoming`` [S, G] (None: zero) for S <= 16 sides of the caller's
+        own.  ``end_side`` int32 [2, n_tracks]: the side every forward / backward traversal ends on, -1 for none.  All None: off."""
+        if boundary is None and end_side is None and albedo is None:
+            _check(lib().rt_solver_set_boundary(self._open(), 0, None, None, None))
+            self.n_sides = 0
+            return
+        if boundary is not None:
+            albedo, incoming = boundary.arrays(self.G)
+        if end_side is None or albedo is None:
+            raise ValueError("a boundary needs end_side [2, n_tracks] and albedos")
+        es = np.ascontiguousarray(end_side, np.int32)
+        if es.ndim != 2 or es.shape[0] != 2:
+            raise ValueError("end_side must have shape [2, n_tracks]")
+        if es.shape[1] != self.dtracks.n:
+            raise ValueError("end_side must have shape [2, n_tracks]")
+        be = np.ascontiguousarray(albedo, np.float64)
+        if be.ndim != 2 or be.shape[1] != self.G:
+            raise ValueError("albedo must have shape [S, G]")
+        inc = None if incoming is None else np.ascontiguousarray(incoming, np.float64)
+        if inc is not None and inc.shape != be.shape:
+            raise ValueError("incoming must have the albedo's shape [S, G]")
+        _check(lib().rt_solver_set_boundary(self._open(), be.shape[0], es.ctypes.data_as(_ip), be.ctypes.data_as(_dp),
+                                            None if inc is None else inc.ctypes.data_as(_dp)))
+        self.n_sides = be.shape[0]
+
+    def fetch_boundary(self) -> dict:
+        """``rt_solver_fetch_boundary``: ``current_out`` (J⁺) and ``current_in`` (J⁻) [S, G] of the last sweep."""
+        S = getattr(self, "n_sides", 0)
+        jo = np.empty((max(S, 1), self.G)); ji = np.empty((max(S, 1), self.G))
+        _check(lib().rt_solver_fetch_boundary(self._open(), jo.ctypes.data_as(_dp), ji.ctypes.data_as(_dp)))
+        return dict(current_out=jo[:S], current_in=ji[:S])
+
+    def boundary_pointers(self) -> dict:
+        """``rt_solver_boundary_pointers``: device addresses (0: no boundary) of ``current_out`` and ``current_in`` [S·G] and their
+        element counts under ``lens``."""
+        ptrs = (_vp * 2)()
+        lens = (C.c_int64 * 2)()
+        _check(lib().rt_solver_boundary_pointers(self._open(), ptrs, lens))
+        names = ("current_out", "current_in")
+        out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
+        out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
+        return out
 
     def fetch_current(self) -> np.ndarray:
         """``rt_solver_fetch_current``: the net current [n_cells, G, 2] of the last run (with first-moment scattering)."""

@@ -507,6 +507,11 @@ struct rt_tracks {
     bool sw_rowsc_valid = false;       // ... sw_ell / sw_cell hold those rows for the last rt_segmentize
     bool sw_links = false, sw_has_w = false, sw_has_xs = false, sw_done = false;
     rt_solver *sw_borrower = nullptr;  // the rt_solver between rt_solver_begin and rt_solver_end that holds this sweep state
+    // host copy of the links as rt_sweep_set_links got them, whatever their bc (rt_solver_set_boundary builds its own gather map
+    // from it): entry slot d'·n + v of source d·n + u (-1: the linked track is not in this track set), in [2][n]
+    std::vector<int32_t> sw_h_entry;
+    bool sw_shard = false;        // ... some next uid was 0: a shard's track set
+    uint64_t sw_links_epoch = 0;  // rt_sweep_set_links calls on this handle
     int32_t sw_groups = 0, sw_last_input = 0, sw_last_gp = 0, sw_last_passes = 0, sw_last_rows = 0;
     int64_t refusals[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // cheap-step refusals of the last call by certificate term
     int64_t n_near_rtol = 0, n_restarts = 0, n_exact_tally = 0;

@@ -416,6 +416,99 @@ __global__ __launch_bounds__(256) void k_solver_track_weights(const int32_t *__r
     if (u < n) w[u] = w4pi[azim[u] - 1];
 }
 
+// ---- boundary (rt_solver_set_boundary): the hand-over behind sided ends, the partial currents per side and group ----------------
+constexpr int kMaxSides = 16;
+constexpr int kTallyEnds = 16;  // track ends per thread of k_solver_bnd_tally
+
+// One thread per (entry slot, component), after the sweep's own k_sweep_link: psi_in = fma(β[s][g], psi_out[source], ψ_inc[s][g])
+// for the entries behind an end on a side s (src_of[slot] = source track · 2 + direction, side_of[slot] = s); the others (-1)
+// keep what k_sweep_link gave them.  FIRST (rt_solver_begin, on the zeroed psi_in): the incoming part alone.
+template <bool FIRST>
+__global__ __launch_bounds__(256) void k_solver_bnd_link(const int32_t *__restrict__ src_of, const int8_t *__restrict__ side_of,
+                                                         const double *__restrict__ beta, const double *__restrict__ inc,
+                                                         const double *__restrict__ psi_out, double *__restrict__ psi_in, int64_t n2,
+                                                         int32_t G, int32_t P, int64_t n) {
+    const int64_t C = (int64_t)G * P;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (entry slot, component)
+    if (i >= n2 * C) return;
+    const int64_t slot = i / C;
+    const int32_t c = (int32_t)(i - slot * C);
+    const int32_t sc = src_of[slot];
+    if (sc < 0) return;
+    const int32_t sg = (int32_t)side_of[slot] * G + c / P;
+    if (FIRST) psi_in[i] = inc[sg];
+    else psi_in[i] = fma(beta[sg], psi_out[((int64_t)(sc & 1) * n + (sc >> 1)) * C + c], inc[sg]);
+}
+
+// Partial currents of one flux array psi [2][n][G·P] (psi_out with the sides the traversals end on: J⁺; psi_in, before the sweep,
+// with the sides they start on: J⁻): partial[block][s·G + g] = Σ_{ends of the block on side s} w[u] Σ_p ω_p sin θ_p psi[end][g·P + p].
+// A workgroup takes kTallyEnds · K consecutive ends, K = 256 / G; thread (k, g) walks the ends k, k + K, ... of that range in order
+// (so that at every step the workgroup reads K·G·P consecutive doubles) and adds into its own column of the LDS accumulators
+// acc[s][thread]; thread j then sums the K columns of (s, g) in order.  No atomics: the same bits in every call.
+__global__ __launch_bounds__(kSolveBlock) void k_solver_bnd_tally(const int8_t *__restrict__ side, const double *__restrict__ w,
+                                                                  const double *__restrict__ pol, const double *__restrict__ psi,
+                                                                  int64_t n2, int64_t n, int32_t G, int32_t P, int32_t S,
+                                                                  double *__restrict__ partial) {
+    __shared__ double acc[kMaxSides * kSolveBlock];
+    const int32_t K = kSolveBlock / G;  // (G <= 256)
+    const int32_t k = threadIdx.x / G, g = threadIdx.x - k * G;
+    for (int32_t s = 0; s < S; ++s) acc[s * kSolveBlock + threadIdx.x] = 0.0;
+    const int64_t e0 = (int64_t)blockIdx.x * kTallyEnds * K;
+    // (every load unconditional on a clamped index, so that the loads of the unrolled steps are in flight together)
+#pragma unroll 4
+    for (int j = 0; j < kTallyEnds; ++j) {
+        const int64_t e = e0 + (int64_t)j * K + k;
+        const bool in = k < K && e < n2;
+        const int64_t ec = in ? e : 0;
+        const int32_t s = side[ec];
+        const double *x = psi + (ec * G + g) * P;
+        double a = 0.0;
+        for (int32_t p = 0; p < P; ++p) a += pol[P + p] * x[p];
+        const double v = w[ec < n ? ec : ec - n] * a;
+        if (in && s >= 0) acc[s * kSolveBlock + threadIdx.x] += v;
+    }
+    __syncthreads();
+    for (int32_t j = threadIdx.x; j < S * G; j += kSolveBlock) {
+        const int32_t s = j / G, gg = j - s * G;
+        double sum = 0.0;
+        for (int32_t kk = 0; kk < K; ++kk) sum += acc[s * kSolveBlock + kk * G + gg];
+        partial[(int64_t)blockIdx.x * S * G + j] = sum;
+    }
+}
+
+// one workgroup: the block partials of the two tallies in a fixed order -> J [2][S][G] (J⁺, then J⁻).  Up to 256 entries at a time:
+// R = 256 / entries rows of threads, row r sums the blocks r, r + R, ... of its entry in eight interleaved chains (eight loads in
+// flight), then one thread per entry sums the R rows in order.
+__global__ __launch_bounds__(kSolveBlock) void k_solver_bnd_reduce(const double *__restrict__ part_out, const double *__restrict__ part_in,
+                                                                   int32_t n_blocks, int32_t SG, double *__restrict__ J) {
+    __shared__ double red[kSolveBlock];
+    const int32_t E = 2 * SG, tid = threadIdx.x;
+    for (int32_t j0 = 0; j0 < E; j0 += kSolveBlock) {
+        const int32_t cols = E - j0 < kSolveBlock ? E - j0 : kSolveBlock, R = kSolveBlock / cols;
+        const int32_t r = tid / cols, c = tid - r * cols;
+        double sum = 0.0;
+        if (r < R) {
+            const int32_t j = j0 + c;
+            const double *part = (j < SG ? part_out : part_in) + (j < SG ? j : j - SG);
+            double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+            int32_t b = r;
+            for (; b + 7 * R < n_blocks; b += 8 * R)
+#pragma unroll
+                for (int u = 0; u < 8; ++u) a[u] += part[(int64_t)(b + u * R) * SG];
+            for (; b < n_blocks; b += R) a[0] += part[(int64_t)b * SG];
+            sum = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+        }
+        red[tid] = sum;
+        __syncthreads();
+        if (tid < cols) {
+            double t = 0.0;
+            for (int32_t rr = 0; rr < R; ++rr) t += red[rr * cols + tid];
+            J[j0 + tid] = t;
+        }
+        __syncthreads();
+    }
+}
+
 }  // namespace rt
 
 struct rt_solver {
@@ -444,10 +537,19 @@ struct rt_solver {
     DevBuf<double> ls_acc, ls_wvol;
     DevBuf<int32_t> ls_ndeg;
     int32_t n_degenerate = 0;
+    // boundary (rt_solver_set_boundary): the gather map of the sided ends by entry slot (source · 2 + direction, -1: none) and the
+    // side of each, the side every traversal ends / starts on [2][n], β and ψ_inc [S][G], the tallies' block partials (J⁺'s, then
+    // J⁻'s) and J [2][S][G] (J⁺, then J⁻) of the last sweep
+    int32_t bnd_S = 0, bnd_blocks = 0;
+    bool bnd_inc = false, bnd_tallied = false;  // some ψ_inc > 0; bnd_J holds the tallies of a sweep of the last run
+    uint64_t bnd_links_epoch = 0;               // the rt_sweep_set_links call whose links the gather map was built from
+    DevBuf<int32_t> bnd_src;
+    DevBuf<int8_t> bnd_side_entry, bnd_side_end, bnd_side_start;
+    DevBuf<double> bnd_beta, bnd_incv, bnd_part, bnd_J;
     std::vector<double> k_hist;
     // the run in progress (rt_solver_begin ... rt_solver_end): `open` while this solver holds the handle's sweep state
     // (rt_tracks::sw_borrower points back here), `swept` between rt_solver_step_sweep and rt_solver_step_fold
-    bool open = false, swept = false, run_eigen = false, run_p1 = false, run_ls = false;
+    bool open = false, swept = false, run_eigen = false, run_p1 = false, run_ls = false, run_bnd = false;
     int32_t it = 0;
     double last_k = 1.0, last_res = INFINITY, last_dk = INFINITY;
     double *h_scal = nullptr;  // pinned, kSolveScalars
@@ -663,6 +765,15 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
     if (S->open) solver_release(S);  // (a second begin starts afresh)
     rt_tracks *t = S->t;
     if (int rc = solver_check_tracks(S, who)) return rc;
+    const bool bnd = S->bnd_S > 0;
+    if (bnd && S->bnd_links_epoch != t->sw_links_epoch) {
+        set_error("%s: rt_sweep_set_links ran again after rt_solver_set_boundary (its gather map is stale): set the boundary again", who);
+        return RT_ERR_INVALID;
+    }
+    if (bnd && S->bnd_inc && mode == RT_SOLVE_EIGENVALUE) {
+        set_error("%s: an incoming boundary flux is set (rt_solver_set_boundary), and an eigenvalue run has no fixed source", who);
+        return RT_ERR_INVALID;
+    }
     if (t->sw_borrower) solver_release(t->sw_borrower);  // (another solver's unfinished run on this handle ends here)
     const bool eigen = mode == RT_SOLVE_EIGENVALUE;
     rt_mesh *m = t->mesh;
@@ -700,8 +811,14 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
         RT_HIP(hipMemsetAsync(S->mom.p, 0, nj * sizeof(double), s));
         t->sw_ls = true; t->sw_ls_cen = S->cen.p; t->sw_ls_ends = S->ends.p;
     }
+    S->bnd_tallied = false;
+    if (bnd) RT_HIP(hipMemsetAsync(S->bnd_J.p, 0, (size_t)2 * S->bnd_S * G * sizeof(double), s));
+    if (bnd && S->bnd_inc && n > 0)  // the first sweep already sees the incoming flux
+        hipLaunchKernelGGL(rt::k_solver_bnd_link<true>, dim3((unsigned)((2 * n * C + 255) / 256)), dim3(256), 0, s, (const int32_t *)S->bnd_src.p,
+                           (const int8_t *)S->bnd_side_entry.p, (const double *)S->bnd_beta.p, (const double *)S->bnd_incv.p,
+                           (const double *)nullptr, t->sw_psi_in.p, 2 * n, G, P, n);
     S->k_hist.clear();
-    S->run_eigen = eigen; S->run_p1 = p1; S->run_ls = ls;
+    S->run_eigen = eigen; S->run_p1 = p1; S->run_ls = ls; S->run_bnd = bnd;
     S->it = 0; S->last_k = 1.0; S->last_res = INFINITY; S->last_dk = INFINITY;
     // φ⁰ = 1, the components' Σt / sin θ, F⁰
     RT_HIP(hipMemsetAsync(S->prod.p, 0, (size_t)std::max(1, nc) * sizeof(double), s));
@@ -731,7 +848,25 @@ int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
                            (const double *)S->tab.p, d.lds_len, (const double *)S->mom.p, (const double *)S->cinv.p, (const double *)S->pol.p,
                            (const double *)S->scal.p, eig, nc, G, P, S->gr.p, t->sw_xs1.p);
     RT_HIP(hipGetLastError());
+    const int64_t n = t->n;
+    const bool bnd = S->run_bnd && n > 0;  // (no tracks: J stays the zeros of rt_solver_begin)
+    const int32_t SG = S->bnd_S * G;
+    auto tally = [&](const int8_t *side, const double *psi, double *part) {
+        hipLaunchKernelGGL(rt::k_solver_bnd_tally, dim3((unsigned)S->bnd_blocks), dim3(rt::kSolveBlock), 0, s, side, (const double *)S->w_track.p,
+                           (const double *)S->pol.p, psi, 2 * n, n, G, P, S->bnd_S, part);
+    };
+    if (bnd) tally(S->bnd_side_start.p, t->sw_psi_in.p, S->bnd_part.p + (size_t)S->bnd_blocks * SG);  // J⁻: the flux that enters this sweep
     if (int32_t rc = rt_sweep(t, d.C, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
+    if (bnd) {  // J⁺ of this sweep, then the hand-over behind the sided ends over what k_sweep_link wrote
+        tally(S->bnd_side_end.p, t->sw_psi_out.p, S->bnd_part.p);
+        hipLaunchKernelGGL(rt::k_solver_bnd_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->bnd_part.p,
+                           (const double *)(S->bnd_part.p + (size_t)S->bnd_blocks * SG), S->bnd_blocks, SG, S->bnd_J.p);
+        hipLaunchKernelGGL(rt::k_solver_bnd_link<false>, dim3((unsigned)((2 * n * d.C + 255) / 256)), dim3(256), 0, s, (const int32_t *)S->bnd_src.p,
+                           (const int8_t *)S->bnd_side_entry.p, (const double *)S->bnd_beta.p, (const double *)S->bnd_incv.p,
+                           (const double *)t->sw_psi_out.p, t->sw_psi_in.p, 2 * n, G, P, n);
+        RT_HIP(hipGetLastError());
+    }
+    S->bnd_tallied = S->run_bnd;
     S->swept = true;
     return RT_SUCCESS;
 }
@@ -803,6 +938,9 @@ int solver_end_impl(rt_solver *S, rt_solver_result *res, const char *who) {
         hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * d.ncg + 255) / 256)), dim3(256), 0, s, S->J.p, 2 * d.ncg, (const double *)S->scal.p);
     if (eigen && d.nc > 0 && S->run_ls)
         hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * d.ncg + 255) / 256)), dim3(256), 0, s, S->mom.p, 2 * d.ncg, (const double *)S->scal.p);
+    if (eigen && S->run_bnd && S->bnd_tallied)  // (the currents of the last sweep, scaled with φ)
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * S->bnd_S * d.G + 255) / 256)), dim3(256), 0, s, S->bnd_J.p,
+                           (int64_t)2 * S->bnd_S * d.G, (const double *)S->scal.p);
     RT_HIP(hipStreamSynchronize(s));
     RT_HIP(hipGetLastError());
     float f = 0.0f;
@@ -994,6 +1132,125 @@ int32_t rt_solver_bilinear(rt_solver *adjoint, rt_solver *forward, int32_t n_for
         set_error("rt_solver_bilinear: %s", e.what());
         return RT_ERR_INVALID;
     }
+}
+
+// The boundary of the following runs: the gather map of the sided ends from the handle's host copy of its links, in the order
+// rt_sweep_set_links builds its own (uid ascending, forward before backward; the last writer of an entry wins, sided or not).
+static int32_t solver_set_boundary_impl(rt_solver *S, int32_t n_sides, const int32_t *end_side, const double *albedo, const double *incoming) {
+    const char *who = "rt_solver_set_boundary";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the boundary cannot change under it", who); return RT_ERR_INVALID; }
+    if (n_sides == 0) { S->bnd_S = 0; S->bnd_inc = false; S->bnd_tallied = false; return RT_SUCCESS; }
+    if (n_sides < 0 || n_sides > rt::kMaxSides) { set_error("%s: bad arguments (n_sides %d, need 0 .. %d)", who, n_sides, rt::kMaxSides); return RT_ERR_INVALID; }
+    if (!end_side || !albedo) { set_error("%s: null argument", who); return RT_ERR_INVALID; }
+    rt_tracks *t = S->t;
+    const int64_t n = t->n;
+    if (!t->sw_links || (int64_t)t->sw_h_entry.size() != 2 * n) { set_error("%s: rt_sweep_set_links has not run", who); return RT_ERR_INVALID; }
+    if (t->sw_shard) {
+        set_error("%s: the track set is a shard (some next uid is 0): boundaries on sharded runs are not supported", who);
+        return RT_ERR_INVALID;
+    }
+    const int32_t G = S->G;
+    const size_t sg = (size_t)n_sides * G;
+    bool any_inc = false;
+    for (size_t i = 0; i < sg; ++i) {
+        if (!std::isfinite(albedo[i]) || albedo[i] < 0.0 || albedo[i] > 1.0) {
+            set_error("%s: albedo[%zu][%zu] = %g (must be finite and in [0, 1])", who, i / G, i % G, albedo[i]);
+            return RT_ERR_INVALID;
+        }
+        if (incoming && (!std::isfinite(incoming[i]) || incoming[i] < 0.0)) {
+            set_error("%s: incoming[%zu][%zu] = %g (must be finite and >= 0)", who, i / G, i % G, incoming[i]);
+            return RT_ERR_INVALID;
+        }
+        any_inc = any_inc || (incoming && incoming[i] > 0.0);
+    }
+    const size_t n2 = (size_t)(2 * n);
+    std::vector<int8_t> side_end(std::max<size_t>(1, n2), -1), side_start(std::max<size_t>(1, n2), -1), side_entry(std::max<size_t>(1, n2), -1);
+    std::vector<int32_t> src(std::max<size_t>(1, n2), -1);
+    for (size_t i = 0; i < n2; ++i) {
+        if (end_side[i] < -1 || end_side[i] >= n_sides) {
+            set_error("%s: end_side[%zu][%zu] = %d is not a side in [0, %d) or -1", who, i / (size_t)n, i % (size_t)n, end_side[i], n_sides);
+            return RT_ERR_INVALID;
+        }
+        side_end[i] = (int8_t)end_side[i];
+        side_start[i < (size_t)n ? i + n : i - n] = (int8_t)end_side[i];  // (d, u) starts where (1 − d, u) ends
+    }
+    for (int64_t u = 0; u < n; ++u)
+        for (int d = 0; d < 2; ++d) {
+            const size_t from = (size_t)d * n + u;
+            const int32_t slot = t->sw_h_entry[from];
+            if (slot < 0) continue;
+            const bool sided = side_end[from] >= 0;
+            src[(size_t)slot] = sided ? (int32_t)(u * 2 + d) : -1;
+            side_entry[(size_t)slot] = sided ? side_end[from] : (int8_t)-1;
+        }
+    std::vector<double> zero;
+    if (!incoming) zero.assign(sg, 0.0);
+    if (int rc = finish_call(t)) return rc;
+    RT_HIP(hipSetDevice(t->mesh->device));
+    hipStream_t s = t->mesh->stream;
+    // (into fresh buffers: a failure leaves the solver what it had)
+    DevBuf<int32_t> d_src;
+    DevBuf<int8_t> d_entry, d_end, d_start;
+    DevBuf<double> d_beta, d_inc, d_part, d_J;
+    const int32_t K = rt::kSolveBlock / G;
+    const int32_t blocks = (int32_t)std::max<int64_t>(1, (2 * n + (int64_t)rt::kTallyEnds * K - 1) / ((int64_t)rt::kTallyEnds * K));
+    if (int rc = upload(d_src, src.data(), src.size(), s)) return rc;
+    if (int rc = upload(d_entry, side_entry.data(), side_entry.size(), s)) return rc;
+    if (int rc = upload(d_end, side_end.data(), side_end.size(), s)) return rc;
+    if (int rc = upload(d_start, side_start.data(), side_start.size(), s)) return rc;
+    if (int rc = upload(d_beta, albedo, sg, s)) return rc;
+    if (int rc = upload(d_inc, incoming ? incoming : zero.data(), sg, s)) return rc;
+    RT_HIP(d_part.reserve((size_t)2 * blocks * sg)); RT_HIP(d_J.reserve(2 * sg));
+    RT_HIP(hipStreamSynchronize(s));  // (the host vectors die here)
+    S->bnd_src = std::move(d_src); S->bnd_side_entry = std::move(d_entry); S->bnd_side_end = std::move(d_end); S->bnd_side_start = std::move(d_start);
+    S->bnd_beta = std::move(d_beta); S->bnd_incv = std::move(d_inc); S->bnd_part = std::move(d_part); S->bnd_J = std::move(d_J);
+    S->bnd_S = n_sides; S->bnd_blocks = blocks; S->bnd_inc = any_inc; S->bnd_tallied = false; S->bnd_links_epoch = t->sw_links_epoch;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_boundary(rt_solver *solver, int32_t n_sides, const int32_t *end_side, const double *albedo, const double *incoming) {
+    try {
+        return solver_set_boundary_impl(solver, n_sides, end_side, albedo, incoming);
+    } catch (const std::exception &e) {
+        set_error("rt_solver_set_boundary: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+int32_t rt_solver_fetch_boundary(rt_solver *solver, double *j_out, double *j_in) {
+    if (!solver) { set_error("rt_solver_fetch_boundary: null solver"); return RT_ERR_INVALID; }
+    if (solver->bnd_S <= 0 || !solver->bnd_tallied) {
+        set_error("rt_solver_fetch_boundary: no sweep with a boundary yet (rt_solver_set_boundary, then a run or rt_solver_step_sweep)");
+        return RT_ERR_INVALID;
+    }
+    if (solver->open)
+        if (int rc = solver_check_epoch(solver, "rt_solver_fetch_boundary")) return rc;
+    try {
+        RT_HIP(hipSetDevice(solver->device));
+        hipStream_t s = solver->t->mesh->stream;
+        const size_t sg = (size_t)solver->bnd_S * solver->G;
+        if (j_out) RT_HIP(hipMemcpyAsync(j_out, solver->bnd_J.p, sg * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (j_in) RT_HIP(hipMemcpyAsync(j_in, solver->bnd_J.p + sg, sg * sizeof(double), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));
+    } catch (const std::exception &e) {
+        set_error("rt_solver_fetch_boundary: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_boundary_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
+    if (!solver) { set_error("rt_solver_boundary_pointers: null solver"); return RT_ERR_INVALID; }
+    // (no wait here: addresses and counts only)
+    const bool on = solver->bnd_S > 0;
+    const int64_t sg = (int64_t)solver->bnd_S * solver->G;
+    for (int i = 0; i < 2; ++i) {
+        if (ptrs_dev) ptrs_dev[i] = on ? solver->bnd_J.p + i * sg : nullptr;
+        if (lens) lens[i] = on ? sg : 0;
+    }
+    return RT_SUCCESS;
 }
 
 int32_t rt_solver_fetch_current(rt_solver *solver, double *J) {

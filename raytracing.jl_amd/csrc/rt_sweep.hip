@@ -514,21 +514,25 @@ static int32_t sweep_set_links_impl(rt_tracks *t, const int64_t *next_fwd, const
     // gather map: entry slot (direction d', track v) <- source (track u, direction d), written in the order a sequential
     // sweep hands fluxes on (uid ascending, forward before backward): the last writer wins where links are not one-to-one
     std::vector<int32_t> src((size_t)std::max<int64_t>(1, 2 * n), -1);
+    std::vector<int32_t> entry((size_t)(2 * n), -1);  // (the same links by source, whatever their bc: rt_tracks::sw_h_entry)
+    bool shard = false;
     for (int64_t u = 0; u < n; ++u)
         for (int d = 0; d < 2; ++d) {
             const int64_t v = (d == 0 ? next_fwd[u] : next_bwd[u]) - 1;  // 1-based uids, as trace! links them
             const int dn = d == 0 ? dir_fwd[u] : dir_bwd[u];             // 0 Forward, 1 Backward (src/track.jl:11-14)
             const int bc = d == 0 ? bc_fwd[u] : bc_bwd[u];               // 0 Vacuum (src/boundary.jl:12-16)
-            if (v == -1) continue;  // uid 0: the linked track is not in this track set (a shard: its owner receives the flux)
+            if (v == -1) { shard = true; continue; }  // uid 0: the linked track is not in this track set (a shard: its owner receives the flux)
             if (v < 0 || v >= n || (dn != 0 && dn != 1) || bc < 0 || bc > 2) {
                 set_error("rt_sweep_set_links: track %lld has a bad link (next uid %lld, dir %d, bc %d)", (long long)(u + 1), (long long)(v + 1), dn, bc);
                 return RT_ERR_INVALID;
             }
             src[(size_t)dn * n + v] = bc == 0 ? -1 : (int32_t)(u * 2 + d);
+            entry[(size_t)d * n + u] = (int32_t)(dn * n + v);
         }
     RT_HIP(hipSetDevice(t->mesh->device));
     if (int rc = upload(t->sw_src, src.data(), src.size(), t->mesh->stream)) return rc;
     RT_HIP(hipStreamSynchronize(t->mesh->stream));
+    t->sw_h_entry.swap(entry); t->sw_shard = shard; ++t->sw_links_epoch;
     t->sw_links = true;
     return RT_SUCCESS;
 }

@@ -13,6 +13,9 @@ gradient); ``SolverResult.flux_moments``, ``flux_gradient`` and ``centroids`` de
 With ``adjoint=True`` the same iteration runs on the transposed problem (``rt_solver_set_adjoint``) and returns the adjoint flux φ†;
 ``perturbation_reactivity`` and ``kinetics_parameters`` weigh cross-section changes and kinetics data with it
 (``rt_solver_bilinear``).
+With ``boundary=SolverBoundary(...)`` the four sides of the domain carry albedos β (ψ_in = β ψ_out + ψ_inc behind every track end
+on that side, whatever ``trace`` linked there) and, in fixed-source runs, an isotropic incoming flux ψ_inc; the result then
+carries the partial currents per side and group and the neutron balance (``rt_solver_set_boundary``).
 """
 from __future__ import annotations
 
@@ -23,10 +26,10 @@ from typing import Optional
 import numpy as np
 
 from . import _capi
-from .trackgenerator import TrackGenerator
+from .trackgenerator import SIDE_NAMES, TrackGenerator, track_end_sides
 
-__all__ = ["CrossSections", "PolarQuadrature", "SolverResult", "exact_azimuthal_weights", "azimuthal_weights",
-           "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters"]
+__all__ = ["CrossSections", "PolarQuadrature", "SolverBoundary", "SolverResult", "exact_azimuthal_weights", "azimuthal_weights",
+           "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "neutron_balance"]
 
 
 class CrossSections:
@@ -151,6 +154,67 @@ def azimuthal_weights(tg: TrackGenerator, spec="exact") -> np.ndarray:
     return a
 
 
+class SolverBoundary:
+    """Albedos and an incoming flux on the four sides of the domain (ids and names as ``track_end_sides``: 0 left, 1 right,
+    2 bottom, 3 top).  ``albedo``: a scalar (all sides, all groups), a dict side name -> scalar or [G] (sides not named: 1,
+    reflective), or an array [4, G]; every β in [0, 1].  ``incoming``: the isotropic angular flux ψ_inc that enters through a side,
+    given the same ways (sides not named: 0), None: none; fixed-source runs only."""
+
+    def __init__(self, albedo=1.0, incoming=None):
+        self.albedo, self.incoming = albedo, incoming
+
+    @staticmethod
+    def _expand(v, G, default, what):
+        if isinstance(v, dict):
+            unknown = sorted(set(v) - set(SIDE_NAMES))
+            if unknown:
+                raise ValueError(f"unknown sides {unknown} in {what} (left, right, bottom, top)")
+            a = np.full((4, G), float(default))
+            for i, name in enumerate(SIDE_NAMES):
+                if name in v:
+                    a[i] = np.broadcast_to(np.asarray(v[name], np.float64), (G,))
+            return a
+        a = np.asarray(v, np.float64)
+        if a.ndim == 0:
+            return np.full((4, G), float(a))
+        if a.shape != (4, G):
+            raise ValueError(f"{what} must be a scalar, a dict by side name or an array [4, G] = {(4, G)}, got {a.shape}")
+        return np.ascontiguousarray(a)
+
+    def arrays(self, G: int):
+        """``(albedo, incoming)`` as [4, G] arrays (``incoming`` None when none was given)."""
+        be = self._expand(self.albedo, G, 1.0, "albedo")
+        if not np.all(np.isfinite(be)) or np.any(be < 0) or np.any(be > 1):
+            raise ValueError("every albedo must be finite and in [0, 1]")
+        inc = None if self.incoming is None else self._expand(self.incoming, G, 0.0, "incoming")
+        if inc is not None and (not np.all(np.isfinite(inc)) or np.any(inc < 0)):
+            raise ValueError("every incoming flux must be finite and >= 0")
+        return be, inc
+
+
+def neutron_balance(xs, cell_material, phi, volumes, k_eff, source, current_out, current_in, adjoint=False) -> dict:
+    """The balance of ``include/rt_segmentize.h`` per group, from a run's last φ and last sweep's currents: ``gain`` [G] =
+    Σ_e V_e (χ_g F_e / k + Σ_g'≠g Σs[g'→g] φ_g' + S_g) (production / k, in-scatter, external source), ``removal`` [G] =
+    Σ_e V_e (Σt_g − Σs[g→g]) φ_g, ``leakage`` [G] = Σ_s (J⁺ − J⁻) and ``defect`` = gain − removal − leakage, of the size of the
+    iteration error.  ``adjoint``: with the transposed data, as the run used them."""
+    mat = np.asarray(cell_material, np.int64)
+    V = np.asarray(volumes, np.float64)[:, None]
+    st, ss, nf, ch = xs.sigma_t[mat], xs.sigma_s[mat], xs.nu_sigma_f[mat], xs.chi[mat]
+    if adjoint:
+        fissile = nf.sum(1, keepdims=True) > 0
+        ss, nf, ch = ss.transpose(0, 2, 1), np.where(fissile, ch, 0.0), nf
+    G = st.shape[1]
+    diag = ss[:, np.arange(G), np.arange(G)]
+    k = 1.0 if k_eff is None else float(k_eff)
+    prod = (nf * phi).sum(1, keepdims=True)
+    gain = ch * prod / k + np.einsum("eh,ehg->eg", phi, ss) - diag * phi
+    if source is not None:
+        gain = gain + np.asarray(source, np.float64)
+    gain, removal = (V * gain).sum(0), (V * (st - diag) * phi).sum(0)
+    leakage = (np.asarray(current_out) - np.asarray(current_in)).sum(0)
+    return dict(gain=gain, removal=removal, leakage=leakage, defect=gain - removal - leakage)
+
+
 @dataclass
 class SolverResult:
     k_eff: Optional[float]        # None in fixed-source mode
@@ -167,6 +231,10 @@ class SolverResult:
     flux_gradient: Optional[np.ndarray] = None  # ... C⁻¹ φ⃗ [n_cells, G, 2]: φ(r) ≈ phi + flux_gradient·(r − centroid)
     centroids: Optional[np.ndarray] = None      # ... track-based cell centroids [n_cells, 2]; all three None when flat
     adjoint: bool = False         # True: phi (current, flux_moments, ...) are the adjoint quantities of include/rt_segmentize.h
+    current_out: Optional[np.ndarray] = None    # boundary=...: the last sweep's partial currents J⁺ [4, G] out through every side
+    current_in: Optional[np.ndarray] = None     # ... J⁻ [4, G], in through every side (left, right, bottom, top)
+    leakage: Optional[np.ndarray] = None        # ... J⁺ − J⁻ [4, G]
+    balance: Optional[dict] = None              # ... neutron_balance: gain, removal, leakage, defect [G]; all four None without
 
 
 def _cell_material(tg, cell_material):
@@ -196,7 +264,8 @@ def _device_tracks(tg, device):
     return dt
 
 
-def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat", adjoint=False):
+def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat", adjoint=False,
+           boundary=None):
     if not isinstance(xs, CrossSections):
         raise TypeError("xs must be a CrossSections")
     if scheme not in ("flat", "linear"):
@@ -204,10 +273,15 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
     linear = scheme == "linear"
     if linear and xs.sigma_s1 is not None:
         raise ValueError('scheme="linear" together with sigma_s1 (P1 scattering) is not supported')
+    if boundary is not None and not isinstance(boundary, SolverBoundary):
+        raise TypeError("boundary must be a SolverBoundary")
+    if boundary is not None:
+        boundary.arrays(xs.n_groups)  # (raises on a bad albedo or incoming flux before anything is built)
     pq = PolarQuadrature(polar)
     alpha = azimuthal_weights(tg, azim_weights)
     dt = _device_tracks(tg, device)
-    sv = _capi.DeviceSolver(dt, _cell_material(tg, cell_material), xs.sigma_t, xs.sigma_s, xs.nu_sigma_f, xs.chi,
+    cm = _cell_material(tg, cell_material)
+    sv = _capi.DeviceSolver(dt, cm, xs.sigma_t, xs.sigma_s, xs.nu_sigma_f, xs.chi,
                             pq.sin_theta, pq.weights, alpha)
     if source is not None:
         sv.set_source(source)
@@ -217,42 +291,57 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         sv.set_linear_source(True)
     if adjoint:
         sv.set_adjoint(True)
+    if boundary is not None:
+        sv.set_boundary(boundary, track_end_sides(tg))
     r = sv.run(mode, int(max_iter), float(tol_k), float(tol_flux))
     f = sv.fetch(r["iterations"])
     mom = sv.fetch_moments() if linear else dict(flux_moments=None, flux_gradient=None)
     centroids = sv.fetch_geometry()["centroids"] if linear else None
     current = sv.fetch_current() if xs.sigma_s1 is not None else None
     it = r["iterations"]
+    bnd = dict(current_out=None, current_in=None, leakage=None, balance=None)
+    if boundary is not None:
+        bnd.update(sv.fetch_boundary())
+        bnd["leakage"] = bnd["current_out"] - bnd["current_in"]
+        eigen = mode == _capi.DeviceSolver.EIGENVALUE
+        bnd["balance"] = neutron_balance(xs, cm, f["phi"], f["volumes"], r["k_eff"] if eigen else None, None if eigen else source,
+                                         bnd["current_out"], bnd["current_in"], adjoint=adjoint)
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
-                        flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids, adjoint=bool(adjoint))
+                        flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids, adjoint=bool(adjoint), **bnd)
 
 
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
-                     tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False) -> SolverResult:
+                     tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
+                     boundary: Optional["SolverBoundary"] = None) -> SolverResult:
     """Power iteration for k_eff on the device.  ``cell_material``: material index per cell [n_cells] (or one index for all,
     or a dict region name -> index over ``tg.mesh.model.cell_region``).  ``polar``: a ``PolarQuadrature`` spec;
     ``azim_weights``: "exact", "equal" or an array.  Uses ``tg.device_tracks`` when ``segmentize(tg, fetch=False)`` has run,
     else segmentizes first; the boundary conditions are the ones ``trace`` linked.  ``scheme``: "flat" (a constant source per cell)
     or "linear" (a source linear in space per cell; not together with ``sigma_s1``).  ``adjoint=True``: the adjoint problem — the
     same k_eff, ``phi`` the adjoint flux φ† scaled to Σ_e V_e Σ_g χ_g φ† = 1 over the fissile cells (``current``: that of the
-    transposed problem, J† = −J*; ``flux_moments``: those of φ†)."""
+    transposed problem, J† = −J*; ``flux_moments``: those of φ†).  ``boundary``: a ``SolverBoundary`` (albedos per side and group;
+    the result then carries ``current_out``, ``current_in``, ``leakage`` and ``balance``); None: what ``trace`` linked, nothing
+    tallied."""
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint)
+                  adjoint, boundary)
 
 
 def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
-                       tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False) -> SolverResult:
+                       tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
+                       boundary: Optional["SolverBoundary"] = None) -> SolverResult:
     """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
     the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``; with ``adjoint=True`` ``source`` is the
-    adjoint source S† (for instance a detector cross section) and ``phi`` the importance φ†: Σ V S† φ = Σ V S φ†."""
+    adjoint source S† (for instance a detector cross section) and ``phi`` the importance φ†: Σ V S† φ = Σ V S φ†.  ``boundary``: a
+    ``SolverBoundary``, here also with an incoming flux per side and group (``source`` may then be zero: a run driven from the
+    boundary)."""
     q = np.asarray(source, np.float64)
     G = xs.n_groups
     if q.ndim == 0 or q.shape == (G,):
         q = np.broadcast_to(q, (tg.mesh.num_cells, G))
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint)
+                  adjoint, boundary)
 
 
 # ---- adjoint-weighted integrals ------------------------------------------------------------------------------------------------

@@ -21,7 +21,7 @@ from .mesh import DiscreteModel, Mesh
 from .quadrature import AzimuthalQuadrature
 
 __all__ = ["TrackGenerator", "trace", "Track", "Segment", "Forward", "Backward",
-           "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd"]
+           "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd", "track_end_sides", "SIDE_NAMES"]
 
 # DirectionType (src/track.jl:11-14)
 Forward = 0
@@ -115,6 +115,29 @@ def _boundary_condition(x, sides, bcs):
     for name in ("left", "right", "bottom", "top"):  # reversed: earlier names in the reference win
         hit = _point_in_segment(sides[name][0], sides[name][1], x)
         out[hit] = int(getattr(bcs, name))
+    return out
+
+
+SIDE_NAMES = ("left", "right", "bottom", "top")  # side ids 0 .. 3 of track_end_sides and solver.SolverBoundary
+
+
+def track_end_sides(t: TrackGenerator) -> np.ndarray:
+    """int32 [2, n_tracks]: the side of the mesh's bounding box (0 left, 1 right, 2 bottom, 3 top) on which every track's forward
+    traversal ends (row 0: its exit point q) and its backward traversal ends (row 1: its origin p); -1 where the point lies on no
+    side.  The point-in-segment rule and the precedence of ``_boundary_condition``: in a corner top wins over bottom over right
+    over left, so that the side named here is the one whose boundary condition ``trace`` gave that end."""
+    if not t.traced:
+        raise ValueError("the tracks are not traced: call trace first")
+    mesh = t.mesh
+    p1 = (mesh.bb_min[0], mesh.bb_min[1])
+    p2 = (mesh.bb_min[0], mesh.bb_max[1])
+    p3 = (mesh.bb_max[0], mesh.bb_max[1])
+    p4 = (mesh.bb_max[0], mesh.bb_min[1])
+    sides = dict(top=(p2, p3), bottom=(p4, p1), right=(p3, p4), left=(p1, p2))
+    out = np.full((2, t.n_total_tracks), -1, np.int32)
+    for row, x in ((0, (t.qx, t.qy)), (1, (t.px, t.py))):
+        for sid, name in enumerate(SIDE_NAMES):  # (later names overwrite earlier ones: the order of _boundary_condition)
+            out[row, _point_in_segment(sides[name][0], sides[name][1], x)] = sid
     return out
 
 

@@ -1,6 +1,8 @@
 """Timing of the device MOC solver (rt_solver) at the headline configuration: pincell, nφ = 128, δ = 1e-3, 7 groups, TY3
 (`--p1`: with linearly anisotropic scattering, Σs1 = 0.3 Σs0; `--linear`: with the linear source; `--adjoint`: the forward
-figures first, then the same runs in adjoint mode (rt_solver_set_adjoint) on the same solver, under "adjoint_*").
+figures first, then the same runs in adjoint mode (rt_solver_set_adjoint) on the same solver, under "adjoint_*"; `--albedo B`: the
+forward figures first, then the same runs with the albedo B on all four sides (rt_solver_set_boundary: the hand-over and the two
+current tallies per iteration) under "albedo_*", with the leakage and the balance defect of the last run).
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
@@ -55,6 +57,8 @@ def main():
     ap.add_argument("--p1", action="store_true", help="linearly anisotropic scattering: a synthetic Σs1 = 0.3 Σs0 (rt_solver_set_scatter_p1)")
     ap.add_argument("--linear", action="store_true", help="the linear source (rt_solver_set_linear_source); not together with --p1")
     ap.add_argument("--adjoint", action="store_true", help="after the forward runs, the same runs in adjoint mode (rt_solver_set_adjoint)")
+    ap.add_argument("--albedo", type=float, default=None, metavar="B",
+                    help="after the forward runs, the same runs with the albedo B in [0, 1] on every side (rt_solver_set_boundary)")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -104,6 +108,23 @@ def main():
         out["adjoint_ms_per_iter_host"] = float(np.median(host_ms))
         out["adjoint_k_eff"] = r["k_eff"]
         sv.set_adjoint(False)
+    if a.albedo is not None:  # (what the boundary's three kernel kinds cost per iteration: compare with ms_per_iter_events above)
+        sv.set_boundary(rt.SolverBoundary(albedo=a.albedo), rt.track_end_sides(tg))
+        sv.run(0, 3, 0.0, 0.0)
+        ev_ms, host_ms = [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            r = sv.run(0, a.iters, 0.0, 0.0)
+            host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+            ev_ms.append(r["device_ms"] / r["iterations"])
+        J = sv.fetch_boundary()
+        out["albedo"] = a.albedo
+        out["albedo_ms_per_iter_events"] = float(np.median(ev_ms))
+        out["albedo_ms_per_iter_host"] = float(np.median(host_ms))
+        out["albedo_over_plain_events"] = out["albedo_ms_per_iter_events"] / out["ms_per_iter_events"]
+        out["albedo_k_eff"] = r["k_eff"]
+        out["albedo_leakage"] = float((J["current_out"] - J["current_in"]).sum())
+        sv.set_boundary()
     if a.steps:
         ev_ms, host_ms = [], []
         for _ in range(a.repeats):
