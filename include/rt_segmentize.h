@@ -564,6 +564,40 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              source, adjoint mode (β is diagonal in the groups and the same for a traversal and its reverse: k† = k) and the
  *              stepwise calls work unchanged.  A solver without a boundary launches exactly what it always did
  *
+ * Reproducible tallies, rt_solver_set_reproducible.  The sweep's tallies T (and Tx, Ty) are the one sum of an iteration whose order
+ * depends on timing: FP64 atomics into an LDS copy and from there into T.  With the option on, a run is bitwise reproducible:
+ * Sweep        a lane neither folds with its neighbours nor adds anywhere: it stores the values w Δψ (w ξ Δψ − ..., as above) of its
+ *              segment to a delta buffer, at the row slot of its record and its direction.  ψ, the exponential forms, the choice
+ *              between the thin series and the general form per wave-row and ψ_out are those of the atomic path.  No LDS copy, so
+ *              the width of a pass is not bound by the mesh: 4 components, 2 with first-moment scattering or the linear source
+ * Order        behind every pass k_sweep_reduce WRITES T of the pass's components: for every cell, the entries of the records that
+ *              lie in it in ascending (track uid, record index), forward before backward; lane l of the cell's wave adds the
+ *              entries l, l + 64, ... in that order to a partial sum that starts at 0, and the 64 partial sums are added in a
+ *              butterfly (distances 32, 16, ..., 1).  A cell no record visits gets 0
+ * Index        the cells' lists (CSR by cell) are built once per segmentation, on first use, by a stable sort of the records by
+ *              cell: their order is a function of the records alone, and rt_segmentize voids them.  Every row variant the sweep
+ *              can read is served: the staging rows, (ℓ, cell) rows, rows made from the compact records, and the compact records
+ *              where they lie ("sweep_rows" 0).  Fewer than 2^31 records and row slots (RT_ERR_INVALID beyond)
+ * Other sums   V_e (rt_solver_create sums it with FP64 atomics) and the linear source's geometry (centroids, C) are sums over the
+ *              tracks as well: the switch-on computes them again through the same index, in the same order — V_e = Σ 2αδ ℓ over the
+ *              cell's records, the geometry's two accumulators likewise (rt_solver_ls_geometry's stages too, while the option
+ *              is on) — and the switch-off restores the V_e it found and recomputes the geometry with the atomic kernels.  A
+ *              caller that OVERWRITES volumes (see "Pointers", "Sharded") does so after the switch-on, and again after a
+ *              switch-off: that puts back the V_e the switch-on found, and what was written in between is lost
+ * Guarantee    two runs with the same input arrays, options and calls return the same bits in k_history, φ, J, φ⃗ and J⁺ / J⁻ — on one
+ *              solver, on a new one, after another rt_segmentize of the same tracks (same options), in every mode (first-moment
+ *              scattering, linear source, adjoint, boundary, fixed source) and through rt_solver_run or the stepwise calls alike
+ * Stepwise     the reductions are queued inside rt_solver_step_sweep, behind their passes: T is complete when that call's queued
+ *              work is done, rt_solver_step_fold does not touch it again, and what "Pointers" below allows — adding to T between
+ *              step_sweep and step_fold — holds unchanged
+ * Not promised the bits of the atomic path (another order of the same sum); equal bits across "sort_mode", shardings or any other
+ *              march order: the thin/general choice is taken per wave-row, so ψ itself differs there in its last bits ("sweep_debug"
+ *              4, the general form everywhere, remains the knob for that); equal bits across the sum over shards of a sharded run
+ * Memory       the delta buffer, 2 · row slots · NT · width · 8 bytes (NT = 3 tallies per component with first-moment scattering or
+ *              the linear source, else 1; row slots: those of the rows read — the staging pool's, the row table's, or the records),
+ *              allocated by the switch-on (rt_solver_begin enlarges it when the mode set since needs more) and freed by the
+ *              switch-off or rt_solver_destroy; the index, 4 bytes per record and per cell, stays with the tracks
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -650,6 +684,14 @@ int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1);
  * launches exactly what it always did.  RT_ERR_INVALID with a run open (rt_solver_begin without rt_solver_end) or after the
  * tracks were segmentized again; the solver then keeps the tables it had. */
 int32_t rt_solver_set_adjoint(rt_solver *solver, int32_t on);
+/* Reproducible tallies (see above) on (non-zero) or off for the following runs.  On: makes the rows the sweep will read and their
+ * cell index if this segmentation has none yet, and allocates the delta buffer; RT_ERR_HIP with a message that names its size when
+ * that fails; V_e and the geometry of a linear source that is on are summed again in the index's order.  Off frees the buffer and
+ * restores both: the solver then launches exactly what it always did.  RT_ERR_INVALID with a run open
+ * (rt_solver_begin without rt_solver_end), between two stages of rt_solver_ls_geometry or after the tracks were segmentized
+ * again.  On any failure the solver keeps what it had (the atomic path, if the option was off: V_e is put back, the buffers are
+ * freed, and the geometry of a linear source that is on is computed by the atomic kernels again). */
+int32_t rt_solver_set_reproducible(rt_solver *solver, int32_t on);
 /* Bilinear forms B_f (see above) of n_forms (1 .. 8) matrix sets A [n_forms][M][G][G] (host memory, A[f][m][g'][g]) into
  * out [n_forms]; out_cell [n_forms][n_cells] (may be NULL) receives each cell's V_e-weighted contribution.  Both solvers must have
  * completed a run and have none open, be bound to the same tracks at the same segmentation and agree in G, M and the number of

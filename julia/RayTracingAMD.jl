@@ -309,6 +309,14 @@ function solver_ls_geometry!(hs::Ptr{Cvoid}, stage::Integer)
     return nothing
 end
 
+# Reproducible sweep tallies for the following runs of an `rt_solver` handle `hs` (include/rt_segmentize.h, "Reproducible tallies"):
+# fixed-order sums in place of FP64 atomics, so that a repeated run returns the same bits; `false` frees the delta buffer again.
+function solver_set_reproducible!(hs::Ptr{Cvoid}, on::Bool=true)
+    rc = ccall((:rt_solver_set_reproducible, LIB), Int32, (Ptr{Cvoid}, Int32), hs, on ? 1 : 0)
+    rc == 0 || error("rt_solver_set_reproducible failed: " * lasterror())
+    return nothing
+end
+
 # (device address, length in doubles) of that accumulator between stage 0 and stage 2; (C_NULL, 0) outside
 function solver_ls_geometry_pointer(hs::Ptr{Cvoid})
     p = Ref{Ptr{Cvoid}}(C_NULL); n = Ref{Int64}(0)

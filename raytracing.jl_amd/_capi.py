@@ -32,7 +32,7 @@ SYMBOLS = (
     "rt_solver_ls_geometry", "rt_solver_ls_geometry_pointer",
     "rt_solver_fetch_current",
     "rt_solver_begin", "rt_solver_step_sweep", "rt_solver_step_fold", "rt_solver_end", "rt_solver_pointers",
-    "rt_solver_set_adjoint", "rt_solver_bilinear",
+    "rt_solver_set_adjoint", "rt_solver_bilinear", "rt_solver_set_reproducible",
     "rt_solver_set_boundary", "rt_solver_fetch_boundary", "rt_solver_boundary_pointers",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
@@ -235,6 +235,12 @@ def lib():
     L.rt_solver_set_scatter_p1.argtypes = [_vp, _dp]
     L.rt_solver_set_adjoint.restype = C.c_int32
     L.rt_solver_set_adjoint.argtypes = [_vp, C.c_int32]
+    try:
+        L.rt_solver_set_reproducible.restype = C.c_int32
+        L.rt_solver_set_reproducible.argtypes = [_vp, C.c_int32]
+    except AttributeError:
+        if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
+            raise
     L.rt_solver_bilinear.restype = C.c_int32
     L.rt_solver_bilinear.argtypes = [_vp, _vp, C.c_int32, _dp, _dp, _dp]
     L.rt_solver_fetch_current.restype = C.c_int32
@@ -673,11 +679,13 @@ class DeviceSolver:
     """``rt_solver`` handle: MOC source iteration on the device over the records of a ``DeviceTracks`` handle on which
     ``segmentize`` and ``sweep_set_links`` have run (``include/rt_segmentize.h`` states the definitions).  Arrays:
     ``cell_material`` [n_cells] (0-based), ``sigma_t`` / ``nu_sigma_f`` / ``chi`` [M, G], ``sigma_s`` [M, G, G] (from g' to g),
-    ``sin_polar`` / ``polar_weight`` [P], ``azim_weight`` [n_azim / 2] (None: the equal set)."""
+    ``sin_polar`` / ``polar_weight`` [P], ``azim_weight`` [n_azim / 2] (None: the equal set).  ``reproducible=True``: the
+    reproducible tallies from the first run on (``set_reproducible``)."""
 
     EIGENVALUE, FIXED_SOURCE = 0, 1
 
-    def __init__(self, dtracks: DeviceTracks, cell_material, sigma_t, sigma_s, nu_sigma_f, chi, sin_polar, polar_weight, azim_weight=None):
+    def __init__(self, dtracks: DeviceTracks, cell_material, sigma_t, sigma_s, nu_sigma_f, chi, sin_polar, polar_weight, azim_weight=None,
+                 reproducible=False):
         L = lib()
         self.dtracks = dtracks  # keeps the tracks alive
         st = np.ascontiguousarray(sigma_t, np.float64)
@@ -706,6 +714,18 @@ class DeviceSolver:
         if getattr(dtracks, "_solvers", None) is None:
             dtracks._solvers = weakref.WeakSet()
         dtracks._solvers.add(self)
+        self.reproducible = False
+        if reproducible:
+            self.set_reproducible(True)
+
+    def set_reproducible(self, on=True):
+        """``rt_solver_set_reproducible``: fixed-order sweep tallies for the following runs — two runs of the same problem return
+        the same bits (False: the FP64 atomics again).  Holds a delta buffer on the device while it is on."""
+        L = lib()
+        if not hasattr(L, "rt_solver_set_reproducible"):
+            raise RtError(f"{LIB_PATH} has no rt_solver_set_reproducible: the library is older than this binding")
+        _check(L.rt_solver_set_reproducible(self._open(), 1 if on else 0))
+        self.reproducible = bool(on)
 
     def set_source(self, source):
         """``rt_solver_set_source``: external volumetric source [n_cells, G] (None: none)."""

@@ -308,6 +308,10 @@ struct DSweep {
     // every component, `cur` receives Σ_c times the moment tallies (Tx, Ty)
     const RT_G double *cen;           // [n_cells][2] track-based centroids
     const RT_G double *ends;          // [n][4] by uid: the first record's entry point, the last record's exit point
+    // reproducible tallies (k_sweep_repro; rt_solver with rt_solver_set_reproducible): no lane fold, no atomics — every active
+    // lane stores the NT·GP values of its segment at delta[(dir · dslots + row slot) · NT·GP], and k_sweep_reduce sums them per cell
+    RT_G double *delta;
+    int64_t dslots;                   // row slots of the variant being swept (staging pool, rows from the compact records, or records)
 };
 
 }  // namespace rt
@@ -505,6 +509,16 @@ struct rt_tracks {
     DevBuf<int32_t> sw_cell;    // codes: cell + 1 of every staged row, beside sw_ell (k_materialise<.., ROWS>)
     DevBuf<int32_t> sw_ctab, sw_plan;  // rows made from the COMPACT records (rt_sweep.hip ensure_rows_from_compact): their own chunk table
     bool sw_rowsc_valid = false;       // ... sw_ell / sw_cell hold those rows for the last rt_segmentize
+    int64_t sw_rowsc_slots = 0;        // ... and their chunk table spans this many row slots
+    // reproducible tallies (rt_solver_set_reproducible; rt_sweep.hip sweep_repro_prepare): the cell index of the last rt_segmentize
+    // — CSR by cell, every cell's row slots in ascending (track uid, record index) — for the row variant `sw_ridx_kind` (0: none
+    // built; 1 the staging pool's slots, 2 the rows made from the compact records, 3 the compact records where they lie)
+    DevBuf<int32_t> sw_ridx_start, sw_ridx_list;  // [n_cells + 1], [total]
+    int sw_ridx_kind = 0;
+    int64_t sw_ridx_slots = 0;         // row slots of that variant: the delta buffer holds 2 · slots · NT · width doubles
+    bool sw_repro = false;             // switched on by an rt_solver for the sweeps of its run, with its delta buffer
+    double *sw_repro_delta = nullptr;
+    size_t sw_repro_cap = 0;           // doubles
     bool sw_links = false, sw_has_w = false, sw_has_xs = false, sw_done = false;
     rt_solver *sw_borrower = nullptr;  // the rt_solver between rt_solver_begin and rt_solver_end that holds this sweep state
     // host copy of the links as rt_sweep_set_links got them, whatever their bc (rt_solver_set_boundary builds its own gather map
@@ -546,6 +560,12 @@ void launch_compaction(rt_tracks *t, const rt::DOut &out, hipStream_t s);
 int ensure_compacted(rt_tracks *t);
 int ensure_rows(rt_tracks *t);
 int ensure_rows_from_compact(rt_tracks *t);  // rt_sweep.hip
+// rt_sweep.hip: the row variant a solver's sweep (input 0) reads now, its rows made and the cell index built for it (once per
+// segmentation and variant); *slots: row slots of the variant.  RT_ERR_INVALID where the reproducible tallies cannot be served
+int sweep_repro_prepare(rt_tracks *t, int64_t *slots);
+// ... and per-cell sums over the records in that index's order: kind 0 volumes (out [n_cells]), 1 / 2 the linear source's first /
+// second moments (out [n_cells][3]), weights w_azim[azim − 1]; `delta`: scratch of `cap` doubles (2 · slots · 1 or 3 needed)
+int sweep_repro_cell_sums(rt_tracks *t, int kind, const double *w_azim, const double *cen, double *delta, size_t cap, double *out);
 void launch_prologue(hipStream_t s, unsigned long long *ctl, double *volumes, int32_t n_cells, int32_t first_chunk, int32_t side_first);
 // the exclusive scan of the counts (two kernels); see k_scan_tile_sums / k_scan_write for the optional pointers
 void launch_scan_fused(hipStream_t s, rt_tracks *t, int64_t n_tiles, unsigned long long *d_ctl, const int32_t *tile_acc, int32_t *tile_acc_next,

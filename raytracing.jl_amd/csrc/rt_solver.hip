@@ -13,6 +13,9 @@
 // k_solver_fold_ls (φ⃗ from the moment tallies).  The cells' geometry (centroids, C, C⁻¹, the tracks' end points) is computed once,
 // when the option is first switched on: k_solver_ls_moments over the compact records, twice (first moments, then second moments
 // about the centroid), and k_solver_ls_centroid / k_solver_ls_cmat per cell.
+// With the reproducible tallies (rt_solver_set_reproducible) the solver launches the same kernels; the sweep it queues runs
+// k_sweep_repro and k_sweep_reduce behind every pass (rt_sweep.hip), into the delta buffer this solver owns, and V_e and the linear
+// source's geometry are summed through the same cell index.  Without the option the solver launches what it always did.
 #include "rt_internal.hpp"
 
 namespace rt {
@@ -546,6 +549,12 @@ struct rt_solver {
     DevBuf<int32_t> bnd_src;
     DevBuf<int8_t> bnd_side_entry, bnd_side_end, bnd_side_start;
     DevBuf<double> bnd_beta, bnd_incv, bnd_part, bnd_J;
+    // reproducible tallies (rt_solver_set_reproducible): the sweep's per-pass delta buffer, 2 · row slots · NT · width doubles, held
+    // from the switch-on to the switch-off (or rt_solver_destroy)
+    bool repro = false;
+    DevBuf<double> delta;
+    // ... and V_e as rt_solver_create summed it (FP64 atomics), kept while `vol` holds the sums in the index's order instead
+    DevBuf<double> vol_atomic;
     std::vector<double> k_hist;
     // the run in progress (rt_solver_begin ... rt_solver_end): `open` while this solver holds the handle's sweep state
     // (rt_tracks::sw_borrower points back here), `swept` between rt_solver_step_sweep and rt_solver_step_fold
@@ -564,6 +573,7 @@ void solver_release(rt_solver *S) {
     if (!S || !S->open) return;
     rt_tracks *t = S->t;
     t->sw_has_w = false; t->sw_p1 = false; t->sw_ls = false; t->sw_ls_cen = t->sw_ls_ends = nullptr;
+    t->sw_repro = false; t->sw_repro_delta = nullptr; t->sw_repro_cap = 0;
     if (t->sw_borrower == S) t->sw_borrower = nullptr;
     S->open = false; S->swept = false;
 }
@@ -761,6 +771,31 @@ int solver_step_enter(const rt_solver *S, bool want_swept, const char *who) {
     return RT_SUCCESS;
 }
 
+// The delta buffer of the reproducible tallies for the row variant the sweep reads now (its rows made and its cell index built on
+// first use) and the tallies per pass of the mode that is set: exactly 2 · slots · NT · width doubles, allocated only when the one
+// held is smaller.  A failed allocation leaves the solver what it had and names the size.
+int solver_repro_reserve(rt_solver *S, const char *who, int min_nv = 1) {
+    rt_tracks *t = S->t;
+    int64_t slots = 0;
+    if (int rc = sweep_repro_prepare(t, &slots)) return rc;
+    const int C = S->G * S->P;
+    // NT · width (rt_sweep.hip: 2 components with three tallies, else 4); min_nv: the geometry's sums take three values per record
+    const int nv = std::max(min_nv, (S->p1 || S->ls) ? 3 * std::min(C, 2) : std::min(C, 4));
+    const size_t need = (size_t)2 * (size_t)slots * (size_t)nv;
+    if (need <= S->delta.cap) return RT_SUCCESS;
+    DevBuf<double> d;
+    if (hipMalloc((void **)&d.p, need * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        d.p = nullptr;
+        set_error("%s: no device memory for the delta buffer of the reproducible tallies: %zu bytes (2 x %lld row slots x %d values x 8)", who,
+                  need * sizeof(double), (long long)slots, nv);
+        return RT_ERR_HIP;
+    }
+    d.cap = need;
+    S->delta = std::move(d);
+    return RT_SUCCESS;
+}
+
 int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
     if (S->open) solver_release(S);  // (a second begin starts afresh)
     rt_tracks *t = S->t;
@@ -810,6 +845,10 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
         RT_HIP(t->sw_xs1.reserve(2 * nxs)); RT_HIP(t->sw_cur.reserve(2 * nxs));
         RT_HIP(hipMemsetAsync(S->mom.p, 0, nj * sizeof(double), s));
         t->sw_ls = true; t->sw_ls_cen = S->cen.p; t->sw_ls_ends = S->ends.p;
+    }
+    if (S->repro) {  // (the mode or the rows may have changed since the switch-on: the buffer grows here if it has to)
+        if (int rc = solver_repro_reserve(S, who)) return rc;
+        t->sw_repro = true; t->sw_repro_delta = S->delta.p; t->sw_repro_cap = S->delta.cap;
     }
     S->bnd_tallied = false;
     if (bnd) RT_HIP(hipMemsetAsync(S->bnd_J.p, 0, (size_t)2 * S->bnd_S * G * sizeof(double), s));
@@ -1305,9 +1344,16 @@ static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged
                            (const double *)t->spx.p, (const double *)t->spy.p, (const double *)t->sqx.p, (const double *)t->sqy.p,
                            (const double *)t->sell.p, (const double *)S->cen.p, nc, S->ls_acc.p, S->ends.p);
     };
+    // reproducible tallies on: the accumulator in the cell index's order instead (the atomic kernel still runs in stage 0: it writes
+    // the tracks' end points, and its sums are overwritten)
+    auto moments_fixed = [&](int kind) -> int {
+        return sweep_repro_cell_sums(t, kind, (const double *)S->ls_wvol.p, (const double *)S->cen.p, S->delta.p, S->delta.cap, S->ls_acc.p);
+    };
     if (stage == 0) {
         S->ls = false; S->has_geom = false; S->ran_ls = false; S->ls_stage = 0;  // (afresh, whatever there was)
         if (int rc = ensure_compacted(t)) return rc;
+        if (S->repro)
+            if (int rc = solver_repro_reserve(S, who, 3)) return rc;
         if (int rc = upload(S->ls_wvol, S->h_wvol.data(), S->h_wvol.size(), s)) return rc;
         RT_HIP(S->ls_acc.reserve(3 * ncs)); RT_HIP(S->ls_ndeg.reserve(1));
         RT_HIP(S->cen.reserve(2 * ncs)); RT_HIP(S->cmat.reserve(3 * ncs)); RT_HIP(S->cinv.reserve(4 * ncs));
@@ -1315,10 +1361,14 @@ static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged
         RT_HIP(hipMemsetAsync(S->ls_ndeg.p, 0, sizeof(int32_t), s));
         RT_HIP(hipMemsetAsync(S->ls_acc.p, 0, 3 * ncs * sizeof(double), s));
         if (n > 0) moments.template operator()<false>();
+        if (S->repro)
+            if (int rc = moments_fixed(1)) return rc;
     } else if (stage == 1) {
         hipLaunchKernelGGL(rt::k_solver_ls_centroid, dim3(cb), dim3(256), 0, s, (const double *)S->ls_acc.p, (const double *)S->vol.p, nc, S->cen.p);
         RT_HIP(hipMemsetAsync(S->ls_acc.p, 0, 3 * ncs * sizeof(double), s));
-        if (n > 0) moments.template operator()<true>();
+        if (S->repro) {
+            if (int rc = moments_fixed(2)) return rc;
+        } else if (n > 0) moments.template operator()<true>();
     } else {
         hipLaunchKernelGGL(rt::k_solver_ls_cmat, dim3(cb), dim3(256), 0, s, (const double *)S->ls_acc.p, (const double *)S->vol.p, nc, S->cmat.p, S->cinv.p,
                            S->ls_ndeg.p);
@@ -1366,6 +1416,89 @@ int32_t rt_solver_ls_geometry(rt_solver *solver, int32_t stage) {
     } catch (const std::exception &e) {
         solver_ls_geometry_drop(solver);
         set_error("rt_solver_ls_geometry: %s", e.what());
+        return RT_ERR_INVALID;
+    }
+}
+
+// Reproducible tallies on or off.  On: the rows' cell index and the delta buffer (solver_repro_reserve), then the solver's own sums
+// over tracks in the index's order too — V_e (what rt_solver_create summed with FP64 atomics is kept aside) and, where the linear
+// source is on, its geometry.  Off: V_e as it was, the geometry by the atomic kernels again, the buffer freed.
+static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
+    const char *who = "rt_solver_set_reproducible";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the tallies cannot change under it", who); return RT_ERR_INVALID; }
+    if (S->ls_stage != 0) { set_error("%s: the linear source's geometry is between two stages (rt_solver_ls_geometry)", who); return RT_ERR_INVALID; }
+    const bool want = on != 0;
+    if (want == S->repro) return RT_SUCCESS;
+    rt_tracks *t = S->t;
+    if (int rc = finish_call(t)) return rc;
+    RT_HIP(hipSetDevice(t->mesh->device));
+    hipStream_t s = t->mesh->stream;
+    const size_t ncs = (size_t)std::max<int32_t>(1, S->n_cells);
+    const bool was_ls = S->ls;
+    auto geometry = [&]() -> int32_t {  // (anew, in the order the option now asks for; a geometry of a linear source that is off is dropped)
+        if (!S->has_geom) return RT_SUCCESS;
+        if (!was_ls) { S->has_geom = false; return RT_SUCCESS; }
+        for (int32_t stage = 0; stage < 3; ++stage)
+            if (int32_t rc = solver_ls_geometry_stage(S, stage, false, who)) return rc;
+        return RT_SUCCESS;
+    };
+    if (want) {
+        bool vol_kept = false;
+        auto switch_on = [&]() -> int32_t {
+            if (int rc = solver_repro_reserve(S, who, was_ls ? 3 : 1)) return rc;
+            if (int rc = upload(S->ls_wvol, S->h_wvol.data(), S->h_wvol.size(), s)) return rc;
+            RT_HIP(S->vol_atomic.reserve(ncs));
+            RT_HIP(hipMemcpyAsync(S->vol_atomic.p, S->vol.p, (size_t)S->n_cells * sizeof(double), hipMemcpyDeviceToDevice, s));
+            RT_HIP(hipStreamSynchronize(s));
+            vol_kept = true;
+            if (int rc = sweep_repro_cell_sums(t, 0, (const double *)S->ls_wvol.p, nullptr, S->delta.p, S->delta.cap, S->vol.p)) return rc;
+            S->repro = true;
+            return geometry();
+        };
+        int32_t rc = RT_ERR_INVALID;
+        try {
+            rc = switch_on();
+        } catch (const std::exception &e) {
+            solver_ls_geometry_drop(S);
+            set_error("%s: %s", who, e.what());
+        }
+        if (rc) {
+            // back to what the solver had: V_e as found, the geometry of a linear source that was on by the atomic kernels again
+            // (the stages had dropped it), no buffers — and the message of the failure, not of the way back
+            const std::string why = g_last_error;
+            S->repro = false;
+            if (vol_kept) (void)hipMemcpyAsync(S->vol.p, S->vol_atomic.p, (size_t)S->n_cells * sizeof(double), hipMemcpyDeviceToDevice, s);
+            if (was_ls && !S->has_geom) {
+                try {
+                    for (int32_t stage = 0; stage < 3; ++stage)
+                        if (solver_ls_geometry_stage(S, stage, false, who)) break;
+                } catch (const std::exception &) { solver_ls_geometry_drop(S); }
+            }
+            (void)hipStreamSynchronize(s);
+            (void)hipGetLastError();
+            S->delta.release(); S->vol_atomic.release();
+            g_last_error = why;
+            return rc;
+        }
+    } else {
+        RT_HIP(hipMemcpyAsync(S->vol.p, S->vol_atomic.p, (size_t)S->n_cells * sizeof(double), hipMemcpyDeviceToDevice, s));
+        S->repro = false;
+        if (int32_t rc = geometry()) return rc;
+        RT_HIP(hipStreamSynchronize(s));
+        S->delta.release(); S->vol_atomic.release();
+    }
+    RT_HIP(hipStreamSynchronize(s));
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_reproducible(rt_solver *solver, int32_t on) {
+    try {
+        return solver_set_reproducible_impl(solver, on);
+    } catch (const std::exception &e) {
+        if (solver) solver_ls_geometry_drop(solver);
+        set_error("rt_solver_set_reproducible: %s", e.what());
         return RT_ERR_INVALID;
     }
 }

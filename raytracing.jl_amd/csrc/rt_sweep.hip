@@ -1,6 +1,8 @@
 // rt_sweep.hip — rt_sweep: the transport sweep over the cyclic tracks, kernels, host code and entry points.
 #include "rt_internal.hpp"
 
+#include <rocprim/device/device_radix_sort.hpp>  // the cell index of the reproducible tallies: one stable sort per segmentation
+
 namespace rt {
 
 // ---- transport sweep over the cyclic tracks ------------------------------------------------------
@@ -41,348 +43,22 @@ namespace rt {
 // (one_minus_exp_neg_both), F2 from ls_f2 / ls_f2_thin (rt_device.hpp).
 // LS instantiations are bounded to eight waves per workgroup: with the series' coefficients and the lane's geometry they need up to
 // ~190 VGPRs, and under the sixteen-wave bound (128 VGPRs) they spilled to scratch.
+// REPRO (reproducible tallies, rt_solver_set_reproducible): a constant of the kernels' shared body, rt_sweep_body.hpp — false in
+// k_sweep, which keeps its six flags, its names in the code object and its instructions, true in the sibling k_sweep_repro.  ψ, the exponential forms, the per-wave-row
+// thin/general choice and psi_out are those of the atomic path; only the tail of `segment` differs: no lane fold, no add to `hist` or
+// `phi` — every active lane stores its NT·GP values w·Δψ at its (row slot, direction) of DSweep::delta (the 16 lanes of a quarter-wave
+// write NT·GP full 128-B lines), and k_sweep_reduce sums every cell's entries in a fixed order after the pass.  No LDS copy (LDS = false),
+// so the pass width is not bound by the mesh: the widths the atomic instantiations' registers were tuned for, 4 components
+// (kSweepGpP1 = 2 with three tallies per component).  The instantiations without the flag compile to what they were.
 template <bool STAGED, int GP, bool LDS, bool ELLROWS, bool P1 = false, bool LS = false>
 __global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep(DSweep a) {
-    static_assert(STAGED || !ELLROWS, "ℓ rows belong to the staging rows");
-    static_assert(!(P1 && LS), "linear source with first-moment scattering is not built");
-    constexpr bool AN = P1 || LS;        // three tallies and two ratios per component
-    constexpr int NT = AN ? 3 : 1;       // tallies per component
-    constexpr int NH = LS ? 2 * GP + 2 : (P1 ? 2 * GP : 1);  // ratios of a pass (one unused slot when isotropic); LS: + the cell's centroid
-    extern __shared__ __attribute__((aligned(16))) unsigned char sweep_smem[];
-    double *hist = reinterpret_cast<double *>(sweep_smem);  // [n_cells * NT * GP] when LDS
-    const int lane = threadIdx.x & 63;
-    const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, and known to be
-    if (LDS) {
-        for (int c = threadIdx.x; c < a.n_cells * (NT * GP); c += blockDim.x) hist[c] = 0.0;
-        __syncthreads();
-    }
-    // a sweep wave = (march wave, direction).  The march waves are ordered longest first and the sweep is bound by
-    // instruction issue, so the waves are dealt to the workgroups round-robin: wave k of workgroup b takes sweep wave
-    // k * gridDim + b — every workgroup gets the same mix of long and short tracks and all finish together (contiguous
-    // blocks of 16 sweep waves left the CU with the longest tracks working 1.6x longer than the average one).
-    const int64_t sw = (int64_t)wib * gridDim.x + blockIdx.x;
-    const int64_t mw = sw >> 1;
-    const int dir = (int)(sw & 1);
-    if (mw < a.n_waves) {
-        const int64_t slot = mw * 64 + lane;
-        const bool have = slot < a.n;
-        const int32_t u = have ? a.perm[slot] : 0;
-        const int32_t cnt = have ? a.counts[u] : 0;
-        int32_t mc = cnt;
-        for (int o = 32; o > 0; o >>= 1) {
-            const int32_t v = __shfl_xor(mc, o, 64);
-            mc = v > mc ? v : mc;
-        }
-        const int maxcnt = __builtin_amdgcn_readfirstlane(mc);
-        const double w = !have ? 0.0 : (a.w ? a.w[u] : a.delta_s[a.azim[u] - 1]);
-        // P1: the traversal's direction cosines d (cos ϕ, sin ϕ) and the weight times them (0 for a lane without a track)
-        double dcs = 0.0, dsn = 0.0, wcs = 0.0, wsn = 0.0;
-        if constexpr (AN) {
-            const double c0 = have ? a.cs[u] : 0.0, s0 = have ? a.sn[u] : 0.0;
-            dcs = dir ? -c0 : c0; dsn = dir ? -s0 : s0;
-            wcs = w * dcs; wsn = w * dsn;
-        }
-        // LS: the traversal's entry point (first record's p forward, last record's q backward) and the path length behind the lane
-        double ex = 0.0, ey = 0.0, srun = 0.0;
-        if constexpr (LS) {
-            if (have) { ex = a.ends[(int64_t)u * 4 + 2 * dir]; ey = a.ends[(int64_t)u * 4 + 2 * dir + 1]; }
-        }
-        const int64_t off = (!STAGED && have) ? a.offsets[u] : 0;
-        const int64_t pbase = ((int64_t)dir * a.n + u) * a.G + a.g0;
-        const int ng = a.ng;
-        double psi[GP];
-#pragma unroll
-        for (int g = 0; g < GP; ++g) psi[g] = (have && g < ng) ? a.psi_in[pbase + g] : 0.0;
-        // step t visits row r(t): 0, 1, ... forward; maxcnt-1, ..., 0 backward (demo/makie.jl:103: "the segments are stored in
-        // reverse order for backward tracks"), all lanes in lockstep — a lane is active while r(t) < its count.  Steps beyond
-        // the end are clamped to the last one (prefetches only).
-        auto row_of = [&](const int t) -> int {
-            const int tc = t < maxcnt ? t : maxcnt - 1;
-            return dir ? maxcnt - 1 - tc : tc;
-        };
-        // cross sections of GP groups of cell `e` (a padded group repeats the last real one; its result is never used)
-        auto load_xs = [&](const int32_t e, double (&st)[GP], double (&qs)[GP], double (&h)[NH]) {
-            const RT_G double *x = a.xs + ((int64_t)e * a.G + a.g0) * 2;
-#pragma unroll
-            for (int g = 0; g < GP; ++g) {
-                const int gi = g < ng ? g : ng - 1;
-                st[g] = x[2 * gi]; qs[g] = x[2 * gi + 1];
-            }
-            if constexpr (AN) {
-                const RT_G double *x1 = a.xs1 + ((int64_t)e * a.G + a.g0) * 2;
-#pragma unroll
-                for (int g = 0; g < GP; ++g) {
-                    const int gi = g < ng ? g : ng - 1;
-                    h[2 * g] = x1[2 * gi]; h[2 * g + 1] = x1[2 * gi + 1];
-                }
-            }
-            if constexpr (LS) { h[2 * GP] = a.cen[(int64_t)e * 2]; h[2 * GP + 1] = a.cen[(int64_t)e * 2 + 1]; }
-        };
-        ExpPoly poly = exp_poly();  // (in vector registers: see one_minus_exp_neg)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) asm volatile("" : "+v"(poly.c[i]));
-        // one segment: attenuation and tally for the GP groups of this pass.  A lane beyond its track's end evaluates a segment
-        // of length 0: τ = 0, 1 − e^{−0} = 0 exactly, Δ = ±0 — its ψ keeps its bits, and one select does for all groups.
-        auto segment = [&](const int32_t e, const double ell_row, const bool act, const double (&st)[GP], const double (&qs0)[GP],
-                           const double (&h)[NH]) {
-            const double ell = act ? ell_row : 0.0;
-            double wd[NT * GP], tau[GP], qs[GP];
-            bool thin = true;
-            // LS: the midpoint relative to the cell's centroid; s moves on by ℓ (0 for a lane beyond its track's end)
-            double xi = 0.0, eta = 0.0;
-            if constexpr (LS) {
-                const double sm = __builtin_fma(0.5, ell, srun);
-                xi = __builtin_fma(dcs, sm, ex - h[2 * GP]);
-                eta = __builtin_fma(dsn, sm, ey - h[2 * GP + 1]);
-                srun += ell;
-            }
-#pragma unroll
-            for (int g = 0; g < GP; ++g) {
-                tau[g] = st[g] * ell;
-                thin = thin && tau[g] < kThinTau;
-                if constexpr (P1) qs[g] = __builtin_fma(dsn, h[2 * g + 1], __builtin_fma(dcs, h[2 * g], qs0[g]));
-                else if constexpr (LS) qs[g] = __builtin_fma(st[g], __builtin_fma(eta, h[2 * g + 1], xi * h[2 * g]), qs0[g]);  // r_m
-                else qs[g] = qs0[g];
-            }
-            // LS: one component from F1 = 1 − e^{−τ} and hF2 = F2/2 (see the head of the kernel)
-            [[maybe_unused]] auto ls_component = [&](const int g, const double F1, const double hF2) {
-                const double rho = __builtin_fma(dsn, h[2 * g + 1], dcs * h[2 * g]);  // ρ / Σ_c
-                const double am = psi[g] - qs[g];
-                const double d = __builtin_fma(am, F1, -(rho * hF2));
-                const double Hs = __builtin_fma(rho, __builtin_fma(0.5, tau[g], 1.0), am) * hF2;  // Σ_c H
-                psi[g] = psi[g] - d;
-                wd[g] = w * d;
-                const double ws = wd[g] * st[g];
-                wd[GP + 2 * g] = __builtin_fma(xi, ws, -(wcs * Hs));
-                wd[GP + 2 * g + 1] = __builtin_fma(eta, ws, -(wsn * Hs));
-            };
-            // −expm1(−τ) to within an ulp (rt_device.hpp): where every lane's segment is optically thin in every group of the pass —
-            // a wave-uniform branch — by the series alone (10 instructions per group instead of 24)
-            // (The choice is per WAVE-row: a segment takes the series when the other 63 lanes' segments are thin too, else the general
-            //  form — the two agree to 2 ulp, so ψ_out is NOT bitwise invariant across march orders, sort modes or shardings of the
-            //  same problem; the tests compare at 1e-12.  "sweep_debug" 4 = the general form everywhere: the reproducible mode.)
-            if constexpr (LS) {
-                if (__ballot(!thin) == 0 && !(a.debug & 4)) {
-#pragma unroll
-                    for (int g = 0; g < GP; ++g) ls_component(g, one_minus_exp_neg_thin(tau[g], poly), 0.5 * ls_f2_thin(tau[g]));
-                } else {
-#pragma unroll
-                    for (int g = 0; g < GP; ++g) {
-                        double E;
-                        const double F1 = one_minus_exp_neg_both(tau[g], E, poly);
-                        ls_component(g, F1, 0.5 * ls_f2(tau[g], E));
-                    }
-                }
-            } else if (__ballot(!thin) == 0 && !(a.debug & 4)) {
-#pragma unroll
-                for (int g = 0; g < GP; ++g) {
-                    const double d = (psi[g] - qs[g]) * one_minus_exp_neg_thin(tau[g], poly);
-                    psi[g] = psi[g] - d;
-                    wd[g] = w * d;
-                    if constexpr (P1) { wd[GP + 2 * g] = wcs * d; wd[GP + 2 * g + 1] = wsn * d; }
-                }
-            } else {
-#pragma unroll
-                for (int g = 0; g < GP; ++g) {
-                    const double d = (psi[g] - qs[g]) * one_minus_exp_neg(tau[g], poly);
-                    psi[g] = psi[g] - d;
-                    wd[g] = w * d;
-                    if constexpr (P1) { wd[GP + 2 * g] = wcs * d; wd[GP + 2 * g + 1] = wsn * d; }
-                }
-            }
-            // Neighbouring lanes are neighbouring parallel tracks: at the same row most of them are in the same cell, and
-            // atomics of one wave instruction to one address are served one lane at a time (measured at C3: the tallies were
-            // 0.21 of the sweep's 0.62 ms).  Lanes of an aligned pair, then quad, with equal cells are therefore summed first —
-            // two DPP row shifts, no LDS traffic — and only the lanes left over add to the tally.  The sweep is bound by
-            // instruction issue, so folding further costs more than the atomics it saves: over 2 / 4 / 8 / 16 lanes the
-            // sweep took 0.440 / 0.438 / 0.466 / 0.494 ms (0.414 without any tally).
-            bool mine = act;
-            if (!(a.debug & 2)) {
-                const int32_t key = act ? e : -1 - lane;  // (an inactive lane matches nobody)
-                // lane l with (l mod 2n) == 0 takes over lane l + n (row_shl:n reads lane l + n of the 16-lane row)
-                auto fold = [&]<int NSH>() {
-                    // (bound_ctrl: a lane whose source lies outside its row reads 0 and no `old` value has to be moved in first;
-                    //  the lanes that use what they read — `take`, `given` — never read across a row's end)
-                    const int32_t key_up = __builtin_amdgcn_update_dpp(0, key, 0x100 + NSH, 0xf, 0xf, true);
-                    const int32_t key_dn = __builtin_amdgcn_update_dpp(0, key, 0x110 + NSH, 0xf, 0xf, true);
-                    const bool take = ((lane & (2 * NSH - 1)) == 0) && key_up == key;
-                    const bool given = ((lane & (2 * NSH - 1)) == NSH) && key_dn == key;
-#pragma unroll
-                    for (int g = 0; g < NT * GP; ++g) {
-                        const uint64_t bits = __builtin_bit_cast(uint64_t, wd[g]);
-                        const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)(uint32_t)bits, 0x100 + NSH, 0xf, 0xf, true);
-                        const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int32_t)(uint32_t)(bits >> 32), 0x100 + NSH, 0xf, 0xf, true);
-                        const double up = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-                        wd[g] = __builtin_fma(up, take ? 1.0 : 0.0, wd[g]);  // (one instruction; the values are finite)
-                    }
-                    mine = mine && !given;
-                };
-                fold.template operator()<1>(); fold.template operator()<2>();
-            }
-            if (mine && !(a.debug & 1)) {
-#pragma unroll
-                for (int g = 0; g < GP; ++g)
-                    if (g < ng) {  // (uniform)
-                        if (LDS) atomicAdd(&hist[e * (NT * GP) + g], wd[g]);
-                        else unsafeAtomicAdd((double *)&a.phi[(int64_t)e * a.G + a.g0 + g], wd[g]);
-                        if constexpr (AN) {
-                            if (LDS) {
-                                atomicAdd(&hist[e * (NT * GP) + GP + 2 * g], wd[GP + 2 * g]);
-                                atomicAdd(&hist[e * (NT * GP) + GP + 2 * g + 1], wd[GP + 2 * g + 1]);
-                            } else {
-                                RT_G double *cu = a.cur + ((int64_t)e * a.G + a.g0 + g) * 2;
-                                unsafeAtomicAdd((double *)cu, wd[GP + 2 * g]);
-                                unsafeAtomicAdd((double *)(cu + 1), wd[GP + 2 * g + 1]);
-                            }
-                        }
-                    }
-            }
-        };
-        if (maxcnt > 0) {
-            if (STAGED) {
-                // the wave's chunk ids: lane j holds chunks j, j + 64, ... (kMaxChunks = 313: five registers cover MAX_ITER rows)
-                const RT_G int32_t *ctab = a.stg.ctab + mw * kMaxChunks;
-                const int nchunks = (maxcnt + kChunkRows - 1) >> kChunkLog2;
-                int32_t cv[5];
-#pragma unroll
-                for (int k = 0; k < 5; ++k) cv[k] = (k * 64 + lane < nchunks) ? ctab[k * 64 + lane] : 0;
-                // (v_readlane reads a lane whether or not it is active: call this in wave-uniform control flow only — inside a
-                //  divergent branch the selected register of an inactive holder lane is stale)
-                auto chunk_of = [&](const int r) -> int32_t {
-                    const int j = r >> kChunkLog2;
-                    const int32_t v = j < 64 ? cv[0] : (j < 128 ? cv[1] : (j < 192 ? cv[2] : (j < 256 ? cv[3] : cv[4])));
-                    return __builtin_amdgcn_readlane(v, j & 63);
-                };
-                struct Row { double qx, qy; int32_t el; };
-                // the chunk id of a row is looked up only when the row stream enters another 32-row chunk (two streams: the row
-                // being evaluated and the one being prefetched); both lookups stay in scalar registers
-                int cj0 = -1, cj2 = -1;
-                int32_t cid0 = 0, cid2 = 0;
-                auto slot_cached = [&](const int r, int &cj, int32_t &cid) -> int64_t {
-                    const int j = r >> kChunkLog2;
-                    if (j != cj) { cj = j; cid = chunk_of(r); }  // (uniform)
-                    return stage_slot(cid, r & (kChunkRows - 1), lane);
-                };
-                auto slot_of = [&](const int r) -> int64_t { return stage_slot(chunk_of(r), r & (kChunkRows - 1), lane); };
-                auto load_row = [&](const int r) -> Row {
-                    const int64_t sl = slot_of(r);
-                    return Row{a.stg.qx[sl], a.stg.qy[sl], a.stg.element[sl]};
-                };
-                auto cell_of = [&](const Row &R, const int r) -> int32_t { return r < cnt ? (R.el < 0 ? -R.el : R.el) - 1 : 0; };
-                // One step: Ra holds row r(t), Rb row r(t + 1) and Rc — until this step's prefetch replaces it — row r(t − 1).  The
-                // loop is unrolled three times with the roles rotated, so that no row register is moved from one stage of the
-                // pipeline to the next; steps t >= maxcnt of the last round do nothing (act is false, their loads are clamped).
-                // Measured at C3, 7 groups, same box: rotating by moves 0.373 ms, three steps per round 0.358, six (the cross
-                // sections' two stages rotated as well; 32 scalar registers spilled) 0.366; one copy of the loop per direction
-                // (forward and backward waves of a CU then run different code) 0.396.
-                if constexpr (!ELLROWS) {
-                    const int DIR = dir;
-                    auto row_d = row_of;
-                    Row R0 = load_row(row_d(0)), R1 = load_row(row_d(1)), R2{0.0, 0.0, 0};
-                    double stA[GP], qsA[GP], stB[GP], qsB[GP], hA[NH], hB[NH];
-                    load_xs(cell_of(R0, row_d(0)), stA, qsA, hA);
-                    auto step = [&](const int t, const Row &Ra, const Row &Rb, Row &Rc, const double (&st0)[GP], const double (&qs0)[GP],
-                                    const double (&h0)[NH], double (&st1)[GP], double (&qs1)[GP], double (&h1)[NH]) {
-                        const int r = row_d(t);
-                        const bool act = r < cnt && t < maxcnt;
-                        // entry point: the previous record's exit point — forward the row before, backward the NEXT step's row — or,
-                        // for marked records (cell < 0: first record of a track, records of the generic step), the staged one
-                        double dx = (DIR ? Rb.qx : Rc.qx) - Ra.qx, dy = (DIR ? Rb.qy : Rc.qy) - Ra.qy;
-                        const int64_t sl0 = slot_cached(r, cj0, cid0);  // (outside the branch: see chunk_of)
-                        double px = 0.0, py = 0.0;
-                        const bool marked = act && Ra.el < 0;
-                        if (marked) { px = a.stg.px[sl0]; py = a.stg.py[sl0]; }
-                        const int64_t sl2 = slot_cached(row_d(t + 2), cj2, cid2);
-                        Rc = Row{a.stg.qx[sl2], a.stg.qy[sl2], a.stg.element[sl2]};
-                        load_xs(cell_of(Rb, row_d(t + 1)), st1, qs1, h1);
-                        if (marked) { dx = px - Ra.qx; dy = py - Ra.qy; }
-                        const double ell = norm2(dx, dy);  // Segment ctor, src/segment.jl:31-33 (as k_compact3)
-                        if (a.ell_rows != nullptr && !DIR && act) a.ell_rows[sl0] = ell;  // (uniform && uniform && lane: for the ELLROWS passes)
-                        segment(cell_of(Ra, r), ell, act, st0, qs0, h0);
-                    };
-                    for (int t = 0; t < maxcnt; t += 3) {
-                        step(t, R0, R1, R2, stA, qsA, hA, stB, qsB, hB);
-                        step(t + 1, R1, R2, R0, stB, qsB, hB, stA, qsA, hA);
-                        step(t + 2, R2, R0, R1, stA, qsA, hA, stB, qsB, hB);
-#pragma unroll
-                        for (int g = 0; g < GP; ++g) { stA[g] = stB[g]; qsA[g] = qsB[g]; }
-                        if constexpr (AN)
-#pragma unroll
-                            for (int g = 0; g < NH; ++g) hA[g] = hB[g];
-                    }
-                }
-                if constexpr (ELLROWS) {
-                    // the same pipeline over (ℓ, cell) rows — ℓ as an earlier pass over these staging rows left it: 12 B per row instead
-                    // of 20, no square root, no entry point to pick
-                    struct LRow { double ell; int32_t el; };
-                    auto load_lrow = [&](const int64_t sl) -> LRow { return LRow{a.ell_rows[sl], a.stg.element[sl]}; };
-                    auto lcell = [&](const LRow &R, const int r) -> int32_t { return r < cnt ? (R.el < 0 ? -R.el : R.el) - 1 : 0; };
-                    LRow L0 = load_lrow(slot_of(row_of(0))), L1 = load_lrow(slot_of(row_of(1))), L2{0.0, 0};
-                    double stA[GP], qsA[GP], stB[GP], qsB[GP], hA[NH], hB[NH];
-                    load_xs(lcell(L0, row_of(0)), stA, qsA, hA);
-                    auto lstep = [&](const int t, const LRow &Ra, const LRow &Rb, LRow &Rc, const double (&st0)[GP], const double (&qs0)[GP],
-                                     const double (&h0)[NH], double (&st1)[GP], double (&qs1)[GP], double (&h1)[NH]) {
-                        const int r = row_of(t);
-                        const bool act = r < cnt && t < maxcnt;
-                        Rc = load_lrow(slot_cached(row_of(t + 2), cj2, cid2));
-                        load_xs(lcell(Rb, row_of(t + 1)), st1, qs1, h1);
-                        segment(lcell(Ra, r), Ra.ell, act, st0, qs0, h0);
-                    };
-                    for (int t = 0; t < maxcnt; t += 3) {
-                        lstep(t, L0, L1, L2, stA, qsA, hA, stB, qsB, hB);
-                        lstep(t + 1, L1, L2, L0, stB, qsB, hB, stA, qsA, hA);
-                        lstep(t + 2, L2, L0, L1, stA, qsA, hA, stB, qsB, hB);
-#pragma unroll
-                        for (int g = 0; g < GP; ++g) { stA[g] = stB[g]; qsA[g] = qsB[g]; }
-                        if constexpr (AN)
-#pragma unroll
-                            for (int g = 0; g < NH; ++g) hA[g] = hB[g];
-                    }
-                }
-            } else {
-                struct Rec { double ell; int32_t el; };
-                auto load_rec = [&](const int r) -> Rec {
-                    const int rc = r < cnt ? r : (cnt > 0 ? cnt - 1 : 0);  // (a lane's own records only; masked where r >= cnt)
-                    if (cnt == 0) return Rec{0.0, 1};                      // (a track without records: offsets[u] may equal the total)
-                    return Rec{a.ell[off + rc], a.element[off + rc]};
-                };
-                auto cell_of = [&](const Rec &R, const int r) -> int32_t { return r < cnt ? R.el - 1 : 0; };
-                Rec R0 = load_rec(row_of(0)), R1 = load_rec(row_of(1));
-                double st0[GP], qs0[GP], h0[NH];
-                load_xs(cell_of(R0, row_of(0)), st0, qs0, h0);
-                for (int t = 0; t < maxcnt; ++t) {
-                    const int r = row_of(t);
-                    const Rec R2 = load_rec(row_of(t + 2));
-                    double st1[GP], qs1[GP], h1[NH];
-                    load_xs(cell_of(R1, row_of(t + 1)), st1, qs1, h1);
-                    segment(cell_of(R0, r), R0.ell, r < cnt, st0, qs0, h0);
-                    R0 = R1; R1 = R2;
-#pragma unroll
-                    for (int g = 0; g < GP; ++g) { st0[g] = st1[g]; qs0[g] = qs1[g]; }
-                    if constexpr (AN)
-#pragma unroll
-                        for (int g = 0; g < NH; ++g) h0[g] = h1[g];
-                }
-            }
-        }
-        if (have)
-#pragma unroll
-            for (int g = 0; g < GP; ++g)
-                if (g < ng) a.psi_out[pbase + g] = psi[g];
-    }
-    if (LDS) {
-        __syncthreads();
-        for (int c = threadIdx.x; c < a.n_cells * (NT * GP); c += blockDim.x) {
-            const double v = hist[c];
-            const int cell = c / (NT * GP), i = c - cell * (NT * GP);
-            if (!AN || i < GP) {
-                if (v != 0.0 && i < a.ng) unsafeAtomicAdd((double *)&a.phi[(int64_t)cell * a.G + a.g0 + i], v);
-            } else {
-                const int g = (i - GP) >> 1;
-                if (v != 0.0 && g < a.ng) unsafeAtomicAdd((double *)&a.cur[((int64_t)cell * a.G + a.g0 + g) * 2 + ((i - GP) & 1)], v);
-            }
-        }
-    }
+    constexpr bool REPRO = false;
+#include "rt_sweep_body.hpp"
+}
+template <bool STAGED, int GP, bool ELLROWS, bool P1 = false, bool LS = false>
+__global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep_repro(DSweep a) {
+    constexpr bool REPRO = true, LDS = false;
+#include "rt_sweep_body.hpp"
 }
 
 // The boundary flux of the next sweep: entry (direction d', track v) receives the outgoing flux of the (direction, track)
@@ -468,6 +144,145 @@ __global__ __launch_bounds__(256) void k_rows_fill(const int32_t *__restrict__ c
 
 constexpr int kSweepGpP1 = 2;  // components per pass of the anisotropic sweep, at most
 
+// ---- reproducible tallies (rt_solver_set_reproducible): the cell index and the reduction behind every pass ---------------------------
+// The index lists, CSR by cell, the row slots of the records that lie in the cell, in ascending (track uid, record index): the order
+// of the compact records, i = offsets[uid] + r.  k_ridx_records writes (cell, row slot) of record i at place i — one lane per track
+// in the march's lane mapping, because the row slot of (track, r) follows from the track's march slot and its wave's chunk table
+// (`ctab`; null: the compact records where they lie, slot = i) —, a STABLE radix sort by cell keeps that order inside every cell, and
+// k_ridx_starts finds the cells' first places.  Nothing here depends on the order in which an atomic handed out anything.  A record
+// whose cell id is out of range goes behind the last cell (key n_cells) and is never read.
+__global__ __launch_bounds__(256) void k_ridx_records(const int32_t *__restrict__ counts, const int64_t *__restrict__ offsets,
+                                                      const int32_t *__restrict__ perm, int64_t n, const int32_t *__restrict__ element,
+                                                      const int32_t *__restrict__ ctab, int32_t n_cells, int32_t *__restrict__ key,
+                                                      int32_t *__restrict__ val) {
+    const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    const int64_t w = slot >> 6;
+    const int lane = (int)(slot & 63);
+    const int32_t u = perm[slot];
+    const int32_t cnt = counts[u];
+    const int64_t off = offsets[u];
+    for (int32_t r = 0; r < cnt; ++r) {
+        const int32_t e = element[off + r] - 1;
+        key[off + r] = (e >= 0 && e < n_cells) ? e : n_cells;
+        val[off + r] = ctab ? (int32_t)stage_slot(ctab[w * kMaxChunks + (r >> kChunkLog2)], r & (kChunkRows - 1), lane) : (int32_t)(off + r);
+    }
+}
+// start[c] = first place of cell c in the sorted keys, c = 0 .. n_cells (start[n_cells]: the end of the last cell's list); thread i
+// looks at the step between places i − 1 and i and writes the cells that begin there (several where cells are empty)
+__global__ __launch_bounds__(256) void k_ridx_starts(const int32_t *__restrict__ key, int64_t total, int32_t n_cells, int32_t *__restrict__ start) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > total) return;
+    const int32_t hi = i < total ? key[i] : n_cells;
+    const int32_t lo = i > 0 ? key[i - 1] + 1 : 0;
+    for (int32_t c = lo; c <= hi && c <= n_cells; ++c) start[c] = (int32_t)i;
+}
+
+// After a pass of k_sweep_repro: T (and Tx, Ty: AN) of the pass's GP components, WRITTEN, not added, for every cell — one wave
+// per cell.  The cell's entries are (record j of its list, direction d), k = 2 j + d: forward before backward; lane l sums the entries
+// l, l + 64, ... in that order, then the 64 partial sums go through a fixed butterfly (both operands of every addition are the same
+// in the two lanes of a pair, so every lane ends with the same bits).  The order is a function of the list alone.  A cell no record
+// visits gets 0.
+template <int NV>
+__device__ __forceinline__ void cell_sum(const int32_t *__restrict__ start, const int32_t *__restrict__ list, const double *__restrict__ delta,
+                                         int64_t dslots, int64_t e, int lane, double (&acc)[NV]) {
+    const int32_t b = start[e];
+    const int64_t n2 = 2 * (int64_t)(start[e + 1] - b);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+#pragma unroll 4
+    for (int64_t k = lane; k < n2; k += 64) {
+        const double *src = delta + ((k & 1) * dslots + list[b + (k >> 1)]) * NV;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) acc[j] += src[j];
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j)
+        for (int o = 32; o > 0; o >>= 1) acc[j] += __shfl_xor(acc[j], o, 64);
+}
+template <int GP, bool AN>
+__global__ __launch_bounds__(256) void k_sweep_reduce(const int32_t *__restrict__ start, const int32_t *__restrict__ list,
+                                                      const double *__restrict__ delta, int64_t dslots, int32_t n_cells, int32_t G, int32_t g0,
+                                                      double *__restrict__ phi, double *__restrict__ cur) {
+    constexpr int NV = (AN ? 3 : 1) * GP;
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= n_cells) return;  // (wave-uniform)
+    double acc[NV];
+    cell_sum<NV>(start, list, delta, dslots, e, lane, acc);
+    if (lane == 0) {
+#pragma unroll
+        for (int g = 0; g < GP; ++g) {
+            phi[e * G + g0 + g] = acc[g];
+            if constexpr (AN) {
+                cur[(e * G + g0 + g) * 2] = acc[GP + 2 * g];
+                cur[(e * G + g0 + g) * 2 + 1] = acc[GP + 2 * g + 1];
+            }
+        }
+    }
+}
+
+
+// The solver's sums over tracks that are not tallies of a sweep, in the same fixed order (an rt_solver with the reproducible tallies
+// on: its volumes and the linear source's geometry were FP64 atomics too).  k_cell_values writes NV values of every record to the
+// forward half of the delta buffer, at the record's row slot, and zeros to the backward half (x + 0 = x: the order of the nonzero
+// terms is the index's); k_cell_reduce is k_sweep_reduce's sum into out[n_cells][NV].  KIND 0: w ℓ (volumes, NV = 1); 1: w ℓ (m_x,
+// m_y), 0; 2: the second moments about `cen` — the expressions of k_solver_ls_moments (rt_solver.hip), w = w_azim[azim − 1].
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cell_values(const int32_t *__restrict__ counts, const int64_t *__restrict__ offsets, const int32_t *__restrict__ perm,
+                                                     int64_t n, const int32_t *__restrict__ ctab, const int32_t *__restrict__ azim,
+                                                     const double *__restrict__ w_azim, const double *__restrict__ cs, const double *__restrict__ sn,
+                                                     const int32_t *__restrict__ element, const double *__restrict__ px, const double *__restrict__ py,
+                                                     const double *__restrict__ qx, const double *__restrict__ qy, const double *__restrict__ ell,
+                                                     const double *__restrict__ cen, int32_t n_cells, double *__restrict__ delta, int64_t dslots) {
+    constexpr int NV = KIND == 0 ? 1 : 3;
+    const int64_t slot = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot >= n) return;
+    const int64_t wv = slot >> 6;
+    const int lane = (int)(slot & 63);
+    const int32_t u = perm[slot];
+    const int32_t cnt = counts[u];
+    const int64_t off = offsets[u];
+    const double w = w_azim[azim[u] - 1];
+    double c = 0.0, sv = 0.0;
+    if (KIND == 2) { c = cs[u]; sv = sn[u]; }
+    for (int32_t r = 0; r < cnt; ++r) {
+        const int64_t i = off + r;
+        const int64_t sl = ctab ? stage_slot(ctab[wv * kMaxChunks + (r >> kChunkLog2)], r & (kChunkRows - 1), lane) : i;
+        double v[3] = {0.0, 0.0, 0.0};
+        const double l = ell[i];
+        if (KIND == 0) {
+            v[0] = w * l;
+        } else {
+            const int32_t e = element[i] - 1;
+            const double mx = 0.5 * (px[i] + qx[i]), my = 0.5 * (py[i] + qy[i]);
+            if (e < 0 || e >= n_cells) {
+            } else if (KIND == 1) {
+                v[0] = w * l * mx; v[1] = w * l * my;
+            } else {
+                const double xi = mx - cen[2 * (int64_t)e], eta = my - cen[2 * (int64_t)e + 1], l3 = l * l * l / 12.0;
+                v[0] = w * (l * xi * xi + c * c * l3);
+                v[1] = w * (l * xi * eta + c * sv * l3);
+                v[2] = w * (l * eta * eta + sv * sv * l3);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NV; ++j) { delta[sl * NV + j] = v[j]; delta[(dslots + sl) * NV + j] = 0.0; }
+    }
+}
+template <int NV>
+__global__ __launch_bounds__(256) void k_cell_reduce(const int32_t *__restrict__ start, const int32_t *__restrict__ list, const double *__restrict__ delta,
+                                                     int64_t dslots, int32_t n_cells, double *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t e = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (e >= n_cells) return;
+    double acc[NV];
+    cell_sum<NV>(start, list, delta, dslots, e, lane, acc);
+    if (lane == 0)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) out[e * NV + j] = acc[j];
+}
+
 }  // namespace rt
 
 namespace rtx {
@@ -478,7 +293,7 @@ int ensure_rows_from_compact(rt_tracks *t) {
     hipStream_t s = t->mesh->stream;
     const int64_t n = t->n;
     const int32_t n_waves = (int32_t)((n + 63) / 64);
-    if (n_waves == 0) { t->sw_rowsc_valid = true; return RT_SUCCESS; }
+    if (n_waves == 0) { t->sw_rowsc_valid = true; t->sw_rowsc_slots = 1; return RT_SUCCESS; }
     RT_HIP(t->sw_plan.reserve(2 * (size_t)n_waves + 8));
     RT_HIP(t->sw_ctab.reserve((size_t)n_waves * rt::kMaxChunks));
     int32_t *nch = t->sw_plan.p, *first = nch + n_waves, *total = first + n_waves;
@@ -489,12 +304,93 @@ int ensure_rows_from_compact(rt_tracks *t) {
     RT_HIP(hipStreamSynchronize(s));
     const size_t slots = (size_t)std::max(1, h_total) * rt::kChunkRows * 64;
     RT_HIP(t->sw_ell.reserve(slots)); RT_HIP(t->sw_cell.reserve(slots));
+    t->sw_rowsc_slots = (int64_t)slots;
     t->sw_ell_valid = false;  // (the buffers now hold rows in THIS chunk table's layout, not the staging pool's)
     hipLaunchKernelGGL(rt::k_rows_fill, dim3((unsigned)n_waves), dim3(256), 0, s, (const int32_t *)t->counts.p, (const int64_t *)t->offsets.p,
                        (const int32_t *)t->perm.p, n, (const double *)t->sell.p, (const int32_t *)t->element.p, (const int32_t *)first, (const int32_t *)nch,
                        t->sw_ctab.p, t->sw_ell.p, t->sw_cell.p);
     RT_HIP(hipGetLastError());
     t->sw_rowsc_valid = true;
+    return RT_SUCCESS;
+}
+
+// which rows a sweep with input 0 (an rt_solver's) reads: 1 the staging rows, 2 rows made from the compact records, 3 those records
+// where they lie ("sweep_rows" 0) — sweep_impl's own choice, restated for the reproducible tallies
+static int sweep_rows_variant(const rt_tracks *t) {
+    const bool staged_ok = t->cplan.staged && !t->cplan.split && t->cplan.n_whole_waves == (t->n + 63) / 64;
+    return staged_ok ? 1 : (t->mesh->sweep_rows ? 2 : 3);
+}
+
+int sweep_repro_prepare(rt_tracks *t, int64_t *slots_out) {
+    rt_mesh *m = t->mesh;
+    hipStream_t s = m->stream;
+    const int kind = sweep_rows_variant(t);
+    if (kind == 2)
+        if (int rc = ensure_rows_from_compact(t)) return rc;
+    if (int rc = ensure_compacted(t)) return rc;  // (the index is built in the order of the compact records)
+    const int64_t total = t->total, n = t->n;
+    const int64_t slots = kind == 1 ? std::max<int64_t>(1, t->pool_chunks) * rt::kChunkRows * 64 : (kind == 2 ? t->sw_rowsc_slots : std::max<int64_t>(1, total));
+    if (slots >= (1ll << 31) || total >= (1ll << 31)) {
+        set_error("reproducible tallies: %lld records in %lld row slots (the cell index holds 32-bit places: fewer than 2^31 of each)", (long long)total, (long long)slots);
+        return RT_ERR_INVALID;
+    }
+    *slots_out = slots;
+    if (t->sw_ridx_kind == kind && t->sw_ridx_slots == slots) return RT_SUCCESS;
+    t->sw_ridx_kind = 0;
+    const int32_t nc = m->n_cells;
+    RT_HIP(t->sw_ridx_start.reserve((size_t)nc + 1));
+    RT_HIP(t->sw_ridx_list.reserve((size_t)std::max<int64_t>(1, total)));
+    if (total == 0 || n == 0) {
+        RT_HIP(hipMemsetAsync(t->sw_ridx_start.p, 0, ((size_t)nc + 1) * sizeof(int32_t), s));
+    } else {
+        DevBuf<int32_t> key_in, key_out, val_in;
+        DevBuf<unsigned char> temp;
+        RT_HIP(key_in.reserve((size_t)total)); RT_HIP(key_out.reserve((size_t)total)); RT_HIP(val_in.reserve((size_t)total));
+        const int32_t *ctab = kind == 1 ? (const int32_t *)t->cplan.stg.ctab : (kind == 2 ? (const int32_t *)t->sw_ctab.p : nullptr);
+        hipLaunchKernelGGL(rt::k_ridx_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t *)t->counts.p, (const int64_t *)t->offsets.p,
+                           (const int32_t *)t->perm.p, n, (const int32_t *)t->element.p, ctab, nc, key_in.p, val_in.p);
+        unsigned bits = 1;
+        while (bits < 32 && (1ll << bits) <= (int64_t)nc) ++bits;  // keys 0 .. n_cells
+        size_t temp_bytes = 0;
+        RT_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, key_in.p, key_out.p, val_in.p, t->sw_ridx_list.p, (size_t)total, 0u, bits, s));
+        RT_HIP(temp.reserve(std::max<size_t>(1, temp_bytes)));
+        RT_HIP(rocprim::radix_sort_pairs((void *)temp.p, temp_bytes, key_in.p, key_out.p, val_in.p, t->sw_ridx_list.p, (size_t)total, 0u, bits, s));
+        hipLaunchKernelGGL(rt::k_ridx_starts, dim3((unsigned)((total + 1 + 255) / 256)), dim3(256), 0, s, (const int32_t *)key_out.p, total, nc, t->sw_ridx_start.p);
+        RT_HIP(hipGetLastError());
+        RT_HIP(hipStreamSynchronize(s));  // (the temporary buffers die here)
+    }
+    t->sw_ridx_kind = kind; t->sw_ridx_slots = slots;
+    return RT_SUCCESS;
+}
+
+// out[n_cells][NV] = the sums of k_cell_values<kind> over the records of every cell, in the index's order (queued on the mesh's
+// stream; `delta`: a buffer of at least 2 · slots · NV doubles, overwritten)
+int sweep_repro_cell_sums(rt_tracks *t, int kind, const double *w_azim, const double *cen, double *delta, size_t cap, double *out) {
+    int64_t slots = 0;
+    if (int rc = sweep_repro_prepare(t, &slots)) return rc;
+    const int nv = kind == 0 ? 1 : 3;
+    if (!delta || (size_t)(2 * slots) * (size_t)nv > cap) { set_error("reproducible tallies: the delta buffer is too small for the cells' sums"); return RT_ERR_INVALID; }
+    rt_mesh *m = t->mesh;
+    hipStream_t s = m->stream;
+    const int64_t n = t->n;
+    const int32_t nc = m->n_cells;
+    const int32_t *ctab = t->sw_ridx_kind == 1 ? (const int32_t *)t->cplan.stg.ctab : (t->sw_ridx_kind == 2 ? (const int32_t *)t->sw_ctab.p : nullptr);
+    auto values = [&]<int KIND>() {
+        if (n > 0)
+            hipLaunchKernelGGL(rt::k_cell_values<KIND>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t *)t->counts.p, (const int64_t *)t->offsets.p,
+                               (const int32_t *)t->perm.p, n, ctab, (const int32_t *)t->azim.p, w_azim, (const double *)t->cs.p, (const double *)t->sn.p,
+                               (const int32_t *)t->element.p, (const double *)t->spx.p, (const double *)t->spy.p, (const double *)t->sqx.p,
+                               (const double *)t->sqy.p, (const double *)t->sell.p, cen, nc, delta, slots);
+    };
+    const unsigned rb = (unsigned)((nc + 3) / 4);
+    if (kind == 0) {
+        values.template operator()<0>();
+        if (nc > 0) hipLaunchKernelGGL(rt::k_cell_reduce<1>, dim3(rb), dim3(256), 0, s, (const int32_t *)t->sw_ridx_start.p, (const int32_t *)t->sw_ridx_list.p, (const double *)delta, slots, nc, out);
+    } else {
+        if (kind == 1) values.template operator()<1>(); else values.template operator()<2>();
+        if (nc > 0) hipLaunchKernelGGL(rt::k_cell_reduce<3>, dim3(rb), dim3(256), 0, s, (const int32_t *)t->sw_ridx_start.p, (const int32_t *)t->sw_ridx_list.p, (const double *)delta, slots, nc, out);
+    }
+    RT_HIP(hipGetLastError());
     return RT_SUCCESS;
 }
 }  // namespace rtx
@@ -635,6 +531,22 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     a.use_lds = (size_t)m->n_cells * gp * nt * sizeof(double) <= lds_cap ? 1 : 0;
     if (!a.use_lds) gp = std::min(G, gp_max);
     if (m->sweep_gp >= 8) a.use_lds = 0;  // experiment: tallies straight to HBM (measured 4x slower at C3: 2.1 ms against 0.48)
+    // reproducible tallies (an rt_solver with rt_solver_set_reproducible has switched them on for its run): no LDS copy, so the pass
+    // width is the widest the kernel is compiled for; the cell index for the rows read below, and the solver's delta buffer
+    const bool repro = t->sw_repro;
+    if (repro) {
+        gp = std::min(G, gp_max);
+        if (m->sweep_gp >= 1 && m->sweep_gp <= 4) gp = std::min(gp, m->sweep_gp);
+        a.use_lds = 0;
+        int64_t rslots = 0;
+        if (int rc = sweep_repro_prepare(t, &rslots)) return rc;
+        if (t->sw_ridx_kind != (rows_compact ? 2 : (staged ? 1 : 3))) { set_error("rt_sweep: the reproducible tallies' cell index is not the one of the rows read"); return RT_ERR_INVALID; }
+        if (!t->sw_repro_delta || (size_t)(2 * rslots) * (size_t)(nt * gp) > t->sw_repro_cap) {
+            set_error("rt_sweep: the delta buffer of the reproducible tallies is too small for these rows (%lld row slots): switch the option on again", (long long)rslots);
+            return RT_ERR_INVALID;
+        }
+        a.delta = as_global(t->sw_repro_delta); a.dslots = rslots;
+    }
     if (!async_sweep) RT_HIP(hipEventRecord(t->ev[0], s));
     RT_HIP(hipMemsetAsync(t->sw_phi.p, 0, nphi * sizeof(double), s));
     if ((p1 || ls) && nphi) RT_HIP(hipMemsetAsync(t->sw_cur.p, 0, 2 * nphi * sizeof(double), s));
@@ -659,11 +571,11 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         else (void)hipGetLastError();  // (no memory for it: every pass derives ℓ itself)
     }
     a.ell_rows = ell_rows ? as_global(t->sw_ell.p) : nullptr;
-    auto launch = [&]<bool STAGED, int GP, bool LDS, bool P1, bool LS = false>(int g0) -> int {
+    auto launch = [&]<bool STAGED, int GP, bool LDS, bool P1, bool LS = false, bool REPRO = false>(int g0) -> int {
         size_t smem = a.use_lds ? (size_t)m->n_cells * GP * ((P1 || LS) ? 3 : 1) * sizeof(double) : 0;
         // (compact records: more than one eight-wave workgroup per CU thrashes its L1 — a pass of few groups asks for LDS it
         //  does not use, so that it still gets a CU to itself: 5 groups = 4 + 1 took 0.88 ms against 0.58 for 7 = 4 + 3)
-        if (!STAGED && a.use_lds) smem = std::max(smem, std::min(lds_cap, (size_t)81 * 1024));
+        if (!STAGED && (a.use_lds || REPRO)) smem = std::max(smem, std::min(lds_cap, (size_t)81 * 1024));
         // one workgroup per CU (its tallies fill the LDS): sixteen waves when the rows are the staging rows (every load
         // instruction reads four full lines), eight when they are the compact records (64 lanes, 64 lines: sixteen waves
         // thrash the CU's L1 — 1.04 against 0.62 ms at C3); two or more workgroups per CU: eight waves each
@@ -675,33 +587,43 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         if (STAGED && ell_rows && (t->sw_ell_valid || rows_compact)) {
             if constexpr (STAGED) {
                 if (smem > 48 * 1024)
-                    RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<true, GP, LDS, true, P1, LS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                hipLaunchKernelGGL((rt::k_sweep<true, GP, LDS, true, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
+                    RT_HIP(hipFuncSetAttribute(REPRO ? (const void *)rt::k_sweep_repro<true, GP, true, P1, LS> : (const void *)rt::k_sweep<true, GP, LDS, true, P1, LS>,
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+                if constexpr (REPRO) hipLaunchKernelGGL((rt::k_sweep_repro<true, GP, true, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
+                else hipLaunchKernelGGL((rt::k_sweep<true, GP, LDS, true, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
             }
         } else {
             if (smem > 48 * 1024)
-                RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep<STAGED, GP, LDS, false, P1, LS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            hipLaunchKernelGGL((rt::k_sweep<STAGED, GP, LDS, false, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
+                RT_HIP(hipFuncSetAttribute(REPRO ? (const void *)rt::k_sweep_repro<STAGED, GP, false, P1, LS> : (const void *)rt::k_sweep<STAGED, GP, LDS, false, P1, LS>,
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+            if constexpr (REPRO) hipLaunchKernelGGL((rt::k_sweep_repro<STAGED, GP, false, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
+            else hipLaunchKernelGGL((rt::k_sweep<STAGED, GP, LDS, false, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
             if (STAGED && ell_rows) { t->sw_ell_valid = true; t->sw_rowsc_valid = false; }  // (the forward waves of this pass have written every row's ℓ)
+        }
+        if constexpr (REPRO) {  // the pass's tallies, in the index's order (the next pass overwrites the delta buffer)
+            if (m->n_cells > 0)
+                hipLaunchKernelGGL((rt::k_sweep_reduce<GP, (P1 || LS)>), dim3((unsigned)((m->n_cells + 3) / 4)), dim3(256), 0, s, (const int32_t *)t->sw_ridx_start.p,
+                                   (const int32_t *)t->sw_ridx_list.p, (const double *)t->sw_repro_delta, a.dslots, m->n_cells, G, g0, t->sw_phi.p,
+                                   (P1 || LS) ? t->sw_cur.p : (double *)nullptr);
         }
         ++passes;
         return RT_SUCCESS;
     };
-    auto launch_all = [&]<bool STAGED, bool LDS>() -> int {
+    auto launch_all = [&]<bool STAGED, bool LDS, bool REPRO = false>() -> int {
         for (int g0 = 0; g0 < G;) {
             const int take = std::min(gp, G - g0);
             int rc;
             if (ls) {
-                if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, false, true>(g0);
-                else rc = launch.template operator()<STAGED, 1, LDS, false, true>(g0);
+                if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, false, true, REPRO>(g0);
+                else rc = launch.template operator()<STAGED, 1, LDS, false, true, REPRO>(g0);
             } else if (p1) {
                 static_assert(rt::kSweepGpP1 == 2, "the anisotropic passes below");
-                if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, true>(g0);
-                else rc = launch.template operator()<STAGED, 1, LDS, true>(g0);
-            } else if (take == 4) rc = launch.template operator()<STAGED, 4, LDS, false>(g0);
-            else if (take == 3) rc = launch.template operator()<STAGED, 3, LDS, false>(g0);
-            else if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, false>(g0);
-            else rc = launch.template operator()<STAGED, 1, LDS, false>(g0);
+                if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, true, false, REPRO>(g0);
+                else rc = launch.template operator()<STAGED, 1, LDS, true, false, REPRO>(g0);
+            } else if (take == 4) rc = launch.template operator()<STAGED, 4, LDS, false, false, REPRO>(g0);
+            else if (take == 3) rc = launch.template operator()<STAGED, 3, LDS, false, false, REPRO>(g0);
+            else if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, false, false, REPRO>(g0);
+            else rc = launch.template operator()<STAGED, 1, LDS, false, false, REPRO>(g0);
             if (rc) return rc;
             g0 += take;
         }
@@ -709,7 +631,8 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     };
     if (n > 0) {
         int rc;
-        if (staged || rows_compact) rc = a.use_lds ? launch_all.template operator()<true, true>() : launch_all.template operator()<true, false>();
+        if (repro) rc = (staged || rows_compact) ? launch_all.template operator()<true, false, true>() : launch_all.template operator()<false, false, true>();
+        else if (staged || rows_compact) rc = a.use_lds ? launch_all.template operator()<true, true>() : launch_all.template operator()<true, false>();
         else rc = a.use_lds ? launch_all.template operator()<false, true>() : launch_all.template operator()<false, false>();
         if (rc) return rc;
         const int64_t nl = 2 * n * G;

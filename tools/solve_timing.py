@@ -2,7 +2,9 @@
 (`--p1`: with linearly anisotropic scattering, Σs1 = 0.3 Σs0; `--linear`: with the linear source; `--adjoint`: the forward
 figures first, then the same runs in adjoint mode (rt_solver_set_adjoint) on the same solver, under "adjoint_*"; `--albedo B`: the
 forward figures first, then the same runs with the albedo B on all four sides (rt_solver_set_boundary: the hand-over and the two
-current tallies per iteration) under "albedo_*", with the leakage and the balance defect of the last run).
+current tallies per iteration) under "albedo_*", with the leakage and the balance defect of the last run; `--reproducible`: the
+forward figures first, then the same runs with the reproducible tallies (rt_solver_set_reproducible) under "reproducible_*", with the
+device memory the switch-on took — delta buffer and cell index — and whether the repeats returned the same bits).
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
@@ -59,6 +61,8 @@ def main():
     ap.add_argument("--adjoint", action="store_true", help="after the forward runs, the same runs in adjoint mode (rt_solver_set_adjoint)")
     ap.add_argument("--albedo", type=float, default=None, metavar="B",
                     help="after the forward runs, the same runs with the albedo B in [0, 1] on every side (rt_solver_set_boundary)")
+    ap.add_argument("--reproducible", action="store_true",
+                    help="after the forward runs, the same runs with the reproducible tallies (rt_solver_set_reproducible)")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -125,6 +129,28 @@ def main():
         out["albedo_k_eff"] = r["k_eff"]
         out["albedo_leakage"] = float((J["current_out"] - J["current_in"]).sum())
         sv.set_boundary()
+    if a.reproducible:  # (the delta buffer written and read once per pass, and k_sweep_reduce behind every pass)
+        import torch
+
+        free0 = torch.cuda.mem_get_info(0)[0]
+        sv.set_reproducible(True)
+        held = free0 - torch.cuda.mem_get_info(0)[0]
+        sv.run(0, 3, 0.0, 0.0)
+        ev_ms, host_ms, phis = [], [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            r = sv.run(0, a.iters, 0.0, 0.0)
+            host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+            ev_ms.append(r["device_ms"] / r["iterations"])
+            f = sv.fetch(r["iterations"])
+            phis.append(f["phi"].tobytes() + f["k_history"].tobytes())
+        out["reproducible_ms_per_iter_events"] = float(np.median(ev_ms))
+        out["reproducible_ms_per_iter_host"] = float(np.median(host_ms))
+        out["reproducible_over_plain_events"] = out["reproducible_ms_per_iter_events"] / out["ms_per_iter_events"]
+        out["reproducible_k_eff"] = r["k_eff"]
+        out["reproducible_bytes_held"] = int(held)
+        out["reproducible_bits_repeat"] = all(p == phis[0] for p in phis)
+        sv.set_reproducible(False)
     if a.steps:
         ev_ms, host_ms = [], []
         for _ in range(a.repeats):
