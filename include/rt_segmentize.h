@@ -616,6 +616,10 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              handed back.  rt_segmentize of the tracks ends the run too, at once (the handle's own sweeps weigh by δs again
  *              whether or not the solver is called once more), and every later call of the stale solver returns the
  *              "segmentized again" error.  A step that fails for another reason (a non-finite k) ends the run as well.
+ *              While a run is open every mode setter — rt_solver_set_source, rt_solver_set_scatter_p1, rt_solver_set_linear_source,
+ *              rt_solver_set_adjoint, rt_solver_set_boundary, rt_solver_set_reproducible (and rt_solver_ls_geometry) — returns
+ *              RT_ERR_INVALID with "<entry point>: a run is open" and changes nothing, whether it would switch something on, off or
+ *              to what it already is: a run iterates on the tables, the source and the buffers it began with.  rt_solver_end first.
  *              While a run is open, the handle's own rt_sweep with explicit cross sections, weights or another group count
  *              is the caller's error: it overwrites what the solver iterates on, and is not detected.
  * Pointers     rt_solver_pointers returns device addresses that the fold reads where they lie.  Between step_sweep and
@@ -668,7 +672,7 @@ typedef struct rt_solver_result {
 rt_solver *rt_solver_create(rt_tracks *tracks, int32_t n_groups, int32_t n_materials, const int32_t *cell_material,
                             const double *sigma_t, const double *sigma_s, const double *nu_sigma_f, const double *chi,
                             int32_t n_polar, const double *sin_polar, const double *polar_weight, const double *azim_weight);
-/* External volumetric source S [n_cells][G] for RT_SOLVE_FIXED_SOURCE (NULL: none). */
+/* External volumetric source S [n_cells][G] for RT_SOLVE_FIXED_SOURCE (NULL: none).  RT_ERR_INVALID with a run open. */
 int32_t rt_solver_set_source(rt_solver *solver, const double *source);
 /* Run from φ⁰ = 1 (every call starts afresh).  out may be NULL. */
 int32_t rt_solver_run(rt_solver *solver, int32_t mode, int32_t max_iter, double tol_k, double tol_flux, rt_solver_result *out);
@@ -677,7 +681,7 @@ int32_t rt_solver_run(rt_solver *solver, int32_t mode, int32_t max_iter, double 
 int32_t rt_solver_fetch(rt_solver *solver, double *phi, double *volumes, double *k_history);
 /* First-moment scattering matrices sigma_s1 [M][G][G] (host memory, copied; see above) for the following runs; NULL: back to
  * isotropic scattering, which runs exactly the kernels of a solver that never had any.  RT_ERR_INVALID when an entry is not
- * finite or exceeds Σs0 in magnitude (the solver keeps what it had). */
+ * finite or exceeds Σs0 in magnitude, or with a run open (the solver keeps what it had). */
 int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1);
 /* Adjoint mode (see above) on (non-zero) or off for the following runs: rebuilds the device material table, and the first-moment
  * table when first-moment scattering is set, from host copies.  Off restores the forward tables; a solver that never had it on
@@ -702,7 +706,7 @@ int32_t rt_solver_bilinear(rt_solver *adjoint, rt_solver *forward, int32_t n_for
 int32_t rt_solver_fetch_current(rt_solver *solver, double *J);
 /* Linear source (see above) on (non-zero) or off for the following runs.  Off runs exactly the kernels of a solver that never
  * had it on.  The first switching-on computes the cells' geometry on the device.  RT_ERR_INVALID while first-moment scattering
- * is set (and rt_solver_set_scatter_p1 fails while the linear source is on). */
+ * is set (and rt_solver_set_scatter_p1 fails while the linear source is on), or with a run open. */
 int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on);
 /* The geometry of the linear source in stages 0, 1, 2 (see "Sharded LS" above), for a caller that sums the accumulator over
  * shards between them; stage 2 switches the linear source on.  Stages 0 and 1 queue their kernels and return; stage 2 waits. */

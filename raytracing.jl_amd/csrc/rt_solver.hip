@@ -1042,6 +1042,7 @@ rt_solver *rt_solver_create(rt_tracks *tracks, int32_t n_groups, int32_t n_mater
 
 int32_t rt_solver_set_source(rt_solver *solver, const double *source) {
     if (!solver) { set_error("rt_solver_set_source: null solver"); return RT_ERR_INVALID; }
+    if (solver->open) { set_error("rt_solver_set_source: a run is open (rt_solver_begin without rt_solver_end): the source cannot change under it"); return RT_ERR_INVALID; }
     if (!source) { solver->has_ext = false; return RT_SUCCESS; }
     const size_t ncg = (size_t)solver->n_cells * solver->G;
     size_t bad = 0;
@@ -1060,6 +1061,7 @@ int32_t rt_solver_set_source(rt_solver *solver, const double *source) {
 
 static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) {
     if (!S) { set_error("rt_solver_set_scatter_p1: null solver"); return RT_ERR_INVALID; }
+    if (S->open) { set_error("rt_solver_set_scatter_p1: a run is open (rt_solver_begin without rt_solver_end): the tables cannot change under it"); return RT_ERR_INVALID; }
     if (!sigma_s1) { S->p1 = false; return RT_SUCCESS; }
     if (S->ls) { set_error("rt_solver_set_scatter_p1: the linear source is on, and the two together are not supported"); return RT_ERR_INVALID; }
     const int32_t G = S->G, M = S->M;
@@ -1392,6 +1394,7 @@ static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged
 int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
     const char *who = "rt_solver_set_linear_source";
     if (!solver) { set_error("rt_solver_set_linear_source: null solver"); return RT_ERR_INVALID; }
+    if (solver->open) { set_error("rt_solver_set_linear_source: a run is open (rt_solver_begin without rt_solver_end): the source's shape cannot change under it"); return RT_ERR_INVALID; }
     if (!on) { solver->ls = false; return RT_SUCCESS; }
     if (solver->p1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
     try {
