@@ -295,6 +295,10 @@ int32_t rt_sweep_info(rt_tracks *tracks, void **ptrs_dev, int32_t *info);
 /* How the last rt_sweep read its records: 0 where they lie (compact records, or the exact march's 20-B staging rows on their first
  * pass), 1 (ℓ, cell) rows in the staging's layout, 2 (ℓ, cell) rows made from the compact records; < 0: RT_ERR_*. */
 int32_t rt_sweep_rows_kind(rt_tracks *tracks);
+/* The precision of the last rt_sweep: RT_PRECISION_DOUBLE (0) or RT_PRECISION_SINGLE (1) — the angular flux in binary32, the sums
+ * in binary64: rt_set_option "sweep_precision" 1, or a solver's run with rt_solver_set_precision (see "Single-precision sweep"
+ * below); < 0: RT_ERR_*. */
+int32_t rt_sweep_precision(rt_tracks *tracks);
 /* The device copy of the cross sections as rt_sweep reads them: [n_cells * n_groups][2] doubles = {sigma_t, source / sigma_t}
  * (0 for the second where sigma_t = 0).  A solver that updates its source on the device writes the second components there —
  * ordered against rt_mesh_get_stream — and calls rt_sweep with sigma_t = source = NULL ("those of the previous call"): no
@@ -598,6 +602,31 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              allocated by the switch-on (rt_solver_begin enlarges it when the mode set since needs more) and freed by the
  *              switch-off or rt_solver_destroy; the index, 4 bytes per record and per cell, stays with the tracks
  *
+ * Single-precision sweep, rt_solver_set_precision(solver, RT_PRECISION_SINGLE) (rt_set_option "sweep_precision" 1 for a bare
+ * rt_sweep).  The angular flux is swept in binary32, every sum stays binary64.  Per segment and component, in binary32:
+ *     σ = (float)(Σt_g / sin θ_p),  r = (float)(q/Σt),  ℓ₃₂ = (float)ℓ,  τ = σ·ℓ₃₂,  F = one_minus_exp_neg_f32(τ)  (rt_device.hpp:
+ *     relative error below 4·2⁻²⁴, fused arithmetic only — host and device agree bit for bit),  Δ = (ψ − r)·F,  ψ ← ψ − Δ;
+ * ψ enters as (float)ψ_in and leaves as (double)ψ: the boundary-flux arrays stay FP64, so the hand-over between the tracks, the
+ * boundary kernels and a sharded run's exchange do not change.  A segment's contribution to the tally is the BINARY64 product
+ * w·(double)Δ, and every sum over segments (lane fold, LDS copy, global atomics) is binary64, as are the source update, the fold,
+ * the reductions, k and the residual.  A lane beyond its track's end evaluates ℓ = 0: F(0) = +0 exactly and ψ keeps its bits.  F is
+ * a function of τ alone — one form per lane —, so ψ_out does not depend on which tracks share a wave.
+ * Works with   eigenvalue and fixed-source runs, adjoint mode, rt_solver_set_boundary, the stepwise calls and rt_solver_pointers, a
+ *              solver on a uid shard (its partial T is FP64): only the sweep kernel is replaced (k_sweep_f32, rt_sweep_f32.hip)
+ * Refused      with first-moment scattering, the linear source or the reproducible tallies: RT_ERR_INVALID with a message that
+ *              names both sides, from whichever of the two is switched on second; the solver keeps the state it had
+ * Rows         the kernel reads (ℓ, cell) rows: rt_sweep_rows_kind 1 or 2 — what every two-phase call leaves or the first sweep
+ *              makes.  A sweep that would read its records where they lie is refused with RT_ERR_INVALID before anything is
+ *              queued, the message naming the rows' kind and the option: "sweep_rows" 0, "sweep_ell" 0, and the first pass over
+ *              the 20-B rows of a march by exact steps only (one double-precision sweep first leaves their ℓ; or "sweep_rows" 2
+ *              with input 1).  The handle stays usable
+ * Debug        "sweep_debug" bits 1 (skip the tallies) and 2 (no fold) apply as before; bit 4 has no meaning here (one form per lane)
+ * Accuracy     DESIGN.md §8: after 12 iterations k differs from the FP64 solver's by 2e-7 at most and φ by 4e-7 of its median — by up
+ *              to 2e-4 in cells that only optically thin chords cross (τ ~ 1e-4): every Δ carries about two binary32 ulp of ψ, and
+ *              the fold divides a cell's sum by Σ w τ
+ * Speed        measured at the headline configuration: not faster than the FP64 sweep beyond noise; off by default
+ * RT_PRECISION_DOUBLE (the default) launches exactly what a solver that never had the option launches.
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -655,6 +684,8 @@ typedef struct rt_solver rt_solver;
 
 #define RT_SOLVE_EIGENVALUE 0
 #define RT_SOLVE_FIXED_SOURCE 1
+#define RT_PRECISION_DOUBLE 0
+#define RT_PRECISION_SINGLE 1
 
 typedef struct rt_solver_result {
     double k_eff;       /* last k (1 in fixed-source mode)                                          */
@@ -696,6 +727,11 @@ int32_t rt_solver_set_adjoint(rt_solver *solver, int32_t on);
  * again.  On any failure the solver keeps what it had (the atomic path, if the option was off: V_e is put back, the buffers are
  * freed, and the geometry of a linear source that is on is computed by the atomic kernels again). */
 int32_t rt_solver_set_reproducible(rt_solver *solver, int32_t on);
+/* The precision of the sweep (see "Single-precision sweep" above) for the following runs: RT_PRECISION_DOUBLE or
+ * RT_PRECISION_SINGLE.  RT_ERR_INVALID for another value, with a run open ("rt_solver_set_precision: a run is open"), after the
+ * tracks were segmentized again, and for SINGLE while first-moment scattering, the linear source or the reproducible tallies are
+ * on (those setters refuse likewise while SINGLE is set); the solver then keeps the precision it had. */
+int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision);
 /* Bilinear forms B_f (see above) of n_forms (1 .. 8) matrix sets A [n_forms][M][G][G] (host memory, A[f][m][g'][g]) into
  * out [n_forms]; out_cell [n_forms][n_cells] (may be NULL) receives each cell's V_e-weighted contribution.  Both solvers must have
  * completed a run and have none open, be bound to the same tracks at the same segmentation and agree in G, M and the number of

@@ -317,6 +317,22 @@ function solver_set_reproducible!(hs::Ptr{Cvoid}, on::Bool=true)
     return nothing
 end
 
+# The precision of the sweep for the following runs of an `rt_solver` handle `hs` (include/rt_segmentize.h, "Single-precision
+# sweep"): `single = true` carries the angular flux in binary32 (every sum, the fold, k and the residual stay Float64), `false` is
+# the Float64 sweep again.  Refused together with first-moment scattering, the linear source or the reproducible tallies.
+function solver_set_precision!(hs::Ptr{Cvoid}, single::Bool=true)
+    rc = ccall((:rt_solver_set_precision, LIB), Int32, (Ptr{Cvoid}, Int32), hs, single ? 1 : 0)
+    rc == 0 || error("rt_solver_set_precision failed: " * lasterror())
+    return nothing
+end
+
+# The precision of the last sweep over the tracks handle `ht`: 0 Float64, 1 the angular flux in binary32
+function sweep_precision(ht::Ptr{Cvoid})
+    rc = ccall((:rt_sweep_precision, LIB), Int32, (Ptr{Cvoid},), ht)
+    rc >= 0 || error("rt_sweep_precision failed: " * lasterror())
+    return Int(rc)
+end
+
 # (device address, length in doubles) of that accumulator between stage 0 and stage 2; (C_NULL, 0) outside
 function solver_ls_geometry_pointer(hs::Ptr{Cvoid})
     p = Ref{Ptr{Cvoid}}(C_NULL); n = Ref{Int64}(0)

@@ -23,7 +23,7 @@ SYMBOLS = (
     "rt_record_order", "rt_device_table", "rt_fetch_table", "rt_fetch_records",
     "rt_result_alloc", "rt_result_fetch", "rt_result_free",
     "rt_last_timing", "rt_set_option", "rt_fill_tau", "rt_fetch_tau",
-    "rt_sweep_set_links", "rt_sweep", "rt_sweep_fetch", "rt_sweep_info", "rt_sweep_rows_kind", "rt_sweep_xs_pointer", "rt_multi_link_rates",
+    "rt_sweep_set_links", "rt_sweep", "rt_sweep_fetch", "rt_sweep_info", "rt_sweep_rows_kind", "rt_sweep_precision", "rt_sweep_xs_pointer", "rt_multi_link_rates",
     "rt_multi_create", "rt_multi_destroy", "rt_multi_set_option", "rt_multi_segmentize", "rt_multi_shards", "rt_multi_shard",
     "rt_multi_failed_tracks", "rt_multi_fetch_offsets", "rt_multi_fetch_segments", "rt_multi_fetch_volumes", "rt_multi_allgather",
     "rt_trace_counts", "rt_trace", "rt_msh_load", "rt_msh_sizes", "rt_msh_fetch", "rt_msh_free",
@@ -32,13 +32,17 @@ SYMBOLS = (
     "rt_solver_ls_geometry", "rt_solver_ls_geometry_pointer",
     "rt_solver_fetch_current",
     "rt_solver_begin", "rt_solver_step_sweep", "rt_solver_step_fold", "rt_solver_end", "rt_solver_pointers",
-    "rt_solver_set_adjoint", "rt_solver_bilinear", "rt_solver_set_reproducible",
+    "rt_solver_set_adjoint", "rt_solver_bilinear", "rt_solver_set_reproducible", "rt_solver_set_precision",
     "rt_solver_set_boundary", "rt_solver_fetch_boundary", "rt_solver_boundary_pointers",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
 # tuples together against every name the header declares.
 SYMBOLS_WITH_DIGITS = ("rt_solver_set_scatter_p1",)
+
+RT_PRECISION_DOUBLE = 0
+RT_PRECISION_SINGLE = 1
+PRECISIONS = {"double": RT_PRECISION_DOUBLE, "single": RT_PRECISION_SINGLE}
 
 RT_TRACK_OK = 0
 RT_TRACK_LOCATE_FAILED = 1
@@ -238,6 +242,14 @@ def lib():
     try:
         L.rt_solver_set_reproducible.restype = C.c_int32
         L.rt_solver_set_reproducible.argtypes = [_vp, C.c_int32]
+    except AttributeError:
+        if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
+            raise
+    try:
+        L.rt_solver_set_precision.restype = C.c_int32
+        L.rt_solver_set_precision.argtypes = [_vp, C.c_int32]
+        L.rt_sweep_precision.restype = C.c_int32
+        L.rt_sweep_precision.argtypes = [_vp]
     except AttributeError:
         if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
             raise
@@ -592,7 +604,9 @@ class DeviceTracks:
         """``rt_sweep``: one transport sweep over the cyclic tracks on the device.  ``sigma_t`` / ``source``: [n_cells, G];
         ``track_weight``: [n_tracks]; ``psi_in``: [2, n_tracks, G] (None: what the previous sweep handed on).  Returns a dict
         with ``ms``, ``input`` ("compact" / "staged"), ``groups_per_pass``, ``passes`` and, with ``fetch``, ``phi`` [n_cells, G],
-        ``psi_out`` and ``psi_next`` [2, n_tracks, G]."""
+        ``psi_out`` and ``psi_next`` [2, n_tracks, G].  ``precision``: "double" or "single", what ``rt_sweep_precision`` reports
+        for this sweep (option "sweep_precision" 1, or a solver's run with ``set_precision("single")``: the angular flux in
+        binary32, the sums in binary64)."""
         G = int(n_groups)
 
         def arr(a, shape):
@@ -611,10 +625,22 @@ class DeviceTracks:
         _check(lib().rt_sweep_info(self._h, None, info))
         out = dict(ms=ms.value, input={1: "compact", 2: "staged"}[int(info[0])], groups_per_pass=int(info[1]), passes=int(info[2]),
                    rows={0: None, 1: "staging", 2: "from compact"}.get(int(lib().rt_sweep_rows_kind(self._h))))
+        if hasattr(lib(), "rt_sweep_precision"):
+            out["precision"] = {0: "double", 1: "single"}[self.sweep_precision()]
         if fetch:
             out["phi"] = np.empty((self.dmesh.n_cells, G)); out["psi_out"] = np.empty((2, self.n, G)); out["psi_next"] = np.empty((2, self.n, G))
             _check(lib().rt_sweep_fetch(self._h, *[out[k].ctypes.data_as(_dp) for k in ("phi", "psi_out", "psi_next")]))
         return out
+
+    def sweep_rows_kind(self) -> int:
+        """``rt_sweep_rows_kind``: 0 the records where they lie, 1 (ℓ, cell) rows in the staging's layout, 2 rows made from the
+        compact records — how the last sweep on this handle read its records."""
+        return _check(lib().rt_sweep_rows_kind(self._h))
+
+    def sweep_precision(self) -> int:
+        """``rt_sweep_precision``: RT_PRECISION_DOUBLE (0) or RT_PRECISION_SINGLE (1) for the last sweep on this handle, a
+        solver's included."""
+        return _check(lib().rt_sweep_precision(self._h))
 
     def sweep_pointers(self) -> dict:
         """``rt_sweep_info``: device addresses of the last sweep's ``phi`` [n_cells, G], ``psi_out`` and ``psi_in`` [2, n_tracks, G]
@@ -680,12 +706,13 @@ class DeviceSolver:
     ``segmentize`` and ``sweep_set_links`` have run (``include/rt_segmentize.h`` states the definitions).  Arrays:
     ``cell_material`` [n_cells] (0-based), ``sigma_t`` / ``nu_sigma_f`` / ``chi`` [M, G], ``sigma_s`` [M, G, G] (from g' to g),
     ``sin_polar`` / ``polar_weight`` [P], ``azim_weight`` [n_azim / 2] (None: the equal set).  ``reproducible=True``: the
-    reproducible tallies from the first run on (``set_reproducible``)."""
+    reproducible tallies from the first run on (``set_reproducible``).  ``precision="single"``: the sweep in binary32 from the
+    first run on (``set_precision``)."""
 
     EIGENVALUE, FIXED_SOURCE = 0, 1
 
     def __init__(self, dtracks: DeviceTracks, cell_material, sigma_t, sigma_s, nu_sigma_f, chi, sin_polar, polar_weight, azim_weight=None,
-                 reproducible=False):
+                 reproducible=False, precision="double"):
         L = lib()
         self.dtracks = dtracks  # keeps the tracks alive
         st = np.ascontiguousarray(sigma_t, np.float64)
@@ -717,6 +744,21 @@ class DeviceSolver:
         self.reproducible = False
         if reproducible:
             self.set_reproducible(True)
+        self.precision = "double"
+        if precision != "double":
+            self.set_precision(precision)
+
+    def set_precision(self, precision="single"):
+        """``rt_solver_set_precision``: "single" sweeps the angular flux in binary32 for the following runs (every sum, the fold, k
+        and the residual stay FP64), "double" the FP64 sweep again.  Refused together with first-moment scattering, the linear
+        source or the reproducible tallies."""
+        L = lib()
+        if precision not in PRECISIONS:
+            raise ValueError('precision must be "double" or "single"')
+        if not hasattr(L, "rt_solver_set_precision"):
+            raise RtError(f"{LIB_PATH} has no rt_solver_set_precision: the library is older than this binding")
+        _check(L.rt_solver_set_precision(self._open(), PRECISIONS[precision]))
+        self.precision = precision
 
     def set_reproducible(self, on=True):
         """``rt_solver_set_reproducible``: fixed-order sweep tallies for the following runs — two runs of the same problem return

@@ -1065,6 +1065,45 @@ RT_HD __forceinline__ double one_minus_exp_neg_thin(double tau, const ExpPoly &h
     return tau * q;
 }
 
+// ---- single-precision sweep (k_sweep_f32, rt_sweep_f32.hip; rt_solver_set_precision) ---------------------------------------------
+// 1 − e^{−τ} in binary32 for τ >= 0, relative error against the exact −expm1(−τ) below 4·2⁻²⁴ (measured on the host over 2²⁰ values:
+// DESIGN §8), F(0) = +0 exactly, 0 <= F <= 1, F = 1 from τ = 17.33 on (e^{−τ} < 2⁻²⁵).  Fused arithmetic only — no hardware
+// exponential —, so host and device agree bit for bit, as the FP64 forms do.  The scheme is the FP64 one with binary32 constants:
+// x = −τ = n·ln2 + r, |r| <= ln2/2, n by the 1.5·2²³ trick, ln2 split in two (the high part has nine trailing zero bits: n·hi is
+// exact for |n| < 2⁹), expm1(r) = r + r²·q(r) by its Taylor polynomial to r⁷ (the next term is below 0.2·2⁻²⁴ of the result), and
+// 1 − e^x = (1 − 2^n) − 2^n·expm1(r) in one fma.  1 − 2^n is exact down to n = −24 and rounds to 1 below, where the result is 1 to
+// half an ulp.
+// The series that 1 − e^{−τ} needs where it cancels is this form's own case n = 0, chosen PER LANE by the range reduction: below
+// τ = ln2/2 the reduction leaves r = x and 2^n = 1, and the result is −expm1(x) = −(x + x² q(x)), the series, without any
+// subtraction from 1.  one_minus_exp_neg_f32_thin is that case alone, without the reduction — the SAME operations on the same
+// values, hence the same bits, for every τ < kThinTauF32 (0.34 < ln2/2: n = 0 for certain).  A kernel may take it where a whole
+// wave-row is thin (8 instructions instead of 17) without changing any lane's result.
+constexpr float kThinTauF32 = 0.34f;
+RT_HD __forceinline__ float expm1_poly_f32(float r) {
+    float q = 1.9841270e-04f;                    // 1/7!
+    q = __builtin_fmaf(q, r, 1.3888889e-03f);    // 1/6!
+    q = __builtin_fmaf(q, r, 8.3333333e-03f);    // 1/5!
+    q = __builtin_fmaf(q, r, 4.1666667e-02f);    // 1/4!
+    q = __builtin_fmaf(q, r, 1.6666667e-01f);    // 1/3!
+    q = __builtin_fmaf(q, r, 0.5f);              // 1/2!
+    return __builtin_fmaf(r * r, q, r);          // expm1(r)
+}
+RT_HD __forceinline__ float one_minus_exp_neg_f32_thin(float tau) {
+    return __builtin_fmaf(-1.0f, expm1_poly_f32(-tau), 0.0f);  // (the general form's last fma at 2^n = 1: −0 becomes +0)
+}
+RT_HD __forceinline__ float one_minus_exp_neg_f32(float tau) {
+    const float x = -__builtin_fminf(tau, 20.0f);  // (τ is never NaN; n >= −29)
+    const float kMagic = 12582912.0f;              // 1.5 · 2^23: adding it rounds to an integer, which sits in the low mantissa bits
+    const float t = __builtin_fmaf(x, 1.44269504f, kMagic);
+    const float n = t - kMagic;
+    const int32_t ni = (int32_t)(__builtin_bit_cast(uint32_t, t) - 0x4B400000u);
+    float r = __builtin_fmaf(n, -6.9314575195e-01f, x);  // ln2 = hi + lo
+    r = __builtin_fmaf(n, -1.4286067653e-06f, r);
+    const float p = expm1_poly_f32(r);
+    const float s2 = __builtin_bit_cast(float, (uint32_t)(ni + 127) << 23);  // 2^n, n in [-29, 0]
+    return __builtin_fmaf(-s2, p, 1.0f - s2);
+}
+
 // ---- linear source (k_sweep<..., LS>) ------------------------------------------------------------------------------------
 // one_minus_exp_neg that also hands out e^{−τ} = 2^n (1 + expm1(r)), itself to an ulp (1 − F1 would lose what F1 cancels).
 RT_HD __forceinline__ double one_minus_exp_neg_both(double tau, double &E, const ExpPoly &hi = exp_poly()) {

@@ -278,6 +278,7 @@ constexpr int kScanBlock = 256;
 constexpr int kScanPer = 4;
 constexpr int kScanTile = kScanBlock * kScanPer;
 constexpr int kTauSegs = 2048;  // segments per workgroup
+constexpr int kSweepGpF32 = 4;  // components per pass of the single-precision sweep, at most (rt_sweep_f32.hip)
 
 // k_sweep's arguments (rt_sweep.hip)
 struct DSweep {
@@ -347,6 +348,7 @@ struct rt_mesh {
     int sweep_rows = 1; // rt_sweep over the compact records: as (ℓ, cell) rows (the staging's, or made once from the records); 0: where they lie
     int sweep_ell = 1;  // rt_sweep over staged rows: keep ℓ of every row from the first pass for the later ones (0: every pass derives it)
     int sweep_debug = 0, compact_debug = 0;
+    int sweep_precision = 0;  // rt_sweep without a solver: 1 the angular flux in binary32 (k_sweep_f32), 0 FP64
     int mat_kernel = 0;      // records of a two-phase call: 0 k_materialise_lin (output order, 16-B stores), 1 k_materialise (chunk tiles; A/B)
     int lin_unit = 0;        // tracks per workgroup of k_materialise_lin: 16, 32, or 0 — by the call's records per track (choose_lin_unit)
     int march_waves = 0;     // 4 / 6: waves per workgroup of the fused march (0: automatic)
@@ -519,6 +521,8 @@ struct rt_tracks {
     bool sw_repro = false;             // switched on by an rt_solver for the sweeps of its run, with its delta buffer
     double *sw_repro_delta = nullptr;
     size_t sw_repro_cap = 0;           // doubles
+    bool sw_f32 = false;               // single-precision sweep, switched on by an rt_solver (rt_solver_set_precision) for the sweeps of its run
+    int32_t sw_last_prec = 0;          // precision of the last sweep (rt_sweep_precision)
     bool sw_links = false, sw_has_w = false, sw_has_xs = false, sw_done = false;
     rt_solver *sw_borrower = nullptr;  // the rt_solver between rt_solver_begin and rt_solver_end that holds this sweep state
     // host copy of the links as rt_sweep_set_links got them, whatever their bc (rt_solver_set_boundary builds its own gather map
@@ -560,6 +564,8 @@ void launch_compaction(rt_tracks *t, const rt::DOut &out, hipStream_t s);
 int ensure_compacted(rt_tracks *t);
 int ensure_rows(rt_tracks *t);
 int ensure_rows_from_compact(rt_tracks *t);  // rt_sweep.hip
+// rt_sweep_f32.hip: one pass of the single-precision sweep kernel over `gp` components from a.g0 (a.use_lds: the tallies' LDS copy)
+int launch_sweep_f32(const rt::DSweep &a, int gp, size_t smem, int waves, unsigned blocks, hipStream_t s);
 // rt_sweep.hip: the row variant a solver's sweep (input 0) reads now, its rows made and the cell index built for it (once per
 // segmentation and variant); *slots: row slots of the variant.  RT_ERR_INVALID where the reproducible tallies cannot be served
 int sweep_repro_prepare(rt_tracks *t, int64_t *slots);

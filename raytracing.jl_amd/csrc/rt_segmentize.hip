@@ -567,6 +567,11 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value) {
     if (!strcmp(name, "fetch_hugepages")) { mesh->fetch_hugepages = value != 0; return RT_SUCCESS; }
     if (!strcmp(name, "sweep_rows")) { mesh->sweep_rows = value < 0 ? 0 : (value > 2 ? 2 : (int)value); return RT_SUCCESS; }
     if (!strcmp(name, "sweep_waves")) { mesh->sweep_waves = (int)value; return RT_SUCCESS; }
+    if (!strcmp(name, "sweep_precision")) {
+        if (value != 0 && value != 1) { set_error("rt_set_option: sweep_precision is 0 (double) or 1 (single), not %lld", (long long)value); return RT_ERR_INVALID; }
+        mesh->sweep_precision = (int)value;
+        return RT_SUCCESS;
+    }
     if (!strcmp(name, "sweep_debug")) { mesh->sweep_debug = (int)value; return RT_SUCCESS; }
     if (!strcmp(name, "compact_debug")) { mesh->compact_debug = (int)value; return RT_SUCCESS; }
     if (!strcmp(name, "mat_kernel")) { mesh->mat_kernel = (int)value; return RT_SUCCESS; }

@@ -553,6 +553,8 @@ struct rt_solver {
     // from the switch-on to the switch-off (or rt_solver_destroy)
     bool repro = false;
     DevBuf<double> delta;
+    // single-precision sweep (rt_solver_set_precision): lent to the handle as rt_tracks::sw_f32 for the solver's runs
+    bool single = false;
     // ... and V_e as rt_solver_create summed it (FP64 atomics), kept while `vol` holds the sums in the index's order instead
     DevBuf<double> vol_atomic;
     std::vector<double> k_hist;
@@ -574,6 +576,7 @@ void solver_release(rt_solver *S) {
     rt_tracks *t = S->t;
     t->sw_has_w = false; t->sw_p1 = false; t->sw_ls = false; t->sw_ls_cen = t->sw_ls_ends = nullptr;
     t->sw_repro = false; t->sw_repro_delta = nullptr; t->sw_repro_cap = 0;
+    t->sw_f32 = false;
     if (t->sw_borrower == S) t->sw_borrower = nullptr;
     S->open = false; S->swept = false;
 }
@@ -850,6 +853,10 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
         if (int rc = solver_repro_reserve(S, who)) return rc;
         t->sw_repro = true; t->sw_repro_delta = S->delta.p; t->sw_repro_cap = S->delta.cap;
     }
+    if (S->single) {  // (the setters keep the combinations apart; a solver that got here with one is refused like them)
+        if (p1 || ls || S->repro) { set_error("%s: the single-precision sweep (rt_solver_set_precision) together with first-moment scattering, the linear source or the reproducible tallies is not supported", who); return RT_ERR_INVALID; }
+        t->sw_f32 = true;
+    }
     S->bnd_tallied = false;
     if (bnd) RT_HIP(hipMemsetAsync(S->bnd_J.p, 0, (size_t)2 * S->bnd_S * G * sizeof(double), s));
     if (bnd && S->bnd_inc && n > 0)  // the first sweep already sees the incoming flux
@@ -1064,6 +1071,7 @@ static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) 
     if (S->open) { set_error("rt_solver_set_scatter_p1: a run is open (rt_solver_begin without rt_solver_end): the tables cannot change under it"); return RT_ERR_INVALID; }
     if (!sigma_s1) { S->p1 = false; return RT_SUCCESS; }
     if (S->ls) { set_error("rt_solver_set_scatter_p1: the linear source is on, and the two together are not supported"); return RT_ERR_INVALID; }
+    if (S->single) { set_error("rt_solver_set_scatter_p1: the single-precision sweep is set (rt_solver_set_precision), and first-moment scattering together with it is not supported"); return RT_ERR_INVALID; }
     const int32_t G = S->G, M = S->M;
     const size_t n1 = (size_t)M * G * G;
     for (size_t i = 0; i < n1; ++i)
@@ -1397,6 +1405,7 @@ int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
     if (solver->open) { set_error("rt_solver_set_linear_source: a run is open (rt_solver_begin without rt_solver_end): the source's shape cannot change under it"); return RT_ERR_INVALID; }
     if (!on) { solver->ls = false; return RT_SUCCESS; }
     if (solver->p1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
+    if (solver->single) { set_error("rt_solver_set_linear_source: the single-precision sweep is set (rt_solver_set_precision), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
     try {
         if (!solver->has_geom)
             for (int32_t stage = 0; stage < 3; ++stage)
@@ -1434,6 +1443,7 @@ static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
     if (S->ls_stage != 0) { set_error("%s: the linear source's geometry is between two stages (rt_solver_ls_geometry)", who); return RT_ERR_INVALID; }
     const bool want = on != 0;
     if (want == S->repro) return RT_SUCCESS;
+    if (want && S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
     rt_tracks *t = S->t;
     if (int rc = finish_call(t)) return rc;
     RT_HIP(hipSetDevice(t->mesh->device));
@@ -1504,6 +1514,25 @@ int32_t rt_solver_set_reproducible(rt_solver *solver, int32_t on) {
         set_error("rt_solver_set_reproducible: %s", e.what());
         return RT_ERR_INVALID;
     }
+}
+
+// The precision of the sweep for the following runs.  Nothing is allocated or computed: rt_solver_begin lends the choice to the
+// handle (rt_tracks::sw_f32), and rt_sweep launches k_sweep_f32 instead of k_sweep.
+int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision) {
+    const char *who = "rt_solver_set_precision";
+    rt_solver *S = solver;
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the sweep cannot change under it", who); return RT_ERR_INVALID; }
+    if (precision != RT_PRECISION_DOUBLE && precision != RT_PRECISION_SINGLE) { set_error("%s: precision %d (RT_PRECISION_DOUBLE = 0 or RT_PRECISION_SINGLE = 1)", who, precision); return RT_ERR_INVALID; }
+    if (precision == RT_PRECISION_SINGLE) {
+        const char *other = S->p1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
+                                  : (S->ls ? "the linear source is on (rt_solver_set_linear_source)"
+                                           : (S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)" : nullptr));
+        if (other) { set_error("%s: %s, and the single-precision sweep together with it is not supported", who, other); return RT_ERR_INVALID; }
+    }
+    S->single = precision == RT_PRECISION_SINGLE;
+    return RT_SUCCESS;
 }
 
 int32_t rt_solver_ls_geometry_pointer(rt_solver *solver, void **acc_dev, int64_t *len) {

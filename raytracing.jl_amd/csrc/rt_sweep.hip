@@ -488,6 +488,23 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         if (staged_ok && m->sweep_rows != 2) staged = true;  // ("sweep_rows" 2, tests / A/B: always from the compact records)
         else rows_compact = true;
     }
+    // Single precision (an rt_solver with rt_solver_set_precision lends `sw_f32` for its run; option "sweep_precision" 1 for the bare
+    // sweep): k_sweep_f32 (rt_sweep_f32.hip), flat and isotropic, over (ℓ, cell) rows — rows kind 1 or 2.  A sweep that would read
+    // its records where they lie is refused before anything is queued, with the rows' kind and the option that decides it.
+    const bool f32 = t->sw_f32 || m->sweep_precision == 1;
+    if (f32) {
+        const char *other = t->sw_p1 ? "first-moment scattering (rt_solver_set_scatter_p1)"
+                                     : (t->sw_ls ? "the linear source (rt_solver_set_linear_source)"
+                                                 : (t->sw_repro ? "the reproducible tallies (rt_solver_set_reproducible)" : nullptr));
+        if (other) { set_error("rt_sweep: the single-precision sweep (rt_solver_set_precision, \"sweep_precision\" 1) together with %s is not supported", other); return RT_ERR_INVALID; }
+        const char *why = nullptr;
+        if (!staged && !rows_compact) why = "the compact records where they lie: option \"sweep_rows\" is 0";
+        else if (staged && !rows_compact && !t->cplan.codes && !m->sweep_ell) why = "the staging's 20-B rows in every pass: option \"sweep_ell\" is 0";
+        else if (staged && !rows_compact && !t->cplan.codes && !t->sw_ell_valid)
+            why = "the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
+                  "double-precision sweep first (\"sweep_precision\" 0), or set option \"sweep_rows\" 2 and name the compact records";
+        if (why) { set_error("rt_sweep: the single-precision sweep (\"sweep_precision\" 1) reads (ℓ, cell) rows, and this sweep would read rows of kind 0 — %s", why); return RT_ERR_INVALID; }
+    }
     if (!staged)
         if (int rc = ensure_compacted(t)) return rc;
     if (rows_compact)
@@ -629,9 +646,28 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         }
         return RT_SUCCESS;
     };
+    // single precision: the passes of k_sweep_f32, with the widths, the LDS copy and the grid chosen above for the FP64 rows kernel
+    auto launch_all_f32 = [&]() -> int {
+        if (!ell_rows || !(t->sw_ell_valid || rows_compact)) {  // (checked before anything was queued; left: no memory for the ℓ rows)
+            set_error("rt_sweep: the single-precision sweep (\"sweep_precision\" 1) found no (ℓ, cell) rows to read (rows of kind 0)");
+            return RT_ERR_INVALID;
+        }
+        for (int g0 = 0; g0 < G;) {
+            const int take = std::min(gp, G - g0);
+            const size_t smem = a.use_lds ? (size_t)m->n_cells * take * sizeof(double) : 0;
+            int W = smem > 79 * 1024 ? 16 : 8;  // (one workgroup per CU when its tallies fill the LDS: see `launch`)
+            if (m->sweep_waves == 4 || m->sweep_waves == 8 || m->sweep_waves == 16) W = m->sweep_waves;
+            a.g0 = g0; a.ng = take;
+            if (int rc = launch_sweep_f32(a, take, smem, W, (unsigned)((2 * (int64_t)a.n_waves + W - 1) / W), s)) return rc;
+            ++passes;
+            g0 += take;
+        }
+        return RT_SUCCESS;
+    };
     if (n > 0) {
         int rc;
-        if (repro) rc = (staged || rows_compact) ? launch_all.template operator()<true, false, true>() : launch_all.template operator()<false, false, true>();
+        if (f32) rc = launch_all_f32();
+        else if (repro) rc =(staged || rows_compact) ? launch_all.template operator()<true, false, true>() : launch_all.template operator()<false, false, true>();
         else if (staged || rows_compact) rc = a.use_lds ? launch_all.template operator()<true, true>() : launch_all.template operator()<true, false>();
         else rc = a.use_lds ? launch_all.template operator()<false, true>() : launch_all.template operator()<false, false>();
         if (rc) return rc;
@@ -654,6 +690,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     // (what the caller's records were: 1 the compact CSR records — named, or all there is —, 2 the staging; and how they were read)
     t->sw_last_input = (input == 1 || rows_compact || !staged) ? 1 : 2;
     t->sw_last_rows = rows_compact ? 2 : (staged && ell_rows ? 1 : 0); t->sw_last_gp = a.use_lds ? gp : 0; t->sw_last_passes = passes;
+    t->sw_last_prec = f32 ? RT_PRECISION_SINGLE : RT_PRECISION_DOUBLE;
     return RT_SUCCESS;
 }
 
@@ -702,6 +739,12 @@ int32_t rt_sweep_rows_kind(rt_tracks *t) {
     if (!t) { set_error("null handle"); return RT_ERR_INVALID; }
     if (!t->sw_done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
     return t->sw_last_rows;
+}
+
+int32_t rt_sweep_precision(rt_tracks *t) {
+    if (!t) { set_error("null handle"); return RT_ERR_INVALID; }
+    if (!t->sw_done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
+    return t->sw_last_prec;
 }
 
 int32_t rt_sweep_xs_pointer(rt_tracks *t, void **xs_dev) {

@@ -236,6 +236,7 @@ class SolverResult:
     leakage: Optional[np.ndarray] = None        # ... J⁺ − J⁻ [4, G]
     balance: Optional[dict] = None              # ... neutron_balance: gain, removal, leakage, defect [G]; all four None without
     reproducible: bool = False    # True: the run used the fixed-order sweep tallies (rt_solver_set_reproducible): its bits repeat
+    precision: str = "double"     # "single": the run swept the angular flux in binary32 (rt_solver_set_precision); sums, fold, k in FP64
 
 
 def _cell_material(tg, cell_material):
@@ -266,7 +267,9 @@ def _device_tracks(tg, device):
 
 
 def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat", adjoint=False,
-           boundary=None, reproducible=False):
+           boundary=None, reproducible=False, precision="double"):
+    if precision not in _capi.PRECISIONS:
+        raise ValueError('precision must be "double" or "single"')
     if not isinstance(xs, CrossSections):
         raise TypeError("xs must be a CrossSections")
     if scheme not in ("flat", "linear"):
@@ -296,6 +299,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         sv.set_boundary(boundary, track_end_sides(tg))
     if reproducible:  # (last: the delta buffer is sized for the mode set above)
         sv.set_reproducible(True)
+    if precision != "double":  # (refused by the library together with sigma_s1, scheme="linear" or reproducible=True)
+        sv.set_precision(precision)
     r = sv.run(mode, int(max_iter), float(tol_k), float(tol_flux))
     f = sv.fetch(r["iterations"])
     mom = sv.fetch_moments() if linear else dict(flux_moments=None, flux_gradient=None)
@@ -313,12 +318,12 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
                         flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids, adjoint=bool(adjoint),
-                        reproducible=bool(reproducible), **bnd)
+                        reproducible=bool(reproducible), precision=precision, **bnd)
 
 
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
                      tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
-                     boundary: Optional["SolverBoundary"] = None, reproducible: bool = False) -> SolverResult:
+                     boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double") -> SolverResult:
     """Power iteration for k_eff on the device.  ``cell_material``: material index per cell [n_cells] (or one index for all,
     or a dict region name -> index over ``tg.mesh.model.cell_region``).  ``polar``: a ``PolarQuadrature`` spec;
     ``azim_weights``: "exact", "equal" or an array.  Uses ``tg.device_tracks`` when ``segmentize(tg, fetch=False)`` has run,
@@ -328,25 +333,28 @@ def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar
     transposed problem, J† = −J*; ``flux_moments``: those of φ†).  ``boundary``: a ``SolverBoundary`` (albedos per side and group;
     the result then carries ``current_out``, ``current_in``, ``leakage`` and ``balance``); None: what ``trace`` linked, nothing
     tallied.  ``reproducible=True``: the sweep tallies in a fixed order instead of FP64 atomics (``rt_solver_set_reproducible``) — a
-    repeated run returns the same bits in every field, at the price of a delta buffer on the device and a slower sweep."""
+    repeated run returns the same bits in every field, at the price of a delta buffer on the device and a slower sweep.
+    ``precision="single"``: the sweep carries the angular flux in binary32 (``rt_solver_set_precision``; every sum, the fold, k and
+    the residual stay FP64) — k then differs from the FP64 run's in about the seventh digit; not together with ``sigma_s1``,
+    ``scheme="linear"`` or ``reproducible=True`` (``RtError``)."""
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible)
+                  adjoint, boundary, reproducible, precision)
 
 
 def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
                        tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
-                       boundary: Optional["SolverBoundary"] = None, reproducible: bool = False) -> SolverResult:
+                       boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double") -> SolverResult:
     """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
     the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``; with ``adjoint=True`` ``source`` is the
     adjoint source S† (for instance a detector cross section) and ``phi`` the importance φ†: Σ V S† φ = Σ V S φ†.  ``boundary``: a
     ``SolverBoundary``, here also with an incoming flux per side and group (``source`` may then be zero: a run driven from the
-    boundary).  ``reproducible``: as for ``solve_eigenvalue``."""
+    boundary).  ``reproducible``, ``precision``: as for ``solve_eigenvalue``."""
     q = np.asarray(source, np.float64)
     G = xs.n_groups
     if q.ndim == 0 or q.shape == (G,):
         q = np.broadcast_to(q, (tg.mesh.num_cells, G))
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible)
+                  adjoint, boundary, reproducible, precision)
 
 
 # ---- adjoint-weighted integrals ------------------------------------------------------------------------------------------------

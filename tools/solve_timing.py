@@ -4,7 +4,9 @@ figures first, then the same runs in adjoint mode (rt_solver_set_adjoint) on the
 forward figures first, then the same runs with the albedo B on all four sides (rt_solver_set_boundary: the hand-over and the two
 current tallies per iteration) under "albedo_*", with the leakage and the balance defect of the last run; `--reproducible`: the
 forward figures first, then the same runs with the reproducible tallies (rt_solver_set_reproducible) under "reproducible_*", with the
-device memory the switch-on took — delta buffer and cell index — and whether the repeats returned the same bits).
+device memory the switch-on took — delta buffer and cell index — and whether the repeats returned the same bits; `--single`: the
+forward figures first, then the same runs with the single-precision sweep (rt_solver_set_precision) under "single_*", with the bare
+single-precision sweep beside the FP64 one and the deviation of k).
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
@@ -63,6 +65,8 @@ def main():
                     help="after the forward runs, the same runs with the albedo B in [0, 1] on every side (rt_solver_set_boundary)")
     ap.add_argument("--reproducible", action="store_true",
                     help="after the forward runs, the same runs with the reproducible tallies (rt_solver_set_reproducible)")
+    ap.add_argument("--single", action="store_true",
+                    help="after the forward runs, the same runs with the single-precision sweep (rt_solver_set_precision); not with --p1 / --linear")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -151,6 +155,21 @@ def main():
         out["reproducible_bytes_held"] = int(held)
         out["reproducible_bits_repeat"] = all(p == phis[0] for p in phis)
         sv.set_reproducible(False)
+    if a.single:  # (k_sweep_f32 in place of k_sweep; everything else of the iteration is what it was)
+        sv.set_precision("single")
+        sv.run(0, 3, 0.0, 0.0)
+        ev_ms, host_ms = [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            r = sv.run(0, a.iters, 0.0, 0.0)
+            host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+            ev_ms.append(r["device_ms"] / r["iterations"])
+        out["single_ms_per_iter_events"] = float(np.median(ev_ms))
+        out["single_ms_per_iter_host"] = float(np.median(host_ms))
+        out["single_over_double_events"] = out["single_ms_per_iter_events"] / out["ms_per_iter_events"]
+        out["single_k_eff"] = r["k_eff"]
+        out["single_k_minus_double"] = r["k_eff"] - out["k_eff"]
+        sv.set_precision("double")
     if a.steps:
         ev_ms, host_ms = [], []
         for _ in range(a.repeats):
@@ -181,6 +200,16 @@ def main():
         out["non_sweep_ms_events"] = out["ms_per_iter_events"] - s
         out["non_sweep_over_sweep"] = (out["ms_per_iter_events"] - s) / s
         out["non_sweep_over_sweep_host"] = (out["ms_per_iter_host"] - s) / s
+        if a.single:  # the same bare sweep through k_sweep_f32 (option "sweep_precision"), beside the FP64 figure above
+            dt.dmesh.set_option("sweep_precision", 1)
+            sw = []
+            for _ in range(10):
+                ms = _capi.C.c_double(0.0)
+                _capi._check(_capi.lib().rt_sweep(dt._h, C, None, None, None, None, 0, _capi.C.byref(ms)))
+                sw.append(ms.value)
+            dt.dmesh.set_option("sweep_precision", 0)
+            out["single_sweep_ms"] = float(np.median(sw[2:]))
+            out["single_sweep_over_double"] = out["single_sweep_ms"] / s
     print(json.dumps(out))
     sv.close()
 
