@@ -4,6 +4,7 @@
 //   rt_records.hip     staging -> records: k_compact3, k_materialise, k_finish, the offsets scan, k_volumes, k_fill_tau
 //   rt_materialise.hip k_materialise_lin: a two-phase call's records in output order
 //   rt_sweep.hip       rt_sweep: k_sweep, k_sweep_link, the sweep's host code and entry points
+//   rt_sweep_plan.hpp  what an rt_sweep call decides (rows, pass width and shape, refusals): host-only, a pure function
 //   rt_solver.hip      rt_solver: source iteration (k_eff / fixed source) around rt_sweep, fold / source / reduction kernels
 //   rt_segmentize.hip  handles, rt_tracks_create, rt_segmentize (the call's host logic), fetches, statistics
 #pragma once
@@ -21,11 +22,14 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/rt_segmentize.h"
 #include "rt_device.hpp"
 #include "rt_mesh_prep.hpp"
+#include "rt_sweep_plan.hpp"
+using rtsweep::SweepMode;
 
 namespace rthost {
 extern thread_local std::string g_last_error;
@@ -318,6 +322,17 @@ struct DSweep {
 }  // namespace rt
 
 // ------------------------------------------------------------------- handles -------------
+// What an rt_solver lends its handle for the rt_sweep calls of a run: assigned once by solver_begin_impl, handed back whole by solver_release.
+struct SweepLoan {
+    rt_solver *borrower = nullptr;    // the solver that holds the handle's sweep state
+    SweepMode mode = SweepMode::Flat; // P1 / Linear: sw_xs1 holds the solver's ratios, sw_cur receives the moment tallies
+    const double *ls_cen = nullptr, *ls_ends = nullptr;  // Linear: the solver's centroids and track ends (DSweep cen, ends)
+    bool repro = false;               // reproducible tallies, into the solver's delta buffer
+    double *repro_delta = nullptr;
+    size_t repro_cap = 0;             // doubles
+    bool f32 = false;                 // single-precision sweep (rt_solver_set_precision)
+};
+
 struct rt_mesh {
     int device = 0;
     hipStream_t own_stream = nullptr;
@@ -502,10 +517,9 @@ struct rt_tracks {
     // rt_sweep: the gather map of the cyclic linking, per-track weights, cross sections, boundary fluxes, tallies
     DevBuf<int32_t> sw_src;
     DevBuf<double> sw_w, sw_xs, sw_psi_in, sw_psi_out, sw_phi;
-    DevBuf<double> sw_xs1, sw_cur;  // the anisotropic sweep's first-moment ratios and tallies (DSweep xs1, cur): rt_solver owns their content
-    bool sw_p1 = false;             // ... and switches the mode on for the sweeps of its run
-    bool sw_ls = false;             // the linear-source mode, switched on by an rt_solver for the sweeps of its run (sw_xs1: gradient
-    const double *sw_ls_cen = nullptr, *sw_ls_ends = nullptr;  // ratios, sw_cur: moment tallies); the solver's centroids and track ends
+    DevBuf<double> sw_xs1, sw_cur;  // the P1 sweep's first-moment ratios and tallies, the linear source's gradient ratios and moment tallies
+                                    // (DSweep xs1, cur): the rt_solver that holds the loan owns their content
+    SweepLoan sw_loan;              // what an rt_solver lends for the sweeps of its run (all of it goes back at once: solver_release)
     DevBuf<double> sw_ell;      // ℓ of every staged row (slot-indexed like the staging pool), left by the first staged pass after a call
     bool sw_ell_valid = false;  // ... of the last rt_segmentize
     DevBuf<int32_t> sw_cell;    // codes: cell + 1 of every staged row, beside sw_ell (k_materialise<.., ROWS>)
@@ -518,13 +532,9 @@ struct rt_tracks {
     DevBuf<int32_t> sw_ridx_start, sw_ridx_list;  // [n_cells + 1], [total]
     int sw_ridx_kind = 0;
     int64_t sw_ridx_slots = 0;         // row slots of that variant: the delta buffer holds 2 · slots · NT · width doubles
-    bool sw_repro = false;             // switched on by an rt_solver for the sweeps of its run, with its delta buffer
-    double *sw_repro_delta = nullptr;
-    size_t sw_repro_cap = 0;           // doubles
-    bool sw_f32 = false;               // single-precision sweep, switched on by an rt_solver (rt_solver_set_precision) for the sweeps of its run
     int32_t sw_last_prec = 0;          // precision of the last sweep (rt_sweep_precision)
-    bool sw_links = false, sw_has_w = false, sw_has_xs = false, sw_done = false;
-    rt_solver *sw_borrower = nullptr;  // the rt_solver between rt_solver_begin and rt_solver_end that holds this sweep state
+    bool sw_links = false, sw_has_xs = false, sw_done = false;
+    bool sw_has_w = false;             // sw_w holds weights: a caller's (rt_sweep sets it) or a solver's (solver_release clears it)
     // host copy of the links as rt_sweep_set_links got them, whatever their bc (rt_solver_set_boundary builds its own gather map
     // from it): entry slot d'·n + v of source d·n + u (-1: the linked track is not in this track set), in [2][n]
     std::vector<int32_t> sw_h_entry;
@@ -545,6 +555,19 @@ hipError_t wait_stream(hipStream_t s);
 hipError_t wait_seq(const unsigned long long *h_res, unsigned long long seq, hipStream_t s);
 void solver_release(rt_solver *s);  // rt_solver.hip: ends a solver's run in progress and hands the handle's sweep state back
 int finish_call(rt_tracks *t);  // every entry point that reads a call's results first waits for a call still on the stream
+// An entry point's body behind the C ABI: what it throws (std::bad_alloc of a host vector, mostly) becomes RT_ERR_INVALID / NULL with
+// "<who>: <what>" as the error text, after `cleanup` where the entry point has something to drop.
+template <class F, class C = void (*)()>
+auto guarded(const char *who, F &&f, C &&cleanup = [] {}) -> decltype(f()) {
+    try {
+        return f();
+    } catch (const std::exception &e) {
+        cleanup();
+        set_error("%s: %s", who, e.what());
+    }
+    if constexpr (std::is_pointer_v<decltype(f())>) return nullptr;  // (rt_solver_create)
+    else return RT_ERR_INVALID;
+}
 template <typename T>
 int upload(DevBuf<T> &b, const T *src, size_t n, hipStream_t s) {
     RT_HIP(b.reserve(n > 0 ? n : 1));

@@ -806,7 +806,7 @@ void rt_tracks_destroy(rt_tracks *tracks) {
     if (!tracks) return;
     (void)hipSetDevice(tracks->mesh->device);
     (void)finish_call(tracks);
-    solver_release(tracks->sw_borrower);  // (a solver in the middle of a run must not reach for these tracks later)
+    solver_release(tracks->sw_loan.borrower);  // (a solver in the middle of a run must not reach for these tracks later)
     free_tracks(tracks);
 }
 
@@ -905,7 +905,7 @@ struct SegmentizeCall {
         n = t->n;
         t->segmentized = false;
         ++t->seg_epoch;
-        solver_release(t->sw_borrower);  // (a solver's run in progress ends here: its records are going, and the handle's own sweeps weigh by δs again)
+        solver_release(t->sw_loan.borrower);  // (a solver's run in progress ends here: its records are going, and the handle's own sweeps weigh by δs again)
         t->tau_groups = 0;  // τ of the previous records is void
         for (double &v : t->ms) v = 0.0;
 

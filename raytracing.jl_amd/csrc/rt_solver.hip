@@ -16,6 +16,9 @@
 // With the reproducible tallies (rt_solver_set_reproducible) the solver launches the same kernels; the sweep it queues runs
 // k_sweep_repro and k_sweep_reduce behind every pass (rt_sweep.hip), into the delta buffer this solver owns, and V_e and the linear
 // source's geometry are summed through the same cell index.  Without the option the solver launches what it always did.
+// Flat, first-moment scattering or linear source is one choice of three, a SweepMode (each setter switches only its own mode off and
+// refuses to switch it on over the other).  What a run's rt_sweep calls need to know — that mode, the linear source's geometry, the
+// reproducible tallies' delta buffer, single precision — goes to the handle as one SweepLoan (rt_internal.hpp) and comes back whole.
 #include "rt_internal.hpp"
 
 namespace rt {
@@ -528,12 +531,13 @@ struct rt_solver {
     std::vector<double> h_nf, h_chi, h_s1;
     bool adjoint = false;
     DevBuf<double> tab1, J, q1r;     // table (see mat_row_p1); net current and q1/Σt [n_cells][G][2]
-    bool p1 = false, ran_p1 = false;
+    // the source's shape as the setters leave it, of the open run, of the last completed run (a mode switched off keeps its table / geometry)
+    SweepMode mode = SweepMode::Flat, run_mode = SweepMode::Flat, ran_mode = SweepMode::Flat;
     // linear source (rt_solver_set_linear_source)
     std::vector<double> h_wvol;              // 2 α δ per azimuthal index (the volumes' weights)
     DevBuf<double> cen, cmat, cinv, ends;    // geometry: [n_cells][2], [n_cells][3], [n_cells][4] (see k_solver_ls_cmat), [n][4]
     DevBuf<double> mom, gr;                  // flux moments φ⃗ and q⃗/Σt_g [n_cells][G][2]
-    bool ls = false, ran_ls = false, has_geom = false;
+    bool has_geom = false;
     // the geometry in stages (rt_solver_ls_geometry): the stage that comes next, 0 outside; the accumulator [n_cells][3] lives
     // from stage 0 to stage 2
     int32_t ls_stage = 0;
@@ -553,14 +557,14 @@ struct rt_solver {
     // from the switch-on to the switch-off (or rt_solver_destroy)
     bool repro = false;
     DevBuf<double> delta;
-    // single-precision sweep (rt_solver_set_precision): lent to the handle as rt_tracks::sw_f32 for the solver's runs
+    // single-precision sweep (rt_solver_set_precision): lent to the handle (SweepLoan::f32) for the solver's runs
     bool single = false;
     // ... and V_e as rt_solver_create summed it (FP64 atomics), kept while `vol` holds the sums in the index's order instead
     DevBuf<double> vol_atomic;
     std::vector<double> k_hist;
     // the run in progress (rt_solver_begin ... rt_solver_end): `open` while this solver holds the handle's sweep state
-    // (rt_tracks::sw_borrower points back here), `swept` between rt_solver_step_sweep and rt_solver_step_fold
-    bool open = false, swept = false, run_eigen = false, run_p1 = false, run_ls = false, run_bnd = false;
+    // (rt_tracks::sw_loan.borrower points back here), `swept` between rt_solver_step_sweep and rt_solver_step_fold
+    bool open = false, swept = false, run_eigen = false, run_bnd = false;
     int32_t it = 0;
     double last_k = 1.0, last_res = INFINITY, last_dk = INFINITY;
     double *h_scal = nullptr;  // pinned, kSolveScalars
@@ -573,11 +577,8 @@ namespace rtx {
 // Called with the tracks alive (rt_tracks_destroy calls it before it frees them).
 void solver_release(rt_solver *S) {
     if (!S || !S->open) return;
-    rt_tracks *t = S->t;
-    t->sw_has_w = false; t->sw_p1 = false; t->sw_ls = false; t->sw_ls_cen = t->sw_ls_ends = nullptr;
-    t->sw_repro = false; t->sw_repro_delta = nullptr; t->sw_repro_cap = 0;
-    t->sw_f32 = false;
-    if (t->sw_borrower == S) t->sw_borrower = nullptr;
+    S->t->sw_loan = SweepLoan{};  // (an open run is the handle's borrower: solver_begin_impl ends every other one)
+    S->t->sw_has_w = false;
     S->open = false; S->swept = false;
 }
 
@@ -783,7 +784,7 @@ int solver_repro_reserve(rt_solver *S, const char *who, int min_nv = 1) {
     if (int rc = sweep_repro_prepare(t, &slots)) return rc;
     const int C = S->G * S->P;
     // NT · width (rt_sweep.hip: 2 components with three tallies, else 4); min_nv: the geometry's sums take three values per record
-    const int nv = std::max(min_nv, (S->p1 || S->ls) ? 3 * std::min(C, 2) : std::min(C, 4));
+    const int nv = std::max(min_nv, S->mode != SweepMode::Flat ? 3 * std::min(C, 2) : std::min(C, 4));
     const size_t need = (size_t)2 * (size_t)slots * (size_t)nv;
     if (need <= S->delta.cap) return RT_SUCCESS;
     DevBuf<double> d;
@@ -812,7 +813,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
         set_error("%s: an incoming boundary flux is set (rt_solver_set_boundary), and an eigenvalue run has no fixed source", who);
         return RT_ERR_INVALID;
     }
-    if (t->sw_borrower) solver_release(t->sw_borrower);  // (another solver's unfinished run on this handle ends here)
+    if (t->sw_loan.borrower) solver_release(t->sw_loan.borrower);  // (another solver's unfinished run on this handle ends here)
     const bool eigen = mode == RT_SOLVE_EIGENVALUE;
     rt_mesh *m = t->mesh;
     if (int rc = finish_call(t)) return rc;
@@ -829,34 +830,32 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
     RT_HIP(t->sw_w.reserve(std::max<int64_t>(1, n)));
     if (n > 0) RT_HIP(hipMemcpyAsync(t->sw_w.p, S->w_track.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
     t->sw_groups = C; t->sw_has_xs = true; t->sw_has_w = true; t->sw_done = false;
-    t->sw_borrower = S; S->open = true; S->swept = false;  // (solver_release hands the state back: the handle's own sweeps weigh by δs again, isotropically)
+    // the run is open from here on (whatever ends it goes through solver_release); the loan becomes the handle's once nothing refuses
+    SweepLoan loan;
+    loan.borrower = S; loan.mode = S->mode;
+    S->open = true; S->swept = false;
     AbortRun abort_run{S};
-    S->ran = false; S->ran_p1 = false; S->ran_ls = false;
-    const bool p1 = S->p1, ls = S->ls;
-    if (p1 && ls) { set_error("%s: linear source together with first-moment scattering is not supported", who); return RT_ERR_INVALID; }
-    if (ls && !S->has_geom) { set_error("%s: the linear source has no geometry", who); return RT_ERR_INVALID; }
-    if (p1) {  // J⁰ = 0; the sweep's first-moment arrays
+    S->ran = false; S->ran_mode = SweepMode::Flat;
+    const SweepMode smode = S->mode;
+    if (smode == SweepMode::Linear && !S->has_geom) { set_error("%s: the linear source has no geometry", who); return RT_ERR_INVALID; }
+    if (smode != SweepMode::Flat) {  // J⁰ = 0 (P1), φ⃗⁰ = 0 (Linear); the sweep's ratios xs1 and its moment tallies, the same buffers for both
+        const bool p1 = smode == SweepMode::P1;
+        DevBuf<double> &mom0 = p1 ? S->J : S->mom, &ratio = p1 ? S->q1r : S->gr;
         const size_t nj = 2 * std::max<size_t>(1, (size_t)nc * G);
-        RT_HIP(S->J.reserve(nj)); RT_HIP(S->q1r.reserve(nj));
+        RT_HIP(mom0.reserve(nj)); RT_HIP(ratio.reserve(nj));
         RT_HIP(t->sw_xs1.reserve(2 * nxs)); RT_HIP(t->sw_cur.reserve(2 * nxs));
-        RT_HIP(hipMemsetAsync(S->J.p, 0, nj * sizeof(double), s));
-        t->sw_p1 = true;
-    }
-    if (ls) {  // φ⃗⁰ = 0; the sweep's gradient ratios and moment tallies (the buffers of the anisotropic mode)
-        const size_t nj = 2 * std::max<size_t>(1, (size_t)nc * G);
-        RT_HIP(S->mom.reserve(nj)); RT_HIP(S->gr.reserve(nj));
-        RT_HIP(t->sw_xs1.reserve(2 * nxs)); RT_HIP(t->sw_cur.reserve(2 * nxs));
-        RT_HIP(hipMemsetAsync(S->mom.p, 0, nj * sizeof(double), s));
-        t->sw_ls = true; t->sw_ls_cen = S->cen.p; t->sw_ls_ends = S->ends.p;
+        RT_HIP(hipMemsetAsync(mom0.p, 0, nj * sizeof(double), s));
+        if (!p1) { loan.ls_cen = S->cen.p; loan.ls_ends = S->ends.p; }
     }
     if (S->repro) {  // (the mode or the rows may have changed since the switch-on: the buffer grows here if it has to)
         if (int rc = solver_repro_reserve(S, who)) return rc;
-        t->sw_repro = true; t->sw_repro_delta = S->delta.p; t->sw_repro_cap = S->delta.cap;
+        loan.repro = true; loan.repro_delta = S->delta.p; loan.repro_cap = S->delta.cap;
     }
     if (S->single) {  // (the setters keep the combinations apart; a solver that got here with one is refused like them)
-        if (p1 || ls || S->repro) { set_error("%s: the single-precision sweep (rt_solver_set_precision) together with first-moment scattering, the linear source or the reproducible tallies is not supported", who); return RT_ERR_INVALID; }
-        t->sw_f32 = true;
+        if (smode != SweepMode::Flat || S->repro) { set_error("%s: the single-precision sweep (rt_solver_set_precision) together with first-moment scattering, the linear source or the reproducible tallies is not supported", who); return RT_ERR_INVALID; }
+        loan.f32 = true;
     }
+    t->sw_loan = loan;
     S->bnd_tallied = false;
     if (bnd) RT_HIP(hipMemsetAsync(S->bnd_J.p, 0, (size_t)2 * S->bnd_S * G * sizeof(double), s));
     if (bnd && S->bnd_inc && n > 0)  // the first sweep already sees the incoming flux
@@ -864,7 +863,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
                            (const int8_t *)S->bnd_side_entry.p, (const double *)S->bnd_beta.p, (const double *)S->bnd_incv.p,
                            (const double *)nullptr, t->sw_psi_in.p, 2 * n, G, P, n);
     S->k_hist.clear();
-    S->run_eigen = eigen; S->run_p1 = p1; S->run_ls = ls; S->run_bnd = bnd;
+    S->run_eigen = eigen; S->run_mode = smode; S->run_bnd = bnd;
     S->it = 0; S->last_k = 1.0; S->last_res = INFINITY; S->last_dk = INFINITY;
     // φ⁰ = 1, the components' Σt / sin θ, F⁰
     RT_HIP(hipMemsetAsync(S->prod.p, 0, (size_t)std::max(1, nc) * sizeof(double), s));
@@ -886,10 +885,10 @@ int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
     hipLaunchKernelGGL(rt::k_solver_source, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
                        (const double *)S->tab.p, d.lds_len, (const double *)S->phi.p, (const double *)S->prod.p, ext, (const double *)S->scal.p, eig,
                        nc, G, P, t->sw_xs.p);
-    if (S->run_p1)
+    if (S->run_mode == SweepMode::P1)
         hipLaunchKernelGGL(rt::k_solver_source_p1, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds1_len * sizeof(double), s, (const int32_t *)S->mat.p,
                            (const double *)S->tab1.p, d.lds1_len, (const double *)S->J.p, (const double *)S->pol.p, nc, G, P, S->q1r.p, t->sw_xs1.p);
-    if (S->run_ls)
+    if (S->run_mode == SweepMode::Linear)
         hipLaunchKernelGGL(rt::k_solver_source_ls, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
                            (const double *)S->tab.p, d.lds_len, (const double *)S->mom.p, (const double *)S->cinv.p, (const double *)S->pol.p,
                            (const double *)S->scal.p, eig, nc, G, P, S->gr.p, t->sw_xs1.p);
@@ -924,10 +923,10 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
     hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
                        (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P,
                        S->partial.p);
-    if (S->run_p1)
+    if (S->run_mode == SweepMode::P1)
         hipLaunchKernelGGL(rt::k_solver_fold_p1, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab1.p,
                            (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->q1r.p, nc, G, P, S->J.p);
-    if (S->run_ls)
+    if (S->run_mode == SweepMode::Linear)
         hipLaunchKernelGGL(rt::k_solver_fold_ls, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
                            (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->gr.p,
                            (const double *)S->cmat.p, (const double *)S->cinv.p, nc, G, P, S->mom.p);
@@ -950,20 +949,12 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
     return RT_SUCCESS;
 }
 
-int solver_step_sweep_impl(rt_solver *S, const char *who) {
-    if (int rc = solver_step_enter(S, false, who)) return rc;
+// one step call: the sweep (fold = false; res unused) or the fold of an open run
+int solver_step_impl(rt_solver *S, bool fold, rt_solver_result *res, const char *who) {
+    if (int rc = solver_step_enter(S, fold, who)) return rc;
     AbortRun abort_run{S};
     RT_HIP(hipSetDevice(S->t->mesh->device));
-    if (int rc = solver_queue_sweep(S, SolverDims(S))) return rc;
-    abort_run.ok = true;
-    return RT_SUCCESS;
-}
-
-int solver_step_fold_impl(rt_solver *S, rt_solver_result *res, const char *who) {
-    if (int rc = solver_step_enter(S, true, who)) return rc;
-    AbortRun abort_run{S};
-    RT_HIP(hipSetDevice(S->t->mesh->device));
-    if (int rc = solver_queue_fold(S, SolverDims(S), res, who)) return rc;
+    if (int rc = fold ? solver_queue_fold(S, SolverDims(S), res, who) : solver_queue_sweep(S, SolverDims(S))) return rc;
     abort_run.ok = true;
     return RT_SUCCESS;
 }
@@ -980,10 +971,9 @@ int solver_end_impl(rt_solver *S, rt_solver_result *res, const char *who) {
     RT_HIP(hipEventRecord(S->ev[1], s));
     if (eigen && d.nc > 0)
         hipLaunchKernelGGL(rt::k_solver_scale, dim3(d.sblocks), dim3(256), 0, s, S->phi.p, d.ncg, (const double *)S->scal.p);
-    if (eigen && d.nc > 0 && S->run_p1)
-        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * d.ncg + 255) / 256)), dim3(256), 0, s, S->J.p, 2 * d.ncg, (const double *)S->scal.p);
-    if (eigen && d.nc > 0 && S->run_ls)
-        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * d.ncg + 255) / 256)), dim3(256), 0, s, S->mom.p, 2 * d.ncg, (const double *)S->scal.p);
+    if (eigen && d.nc > 0 && S->run_mode != SweepMode::Flat)  // (the moments of the mode, scaled with φ)
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * d.ncg + 255) / 256)), dim3(256), 0, s,
+                           S->run_mode == SweepMode::P1 ? S->J.p : S->mom.p, 2 * d.ncg, (const double *)S->scal.p);
     if (eigen && S->run_bnd && S->bnd_tallied)  // (the currents of the last sweep, scaled with φ)
         hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * S->bnd_S * d.G + 255) / 256)), dim3(256), 0, s, S->bnd_J.p,
                            (int64_t)2 * S->bnd_S * d.G, (const double *)S->scal.p);
@@ -992,7 +982,7 @@ int solver_end_impl(rt_solver *S, rt_solver_result *res, const char *who) {
     float f = 0.0f;
     RT_HIP(hipEventElapsedTime(&f, S->ev[0], S->ev[1]));
     t->in_flight = false;
-    S->ran = true; S->ran_p1 = S->run_p1; S->ran_ls = S->run_ls;
+    S->ran = true; S->ran_mode = S->run_mode;
     if (res) {
         res->k_eff = eigen ? S->last_k : 1.0; res->residual = S->last_res; res->dk = S->last_dk; res->device_ms = f;
         res->iterations = S->it; res->converged = 0;
@@ -1035,16 +1025,13 @@ extern "C" {
 rt_solver *rt_solver_create(rt_tracks *tracks, int32_t n_groups, int32_t n_materials, const int32_t *cell_material, const double *sigma_t,
                             const double *sigma_s, const double *nu_sigma_f, const double *chi, int32_t n_polar, const double *sin_polar,
                             const double *polar_weight, const double *azim_weight) {
-    try {
+    return guarded("rt_solver_create", [&]() -> rt_solver * {
         rt_solver *s = nullptr;
         if (solver_create_impl(tracks, n_groups, n_materials, cell_material, sigma_t, sigma_s, nu_sigma_f, chi, n_polar, sin_polar,
                                polar_weight, azim_weight, &s))
             return nullptr;
         return s;
-    } catch (const std::exception &e) {
-        set_error("rt_solver_create: %s", e.what());
-        return nullptr;
-    }
+    });
 }
 
 int32_t rt_solver_set_source(rt_solver *solver, const double *source) {
@@ -1054,23 +1041,20 @@ int32_t rt_solver_set_source(rt_solver *solver, const double *source) {
     const size_t ncg = (size_t)solver->n_cells * solver->G;
     size_t bad = 0;
     if (!finite_nonneg(source, ncg, &bad)) { set_error("rt_solver_set_source: source[%zu] = %g (must be finite and >= 0)", bad, source[bad]); return RT_ERR_INVALID; }
-    try {
+    return guarded("rt_solver_set_source", [&]() -> int32_t {
         RT_HIP(hipSetDevice(solver->t->mesh->device));
         if (int rc = upload(solver->ext, source, ncg, solver->t->mesh->stream)) return rc;
         RT_HIP(hipStreamSynchronize(solver->t->mesh->stream));
-    } catch (const std::exception &e) {
-        set_error("rt_solver_set_source: %s", e.what());
-        return RT_ERR_INVALID;
-    }
-    solver->has_ext = true;
-    return RT_SUCCESS;
+        solver->has_ext = true;
+        return RT_SUCCESS;
+    });
 }
 
 static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) {
     if (!S) { set_error("rt_solver_set_scatter_p1: null solver"); return RT_ERR_INVALID; }
     if (S->open) { set_error("rt_solver_set_scatter_p1: a run is open (rt_solver_begin without rt_solver_end): the tables cannot change under it"); return RT_ERR_INVALID; }
-    if (!sigma_s1) { S->p1 = false; return RT_SUCCESS; }
-    if (S->ls) { set_error("rt_solver_set_scatter_p1: the linear source is on, and the two together are not supported"); return RT_ERR_INVALID; }
+    if (!sigma_s1) { if (S->mode == SweepMode::P1) S->mode = SweepMode::Flat; return RT_SUCCESS; }
+    if (S->mode == SweepMode::Linear) { set_error("rt_solver_set_scatter_p1: the linear source is on, and the two together are not supported"); return RT_ERR_INVALID; }
     if (S->single) { set_error("rt_solver_set_scatter_p1: the single-precision sweep is set (rt_solver_set_precision), and first-moment scattering together with it is not supported"); return RT_ERR_INVALID; }
     const int32_t G = S->G, M = S->M;
     const size_t n1 = (size_t)M * G * G;
@@ -1086,17 +1070,12 @@ static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) 
     if (int rc = upload(S->tab1, tab.data(), tab.size(), S->t->mesh->stream)) return rc;
     RT_HIP(hipStreamSynchronize(S->t->mesh->stream));
     S->h_s1.swap(keep);
-    S->p1 = true;
+    S->mode = SweepMode::P1;
     return RT_SUCCESS;
 }
 
 int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1) {
-    try {
-        return solver_set_scatter_p1_impl(solver, sigma_s1);
-    } catch (const std::exception &e) {
-        set_error("rt_solver_set_scatter_p1: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_set_scatter_p1", [&] { return solver_set_scatter_p1_impl(solver, sigma_s1); });
 }
 
 // Adjoint mode: the device tables of the transposed problem (solver_table, solver_table_p1), or the forward ones again.  The
@@ -1110,12 +1089,13 @@ static int32_t solver_set_adjoint_impl(rt_solver *S, int32_t on) {
     if (adj == S->adjoint) return RT_SUCCESS;
     const std::vector<double> tab = solver_table(S, adj);
     std::vector<double> tab1;
-    if (S->p1) tab1 = solver_table_p1(S, S->h_s1.data(), adj);
+    const bool p1 = S->mode == SweepMode::P1;
+    if (p1) tab1 = solver_table_p1(S, S->h_s1.data(), adj);
     if (int rc = finish_call(S->t)) return rc;
     RT_HIP(hipSetDevice(S->t->mesh->device));
     hipStream_t s = S->t->mesh->stream;
     if (int rc = upload(S->tab, tab.data(), tab.size(), s)) return rc;
-    if (S->p1)
+    if (p1)
         if (int rc = upload(S->tab1, tab1.data(), tab1.size(), s)) return rc;
     RT_HIP(hipStreamSynchronize(s));  // (the host vectors die here)
     S->adjoint = adj;
@@ -1123,12 +1103,7 @@ static int32_t solver_set_adjoint_impl(rt_solver *S, int32_t on) {
 }
 
 int32_t rt_solver_set_adjoint(rt_solver *solver, int32_t on) {
-    try {
-        return solver_set_adjoint_impl(solver, on);
-    } catch (const std::exception &e) {
-        set_error("rt_solver_set_adjoint: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_set_adjoint", [&] { return solver_set_adjoint_impl(solver, on); });
 }
 
 static int32_t solver_bilinear_impl(rt_solver *Sa, rt_solver *Sf, int32_t n_forms, const double *A, double *out, double *out_cell) {
@@ -1175,12 +1150,7 @@ static int32_t solver_bilinear_impl(rt_solver *Sa, rt_solver *Sf, int32_t n_form
 }
 
 int32_t rt_solver_bilinear(rt_solver *adjoint, rt_solver *forward, int32_t n_forms, const double *A, double *out, double *out_cell) {
-    try {
-        return solver_bilinear_impl(adjoint, forward, n_forms, A, out, out_cell);
-    } catch (const std::exception &e) {
-        set_error("rt_solver_bilinear: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_bilinear", [&] { return solver_bilinear_impl(adjoint, forward, n_forms, A, out, out_cell); });
 }
 
 // The boundary of the following runs: the gather map of the sided ends from the handle's host copy of its links, in the order
@@ -1260,12 +1230,7 @@ static int32_t solver_set_boundary_impl(rt_solver *S, int32_t n_sides, const int
 }
 
 int32_t rt_solver_set_boundary(rt_solver *solver, int32_t n_sides, const int32_t *end_side, const double *albedo, const double *incoming) {
-    try {
-        return solver_set_boundary_impl(solver, n_sides, end_side, albedo, incoming);
-    } catch (const std::exception &e) {
-        set_error("rt_solver_set_boundary: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_set_boundary", [&] { return solver_set_boundary_impl(solver, n_sides, end_side, albedo, incoming); });
 }
 
 int32_t rt_solver_fetch_boundary(rt_solver *solver, double *j_out, double *j_in) {
@@ -1276,18 +1241,15 @@ int32_t rt_solver_fetch_boundary(rt_solver *solver, double *j_out, double *j_in)
     }
     if (solver->open)
         if (int rc = solver_check_epoch(solver, "rt_solver_fetch_boundary")) return rc;
-    try {
+    return guarded("rt_solver_fetch_boundary", [&]() -> int32_t {
         RT_HIP(hipSetDevice(solver->device));
         hipStream_t s = solver->t->mesh->stream;
         const size_t sg = (size_t)solver->bnd_S * solver->G;
         if (j_out) RT_HIP(hipMemcpyAsync(j_out, solver->bnd_J.p, sg * sizeof(double), hipMemcpyDeviceToHost, s));
         if (j_in) RT_HIP(hipMemcpyAsync(j_in, solver->bnd_J.p + sg, sg * sizeof(double), hipMemcpyDeviceToHost, s));
         RT_HIP(hipStreamSynchronize(s));
-    } catch (const std::exception &e) {
-        set_error("rt_solver_fetch_boundary: %s", e.what());
-        return RT_ERR_INVALID;
-    }
-    return RT_SUCCESS;
+        return RT_SUCCESS;
+    });
 }
 
 int32_t rt_solver_boundary_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
@@ -1304,7 +1266,7 @@ int32_t rt_solver_boundary_pointers(rt_solver *solver, void **ptrs_dev, int64_t 
 
 int32_t rt_solver_fetch_current(rt_solver *solver, double *J) {
     if (!solver || !J) { set_error("rt_solver_fetch_current: null argument"); return RT_ERR_INVALID; }
-    if (!solver->ran || !solver->ran_p1) {
+    if (!solver->ran || solver->ran_mode != SweepMode::P1) {
         set_error("rt_solver_fetch_current: no completed rt_solver_run with first-moment scattering (rt_solver_set_scatter_p1)");
         return RT_ERR_INVALID;
     }
@@ -1333,7 +1295,7 @@ static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged
         set_error("%s: the tracks were segmentized again after rt_solver_create: create a new solver", who);
         return RT_ERR_INVALID;
     }
-    if (S->p1) { set_error("%s: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported", who); return RT_ERR_INVALID; }
+    if (S->mode == SweepMode::P1) { set_error("%s: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported", who); return RT_ERR_INVALID; }
     if (staged && S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the geometry cannot change under it", who); return RT_ERR_INVALID; }
     if (stage != 0 && stage != S->ls_stage) {
         set_error("%s: stage %d out of order (%s)", who, stage,
@@ -1360,7 +1322,8 @@ static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged
         return sweep_repro_cell_sums(t, kind, (const double *)S->ls_wvol.p, (const double *)S->cen.p, S->delta.p, S->delta.cap, S->ls_acc.p);
     };
     if (stage == 0) {
-        S->ls = false; S->has_geom = false; S->ran_ls = false; S->ls_stage = 0;  // (afresh, whatever there was)
+        S->mode = SweepMode::Flat; S->has_geom = false; S->ls_stage = 0;  // (afresh, whatever there was)
+        if (S->ran_mode == SweepMode::Linear) S->ran_mode = SweepMode::Flat;
         if (int rc = ensure_compacted(t)) return rc;
         if (S->repro)
             if (int rc = solver_repro_reserve(S, who, 3)) return rc;
@@ -1388,7 +1351,7 @@ static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged
         RT_HIP(hipGetLastError());
         solver_ls_geometry_drop(S);
         S->n_degenerate = h;
-        S->has_geom = true; S->ls = true;
+        S->has_geom = true; S->mode = SweepMode::Linear;
         drop.ok = true;
         return RT_SUCCESS;
     }
@@ -1403,33 +1366,23 @@ int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
     const char *who = "rt_solver_set_linear_source";
     if (!solver) { set_error("rt_solver_set_linear_source: null solver"); return RT_ERR_INVALID; }
     if (solver->open) { set_error("rt_solver_set_linear_source: a run is open (rt_solver_begin without rt_solver_end): the source's shape cannot change under it"); return RT_ERR_INVALID; }
-    if (!on) { solver->ls = false; return RT_SUCCESS; }
-    if (solver->p1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
+    if (!on) { if (solver->mode == SweepMode::Linear) solver->mode = SweepMode::Flat; return RT_SUCCESS; }
+    if (solver->mode == SweepMode::P1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
     if (solver->single) { set_error("rt_solver_set_linear_source: the single-precision sweep is set (rt_solver_set_precision), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
-    try {
+    return guarded(who, [&]() -> int32_t {
         if (!solver->has_geom)
             for (int32_t stage = 0; stage < 3; ++stage)
                 if (int32_t rc = solver_ls_geometry_stage(solver, stage, false, who)) return rc;
-    } catch (const std::exception &e) {
-        solver_ls_geometry_drop(solver);
-        set_error("rt_solver_set_linear_source: %s", e.what());
-        return RT_ERR_INVALID;
-    }
-    solver->ls = true;
-    return RT_SUCCESS;
+        solver->mode = SweepMode::Linear;
+        return RT_SUCCESS;
+    }, [&] { solver_ls_geometry_drop(solver); });
 }
 
 int32_t rt_solver_ls_geometry(rt_solver *solver, int32_t stage) {
     const char *who = "rt_solver_ls_geometry";
     if (!solver) { set_error("rt_solver_ls_geometry: null solver"); return RT_ERR_INVALID; }
     if (stage < 0 || stage > 2) { set_error("rt_solver_ls_geometry: bad arguments (stage %d)", stage); return RT_ERR_INVALID; }
-    try {
-        return solver_ls_geometry_stage(solver, stage, true, who);
-    } catch (const std::exception &e) {
-        solver_ls_geometry_drop(solver);
-        set_error("rt_solver_ls_geometry: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_ls_geometry", [&] { return solver_ls_geometry_stage(solver, stage, true, who); }, [&] { solver_ls_geometry_drop(solver); });
 }
 
 // Reproducible tallies on or off.  On: the rows' cell index and the delta buffer (solver_repro_reserve), then the solver's own sums
@@ -1449,7 +1402,7 @@ static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
     RT_HIP(hipSetDevice(t->mesh->device));
     hipStream_t s = t->mesh->stream;
     const size_t ncs = (size_t)std::max<int32_t>(1, S->n_cells);
-    const bool was_ls = S->ls;
+    const bool was_ls = S->mode == SweepMode::Linear;
     auto geometry = [&]() -> int32_t {  // (anew, in the order the option now asks for; a geometry of a linear source that is off is dropped)
         if (!S->has_geom) return RT_SUCCESS;
         if (!was_ls) { S->has_geom = false; return RT_SUCCESS; }
@@ -1507,17 +1460,11 @@ static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
 }
 
 int32_t rt_solver_set_reproducible(rt_solver *solver, int32_t on) {
-    try {
-        return solver_set_reproducible_impl(solver, on);
-    } catch (const std::exception &e) {
-        if (solver) solver_ls_geometry_drop(solver);
-        set_error("rt_solver_set_reproducible: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_set_reproducible", [&] { return solver_set_reproducible_impl(solver, on); }, [&] { if (solver) solver_ls_geometry_drop(solver); });
 }
 
 // The precision of the sweep for the following runs.  Nothing is allocated or computed: rt_solver_begin lends the choice to the
-// handle (rt_tracks::sw_f32), and rt_sweep launches k_sweep_f32 instead of k_sweep.
+// handle (SweepLoan::f32), and rt_sweep launches k_sweep_f32 instead of k_sweep.
 int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision) {
     const char *who = "rt_solver_set_precision";
     rt_solver *S = solver;
@@ -1526,8 +1473,8 @@ int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision) {
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the sweep cannot change under it", who); return RT_ERR_INVALID; }
     if (precision != RT_PRECISION_DOUBLE && precision != RT_PRECISION_SINGLE) { set_error("%s: precision %d (RT_PRECISION_DOUBLE = 0 or RT_PRECISION_SINGLE = 1)", who, precision); return RT_ERR_INVALID; }
     if (precision == RT_PRECISION_SINGLE) {
-        const char *other = S->p1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
-                                  : (S->ls ? "the linear source is on (rt_solver_set_linear_source)"
+        const char *other = S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
+                                  : (S->mode == SweepMode::Linear ? "the linear source is on (rt_solver_set_linear_source)"
                                            : (S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)" : nullptr));
         if (other) { set_error("%s: %s, and the single-precision sweep together with it is not supported", who, other); return RT_ERR_INVALID; }
     }
@@ -1559,11 +1506,11 @@ int32_t rt_solver_fetch_geometry(rt_solver *solver, double *centroid, double *cm
 
 int32_t rt_solver_fetch_moments(rt_solver *solver, double *phi_xy, double *grad) {
     if (!solver) { set_error("rt_solver_fetch_moments: null solver"); return RT_ERR_INVALID; }
-    if (!solver->ran || !solver->ran_ls) {
+    if (!solver->ran || solver->ran_mode != SweepMode::Linear) {
         set_error("rt_solver_fetch_moments: no completed rt_solver_run with the linear source (rt_solver_set_linear_source)");
         return RT_ERR_INVALID;
     }
-    try {
+    return guarded("rt_solver_fetch_moments", [&]() -> int32_t {
         RT_HIP(hipSetDevice(solver->t->mesh->device));
         hipStream_t s = solver->t->mesh->stream;
         const size_t nc = (size_t)solver->n_cells, G = (size_t)solver->G, nj = nc * G * 2;
@@ -1581,68 +1528,40 @@ int32_t rt_solver_fetch_moments(rt_solver *solver, double *phi_xy, double *grad)
                     grad[(e * G + g) * 2] = ci[4 * e] * mx + ci[4 * e + 1] * my;
                     grad[(e * G + g) * 2 + 1] = ci[4 * e + 1] * mx + ci[4 * e + 2] * my;
                 }
-    } catch (const std::exception &e) {
-        set_error("rt_solver_fetch_moments: %s", e.what());
-        return RT_ERR_INVALID;
-    }
-    return RT_SUCCESS;
+        return RT_SUCCESS;
+    });
 }
 
 int32_t rt_solver_run(rt_solver *solver, int32_t mode, int32_t max_iter, double tol_k, double tol_flux, rt_solver_result *out) {
-    try {
-        return solver_run_impl(solver, mode, max_iter, tol_k, tol_flux, out);
-    } catch (const std::exception &e) {
-        set_error("rt_solver_run: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_run", [&] { return solver_run_impl(solver, mode, max_iter, tol_k, tol_flux, out); });
 }
 
 int32_t rt_solver_begin(rt_solver *solver, int32_t mode) {
     if (!solver) { set_error("rt_solver_begin: null solver"); return RT_ERR_INVALID; }
     if (!solver_mode_ok(mode)) { set_error("rt_solver_begin: bad arguments (mode %d)", mode); return RT_ERR_INVALID; }
-    try {
-        return solver_begin_impl(solver, mode, "rt_solver_begin");
-    } catch (const std::exception &e) {
-        set_error("rt_solver_begin: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_begin", [&] { return solver_begin_impl(solver, mode, "rt_solver_begin"); });
 }
 
 int32_t rt_solver_step_sweep(rt_solver *solver) {
     if (!solver) { set_error("rt_solver_step_sweep: null solver"); return RT_ERR_INVALID; }
-    try {
-        return solver_step_sweep_impl(solver, "rt_solver_step_sweep");
-    } catch (const std::exception &e) {
-        set_error("rt_solver_step_sweep: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_step_sweep", [&] { return solver_step_impl(solver, false, nullptr, "rt_solver_step_sweep"); });
 }
 
 int32_t rt_solver_step_fold(rt_solver *solver, rt_solver_result *out) {
     if (!solver) { set_error("rt_solver_step_fold: null solver"); return RT_ERR_INVALID; }
-    try {
-        return solver_step_fold_impl(solver, out, "rt_solver_step_fold");
-    } catch (const std::exception &e) {
-        set_error("rt_solver_step_fold: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_step_fold", [&] { return solver_step_impl(solver, true, out, "rt_solver_step_fold"); });
 }
 
 int32_t rt_solver_end(rt_solver *solver, rt_solver_result *out) {
     if (!solver) { set_error("rt_solver_end: null solver"); return RT_ERR_INVALID; }
-    try {
-        return solver_end_impl(solver, out, "rt_solver_end");
-    } catch (const std::exception &e) {
-        set_error("rt_solver_end: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_solver_end", [&] { return solver_end_impl(solver, out, "rt_solver_end"); });
 }
 
 int32_t rt_solver_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
     if (!solver) { set_error("rt_solver_pointers: null solver"); return RT_ERR_INVALID; }
     // (no wait here: addresses and counts only)
     const int64_t nc = solver->n_cells, C = (int64_t)solver->G * solver->P;
-    const bool open = solver->open, mom = open && (solver->run_p1 || solver->run_ls);
+    const bool open = solver->open, mom = open && solver->run_mode != SweepMode::Flat;
     void *p[4] = {solver->vol.p, open ? solver->t->sw_phi.p : nullptr, mom ? solver->t->sw_cur.p : nullptr, solver->phi.p};
     const int64_t l[4] = {nc, open ? nc * C : 0, mom ? 2 * nc * C : 0, nc * solver->G};
     for (int i = 0; i < 4; ++i) {

@@ -1,4 +1,6 @@
 // rt_sweep.hip — rt_sweep: the transport sweep over the cyclic tracks, kernels, host code and entry points.
+// What a call decides — rows, pass width and shape, refusals — is plan_sweep (rt_sweep_plan.hpp, a pure function checked on the host);
+// sweep_impl fills its facts from the handle and an rt_solver's loan (rt_tracks::sw_loan), makes the rows it names and launches.
 #include "rt_internal.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>  // the cell index of the reproducible tallies: one stable sort per segmentation
@@ -142,7 +144,6 @@ __global__ __launch_bounds__(256) void k_rows_fill(const int32_t *__restrict__ c
     }
 }
 
-constexpr int kSweepGpP1 = 2;  // components per pass of the anisotropic sweep, at most
 
 // ---- reproducible tallies (rt_solver_set_reproducible): the cell index and the reduction behind every pass ---------------------------
 // The index lists, CSR by cell, the row slots of the records that lie in the cell, in ascending (track uid, record index): the order
@@ -314,12 +315,12 @@ int ensure_rows_from_compact(rt_tracks *t) {
     return RT_SUCCESS;
 }
 
-// which rows a sweep with input 0 (an rt_solver's) reads: 1 the staging rows, 2 rows made from the compact records, 3 those records
-// where they lie ("sweep_rows" 0) — sweep_impl's own choice, restated for the reproducible tallies
-static int sweep_rows_variant(const rt_tracks *t) {
-    const bool staged_ok = t->cplan.staged && !t->cplan.split && t->cplan.n_whole_waves == (t->n + 63) / 64;
-    return staged_ok ? 1 : (t->mesh->sweep_rows ? 2 : 3);
-}
+// the last rt_segmentize left whole-track staging rows (single-pass calls over whole tracks do)
+static bool sweep_staged_ok(const rt_tracks *t) { return t->cplan.staged && !t->cplan.split && t->cplan.n_whole_waves == (t->n + 63) / 64; }
+
+// which rows a sweep with input 0 (an rt_solver's) reads, as the cell index's kind: 1 the staging rows, 2 rows made from the compact
+// records, 3 those records where they lie ("sweep_rows" 0) — the plan's choice, before a sweep has run
+static int sweep_rows_variant(const rt_tracks *t) { return sweep_staged_ok(t) ? 1 : (t->mesh->sweep_rows ? 2 : 3); }
 
 int sweep_repro_prepare(rt_tracks *t, int64_t *slots_out) {
     rt_mesh *m = t->mesh;
@@ -395,11 +396,8 @@ int sweep_repro_cell_sums(rt_tracks *t, int kind, const double *w_azim, const do
 }
 }  // namespace rtx
 
-
-
 using namespace rtx;
-
-extern "C" {
+using namespace rtsweep;
 
 // ---- rt_sweep -----------------------------------------------------------------------------------------------------
 static int32_t sweep_set_links_impl(rt_tracks *t, const int64_t *next_fwd, const int64_t *next_bwd, const int8_t *dir_fwd,
@@ -430,6 +428,50 @@ static int32_t sweep_set_links_impl(rt_tracks *t, const int64_t *next_fwd, const
     RT_HIP(hipStreamSynchronize(t->mesh->stream));
     t->sw_h_entry.swap(entry); t->sw_shard = shard; ++t->sw_links_epoch;
     t->sw_links = true;
+    return RT_SUCCESS;
+}
+
+// The kernel of a pass: a compile-time table over what the plan decided (the names and template arguments the code object lists).
+template <bool STAGED, int GP, bool LDS, bool P1, bool LS>
+static const void *sweep_kernel(bool repro, bool ellrows) {
+    if constexpr (STAGED)
+        if (ellrows) return repro ? (const void *)rt::k_sweep_repro<true, GP, true, P1, LS> : (const void *)rt::k_sweep<true, GP, LDS, true, P1, LS>;
+    return repro ? (const void *)rt::k_sweep_repro<STAGED, GP, false, P1, LS> : (const void *)rt::k_sweep<STAGED, GP, LDS, false, P1, LS>;
+}
+template <bool STAGED, bool LDS>
+static const void *sweep_kernel(SweepMode mode, int take, bool repro, bool ellrows) {
+    static_assert(rtsweep::kSweepGpP1 == 2 && rt::kSweepGpF32 == 4, "the pass widths below");
+    if (mode == SweepMode::Linear) return take == 2 ? sweep_kernel<STAGED, 2, LDS, false, true>(repro, ellrows) : sweep_kernel<STAGED, 1, LDS, false, true>(repro, ellrows);
+    if (mode == SweepMode::P1) return take == 2 ? sweep_kernel<STAGED, 2, LDS, true, false>(repro, ellrows) : sweep_kernel<STAGED, 1, LDS, true, false>(repro, ellrows);
+    if (take == 4) return sweep_kernel<STAGED, 4, LDS, false, false>(repro, ellrows);
+    if (take == 3) return sweep_kernel<STAGED, 3, LDS, false, false>(repro, ellrows);
+    return take == 2 ? sweep_kernel<STAGED, 2, LDS, false, false>(repro, ellrows) : sweep_kernel<STAGED, 1, LDS, false, false>(repro, ellrows);
+}
+static const void *sweep_kernel(bool staged, bool lds, SweepMode mode, int take, bool repro, bool ellrows) {
+    if (staged) return lds ? sweep_kernel<true, true>(mode, take, repro, ellrows) : sweep_kernel<true, false>(mode, take, repro, ellrows);
+    return lds ? sweep_kernel<false, true>(mode, take, repro, ellrows) : sweep_kernel<false, false>(mode, take, repro, ellrows);
+}
+static const void *sweep_reduce_kernel(bool moments, int take) {
+    if (moments) return take == 2 ? (const void *)rt::k_sweep_reduce<2, true> : (const void *)rt::k_sweep_reduce<1, true>;
+    if (take == 4) return (const void *)rt::k_sweep_reduce<4, false>;
+    if (take == 3) return (const void *)rt::k_sweep_reduce<3, false>;
+    return take == 2 ? (const void *)rt::k_sweep_reduce<2, false> : (const void *)rt::k_sweep_reduce<1, false>;
+}
+
+// one FP64 pass of `a.ng` components from a.g0 and, behind it, the reduction of the reproducible tallies
+static int launch_sweep_f64(rt_tracks *t, const rt::DSweep &a, const SweepPlan &plan, const PassShape &shape, hipStream_t s) {
+    const bool moments = plan.f.mode != SweepMode::Flat;
+    const void *k = sweep_kernel(rows_staged(plan.rows), plan.use_lds, plan.f.mode, a.ng, plan.f.repro, rows_read_ell(plan.rows));
+    if (shape.smem > 48 * 1024) RT_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.smem));
+    void *args[] = {(void *)&a};
+    RT_HIP(hipLaunchKernel(k, dim3(shape.blocks), dim3(64 * shape.waves), args, shape.smem, s));
+    if (plan.f.repro && a.n_cells > 0) {  // the pass's tallies, in the index's order (the next pass overwrites the delta buffer)
+        const int32_t *start = t->sw_ridx_start.p, *list = t->sw_ridx_list.p;
+        const double *delta = t->sw_loan.repro_delta;
+        double *phi = t->sw_phi.p, *cur = moments ? t->sw_cur.p : nullptr;
+        void *rargs[] = {&start, &list, &delta, (void *)&a.dslots, (void *)&a.n_cells, (void *)&a.G, (void *)&a.g0, &phi, &cur};
+        RT_HIP(hipLaunchKernel(sweep_reduce_kernel(moments, a.ng), dim3((unsigned)((a.n_cells + 3) / 4)), dim3(256), rargs, 0, s));
+    }
     return RT_SUCCESS;
 }
 
@@ -476,38 +518,20 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     // arrays has to be on the device before that
     const bool async_sweep = m->async_calls && !m->timing;
     if (async_sweep && (track_weight || (psi_in && n > 0))) RT_HIP(hipStreamSynchronize(s));
-    // which records: the march's staging rows (whole-track single-pass calls leave them behind) or the compact CSR arrays
-    const bool staged_ok = t->cplan.staged && !t->cplan.split && t->cplan.n_whole_waves == (n + 63) / 64;
-    if (input == 2 && !staged_ok) { set_error("rt_sweep: the last rt_segmentize left no whole-track staging rows (track pieces or two-pass mode)"); return RT_ERR_INVALID; }
-    bool staged = input == 2 || (input == 0 && staged_ok);
-    // The compact records asked for (or all there is: tracks marched in pieces): swept as ROWS all the same (option "sweep_rows",
-    // on by default) — the staging's, while the handle still has them; else rows made once from the compact records
-    // (ensure_rows_from_compact).  "sweep_rows" 0: the records where they lie (k_sweep<false, ...>; A/B and tests).
-    bool rows_compact = false;
-    if (!staged && m->sweep_rows) {
-        if (staged_ok && m->sweep_rows != 2) staged = true;  // ("sweep_rows" 2, tests / A/B: always from the compact records)
-        else rows_compact = true;
-    }
-    // Single precision (an rt_solver with rt_solver_set_precision lends `sw_f32` for its run; option "sweep_precision" 1 for the bare
-    // sweep): k_sweep_f32 (rt_sweep_f32.hip), flat and isotropic, over (ℓ, cell) rows — rows kind 1 or 2.  A sweep that would read
-    // its records where they lie is refused before anything is queued, with the rows' kind and the option that decides it.
-    const bool f32 = t->sw_f32 || m->sweep_precision == 1;
-    if (f32) {
-        const char *other = t->sw_p1 ? "first-moment scattering (rt_solver_set_scatter_p1)"
-                                     : (t->sw_ls ? "the linear source (rt_solver_set_linear_source)"
-                                                 : (t->sw_repro ? "the reproducible tallies (rt_solver_set_reproducible)" : nullptr));
-        if (other) { set_error("rt_sweep: the single-precision sweep (rt_solver_set_precision, \"sweep_precision\" 1) together with %s is not supported", other); return RT_ERR_INVALID; }
-        const char *why = nullptr;
-        if (!staged && !rows_compact) why = "the compact records where they lie: option \"sweep_rows\" is 0";
-        else if (staged && !rows_compact && !t->cplan.codes && !m->sweep_ell) why = "the staging's 20-B rows in every pass: option \"sweep_ell\" is 0";
-        else if (staged && !rows_compact && !t->cplan.codes && !t->sw_ell_valid)
-            why = "the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
-                  "double-precision sweep first (\"sweep_precision\" 0), or set option \"sweep_rows\" 2 and name the compact records";
-        if (why) { set_error("rt_sweep: the single-precision sweep (\"sweep_precision\" 1) reads (ℓ, cell) rows, and this sweep would read rows of kind 0 — %s", why); return RT_ERR_INVALID; }
-    }
-    if (!staged)
+    // what this sweep reads and how wide its passes are, from the handle's state, the options and an rt_solver's loan for its run
+    const SweepLoan &loan = t->sw_loan;
+    const SweepMode mode = loan.mode;
+    const bool moments = mode != SweepMode::Flat, repro = loan.repro;
+    const SweepFacts facts{.n = n, .n_cells = m->n_cells, .G = G, .input = input, .mode = mode, .repro = repro,
+                           .f32 = loan.f32 || m->sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
+                           .sw_ell_valid = t->sw_ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
+                           .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves};
+    SweepPlan plan = plan_sweep(facts);
+    if (plan.refusal) { set_error("%s", plan.message); return plan.refusal; }
+    // the rows the plan names, made once per segmentation: from the compact records here, the staging's below (inside `ms`, as ever)
+    if (!rows_staged(plan.rows) || plan.rows == SweepRows::FromCompact)
         if (int rc = ensure_compacted(t)) return rc;
-    if (rows_compact)
+    if (plan.rows == SweepRows::FromCompact)
         if (int rc = ensure_rows_from_compact(t)) return rc;
     using rt::as_global;
     rt::DSweep a{};
@@ -520,157 +544,62 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     a.xs = as_global((const double *)t->sw_xs.p);
     a.psi_in = as_global((const double *)t->sw_psi_in.p); a.psi_out = as_global(t->sw_psi_out.p); a.phi = as_global(t->sw_phi.p);
     a.n = n; a.n_waves = (int32_t)((n + 63) / 64); a.n_cells = m->n_cells; a.G = G; a.debug = m->sweep_debug;
-    // the anisotropic mode (an rt_solver with first-moment scattering has filled sw_xs1 for these G components)
-    const bool p1 = t->sw_p1, ls = t->sw_ls;
-    const int nt = (p1 || ls) ? 3 : 1;  // tallies per component
-    if (p1 && ls) { set_error("rt_sweep: linear source together with first-moment scattering"); return RT_ERR_INVALID; }
-    if (ls) {  // the linear-source mode (an rt_solver with rt_solver_set_linear_source has filled sw_xs1 with the gradient ratios)
-        if (!t->sw_xs1.p || !t->sw_cur.p || !t->sw_ls_cen || !t->sw_ls_ends) { set_error("rt_sweep: the linear-source mode has no geometry arrays"); return RT_ERR_INVALID; }
-        a.xs1 = as_global((const double *)t->sw_xs1.p); a.cur = as_global(t->sw_cur.p);
-        a.cs = as_global((const double *)t->cs.p); a.sn = as_global((const double *)t->sn.p);
-        a.cen = as_global(t->sw_ls_cen); a.ends = as_global(t->sw_ls_ends);
-    }
-    if (p1) {
+    a.use_lds = plan.use_lds ? 1 : 0;
+    if (moments) {  // the solver has filled sw_xs1 for these G components: first-moment ratios (P1), gradient ratios (Linear)
+        if (mode == SweepMode::Linear && (!t->sw_xs1.p || !t->sw_cur.p || !loan.ls_cen || !loan.ls_ends)) { set_error("rt_sweep: the linear-source mode has no geometry arrays"); return RT_ERR_INVALID; }
         if (!t->sw_xs1.p || !t->sw_cur.p) { set_error("rt_sweep: the anisotropic mode has no first-moment arrays"); return RT_ERR_INVALID; }
         a.xs1 = as_global((const double *)t->sw_xs1.p); a.cur = as_global(t->sw_cur.p);
         a.cs = as_global((const double *)t->cs.p); a.sn = as_global((const double *)t->sn.p);
+        a.cen = as_global(loan.ls_cen); a.ends = as_global(loan.ls_ends);
     }
-    // groups per pass: as many as an LDS-private copy of their tallies allows (up to 4); none fits: global atomics.  The last pass
-    // takes what is left with the kernel compiled for that many groups (7 groups = 4 + 3: a padded fourth group was an eighth
-    // of the sweep's arithmetic).
-    // Anisotropic: three tallies per component, so a mesh that fits 4 components fits 1; at most kSweepGpP1 per pass (the kernel
-    // carries two more ratios per pipeline stage and two more deltas per component: see DESIGN.md for the registers).
-    const size_t lds_cap = (size_t)std::min(m->lds_per_block, 160 * 1024) - 1024;
-    const int gp_max = (p1 || ls) ? rt::kSweepGpP1 : 4;  // (linear source: the same three tallies per component, the same limit)
-    int gp = std::min(G, gp_max);
-    if (m->sweep_gp >= 1 && m->sweep_gp <= 4) gp = std::min(gp, m->sweep_gp);
-    while (gp > 1 && (size_t)m->n_cells * gp * nt * sizeof(double) > lds_cap) --gp;
-    a.use_lds = (size_t)m->n_cells * gp * nt * sizeof(double) <= lds_cap ? 1 : 0;
-    if (!a.use_lds) gp = std::min(G, gp_max);
-    if (m->sweep_gp >= 8) a.use_lds = 0;  // experiment: tallies straight to HBM (measured 4x slower at C3: 2.1 ms against 0.48)
-    // reproducible tallies (an rt_solver with rt_solver_set_reproducible has switched them on for its run): no LDS copy, so the pass
-    // width is the widest the kernel is compiled for; the cell index for the rows read below, and the solver's delta buffer
-    const bool repro = t->sw_repro;
-    if (repro) {
-        gp = std::min(G, gp_max);
-        if (m->sweep_gp >= 1 && m->sweep_gp <= 4) gp = std::min(gp, m->sweep_gp);
-        a.use_lds = 0;
+    if (repro) {  // the cell index for the rows the plan names, and the solver's delta buffer
         int64_t rslots = 0;
         if (int rc = sweep_repro_prepare(t, &rslots)) return rc;
-        if (t->sw_ridx_kind != (rows_compact ? 2 : (staged ? 1 : 3))) { set_error("rt_sweep: the reproducible tallies' cell index is not the one of the rows read"); return RT_ERR_INVALID; }
-        if (!t->sw_repro_delta || (size_t)(2 * rslots) * (size_t)(nt * gp) > t->sw_repro_cap) {
+        if (t->sw_ridx_kind != rows_index_kind(plan.rows)) { set_error("rt_sweep: the reproducible tallies' cell index is not the one of the rows read"); return RT_ERR_INVALID; }
+        if (!loan.repro_delta || (size_t)(2 * rslots) * (size_t)((moments ? 3 : 1) * plan.gp) > loan.repro_cap) {
             set_error("rt_sweep: the delta buffer of the reproducible tallies is too small for these rows (%lld row slots): switch the option on again", (long long)rslots);
             return RT_ERR_INVALID;
         }
-        a.delta = as_global(t->sw_repro_delta); a.dslots = rslots;
+        a.delta = as_global(loan.repro_delta); a.dslots = rslots;
     }
     if (!async_sweep) RT_HIP(hipEventRecord(t->ev[0], s));
     RT_HIP(hipMemsetAsync(t->sw_phi.p, 0, nphi * sizeof(double), s));
-    if ((p1 || ls) && nphi) RT_HIP(hipMemsetAsync(t->sw_cur.p, 0, 2 * nphi * sizeof(double), s));
-    int passes = 0;
-    // Staged rows: the first pass after an rt_segmentize derives ℓ from the exit points and leaves it in `sw_ell`, slot-indexed
-    // like the rows; every later pass — of this sweep and of all following sweeps over the same segmentation — reads (ℓ, cell)
-    // rows instead (12 B instead of 20, no square root, no entry point).  Option "sweep_ell" = 0 switches this off.
-    bool ell_rows = false;
-    if (rows_compact) {
+    if (moments && nphi) RT_HIP(hipMemsetAsync(t->sw_cur.p, 0, 2 * nphi * sizeof(double), s));
+    if (plan.rows == SweepRows::FromCompact) {
         a.stg = rt::DStage{};
         a.stg.ctab = as_global(t->sw_ctab.p); a.stg.element = as_global(t->sw_cell.p);
-        ell_rows = true;
-    } else if (staged && t->cplan.codes) {
-        // a two-phase call staged codes: the sweep reads (ℓ, cell) rows, which the call itself left ("compact" = 0) or which
-        // k_materialise writes now, once per segmentation
+    } else if (plan.rows == SweepRows::FromCodes) {  // (which the call itself left ("compact" = 0) or which k_materialise writes now)
         if (int rc = ensure_rows(t)) return rc;
         a.stg.element = as_global(t->sw_cell.p);
-        ell_rows = true;
-    } else if (staged && m->sweep_ell) {
+    } else if (plan.try_ell) {
         const size_t slots = (size_t)t->pool_chunks * rt::kChunkRows * 64;
-        if (t->sw_ell.reserve(slots > 0 ? slots : 1) == hipSuccess) ell_rows = true;
-        else (void)hipGetLastError();  // (no memory for it: every pass derives ℓ itself)
+        if (t->sw_ell.reserve(slots > 0 ? slots : 1) != hipSuccess) {  // (no memory for it: every pass derives ℓ itself)
+            (void)hipGetLastError();
+            plan.rows = SweepRows::Staged20;
+        }
     }
-    a.ell_rows = ell_rows ? as_global(t->sw_ell.p) : nullptr;
-    auto launch = [&]<bool STAGED, int GP, bool LDS, bool P1, bool LS = false, bool REPRO = false>(int g0) -> int {
-        size_t smem = a.use_lds ? (size_t)m->n_cells * GP * ((P1 || LS) ? 3 : 1) * sizeof(double) : 0;
-        // (compact records: more than one eight-wave workgroup per CU thrashes its L1 — a pass of few groups asks for LDS it
-        //  does not use, so that it still gets a CU to itself: 5 groups = 4 + 1 took 0.88 ms against 0.58 for 7 = 4 + 3)
-        if (!STAGED && (a.use_lds || REPRO)) smem = std::max(smem, std::min(lds_cap, (size_t)81 * 1024));
-        // one workgroup per CU (its tallies fill the LDS): sixteen waves when the rows are the staging rows (every load
-        // instruction reads four full lines), eight when they are the compact records (64 lanes, 64 lines: sixteen waves
-        // thrash the CU's L1 — 1.04 against 0.62 ms at C3); two or more workgroups per CU: eight waves each
-        int W = (smem > 79 * 1024 && STAGED) ? 16 : 8;
-        if (m->sweep_waves == 4 || m->sweep_waves == 8 || m->sweep_waves == 16) W = m->sweep_waves;
-        if (LS && W > 8) W = 8;  // (the linear-source kernels are compiled for eight waves at most)
-        const unsigned blocks = (unsigned)((2 * (int64_t)a.n_waves + W - 1) / W);
-        a.g0 = g0; a.ng = GP;
-        if (STAGED && ell_rows && (t->sw_ell_valid || rows_compact)) {
-            if constexpr (STAGED) {
-                if (smem > 48 * 1024)
-                    RT_HIP(hipFuncSetAttribute(REPRO ? (const void *)rt::k_sweep_repro<true, GP, true, P1, LS> : (const void *)rt::k_sweep<true, GP, LDS, true, P1, LS>,
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-                if constexpr (REPRO) hipLaunchKernelGGL((rt::k_sweep_repro<true, GP, true, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
-                else hipLaunchKernelGGL((rt::k_sweep<true, GP, LDS, true, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
+    a.ell_rows = rows_kind(plan.rows) ? as_global(t->sw_ell.p) : nullptr;
+    int passes = 0;
+    for (int g0 = 0; n > 0 && g0 < G; ++passes) {
+        const int take = std::min(plan.gp, G - g0);
+        const PassShape shape = plan.pass_shape(take);
+        a.g0 = g0; a.ng = take;
+        if (facts.f32) {
+            if (!rows_read_ell(plan.rows)) {  // (checked before anything was queued; left: no memory for the ℓ rows)
+                set_error("rt_sweep: the single-precision sweep (\"sweep_precision\" 1) found no (ℓ, cell) rows to read (rows of kind 0)");
+                return RT_ERR_INVALID;
             }
+            if (int rc = launch_sweep_f32(a, take, shape.smem, shape.waves, shape.blocks, s)) return rc;
         } else {
-            if (smem > 48 * 1024)
-                RT_HIP(hipFuncSetAttribute(REPRO ? (const void *)rt::k_sweep_repro<STAGED, GP, false, P1, LS> : (const void *)rt::k_sweep<STAGED, GP, LDS, false, P1, LS>,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-            if constexpr (REPRO) hipLaunchKernelGGL((rt::k_sweep_repro<STAGED, GP, false, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
-            else hipLaunchKernelGGL((rt::k_sweep<STAGED, GP, LDS, false, P1, LS>), dim3(blocks), dim3(64 * W), smem, s, a);
-            if (STAGED && ell_rows) { t->sw_ell_valid = true; t->sw_rowsc_valid = false; }  // (the forward waves of this pass have written every row's ℓ)
+            if (int rc = launch_sweep_f64(t, a, plan, shape, s)) return rc;
+            if (plan.rows == SweepRows::Staged20WriteEll) {  // (the forward waves of this pass have written every row's ℓ)
+                t->sw_ell_valid = true; t->sw_rowsc_valid = false;
+                plan.rows = SweepRows::StagedEll;
+            }
         }
-        if constexpr (REPRO) {  // the pass's tallies, in the index's order (the next pass overwrites the delta buffer)
-            if (m->n_cells > 0)
-                hipLaunchKernelGGL((rt::k_sweep_reduce<GP, (P1 || LS)>), dim3((unsigned)((m->n_cells + 3) / 4)), dim3(256), 0, s, (const int32_t *)t->sw_ridx_start.p,
-                                   (const int32_t *)t->sw_ridx_list.p, (const double *)t->sw_repro_delta, a.dslots, m->n_cells, G, g0, t->sw_phi.p,
-                                   (P1 || LS) ? t->sw_cur.p : (double *)nullptr);
-        }
-        ++passes;
-        return RT_SUCCESS;
-    };
-    auto launch_all = [&]<bool STAGED, bool LDS, bool REPRO = false>() -> int {
-        for (int g0 = 0; g0 < G;) {
-            const int take = std::min(gp, G - g0);
-            int rc;
-            if (ls) {
-                if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, false, true, REPRO>(g0);
-                else rc = launch.template operator()<STAGED, 1, LDS, false, true, REPRO>(g0);
-            } else if (p1) {
-                static_assert(rt::kSweepGpP1 == 2, "the anisotropic passes below");
-                if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, true, false, REPRO>(g0);
-                else rc = launch.template operator()<STAGED, 1, LDS, true, false, REPRO>(g0);
-            } else if (take == 4) rc = launch.template operator()<STAGED, 4, LDS, false, false, REPRO>(g0);
-            else if (take == 3) rc = launch.template operator()<STAGED, 3, LDS, false, false, REPRO>(g0);
-            else if (take == 2) rc = launch.template operator()<STAGED, 2, LDS, false, false, REPRO>(g0);
-            else rc = launch.template operator()<STAGED, 1, LDS, false, false, REPRO>(g0);
-            if (rc) return rc;
-            g0 += take;
-        }
-        return RT_SUCCESS;
-    };
-    // single precision: the passes of k_sweep_f32, with the widths, the LDS copy and the grid chosen above for the FP64 rows kernel
-    auto launch_all_f32 = [&]() -> int {
-        if (!ell_rows || !(t->sw_ell_valid || rows_compact)) {  // (checked before anything was queued; left: no memory for the ℓ rows)
-            set_error("rt_sweep: the single-precision sweep (\"sweep_precision\" 1) found no (ℓ, cell) rows to read (rows of kind 0)");
-            return RT_ERR_INVALID;
-        }
-        for (int g0 = 0; g0 < G;) {
-            const int take = std::min(gp, G - g0);
-            const size_t smem = a.use_lds ? (size_t)m->n_cells * take * sizeof(double) : 0;
-            int W = smem > 79 * 1024 ? 16 : 8;  // (one workgroup per CU when its tallies fill the LDS: see `launch`)
-            if (m->sweep_waves == 4 || m->sweep_waves == 8 || m->sweep_waves == 16) W = m->sweep_waves;
-            a.g0 = g0; a.ng = take;
-            if (int rc = launch_sweep_f32(a, take, smem, W, (unsigned)((2 * (int64_t)a.n_waves + W - 1) / W), s)) return rc;
-            ++passes;
-            g0 += take;
-        }
-        return RT_SUCCESS;
-    };
+        g0 += take;
+    }
     if (n > 0) {
-        int rc;
-        if (f32) rc = launch_all_f32();
-        else if (repro) rc =(staged || rows_compact) ? launch_all.template operator()<true, false, true>() : launch_all.template operator()<false, false, true>();
-        else if (staged || rows_compact) rc = a.use_lds ? launch_all.template operator()<true, true>() : launch_all.template operator()<true, false>();
-        else rc = a.use_lds ? launch_all.template operator()<false, true>() : launch_all.template operator()<false, false>();
-        if (rc) return rc;
         const int64_t nl = 2 * n * G;
         hipLaunchKernelGGL(rt::k_sweep_link, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, (const int32_t *)t->sw_src.p,
                            (const double *)t->sw_psi_out.p, t->sw_psi_in.p, 2 * n, G, n);
@@ -687,31 +616,22 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         t->in_flight = false;  // (the sweep waited for the stream)
     }
     t->sw_done = true;
-    // (what the caller's records were: 1 the compact CSR records — named, or all there is —, 2 the staging; and how they were read)
-    t->sw_last_input = (input == 1 || rows_compact || !staged) ? 1 : 2;
-    t->sw_last_rows = rows_compact ? 2 : (staged && ell_rows ? 1 : 0); t->sw_last_gp = a.use_lds ? gp : 0; t->sw_last_passes = passes;
-    t->sw_last_prec = f32 ? RT_PRECISION_SINGLE : RT_PRECISION_DOUBLE;
+    t->sw_last_input = rows_input_code(plan.rows, input); t->sw_last_rows = rows_kind(plan.rows);
+    t->sw_last_gp = plan.use_lds ? plan.gp : 0; t->sw_last_passes = passes;
+    t->sw_last_prec = facts.f32 ? RT_PRECISION_SINGLE : RT_PRECISION_DOUBLE;
     return RT_SUCCESS;
 }
 
+extern "C" {
+
 int32_t rt_sweep_set_links(rt_tracks *t, const int64_t *next_fwd, const int64_t *next_bwd, const int8_t *dir_fwd,
                            const int8_t *dir_bwd, const int8_t *bc_fwd, const int8_t *bc_bwd) {
-    try {
-        return sweep_set_links_impl(t, next_fwd, next_bwd, dir_fwd, dir_bwd, bc_fwd, bc_bwd);
-    } catch (const std::exception &e) {
-        set_error("rt_sweep_set_links: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_sweep_set_links", [&] { return sweep_set_links_impl(t, next_fwd, next_bwd, dir_fwd, dir_bwd, bc_fwd, bc_bwd); });
 }
 
 int32_t rt_sweep(rt_tracks *t, int32_t n_groups, const double *sigma_t, const double *source, const double *track_weight,
                  const double *psi_in, int32_t input, double *ms) {
-    try {
-        return sweep_impl(t, n_groups, sigma_t, source, track_weight, psi_in, input, ms);
-    } catch (const std::exception &e) {
-        set_error("rt_sweep: %s", e.what());
-        return RT_ERR_INVALID;
-    }
+    return guarded("rt_sweep", [&] { return sweep_impl(t, n_groups, sigma_t, source, track_weight, psi_in, input, ms); });
 }
 
 int32_t rt_sweep_fetch(rt_tracks *t, double *phi, double *psi_out, double *psi_next) {
