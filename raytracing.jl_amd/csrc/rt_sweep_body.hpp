@@ -109,7 +109,9 @@
             [[maybe_unused]] auto ls_component = [&](const int g, const double F1, const double hF2) {
                 const double rho = __builtin_fma(dsn, h[2 * g + 1], dcs * h[2 * g]);  // ρ / Σ_c
                 const double am = psi[g] - qs[g];
-                const double d = __builtin_fma(am, F1, -(rho * hF2));
+                // (−ρ hF2 as an fma onto +0 rather than a negated product — the same value, and never −0: at τ = 0 both terms of d are
+                //  zeros, d is +0 whatever the signs of ψ − r_m and ρ, and ψ − d keeps ψ's bits, those of ψ = −0 included)
+                const double d = __builtin_fma(am, F1, __builtin_fma(-rho, hF2, 0.0));
                 const double Hs = __builtin_fma(rho, __builtin_fma(0.5, tau[g], 1.0), am) * hF2;  // Σ_c H
                 psi[g] = psi[g] - d;
                 wd[g] = w * d;

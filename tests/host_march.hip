@@ -331,6 +331,22 @@ void hostmarch_one_minus_exp_neg(const double *tau, int64_t n, double *out) {
 void hostmarch_one_minus_exp_neg_thin(const double *tau, int64_t n, double *out) {
     for (int64_t i = 0; i < n; ++i) out[i] = rt::one_minus_exp_neg_thin(tau[i]);
 }
+// The linear source's forms (rt_device.hpp), for tests/test_sweep_functions_cpu.py: F1 and E = e^{-tau} of
+// one_minus_exp_neg_both, and F2 = ls_f2(tau, E) with that E, as the sweep's general branch evaluates them ...
+void hostmarch_one_minus_exp_neg_both(const double *tau, int64_t n, double *f1, double *e) {
+    for (int64_t i = 0; i < n; ++i) f1[i] = rt::one_minus_exp_neg_both(tau[i], e[i]);
+}
+void hostmarch_ls_f2(const double *tau, int64_t n, double *out) {
+    for (int64_t i = 0; i < n; ++i) {
+        double E;
+        rt::one_minus_exp_neg_both(tau[i], E);
+        out[i] = rt::ls_f2(tau[i], E);
+    }
+}
+// ... and F2's form for optically thin segments (tau < rt::kThinTau)
+void hostmarch_ls_f2_thin(const double *tau, int64_t n, double *out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = rt::ls_f2_thin(tau[i]);
+}
 
 // bf16_up / bf16_value of the preprocessing (the cheap step's four per-record constants are stored as bfloat16 rounded UP).
 void hostmarch_bf16(const double *v, int64_t n, uint16_t *pattern, double *value) {

@@ -41,6 +41,9 @@ def lib():
         L.hostmarch_bf16.argtypes = [_dp, C.c_int64, C.POINTER(C.c_uint16), _dp]
         L.hostmarch_one_minus_exp_neg.argtypes = [_dp, C.c_int64, _dp]
         L.hostmarch_one_minus_exp_neg_thin.argtypes = [_dp, C.c_int64, _dp]
+        L.hostmarch_one_minus_exp_neg_both.argtypes = [_dp, C.c_int64, _dp, _dp]
+        L.hostmarch_ls_f2.argtypes = [_dp, C.c_int64, _dp]
+        L.hostmarch_ls_f2_thin.argtypes = [_dp, C.c_int64, _dp]
         L.hostmarch_chain.argtypes = [C.c_int64, _dp, _dp, _dp, C.c_double, C.c_double, _ip, _dp, _dp]
         L.hostmarch_topo.restype = C.c_int32
         L.hostmarch_topo.argtypes = [_dp, _dp, C.c_int32, _ip, C.c_int32, _dp, _ip] + [_dp] * 6
@@ -142,6 +145,25 @@ def one_minus_exp_neg(tau, thin=False):
     tau = _f(tau)
     out = np.zeros(len(tau))
     f = lib().hostmarch_one_minus_exp_neg_thin if thin else lib().hostmarch_one_minus_exp_neg
+    f(tau.ctypes.data_as(_dp), len(tau), out.ctypes.data_as(_dp))
+    return out
+
+
+def one_minus_exp_neg_both(tau):
+    """rt::one_minus_exp_neg_both (rt_device.hpp), evaluated on the host: (F1, E) = (1 - exp(-tau), exp(-tau)), the linear
+    source's general form (E is the clamped exp(-41.5) beyond tau = 41.5)."""
+    tau = _f(tau)
+    f1, e = np.zeros(len(tau)), np.zeros(len(tau))
+    lib().hostmarch_one_minus_exp_neg_both(tau.ctypes.data_as(_dp), len(tau), f1.ctypes.data_as(_dp), e.ctypes.data_as(_dp))
+    return f1, e
+
+
+def ls_f2(tau, thin=False):
+    """rt::ls_f2(tau, E) with E from one_minus_exp_neg_both, evaluated on the host: the linear source's F2; `thin`:
+    rt::ls_f2_thin, its form for optically thin segments (tau < 1/8: the alternating series, no exponential)."""
+    tau = _f(tau)
+    out = np.zeros(len(tau))
+    f = lib().hostmarch_ls_f2_thin if thin else lib().hostmarch_ls_f2
     f(tau.ctypes.data_as(_dp), len(tau), out.ctypes.data_as(_dp))
     return out
 

@@ -294,3 +294,121 @@ def test_linear_source_kernels_in_the_code_object(rt, tmp_path):
     for key, v in found.items():
         assert v["private_segment_fixed_size"] == 0 and v["vgpr_spill_count"] == 0 and v["vgpr_count"] <= 256, (key, v)
         assert v["max_flat_workgroup_size"] == 512, (key, v)
+
+
+# ---- the τ regimes of the LS branch ----------------------------------------------------------------------------------------------
+SCALES = [0.02, 0.2, 6, 40, 1000]
+_REGIME_TWINS = {}
+
+
+def scaled_xs(rt, xs, scale):
+    """Σt, Σs, νΣf (and Σs1) times `scale`: every optical length times `scale`."""
+    s1 = None if xs.sigma_s1 is None else xs.sigma_s1 * scale
+    return rt.CrossSections(xs.sigma_t * scale, xs.sigma_s * scale, xs.nu_sigma_f * scale, xs.chi, sigma_s1=s1)
+
+
+def regime_shares(rt, rec, xs, cm, polar):
+    """Over the ORACLE's records, on the CPU: the share of records thin (τ < 1/8) in every component, and of the (record, component)
+    pairs below 1/8, in [1/8, 1.5), in [1.5, 41.5) and from 41.5 on; τ = Σt_g ℓ / sin θ_p."""
+    sp = rt.PolarQuadrature(polar).sin_theta
+    sig = (xs.sigma_t[np.asarray(cm, np.int64)][:, :, None] / sp[None, None, :]).reshape(len(cm), -1)
+    tau = sig[rec["element"] - 1] * rec["ell"][:, None]
+    return dict(all_thin=float((tau.max(1) < 0.125).mean()), thin=float((tau < 0.125).mean()), series=float(((tau >= 0.125) & (tau < 1.5)).mean()),
+                closed=float(((tau >= 1.5) & (tau < 41.5)).mean()), clamp=float((tau >= 41.5).mean()))
+
+
+def assert_regime(scale, s):
+    """The preconditions of the regime tests (the measured shares: see test_attenuation_regimes)."""
+    ok = {0.02: s["all_thin"] == 1.0,                               # every wave-row takes the series forms
+          0.2: 0.1 < s["all_thin"] < 0.9,                           # wave-rows of both kinds
+          6: s["series"] >= 0.3 and s["closed"] >= 0.3,             # both branches of ls_f2
+          40: s["clamp"] >= 0.05 and s["closed"] >= 0.5,            # the clamp at 41.5 runs
+          1000: s["thin"] == 0.0 and s["clamp"] >= 0.8}[scale]
+    assert ok, (scale, s)
+
+
+def _handle_opts(rt, tg, **opts):
+    from raytracing_jl_amd import _capi
+
+    dm = _capi.DeviceMesh(tg.mesh, 0)
+    for k, v in opts.items():
+        dm.set_option(k, v)
+    dt = _capi.DeviceTracks(dm, tg.px, tg.py, tg.phi, tg.cos_phi, tg.sin_phi, tg.A, tg.B, tg.C, tg.ell, tg.azim_idx)
+    aq = tg.azimuthal_quadrature
+    dt.segmentize(tg.tiny_step, 5, rt.RTOL_DEFAULT, aq.delta_s, aq.n_azim_2)
+    dt.sweep_set_links(tg)
+    return dt
+
+
+def _last_sweep(dt, ref):
+    from raytracing_jl_amd import _capi
+
+    psi, T = np.empty(ref["psi_out"].shape), np.empty(ref["tally"].shape)
+    _capi._check(_capi.lib().rt_sweep_fetch(dt._h, T.ctypes.data_as(_capi._dp), psi.ctypes.data_as(_capi._dp), None))
+    return psi, T
+
+
+@pytest.mark.parametrize("scale", SCALES)
+def test_attenuation_regimes(rt, square, scale):
+    """The LS branch of rt_sweep_body.hpp picks per wave-row: the series forms (one_minus_exp_neg_thin, ls_f2_thin) where all 64 lanes
+    are thin in both components of the pass, else one_minus_exp_neg_both with ls_f2 (its series below 1.5, the closed form above, E
+    clamped from 41.5 on).  The 288-cell square, G = 3 x TY3 (nine components, passes 2 + 2 + 2 + 2 + 1), 12 iterations, with Σt, Σs,
+    νΣf times `scale`; the regime is asserted from the oracle's 6,384 records before anything runs on the device.  Measured shares
+    (records thin in all nine components; pairs below 1/8, [1/8, 1.5), [1.5, 41.5), >= 41.5):
+        0.02  1.000;  1.000 0     0     0        (τ <= 0.0455)
+        0.2   0.336;  0.821 0.179 0     0
+        6     0;      0.046 0.507 0.447 0
+        40    0;      0.002 0.091 0.810 0.097
+        1000  0;      0     0.000 0.104 0.896    (τ >= 1.22)
+    Each scale against the twin at the bounds of this file (k 1e-11, φ and φ⃗ 1e-10, the last sweep's ψ_out and T 1e-10); at 0.02 and
+    0.2 also "sweep_debug" 4 (the general form everywhere) within 1e-12 of the default run; at 1000 a fixed-source run; at 0.02 and
+    40 the row variants "sweep_ell" 0, "sweep_rows" 0 and "compact" 0.
+    What these bounds can see (measured on the CPU: the twin with its F2 times (1 + ε) against the twin as it is, smallest ε of
+    1e-9 … 1e-1 that breaks an assertion): 1e-8 at 0.02, 1e-7 at 0.2, 1e-9 at 6, 40 and 1000.  So a wrong branch or a wrong leading
+    coefficient shows at every scale; what does not show at 0.02 is an error in the high terms of ls_f2_thin (its n = 13 term is
+    1e-19 of the sum at τ = 0.045): tests/test_gpu_sweep_functions.py guards the function's values, this test the branch's wiring.
+    Measured on an MI355X (k, φ, φ⃗, last ψ_out, last T against the twin; the row variants within these): 0.02: 7e-16, 1.4e-14, 2.0e-14,
+    6.1e-14, 1.3e-14; 0.2: 7e-16, 2.4e-15, 1.5e-15, 1.2e-14, 3.9e-15; 6: 4e-16, 2.8e-15, 8e-16, 6.3e-15, 7.3e-15; 40: 4e-16, 4.4e-15,
+    2.9e-15, 8.8e-15, 1.0e-14; 1000: 4e-16, 8e-16, 5.9e-15, 2.6e-15, 1.8e-15 (fixed source: φ 5e-17, φ⃗ 3.5e-15); "sweep_debug" 4
+    against the default run: at most 3.6e-14 (ψ_out at 0.02)."""
+    tg, rec = square["mixed"]
+    G, n, polar = 3, 12, "TY3"
+    xs, cm = scaled_xs(rt, _xs(rt, G, 9), scale), _bands(tg)
+    shares = regime_shares(rt, rec, xs, cm, polar)
+    print("scale %g: %s" % (scale, " ".join("%s %.3f" % kv for kv in shares.items())))
+    assert_regime(scale, shares)
+    ref = twin_ls(rt, tg, rec, xs, cm, polar=polar, max_iter=n, **EXACT)
+
+    def run(mode=EIG, against=ref, **opts):
+        dt = _handle_opts(rt, tg, **opts)
+        sv = _solver(rt, tg, dt, xs, cm, polar)
+        sv.set_linear_source(True)
+        if mode == FIX:
+            sv.set_source(_source(tg, np.asarray(cm), G))
+        r = _run(sv, mode, n)
+        info = _sweep_info(dt)
+        assert info["groups"] == 9 and info["groups_per_pass"] == 2 and info["passes"] == 5, info
+        print("scale %g %s %s" % (scale, "fixed source" if mode == FIX else "eigenvalue", opts or ""))
+        _assert_twin(tg, r, against, n)
+        _assert_last_sweep(dt, against)
+        r["psi_out"], r["tally"] = _last_sweep(dt, against)
+        sv.close()
+        return r
+
+    a = run()
+    if scale in (0.02, 0.2):
+        b = run(sweep_debug=4)
+        # each field on the scale _assert_twin and _assert_last_sweep give it: φ⃗ is a moment about the centroid, a difference of
+        # tallies of the size of φ times the domain (here 2e-3 of it), so its scale is the median φ times the domain size
+        med = float(np.median(np.abs(b["phi"])))
+        for key in ("k_history", "phi", "flux_moments", "psi_out", "tally"):
+            err = np.abs(a[key] - b[key]).max() / (med * _size(tg) if key == "flux_moments" else np.abs(b[key]).max())
+            print("thin forms against the general ones, %s: %.2e" % (key, err))
+            assert err <= 1e-12, (key, err)
+    if scale == 1000:
+        S = _source(tg, np.asarray(cm), G)
+        run(FIX, twin_ls(rt, tg, rec, xs, cm, polar=polar, mode="fixed", source=S, max_iter=n, **EXACT))
+    if scale in (0.02, 40):
+        for opts in (dict(sweep_ell=0), dict(sweep_rows=0), dict(compact=0)):
+            run(**opts)
+

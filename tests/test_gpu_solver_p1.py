@@ -332,3 +332,28 @@ def test_error_paths(rt, pin):
     sv.set_source(np.ones((tg.mesh.num_cells, G)))
     assert sv.run(FIX, 2, 0.0, 0.0)["iterations"] == 2 and np.isfinite(sv.fetch_current()).all()
     sv.close()
+
+
+# ---- 12. the τ regimes of the P1 branch -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scale", [0.02, 0.2, 40])
+def test_attenuation_regimes(rt, square, scale):
+    """The P1 sweep has its own copy of the thin and general branches (rt_sweep_body.hpp: one_minus_exp_neg_thin where a wave-row
+    is thin in both components of the pass, one_minus_exp_neg elsewhere).  The 288-cell square, G = 3 x TY3, with Σt, Σs, Σs1, νΣf
+    times `scale`: every wave-row thin (0.02), wave-rows of both kinds (0.2: a third of the records thin in all nine components),
+    thick with a tenth of the optical lengths beyond the clamp at 41.5 (40) — asserted from the oracle's records before anything
+    runs on the device —, against the twin at this file's bounds."""
+    from test_gpu_solver_ls import assert_regime, regime_shares, scaled_xs
+
+    tg, rec = square
+    G, n = 3, 12
+    xs, cm = scaled_xs(rt, _with_s1(rt, _xs(rt, G, 9), 10), scale), _bands(tg)
+    shares = regime_shares(rt, rec, xs, cm, "TY3")
+    print("scale %g: %s" % (scale, " ".join("%s %.3f" % kv for kv in shares.items())))
+    assert_regime(scale, shares)
+    dt = _handle(rt, tg)
+    sv = _solver(rt, tg, dt, xs, cm, "TY3")
+    r = _run(sv, EIG, n)
+    info = _sweep_info(dt)
+    assert info["groups"] == 9 and info["groups_per_pass"] == 2 and info["passes"] == 5, info
+    _assert_twin(r, twin_p1(rt, tg, rec, xs, cm, polar="TY3", max_iter=n, **EXACT), n)
+    sv.close()

@@ -346,3 +346,29 @@ def test_refusals_leave_the_solver_usable(rt, problems):
     again = _make(rt, tg, dt, xs, cm, "TY3", "flat")  # a new solver on the new segmentation: a new index, the same bits
     _assert_same_bits(a, _run(again, "flat"), "after the re-segmentize")
     again.close()
+
+
+# ---- 7: k_sweep_repro's copy of the linear-source branch through its τ regimes -------------------------------------------------------------
+@pytest.mark.parametrize("scale", [0.02, 40])
+def test_linear_source_regimes(rt, problems, scale):
+    """tests/test_gpu_solver_ls.py::test_attenuation_regimes with the reproducible tallies on: every wave-row thin (0.02: the series
+    forms), and thick with a tenth of the optical lengths beyond the clamp at 41.5 (40) — the regime asserted from the oracle's
+    records first.  Two runs byte for byte, and the twin's answer at the bounds of both files, the last sweep's ψ_out and T included."""
+    from test_gpu_solver_ls import _assert_last_sweep, assert_regime, regime_shares, scaled_xs
+
+    tg, rec, cm = problems["square"]
+    xs = scaled_xs(rt, _xs(rt, 3, 9), scale)
+    shares = regime_shares(rt, rec, xs, cm, "TY3")
+    print("scale %g: %s" % (scale, " ".join("%s %.3f" % kv for kv in shares.items())))
+    assert_regime(scale, shares)
+    dt = _handle(rt, tg)
+    sv = _make(rt, tg, dt, xs, cm, "TY3", "linear")
+    assert sv.reproducible
+    a, b = _run(sv, "linear"), _run(sv, "linear")
+    _assert_same_bits(a, b, "the same solver again")
+    ref = moc_ref.solve_tg(rt, tg, rec, xs, cm, "TY3", scheme="linear", max_iter=N, tol_k=0.0, tol_flux=0.0)
+    _assert_twin(tg, a, ref, "linear")
+    top = np.abs(ref["phi"]).max()
+    assert np.abs(a["phi"] - ref["phi"]).max() <= 1e-10 * top
+    _assert_last_sweep(dt, ref)
+    sv.close()
