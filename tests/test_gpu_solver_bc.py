@@ -6,6 +6,7 @@ Shapes: a 2 x 2 x 2-triangle square at nφ = 4, δ = 0.1 (60 tracks: fewer than 
 group and one polar angle, and an 8 x 8 x 2-triangle square at nφ = 8, δ = 0.02 (1048 tracks = 16·64 + 24 = 4·256 + 24; 2096 track
 ends: two tally workgroups of 1360 ends at G = 3) with 3 groups x TY3 = 9 components; four sides, five sides of which one has no
 end, one side for every end, one side whose β differs per group, and two sides traced Reflective and left at side −1.
+The branches of the boundary kernels that (G, P, S, number of ends) select are in tests/test_gpu_solver_bc_shapes.py.
 
 Measured on an MI355X (12 iterations; the bounds are the project's for rounding-only comparisons, k 1e-11, the rest 1e-10): see
 DESIGN.md §8 — k <= 8.9e-16, φ <= 1.7e-14 of the median φ (the linear source; 4.7e-15 otherwise), J⁺ <= 1.9e-15 and J⁻ <= 1.1e-15 of
