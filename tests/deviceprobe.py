@@ -15,7 +15,9 @@ _OUT = os.path.join(_HERE, "build", "libdeviceprobe.so")
 _CSRC = os.path.join(_HERE, "..", "raytracing.jl_amd", "csrc")
 _lib = None
 _dp = C.POINTER(C.c_double)
+_fp = C.POINTER(C.c_float)
 NAMES = ("one_minus_exp_neg", "one_minus_exp_neg_thin", "both_f1", "both_e", "ls_f2", "ls_f2_thin")
+NAMES_F32 = ("one_minus_exp_neg_f32", "one_minus_exp_neg_f32_thin")
 
 
 def makefile_flags():
@@ -46,6 +48,8 @@ def lib():
         L = C.CDLL(build())
         L.deviceprobe_run.restype = C.c_int
         L.deviceprobe_run.argtypes = [_dp, C.c_int64, _dp]
+        L.deviceprobe_run_f32.restype = C.c_int
+        L.deviceprobe_run_f32.argtypes = [_fp, C.c_int64, _fp]
         _lib = L
     return _lib
 
@@ -58,3 +62,14 @@ def run(tau):
     if st != 0:
         raise RuntimeError("deviceprobe_run: HIP status %d" % st)
     return dict(zip(NAMES, out))
+
+
+def run_f32(tau):
+    """NAMES_F32 -> float32 array [len(tau)]: the single-precision sweep's factor at every binary32 τ in ONE launch (the thin form:
+    0 where τ >= kThinTauF32)."""
+    tau = np.ascontiguousarray(tau, np.float32)
+    out = np.full((2, len(tau)), np.nan, np.float32)
+    st = lib().deviceprobe_run_f32(tau.ctypes.data_as(_fp), len(tau), out.ctypes.data_as(_fp))
+    if st != 0:
+        raise RuntimeError("deviceprobe_run_f32: HIP status %d" % st)
+    return dict(zip(NAMES_F32, out))
