@@ -568,6 +568,40 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              source, adjoint mode (β is diagonal in the groups and the same for a traversal and its reverse: k† = k) and the
  *              stepwise calls work unchanged.  A solver without a boundary launches exactly what it always did
  *
+ * Regions, rt_solver_set_regions: the partial currents between cell regions, per sweep.  The caller gives R <= 127 regions and
+ * cell_region[e] in 0 .. R − 1 for every cell; index R stands for "outside the track".  A traversal (d, u) visits its records in
+ * order (backward: reversed); for every component c = g·P + p
+ * Tally        before its first record       S[R → r₁][c]      += w[u] ψ,   ψ = ψ_in[(d, u)][c]
+ *              before every later record whose cell's region r differs from the previous record's r_prev
+ *                                            S[r_prev → r][c]  += w[u] ψ,   ψ as it stands between the two segments
+ *              after its last record         S[r_last → R][c]  += w[u] ψ_out[(d, u)][c]
+ *              A track without records tallies nothing; records of one region that follow each other tally nothing, whatever
+ *              their cells.  S [(R + 1)][(R + 1)][G·P] is that of ONE sweep: every sweep starts it from zero
+ * Currents     the fold of S over the polar angles, with the boundary currents' weights:
+ *                  J[a → b][g] = Σ_p ω_p sin θ_p S[a → b][g·P + p]
+ *              the partial currents of the LAST sweep (eigenvalue mode: rt_solver_end scales them with φ, as it scales J⁺ / J⁻; S
+ *              stays the sweep's).  Σ_a J[a → R] is what leaves through the track ends, Σ_a J[R → a] what enters there
+ * Identity     T[e] sums w (ψ_before − ψ_after) over segments, and along a traversal the sum over the consecutive records of one
+ *              region telescopes: for every sweep, region a < R and component c, up to the rounding of the sums,
+ *                  Σ_{e in a} T[e][c] = Σ_{b ≠ a, b <= R} (S[b → a][c] − S[a → b][c])
+ * Balance      with the fold, per region and group:  Σ_{e in a} V_e (Σt φ − 4π q) = Σ_b (J[b → a] − J[a → b]); formed with the last
+ *              φ its defect is of the size of the iteration error
+ * Sweep        k_sweep_iface (rt_sweep_iface.hip), the FP64 sweep over (ℓ, cell) rows — flat, first-moment scattering and linear
+ *              source — with a workgroup-private table of the pass in LDS, (R + 1)² doubles per component behind the φ copy, flushed
+ *              once per workgroup by FP64 atomics into S: S (and so J) is an atomic sum and repeats to its last bits only.  The
+ *              width of a pass: the φ copy is kept while it and the table fit the LDS, the pass narrowed for both; else T takes
+ *              global atomics and the pass is narrowed until the table alone fits (R = 127: one component, 128 KiB).
+ *              k_solver_iface_fold forms J behind the last pass, one thread per (a, b, g), the P terms in order
+ * Rows         rt_sweep_rows_kind 1 or 2, as the single-precision sweep: a sweep that would read its records where they lie
+ *              ("sweep_rows" 0, "sweep_ell" 0, the first pass over the 20-B rows of a march by exact steps) is refused with
+ *              RT_ERR_INVALID before anything is queued, the message naming the rows' kind and the option
+ * Refused      with the reproducible tallies (S is an atomic sum), with the single-precision sweep (another kernel), and on a
+ *              shard's track set (a next uid of 0): RT_ERR_INVALID with a message that names both sides, from whichever of the two
+ *              is switched on second (a shard's links set after the regions: from rt_solver_begin); the solver keeps its state
+ * Works with   eigenvalue and fixed-source runs, rt_solver_set_boundary, the stepwise calls, and adjoint mode — where the currents
+ *              are those of the TRANSPOSED problem: ψ*(Ω) = ψ†(−Ω), so J†[a → b] = J*[b → a]
+ * A solver without regions launches exactly what it always did.
+ *
  * Reproducible tallies, rt_solver_set_reproducible.  The sweep's tallies T (and Tx, Ty) are the one sum of an iteration whose order
  * depends on timing: FP64 atomics into an LDS copy and from there into T.  With the option on, a run is bitwise reproducible:
  * Sweep        a lane neither folds with its neighbours nor adds anywhere: it stores the values w Δψ (w ξ Δψ − ..., as above) of its
@@ -787,6 +821,20 @@ int32_t rt_solver_fetch_boundary(rt_solver *solver, double *j_out, double *j_in)
 /* Device addresses ptrs_dev[2] and element counts lens[2] (either may be NULL) of J⁺ and J⁻ [n_sides·G], valid while a boundary is
  * set (NULL / 0 without one); the content is that of rt_solver_fetch_boundary.  Does not wait. */
 int32_t rt_solver_boundary_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
+/* Regions (see above) for the following runs: n_regions = R in 1 .. 127 and cell_region [n_cells] (host memory, copied), every
+ * entry in 0 .. R − 1.  n_regions = 0 or cell_region = NULL switches them off: the solver then launches exactly what one that
+ * never had regions does.  RT_ERR_INVALID for R > 127, a region id outside 0 .. R − 1, while the reproducible tallies or the
+ * single-precision sweep are on (those setters refuse likewise while regions are set), on a shard's track set, with a run open or
+ * after the tracks were segmentized again; the solver then keeps what it had. */
+int32_t rt_solver_set_regions(rt_solver *solver, int32_t n_regions, const int32_t *cell_region);
+/* The partial currents of the last sweep, J [(R + 1)][(R + 1)][G] (J[a][b]: from region a to region b; R: outside the track): after
+ * a run, and in an open run after an rt_solver_step_sweep (waits for it).  RT_ERR_INVALID without regions, or before the first sweep
+ * with them. */
+int32_t rt_solver_fetch_regions(rt_solver *solver, double *J);
+/* Device addresses ptrs_dev[2] and element counts lens[2] (either may be NULL) of [0] the sweep's tally S [(R + 1)²·G·P] and [1] J
+ * [(R + 1)²·G], valid while regions are set (NULL / 0 without them).  S is complete when the work rt_solver_step_sweep queued is
+ * done: a stepwise caller reads it between step_sweep and step_fold.  Does not wait. */
+int32_t rt_solver_region_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

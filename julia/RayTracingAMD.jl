@@ -326,6 +326,25 @@ function solver_set_precision!(hs::Ptr{Cvoid}, single::Bool=true)
     return nothing
 end
 
+# Region currents for the following runs of an `rt_solver` handle `hs` (include/rt_segmentize.h, "Regions"): `cell_region` holds a
+# 0-based region id below `n_regions` <= 127 for every cell; an empty vector switches them off.  Refused together with the
+# reproducible tallies, the single-precision sweep and on a shard's track set.
+function solver_set_regions!(hs::Ptr{Cvoid}, n_regions::Integer, cell_region::Vector{Int32})
+    rc = isempty(cell_region) ? ccall((:rt_solver_set_regions, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), hs, 0, C_NULL) :
+                                ccall((:rt_solver_set_regions, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Int32}), hs, n_regions, cell_region)
+    rc == 0 || error("rt_solver_set_regions failed: " * lasterror())
+    return nothing
+end
+
+# The last sweep's partial currents J[g, b, a] (column-major view of the library's [a][b][g]: from region a to region b, index
+# n_regions + 1: outside the track) of a solver with `n_regions` regions and `n_groups` groups
+function solver_fetch_regions(hs::Ptr{Cvoid}, n_regions::Integer, n_groups::Integer)
+    J = Array{Float64}(undef, n_groups, n_regions + 1, n_regions + 1)
+    rc = ccall((:rt_solver_fetch_regions, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}), hs, J)
+    rc == 0 || error("rt_solver_fetch_regions failed: " * lasterror())
+    return J
+end
+
 # The precision of the last sweep over the tracks handle `ht`: 0 Float64, 1 the angular flux in binary32
 function sweep_precision(ht::Ptr{Cvoid})
     rc = ccall((:rt_sweep_precision, LIB), Int32, (Ptr{Cvoid},), ht)

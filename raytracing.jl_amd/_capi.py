@@ -34,6 +34,7 @@ SYMBOLS = (
     "rt_solver_begin", "rt_solver_step_sweep", "rt_solver_step_fold", "rt_solver_end", "rt_solver_pointers",
     "rt_solver_set_adjoint", "rt_solver_bilinear", "rt_solver_set_reproducible", "rt_solver_set_precision",
     "rt_solver_set_boundary", "rt_solver_fetch_boundary", "rt_solver_boundary_pointers",
+    "rt_solver_set_regions", "rt_solver_fetch_regions", "rt_solver_region_pointers",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -283,6 +284,16 @@ def lib():
     L.rt_solver_boundary_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
     L.rt_solver_pointers.restype = C.c_int32
     L.rt_solver_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
+    try:
+        L.rt_solver_set_regions.restype = C.c_int32
+        L.rt_solver_set_regions.argtypes = [_vp, C.c_int32, _ip]
+        L.rt_solver_fetch_regions.restype = C.c_int32
+        L.rt_solver_fetch_regions.argtypes = [_vp, _dp]
+        L.rt_solver_region_pointers.restype = C.c_int32
+        L.rt_solver_region_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
+    except AttributeError:
+        if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
+            raise
     if L.rt_abi_version() != 1:
         raise RtError("librt_segmentize.so: ABI version mismatch")
     _lib = L
@@ -864,6 +875,45 @@ class DeviceSolver:
         lens = (C.c_int64 * 2)()
         _check(lib().rt_solver_boundary_pointers(self._open(), ptrs, lens))
         names = ("current_out", "current_in")
+        out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
+        out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
+        return out
+
+    def set_regions(self, cell_region=None, n_regions=None):
+        """``rt_solver_set_regions`` for the following runs: ``cell_region`` int [n_cells], every entry in 0 .. R − 1, and
+        ``n_regions`` = R <= 127 (None: the largest id + 1).  ``cell_region`` None: off.  The partial currents between the regions
+        are then tallied by every sweep (``fetch_regions``)."""
+        L = lib()
+        if not hasattr(L, "rt_solver_set_regions"):
+            raise RtError(f"{LIB_PATH} has no rt_solver_set_regions: the library is older than this binding")
+        if cell_region is None:
+            _check(L.rt_solver_set_regions(self._open(), 0, None))
+            self.n_regions = 0
+            return
+        cr, crp = _i32(cell_region)
+        if cr.shape != (self.n_cells,):
+            raise ValueError("cell_region must have one entry per cell")
+        R = int(cr.max(initial=-1)) + 1 if n_regions is None else int(n_regions)
+        if R < 1:
+            raise ValueError("regions need n_regions >= 1")
+        _check(L.rt_solver_set_regions(self._open(), R, crp))
+        self.n_regions = R
+
+    def fetch_regions(self) -> np.ndarray:
+        """``rt_solver_fetch_regions``: the last sweep's partial currents J [R + 1, R + 1, G], ``J[a, b]`` from region a to region b
+        (index R: outside the track)."""
+        R = getattr(self, "n_regions", 0)
+        J = np.empty((R + 1, R + 1, self.G))
+        _check(lib().rt_solver_fetch_regions(self._open(), J.ctypes.data_as(_dp)))
+        return J
+
+    def region_pointers(self) -> dict:
+        """``rt_solver_region_pointers``: device addresses (0: no regions) of the sweep's tally ``S`` [(R + 1)², G·P] and its fold
+        ``J`` [(R + 1)², G], and their element counts under ``lens``."""
+        ptrs = (_vp * 2)()
+        lens = (C.c_int64 * 2)()
+        _check(lib().rt_solver_region_pointers(self._open(), ptrs, lens))
+        names = ("S", "J")
         out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
         out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
         return out

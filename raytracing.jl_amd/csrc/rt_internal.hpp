@@ -317,6 +317,11 @@ struct DSweep {
     // lane stores the NT·GP values of its segment at delta[(dir · dslots + row slot) · NT·GP], and k_sweep_reduce sums them per cell
     RT_G double *delta;
     int64_t dslots;                   // row slots of the variant being swept (staging pool, rows from the compact records, or records)
+    // partial currents between cell regions (k_sweep_iface; rt_solver with rt_solver_set_regions): a lane adds w ψ at every change of
+    // region along its traversal to the workgroup's LDS table, which is flushed into if_S[(from · (if_R + 1) + to) · G + component]
+    const RT_G int32_t *if_region;    // [n_cells] region of every cell, 0 .. if_R − 1
+    RT_G double *if_S;                // [(if_R + 1)][(if_R + 1)][G]; index if_R: outside the track
+    int32_t if_R, if_pad;
 };
 
 }  // namespace rt
@@ -331,6 +336,9 @@ struct SweepLoan {
     double *repro_delta = nullptr;
     size_t repro_cap = 0;             // doubles
     bool f32 = false;                 // single-precision sweep (rt_solver_set_precision)
+    const int32_t *region = nullptr;  // region currents (rt_solver_set_regions): the cells' regions [n_cells] (DSweep if_region),
+    double *iface_S = nullptr;        // the sweep's tally S [(R + 1)][(R + 1)][components], zeroed by every sweep (DSweep if_S),
+    int32_t n_regions = 0;            // and R (0: off)
 };
 
 struct rt_mesh {
@@ -589,6 +597,7 @@ int ensure_rows(rt_tracks *t);
 int ensure_rows_from_compact(rt_tracks *t);  // rt_sweep.hip
 // rt_sweep_f32.hip: one pass of the single-precision sweep kernel over `gp` components from a.g0 (a.use_lds: the tallies' LDS copy)
 int launch_sweep_f32(const rt::DSweep &a, int gp, size_t smem, int waves, unsigned blocks, hipStream_t s);
+int launch_sweep_iface(const rt::DSweep &a, SweepMode mode, size_t smem, int waves, unsigned blocks, hipStream_t s);  // rt_sweep_iface.hip
 // rt_sweep.hip: the row variant a solver's sweep (input 0) reads now, its rows made and the cell index built for it (once per
 // segmentation and variant); *slots: row slots of the variant.  RT_ERR_INVALID where the reproducible tallies cannot be served
 int sweep_repro_prepare(rt_tracks *t, int64_t *slots);

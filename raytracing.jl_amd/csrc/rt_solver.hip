@@ -16,6 +16,8 @@
 // With the reproducible tallies (rt_solver_set_reproducible) the solver launches the same kernels; the sweep it queues runs
 // k_sweep_repro and k_sweep_reduce behind every pass (rt_sweep.hip), into the delta buffer this solver owns, and V_e and the linear
 // source's geometry are summed through the same cell index.  Without the option the solver launches what it always did.
+// With regions (rt_solver_set_regions) the sweep it queues runs k_sweep_iface (rt_sweep_iface.hip), which also tallies the partial
+// currents between the cell regions into S, and k_solver_iface_fold forms J from S behind it.  Without them: what it always did.
 // Flat, first-moment scattering or linear source is one choice of three, a SweepMode (each setter switches only its own mode off and
 // refuses to switch it on over the other).  What a run's rt_sweep calls need to know — that mode, the linear source's geometry, the
 // reproducible tallies' delta buffer, single precision — goes to the handle as one SweepLoan (rt_internal.hpp) and comes back whole.
@@ -515,6 +517,18 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_bnd_reduce(const double 
     }
 }
 
+// ---- region currents (rt_solver_set_regions): the fold of the sweep's tally S over the polar angles ---------------------------------
+// One thread per (a, b, g) behind the sweep's last pass: J[a → b][g] = Σ_p ω_p sin θ_p S[a → b][g·P + p], the P terms in order.  No atomics.
+__global__ __launch_bounds__(kSolveBlock) void k_solver_iface_fold(const double *__restrict__ S, const double *__restrict__ pol, int32_t pairs,
+                                                                   int32_t G, int32_t P, double *__restrict__ J) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // (pair a·(R + 1) + b, group)
+    if (i >= (int64_t)pairs * G) return;
+    const double *x = S + i * P;
+    double acc = 0.0;
+    for (int32_t p = 0; p < P; ++p) acc += pol[P + p] * x[p];
+    J[i] = acc;
+}
+
 }  // namespace rt
 
 struct rt_solver {
@@ -553,6 +567,12 @@ struct rt_solver {
     DevBuf<int32_t> bnd_src;
     DevBuf<int8_t> bnd_side_entry, bnd_side_end, bnd_side_start;
     DevBuf<double> bnd_beta, bnd_incv, bnd_part, bnd_J;
+    // region currents (rt_solver_set_regions): R, the cells' regions [n_cells], the sweep's tally S [(R + 1)²][G·P] and its fold over
+    // the polar angles J [(R + 1)²][G] of the last sweep; both lent to the handle's sweeps for a run (SweepLoan)
+    int32_t reg_R = 0;
+    bool reg_tallied = false, run_reg = false;  // reg_J holds a sweep of the last run; the open run tallies
+    DevBuf<int32_t> reg_cell;
+    DevBuf<double> reg_S, reg_J;
     // reproducible tallies (rt_solver_set_reproducible): the sweep's per-pass delta buffer, 2 · row slots · NT · width doubles, held
     // from the switch-on to the switch-off (or rt_solver_destroy)
     bool repro = false;
@@ -855,6 +875,14 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
         if (smode != SweepMode::Flat || S->repro) { set_error("%s: the single-precision sweep (rt_solver_set_precision) together with first-moment scattering, the linear source or the reproducible tallies is not supported", who); return RT_ERR_INVALID; }
         loan.f32 = true;
     }
+    const bool reg = S->reg_R > 0;
+    if (reg) {  // (the setters keep the combinations apart; the links may have become a shard's since)
+        if (S->repro || S->single) { set_error("%s: the region currents (rt_solver_set_regions) together with the reproducible tallies or the single-precision sweep are not supported", who); return RT_ERR_INVALID; }
+        if (t->sw_shard) { set_error("%s: region currents are set (rt_solver_set_regions) and the track set is a shard (some next uid is 0): regions on sharded runs are not supported", who); return RT_ERR_INVALID; }
+        loan.region = S->reg_cell.p; loan.iface_S = S->reg_S.p; loan.n_regions = S->reg_R;
+        RT_HIP(hipMemsetAsync(S->reg_J.p, 0, (size_t)(S->reg_R + 1) * (S->reg_R + 1) * G * sizeof(double), s));
+    }
+    S->reg_tallied = false;
     t->sw_loan = loan;
     S->bnd_tallied = false;
     if (bnd) RT_HIP(hipMemsetAsync(S->bnd_J.p, 0, (size_t)2 * S->bnd_S * G * sizeof(double), s));
@@ -863,7 +891,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
                            (const int8_t *)S->bnd_side_entry.p, (const double *)S->bnd_beta.p, (const double *)S->bnd_incv.p,
                            (const double *)nullptr, t->sw_psi_in.p, 2 * n, G, P, n);
     S->k_hist.clear();
-    S->run_eigen = eigen; S->run_mode = smode; S->run_bnd = bnd;
+    S->run_eigen = eigen; S->run_mode = smode; S->run_bnd = bnd; S->run_reg = reg;
     S->it = 0; S->last_k = 1.0; S->last_res = INFINITY; S->last_dk = INFINITY;
     // φ⁰ = 1, the components' Σt / sin θ, F⁰
     RT_HIP(hipMemsetAsync(S->prod.p, 0, (size_t)std::max(1, nc) * sizeof(double), s));
@@ -902,6 +930,13 @@ int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
     };
     if (bnd) tally(S->bnd_side_start.p, t->sw_psi_in.p, S->bnd_part.p + (size_t)S->bnd_blocks * SG);  // J⁻: the flux that enters this sweep
     if (int32_t rc = rt_sweep(t, d.C, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
+    if (S->run_reg && n > 0) {  // J of this sweep from its S, behind the last pass (no tracks: the zeros of rt_solver_begin)
+        const int32_t pairs = (S->reg_R + 1) * (S->reg_R + 1);
+        hipLaunchKernelGGL(rt::k_solver_iface_fold, dim3((unsigned)(((int64_t)pairs * G + rt::kSolveBlock - 1) / rt::kSolveBlock)), dim3(rt::kSolveBlock), 0, s,
+                           (const double *)S->reg_S.p, (const double *)S->pol.p, pairs, G, P, S->reg_J.p);
+        RT_HIP(hipGetLastError());
+    }
+    S->reg_tallied = S->run_reg;
     if (bnd) {  // J⁺ of this sweep, then the hand-over behind the sided ends over what k_sweep_link wrote
         tally(S->bnd_side_end.p, t->sw_psi_out.p, S->bnd_part.p);
         hipLaunchKernelGGL(rt::k_solver_bnd_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->bnd_part.p,
@@ -977,6 +1012,10 @@ int solver_end_impl(rt_solver *S, rt_solver_result *res, const char *who) {
     if (eigen && S->run_bnd && S->bnd_tallied)  // (the currents of the last sweep, scaled with φ)
         hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * S->bnd_S * d.G + 255) / 256)), dim3(256), 0, s, S->bnd_J.p,
                            (int64_t)2 * S->bnd_S * d.G, (const double *)S->scal.p);
+    if (eigen && S->run_reg && S->reg_tallied) {  // (the region currents of the last sweep, scaled with φ; S stays the sweep's)
+        const int64_t nj = (int64_t)(S->reg_R + 1) * (S->reg_R + 1) * d.G;
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((nj + 255) / 256)), dim3(256), 0, s, S->reg_J.p, nj, (const double *)S->scal.p);
+    }
     RT_HIP(hipStreamSynchronize(s));
     RT_HIP(hipGetLastError());
     float f = 0.0f;
@@ -1264,6 +1303,79 @@ int32_t rt_solver_boundary_pointers(rt_solver *solver, void **ptrs_dev, int64_t 
     return RT_SUCCESS;
 }
 
+// The regions of the following runs.  Nothing is computed: rt_solver_begin lends the arrays to the handle (SweepLoan), and rt_sweep
+// launches k_sweep_iface instead of k_sweep.
+static int32_t solver_set_regions_impl(rt_solver *S, int32_t n_regions, const int32_t *cell_region) {
+    const char *who = "rt_solver_set_regions";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the regions cannot change under it", who); return RT_ERR_INVALID; }
+    if (n_regions == 0 || !cell_region) { S->reg_R = 0; S->reg_tallied = false; return RT_SUCCESS; }
+    if (n_regions < 1 || n_regions > rtsweep::kMaxRegions) { set_error("%s: bad arguments (n_regions %d, need 1 .. %d)", who, n_regions, rtsweep::kMaxRegions); return RT_ERR_INVALID; }
+    if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and region currents — an atomic sum — together with them are not supported", who); return RT_ERR_INVALID; }
+    if (S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision: another kernel), and region currents together with it are not supported", who); return RT_ERR_INVALID; }
+    rt_tracks *t = S->t;
+    if (t->sw_shard) { set_error("%s: the track set is a shard (some next uid is 0): regions on sharded runs are not supported", who); return RT_ERR_INVALID; }
+    const size_t nc = (size_t)S->n_cells;
+    for (size_t e = 0; e < nc; ++e)
+        if (cell_region[e] < 0 || cell_region[e] >= n_regions) {
+            set_error("%s: cell_region[%zu] = %d is not a region in [0, %d)", who, e, cell_region[e], n_regions);
+            return RT_ERR_INVALID;
+        }
+    if (int rc = finish_call(t)) return rc;
+    RT_HIP(hipSetDevice(t->mesh->device));
+    hipStream_t s = t->mesh->stream;
+    // (into fresh buffers: a failure leaves the solver what it had)
+    DevBuf<int32_t> d_cell;
+    DevBuf<double> d_S, d_J;
+    const size_t pairs = (size_t)(n_regions + 1) * (n_regions + 1);
+    std::vector<int32_t> one(1, 0);
+    if (int rc = upload(d_cell, nc ? cell_region : one.data(), std::max<size_t>(1, nc), s)) return rc;
+    RT_HIP(d_S.reserve(pairs * S->G * S->P)); RT_HIP(d_J.reserve(pairs * S->G));
+    RT_HIP(hipMemsetAsync(d_S.p, 0, pairs * S->G * S->P * sizeof(double), s));
+    RT_HIP(hipMemsetAsync(d_J.p, 0, pairs * S->G * sizeof(double), s));
+    RT_HIP(hipStreamSynchronize(s));  // (the caller's array may go)
+    S->reg_cell = std::move(d_cell); S->reg_S = std::move(d_S); S->reg_J = std::move(d_J);
+    S->reg_R = n_regions; S->reg_tallied = false;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_regions(rt_solver *solver, int32_t n_regions, const int32_t *cell_region) {
+    return guarded("rt_solver_set_regions", [&] { return solver_set_regions_impl(solver, n_regions, cell_region); });
+}
+
+int32_t rt_solver_fetch_regions(rt_solver *solver, double *J) {
+    if (!solver) { set_error("rt_solver_fetch_regions: null solver"); return RT_ERR_INVALID; }
+    if (solver->reg_R <= 0 || !solver->reg_tallied) {
+        set_error("rt_solver_fetch_regions: no sweep with regions yet (rt_solver_set_regions, then a run or rt_solver_step_sweep)");
+        return RT_ERR_INVALID;
+    }
+    if (solver->open)
+        if (int rc = solver_check_epoch(solver, "rt_solver_fetch_regions")) return rc;
+    return guarded("rt_solver_fetch_regions", [&]() -> int32_t {
+        RT_HIP(hipSetDevice(solver->device));
+        hipStream_t s = solver->t->mesh->stream;
+        const size_t nj = (size_t)(solver->reg_R + 1) * (solver->reg_R + 1) * solver->G;
+        if (J) RT_HIP(hipMemcpyAsync(J, solver->reg_J.p, nj * sizeof(double), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));
+        return RT_SUCCESS;
+    });
+}
+
+int32_t rt_solver_region_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
+    if (!solver) { set_error("rt_solver_region_pointers: null solver"); return RT_ERR_INVALID; }
+    // (no wait here: addresses and counts only)
+    const bool on = solver->reg_R > 0;
+    const int64_t pairs = (int64_t)(solver->reg_R + 1) * (solver->reg_R + 1);
+    void *p[2] = {on ? solver->reg_S.p : nullptr, on ? solver->reg_J.p : nullptr};
+    const int64_t l[2] = {on ? pairs * solver->G * solver->P : 0, on ? pairs * solver->G : 0};
+    for (int i = 0; i < 2; ++i) {
+        if (ptrs_dev) ptrs_dev[i] = p[i];
+        if (lens) lens[i] = l[i];
+    }
+    return RT_SUCCESS;
+}
+
 int32_t rt_solver_fetch_current(rt_solver *solver, double *J) {
     if (!solver || !J) { set_error("rt_solver_fetch_current: null argument"); return RT_ERR_INVALID; }
     if (!solver->ran || solver->ran_mode != SweepMode::P1) {
@@ -1397,6 +1509,7 @@ static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
     const bool want = on != 0;
     if (want == S->repro) return RT_SUCCESS;
     if (want && S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
+    if (want && S->reg_R > 0) { set_error("%s: region currents are set (rt_solver_set_regions: their tally is an atomic sum), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
     rt_tracks *t = S->t;
     if (int rc = finish_call(t)) return rc;
     RT_HIP(hipSetDevice(t->mesh->device));
@@ -1475,7 +1588,8 @@ int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision) {
     if (precision == RT_PRECISION_SINGLE) {
         const char *other = S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
                                   : (S->mode == SweepMode::Linear ? "the linear source is on (rt_solver_set_linear_source)"
-                                           : (S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)" : nullptr));
+                                           : (S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
+                                                       : (S->reg_R > 0 ? "region currents are set (rt_solver_set_regions: another kernel)" : nullptr)));
         if (other) { set_error("%s: %s, and the single-precision sweep together with it is not supported", who, other); return RT_ERR_INVALID; }
     }
     S->single = precision == RT_PRECISION_SINGLE;

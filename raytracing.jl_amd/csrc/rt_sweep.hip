@@ -52,14 +52,17 @@ namespace rt {
 // write NT·GP full 128-B lines), and k_sweep_reduce sums every cell's entries in a fixed order after the pass.  No LDS copy (LDS = false),
 // so the pass width is not bound by the mesh: the widths the atomic instantiations' registers were tuned for, 4 components
 // (kSweepGpP1 = 2 with three tallies per component).  The instantiations without the flag compile to what they were.
+// IFACE (region currents, rt_solver_set_regions): a second constant of the shared body, false in both kernels here and true in
+// k_sweep_iface (rt_sweep_iface.hip); sweep_impl lends it the solver's region array and tally, zeroes the tally before the first
+// pass and launches it in k_sweep's place (launch_sweep_iface).  The kernels of this file compile to what they were.
 template <bool STAGED, int GP, bool LDS, bool ELLROWS, bool P1 = false, bool LS = false>
 __global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep(DSweep a) {
-    constexpr bool REPRO = false;
+    constexpr bool REPRO = false, IFACE = false;
 #include "rt_sweep_body.hpp"
 }
 template <bool STAGED, int GP, bool ELLROWS, bool P1 = false, bool LS = false>
 __global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep_repro(DSweep a) {
-    constexpr bool REPRO = true, LDS = false;
+    constexpr bool REPRO = true, LDS = false, IFACE = false;
 #include "rt_sweep_body.hpp"
 }
 
@@ -525,7 +528,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     const SweepFacts facts{.n = n, .n_cells = m->n_cells, .G = G, .input = input, .mode = mode, .repro = repro,
                            .f32 = loan.f32 || m->sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
                            .sw_ell_valid = t->sw_ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
-                           .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves};
+                           .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves, .regions = loan.n_regions};
     SweepPlan plan = plan_sweep(facts);
     if (plan.refusal) { set_error("%s", plan.message); return plan.refusal; }
     // the rows the plan names, made once per segmentation: from the compact records here, the staging's below (inside `ms`, as ever)
@@ -562,7 +565,13 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         }
         a.delta = as_global(loan.repro_delta); a.dslots = rslots;
     }
+    const bool iface = facts.regions > 0;
+    if (iface) {  // the solver's region array and its tally S, zeroed before the first pass
+        if (!loan.region || !loan.iface_S) { set_error("rt_sweep: the region currents have no arrays"); return RT_ERR_INVALID; }
+        a.if_region = as_global(loan.region); a.if_S = as_global(loan.iface_S); a.if_R = facts.regions;
+    }
     if (!async_sweep) RT_HIP(hipEventRecord(t->ev[0], s));
+    if (iface) RT_HIP(hipMemsetAsync(loan.iface_S, 0, (size_t)(facts.regions + 1) * (facts.regions + 1) * G * sizeof(double), s));
     RT_HIP(hipMemsetAsync(t->sw_phi.p, 0, nphi * sizeof(double), s));
     if (moments && nphi) RT_HIP(hipMemsetAsync(t->sw_cur.p, 0, 2 * nphi * sizeof(double), s));
     if (plan.rows == SweepRows::FromCompact) {
@@ -590,6 +599,12 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
                 return RT_ERR_INVALID;
             }
             if (int rc = launch_sweep_f32(a, take, shape.smem, shape.waves, shape.blocks, s)) return rc;
+        } else if (iface) {
+            if (!rows_read_ell(plan.rows)) {  // (checked before anything was queued; left: no memory for the ℓ rows)
+                set_error("rt_sweep: the region currents (rt_solver_set_regions) found no (ℓ, cell) rows to read (rows of kind 0)");
+                return RT_ERR_INVALID;
+            }
+            if (int rc = launch_sweep_iface(a, mode, shape.smem, shape.waves, shape.blocks, s)) return rc;
         } else {
             if (int rc = launch_sweep_f64(t, a, plan, shape, s)) return rc;
             if (plan.rows == SweepRows::Staged20WriteEll) {  // (the forward waves of this pass have written every row's ℓ)

@@ -2,8 +2,11 @@
 // k_sweep_repro (REPRO = true, LDS = false): one text, two kernels, and k_sweep compiles to the instructions it had as a kernel of
 // its own (called as an inlined device function it did not).  Expects the template flags STAGED, GP, LDS, ELLROWS, P1, LS, the
 // constant REPRO and the kernel argument `DSweep a` in scope; rt_sweep.hip's head comment describes what it does.
+// A third kernel, k_sweep_iface (rt_sweep_iface.hip), includes it with the constant IFACE = true (false in the two above, whose
+// instructions stay what they were): the partial currents between cell regions, `if constexpr (IFACE)` below.
     static_assert(STAGED || !ELLROWS, "ℓ rows belong to the staging rows");
     static_assert(!(REPRO && LDS), "the reproducible tallies keep no LDS copy");
+    static_assert(!IFACE || (STAGED && ELLROWS && !REPRO), "the region currents are tallied over (ℓ, cell) rows, by atomics");
     static_assert(!(P1 && LS), "linear source with first-moment scattering is not built");
     constexpr bool AN = P1 || LS;        // three tallies and two ratios per component
     constexpr int NT = AN ? 3 : 1;       // tallies per component
@@ -12,10 +15,18 @@
     double *hist = reinterpret_cast<double *>(sweep_smem);  // [n_cells * NT * GP] when LDS
     const int lane = threadIdx.x & 63;
     const int wib = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // wave-uniform, and known to be
-    if (LDS) {
-        for (int c = threadIdx.x; c < a.n_cells * (NT * GP); c += blockDim.x) hist[c] = 0.0;
-        __syncthreads();
+    // IFACE: the workgroup's table of the pass, S[from][to][g] with from, to in 0 .. R (R: outside the track), behind the φ copy
+    [[maybe_unused]] double *itab = nullptr;
+    [[maybe_unused]] int R1 = 1, ntab = 0;
+    if constexpr (IFACE) {
+        itab = hist + (LDS ? a.n_cells * (NT * GP) : 0);
+        R1 = a.if_R + 1; ntab = R1 * R1 * GP;
     }
+    if (LDS)
+        for (int c = threadIdx.x; c < a.n_cells * (NT * GP); c += blockDim.x) hist[c] = 0.0;
+    if constexpr (IFACE)
+        for (int c = threadIdx.x; c < ntab; c += blockDim.x) itab[c] = 0.0;
+    if (LDS || IFACE) __syncthreads();
     // a sweep wave = (march wave, direction).  The march waves are ordered longest first and the sweep is bound by
     // instruction issue, so the waves are dealt to the workgroups round-robin: wave k of workgroup b takes sweep wave
     // k * gridDim + b — every workgroup gets the same mix of long and short tracks and all finish together (contiguous
@@ -53,6 +64,19 @@
         double psi[GP];
 #pragma unroll
         for (int g = 0; g < GP; ++g) psi[g] = (have && g < ng) ? a.psi_in[pbase + g] : 0.0;
+        // IFACE: the region of the lane's previous record (R before its first one), and the add of w ψ to the table's [from][to]
+        [[maybe_unused]] int32_t rprev = 0;
+        if constexpr (IFACE) rprev = a.if_R;
+        [[maybe_unused]] auto iface_add = [&](const int32_t from, const int32_t to) {
+#pragma unroll
+            for (int g = 0; g < GP; ++g)
+                if (g < ng) atomicAdd(&itab[(from * R1 + to) * GP + g], w * psi[g]);  // (ng: uniform)
+        };
+        // the region of cell `e`, fetched with the cross sections of its step (0 without the flag)
+        [[maybe_unused]] auto load_region = [&](const int32_t e) -> int32_t {
+            if constexpr (IFACE) return a.if_region[e];
+            else return 0;
+        };
         // step t visits row r(t): 0, 1, ... forward; maxcnt-1, ..., 0 backward (demo/makie.jl:103: "the segments are stored in
         // reverse order for backward tracks"), all lanes in lockstep — a lane is active while r(t) < its count.  Steps beyond
         // the end are clamped to the last one (prefetches only).
@@ -85,8 +109,17 @@
         // of length 0: τ = 0, 1 − e^{−0} = 0 exactly, Δ = ±0 — its ψ keeps its bits, and one select does for all groups.
         // (dsl: the row's slot in DSweep::delta, read by the REPRO instantiations only)
         auto segment = [&](const int32_t e, const double ell_row, const bool act, const double (&st)[GP], const double (&qs0)[GP],
-                           const double (&h)[NH], [[maybe_unused]] const int64_t dsl) {
+                           const double (&h)[NH], [[maybe_unused]] const int64_t dsl, [[maybe_unused]] const int32_t rg = 0) {
             const double ell = act ? ell_row : 0.0;
+            // IFACE: ψ as it stands between the previous record and this one crosses into region rg (rare and divergent; ahead of the
+            // arithmetic and far from the fold).  An inactive lane — beyond its track's end, or a backward lane before its track's first
+            // row — neither tallies nor moves its register.
+            if constexpr (IFACE) {
+                if (act) {
+                    if (rg != rprev) iface_add(rprev, rg);
+                    rprev = rg;
+                }
+            }
             double wd[NT * GP], tau[GP], qs[GP];
             bool thin = true;
             // LS: the midpoint relative to the cell's centroid; s moves on by ℓ (0 for a lane beyond its track's end)
@@ -293,20 +326,25 @@
                     LRow L0 = load_lrow(slot_of(row_of(0))), L1 = load_lrow(slot_of(row_of(1))), L2{0.0, 0};
                     double stA[GP], qsA[GP], stB[GP], qsB[GP], hA[NH], hB[NH];
                     load_xs(lcell(L0, row_of(0)), stA, qsA, hA);
+                    // (IFACE: the cells' regions travel with the cross sections' two stages)
+                    [[maybe_unused]] int32_t rgA = load_region(lcell(L0, row_of(0))), rgB = 0;
                     auto lstep = [&](const int t, const LRow &Ra, const LRow &Rb, LRow &Rc, const double (&st0)[GP], const double (&qs0)[GP],
-                                     const double (&h0)[NH], double (&st1)[GP], double (&qs1)[GP], double (&h1)[NH]) {
+                                     const double (&h0)[NH], double (&st1)[GP], double (&qs1)[GP], double (&h1)[NH],
+                                     [[maybe_unused]] const int32_t rg0, [[maybe_unused]] int32_t &rg1) {
                         const int r = row_of(t);
                         const bool act = r < cnt && t < maxcnt;
                         int64_t sl0 = 0;
                         if constexpr (REPRO) sl0 = slot_cached(r, cj0, cid0);  // (the slot of the row being evaluated: uniform lookup, see chunk_of)
                         Rc = load_lrow(slot_cached(row_of(t + 2), cj2, cid2));
                         load_xs(lcell(Rb, row_of(t + 1)), st1, qs1, h1);
-                        segment(lcell(Ra, r), Ra.ell, act, st0, qs0, h0, sl0);
+                        if constexpr (IFACE) rg1 = load_region(lcell(Rb, row_of(t + 1)));
+                        segment(lcell(Ra, r), Ra.ell, act, st0, qs0, h0, sl0, rg0);
                     };
                     for (int t = 0; t < maxcnt; t += 3) {
-                        lstep(t, L0, L1, L2, stA, qsA, hA, stB, qsB, hB);
-                        lstep(t + 1, L1, L2, L0, stB, qsB, hB, stA, qsA, hA);
-                        lstep(t + 2, L2, L0, L1, stA, qsA, hA, stB, qsB, hB);
+                        lstep(t, L0, L1, L2, stA, qsA, hA, stB, qsB, hB, rgA, rgB);
+                        lstep(t + 1, L1, L2, L0, stB, qsB, hB, stA, qsA, hA, rgB, rgA);
+                        lstep(t + 2, L2, L0, L1, stA, qsA, hA, stB, qsB, hB, rgA, rgB);
+                        if constexpr (IFACE) rgA = rgB;
 #pragma unroll
                         for (int g = 0; g < GP; ++g) { stA[g] = stB[g]; qsA[g] = qsB[g]; }
                         if constexpr (AN)
@@ -344,9 +382,18 @@
 #pragma unroll
             for (int g = 0; g < GP; ++g)
                 if (g < ng) a.psi_out[pbase + g] = psi[g];
+        // IFACE: ψ_out leaves the last record's region (a track without records tallies nothing)
+        if constexpr (IFACE)
+            if (have && cnt > 0) iface_add(rprev, a.if_R);
     }
+    if (LDS || IFACE) __syncthreads();
+    if constexpr (IFACE)
+        for (int c = threadIdx.x; c < ntab; c += blockDim.x) {
+            const double v = itab[c];
+            const int pair = c / GP, g = c - pair * GP;
+            if (v != 0.0 && g < a.ng) unsafeAtomicAdd((double *)&a.if_S[(int64_t)pair * a.G + a.g0 + g], v);
+        }
     if (LDS) {
-        __syncthreads();
         for (int c = threadIdx.x; c < a.n_cells * (NT * GP); c += blockDim.x) {
             const double v = hist[c];
             const int cell = c / (NT * GP), i = c - cell * (NT * GP);

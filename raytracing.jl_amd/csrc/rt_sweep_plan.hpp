@@ -49,7 +49,10 @@ struct SweepFacts {
     bool sw_ell_valid = false; // the staging's (ℓ, cell) rows of the last rt_segmentize exist
     int lds_per_block = 0;
     int sweep_rows = 1, sweep_ell = 1, sweep_gp = 0, sweep_waves = 0;  // the options
+    int regions = 0;           // R of the region currents (lent by a solver, rt_solver_set_regions); 0: off
 };
+
+constexpr int kMaxRegions = 127;  // (R + 1)² doubles of one component fit the LDS of a workgroup: 128 KiB
 
 struct PassShape { size_t smem; int waves; unsigned blocks; };  // dynamic LDS bytes, waves per workgroup, workgroups
 
@@ -63,6 +66,11 @@ struct SweepPlan {
     SweepFacts f;                   // what it was made from
     size_t lds_cap = 0;             // bytes of LDS a pass may ask for
 
+    // bytes of the region currents' workgroup table for a pass of `take` components: (R + 1)² doubles each; 0 without regions
+    size_t iface_table(int take) const {
+        return f.regions > 0 ? (size_t)(f.regions + 1) * (size_t)(f.regions + 1) * (size_t)take * sizeof(double) : 0;
+    }
+
     // A pass of `take` components.  One workgroup per CU where its tallies fill the LDS: sixteen waves when the rows are in the
     // march's lane mapping (every load instruction reads four full lines), eight when they are the compact records (64 lanes, 64
     // lines: sixteen waves thrash the CU's L1 — 1.04 against 0.62 ms at C3); two or more workgroups per CU: eight waves each.
@@ -72,6 +80,7 @@ struct SweepPlan {
     PassShape pass_shape(int take) const {
         const bool staged = rows_staged(rows);
         size_t smem = use_lds ? (size_t)f.n_cells * take * (f.mode != SweepMode::Flat ? 3 : 1) * sizeof(double) : 0;
+        smem += iface_table(take);  // (the region currents' table, behind the φ copy)
         if (!staged && (use_lds || f.repro)) smem = std::max(smem, std::min(lds_cap, (size_t)81 * 1024));
         int W = (smem > 79 * 1024 && staged) ? 16 : 8;
         if (f.sweep_waves == 4 || f.sweep_waves == 8 || f.sweep_waves == 16) W = f.sweep_waves;
@@ -82,6 +91,9 @@ struct SweepPlan {
 
 #define RT_F32_WITH(other) "rt_sweep: the single-precision sweep (rt_solver_set_precision, \"sweep_precision\" 1) together with " other " is not supported"
 #define RT_F32_ROWS(why) "rt_sweep: the single-precision sweep (\"sweep_precision\" 1) reads (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
+
+#define RT_IFACE_WITH(other) "rt_sweep: the region currents (rt_solver_set_regions) together with " other " — not supported"
+#define RT_IFACE_ROWS(why) "rt_sweep: the region currents (rt_solver_set_regions) are tallied over (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
 
 inline SweepPlan plan_sweep(const SweepFacts &f) {
     SweepPlan p;
@@ -113,6 +125,17 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
             return refuse(RT_F32_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
                                       "double-precision sweep first (\"sweep_precision\" 0), or set option \"sweep_rows\" 2 and name the compact records"));
     }
+    // region currents: k_sweep_iface, FP64 atomics, over (ℓ, cell) rows — refused like the single-precision sweep, before anything is queued
+    if (f.regions > 0) {
+        if (f.regions > kMaxRegions) return refuse("rt_sweep: the region currents (rt_solver_set_regions) take at most 127 regions");
+        if (f.repro) return refuse(RT_IFACE_WITH("the reproducible tallies (rt_solver_set_reproducible): the regions' tally is an atomic sum"));
+        if (f.f32) return refuse(RT_IFACE_WITH("the single-precision sweep (rt_solver_set_precision, \"sweep_precision\" 1): that is another kernel"));
+        if (p.rows == SweepRows::Records) return refuse(RT_IFACE_ROWS("the compact records where they lie: option \"sweep_rows\" is 0"));
+        if (p.rows == SweepRows::Staged20) return refuse(RT_IFACE_ROWS("the staging's 20-B rows in every pass: option \"sweep_ell\" is 0"));
+        if (p.rows == SweepRows::Staged20WriteEll)
+            return refuse(RT_IFACE_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
+                                        "sweep without regions first, or set option \"sweep_rows\" 2 and name the compact records"));
+    }
     // components per pass: as many as an LDS-private copy of their tallies allows (up to 4); none fits: global atomics.  The last
     // pass takes what is left with the kernel compiled for that many (7 groups = 4 + 3: a padded fourth group was an eighth of the
     // sweep's arithmetic).  First-moment scattering and the linear source: three tallies per component, so a mesh that fits 4
@@ -129,10 +152,28 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
     if (f.sweep_gp >= 8) p.use_lds = false;  // experiment: tallies straight to HBM (measured 4x slower at C3: 2.1 ms against 0.48)
     // reproducible tallies: no LDS copy, so the pass width is the widest the kernel is compiled for
     if (f.repro) { p.gp = gp_opt; p.use_lds = false; }
+    // region currents: (1) the table of a pass, (R + 1)² doubles per component, always lives in LDS; (2) the φ copy is kept while both
+    // fit, the pass narrowed for the two as it is narrowed for the copy alone; (3) where they do not fit even one component wide the
+    // copy gives way and T takes global atomics, as on large meshes; (4) the pass is then narrowed until the table alone fits —
+    // R <= 127 makes one component fit (128 KiB).  Without regions nothing above changes.
+    if (f.regions > 0) {
+        const auto both = [&](int gp) { return (size_t)f.n_cells * gp * nt * sizeof(double) + p.iface_table(gp) <= p.lds_cap; };
+        int gp = gp_opt;
+        while (gp > 1 && !both(gp)) --gp;
+        if (both(gp) && f.sweep_gp < 8) {
+            p.gp = gp; p.use_lds = true;
+        } else {
+            p.gp = gp_opt; p.use_lds = false;
+            while (p.gp > 1 && p.iface_table(p.gp) > p.lds_cap) --p.gp;
+            if (p.iface_table(p.gp) > p.lds_cap) return refuse("rt_sweep: the region currents' table of one component does not fit the LDS of a workgroup");
+        }
+    }
     return p;
 }
 
 #undef RT_F32_WITH
 #undef RT_F32_ROWS
+#undef RT_IFACE_WITH
+#undef RT_IFACE_ROWS
 
 }  // namespace rtsweep

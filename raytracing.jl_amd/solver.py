@@ -16,6 +16,8 @@ With ``adjoint=True`` the same iteration runs on the transposed problem (``rt_so
 With ``boundary=SolverBoundary(...)`` the four sides of the domain carry albedos β (ψ_in = β ψ_out + ψ_inc behind every track end
 on that side, whatever ``trace`` linked there) and, in fixed-source runs, an isotropic incoming flux ψ_inc; the result then
 carries the partial currents per side and group and the neutron balance (``rt_solver_set_boundary``).
+With ``regions=...`` (an int per cell, or ``"material"``) every sweep also tallies the partial currents between the cell regions
+(``rt_solver_set_regions``): ``SolverResult.region_current`` and the balance of every region, ``region_balance``.
 """
 from __future__ import annotations
 
@@ -29,7 +31,7 @@ from . import _capi
 from .trackgenerator import SIDE_NAMES, TrackGenerator, track_end_sides
 
 __all__ = ["CrossSections", "PolarQuadrature", "SolverBoundary", "SolverResult", "exact_azimuthal_weights", "azimuthal_weights",
-           "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "neutron_balance"]
+           "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "neutron_balance", "region_balance"]
 
 
 class CrossSections:
@@ -215,6 +217,27 @@ def neutron_balance(xs, cell_material, phi, volumes, k_eff, source, current_out,
     return dict(gain=gain, removal=removal, leakage=leakage, defect=gain - removal - leakage)
 
 
+def region_balance(xs, cell_material, cell_region, phi, volumes, k_eff, source, region_current, adjoint=False) -> dict:
+    """``neutron_balance`` per region, from a run's last φ and the last sweep's ``region_current`` J [R + 1, R + 1, G]: for region a
+    the cells with ``cell_region == a``, J⁺ = J[a → b] and J⁻ = J[b → a] over b ≠ a (b = R: outside the track, i.e. the domain's
+    boundary).  Returns ``gain``, ``removal``, ``leakage`` (net outflow), ``net_inflow`` = −leakage and ``defect`` =
+    gain − removal − leakage, each [R, G]; the defect is of the size of the iteration error."""
+    J = np.asarray(region_current, np.float64)
+    R = J.shape[0] - 1
+    reg = np.asarray(cell_region, np.int64)
+    mat = np.asarray(cell_material, np.int64)
+    phi, V = np.asarray(phi, np.float64), np.asarray(volumes, np.float64)
+    src = None if source is None else np.asarray(source, np.float64)
+    rows = []
+    for a in range(R):
+        m = reg == a
+        others = np.arange(R + 1) != a
+        rows.append(neutron_balance(xs, mat[m], phi[m], V[m], k_eff, None if src is None else src[m], J[a, others], J[others, a], adjoint=adjoint))
+    out = {key: np.stack([r[key] for r in rows]) for key in ("gain", "removal", "leakage", "defect")}
+    out["net_inflow"] = -out["leakage"]
+    return out
+
+
 @dataclass
 class SolverResult:
     k_eff: Optional[float]        # None in fixed-source mode
@@ -237,6 +260,8 @@ class SolverResult:
     balance: Optional[dict] = None              # ... neutron_balance: gain, removal, leakage, defect [G]; all four None without
     reproducible: bool = False    # True: the run used the fixed-order sweep tallies (rt_solver_set_reproducible): its bits repeat
     precision: str = "double"     # "single": the run swept the angular flux in binary32 (rt_solver_set_precision); sums, fold, k in FP64
+    region_current: Optional[np.ndarray] = None  # regions=...: the last sweep's partial currents J [R + 1, R + 1, G], J[a, b] from a to b (R: outside)
+    region_balance: Optional[dict] = None        # ... region_balance: gain, removal, leakage, net_inflow, defect [R, G]; both None without
 
 
 def _cell_material(tg, cell_material):
@@ -254,6 +279,20 @@ def _cell_material(tg, cell_material):
     return np.ascontiguousarray(cm, np.int32)
 
 
+def _cell_regions(cm, regions):
+    """``regions`` as an int32 array per cell: ``"material"`` is ``cell_material``."""
+    if isinstance(regions, str):
+        if regions != "material":
+            raise ValueError(f'unknown regions {regions!r} ("material" or an int array per cell)')
+        return np.ascontiguousarray(cm, np.int32)
+    reg = np.asarray(regions)
+    if reg.shape != np.shape(cm) or not np.issubdtype(reg.dtype, np.integer):
+        raise ValueError("regions must be an int array with one entry per cell")
+    if reg.size and (reg.min() < 0 or reg.max() >= 127):
+        raise ValueError("region ids must lie in 0 .. 126 (at most 127 regions)")
+    return np.ascontiguousarray(reg, np.int32)
+
+
 def _device_tracks(tg, device):
     """The tracks' device handle after ``segmentize`` (run here with ``fetch=False`` if it has not run), links set."""
     from .segmentize import segmentize
@@ -267,7 +306,7 @@ def _device_tracks(tg, device):
 
 
 def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat", adjoint=False,
-           boundary=None, reproducible=False, precision="double"):
+           boundary=None, reproducible=False, precision="double", regions=None):
     if precision not in _capi.PRECISIONS:
         raise ValueError('precision must be "double" or "single"')
     if not isinstance(xs, CrossSections):
@@ -285,6 +324,7 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
     alpha = azimuthal_weights(tg, azim_weights)
     dt = _device_tracks(tg, device)
     cm = _cell_material(tg, cell_material)
+    reg = None if regions is None else _cell_regions(cm, regions)
     sv = _capi.DeviceSolver(dt, cm, xs.sigma_t, xs.sigma_s, xs.nu_sigma_f, xs.chi,
                             pq.sin_theta, pq.weights, alpha)
     if source is not None:
@@ -297,6 +337,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         sv.set_adjoint(True)
     if boundary is not None:
         sv.set_boundary(boundary, track_end_sides(tg))
+    if reg is not None:  # (refused by the library together with reproducible=True or precision="single")
+        sv.set_regions(reg)
     if reproducible:  # (last: the delta buffer is sized for the mode set above)
         sv.set_reproducible(True)
     if precision != "double":  # (refused by the library together with sigma_s1, scheme="linear" or reproducible=True)
@@ -314,6 +356,11 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         eigen = mode == _capi.DeviceSolver.EIGENVALUE
         bnd["balance"] = neutron_balance(xs, cm, f["phi"], f["volumes"], r["k_eff"] if eigen else None, None if eigen else source,
                                          bnd["current_out"], bnd["current_in"], adjoint=adjoint)
+    if reg is not None:
+        eigen = mode == _capi.DeviceSolver.EIGENVALUE
+        bnd["region_current"] = sv.fetch_regions()
+        bnd["region_balance"] = region_balance(xs, cm, reg, f["phi"], f["volumes"], r["k_eff"] if eigen else None, None if eigen else source,
+                                               bnd["region_current"], adjoint=adjoint)
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
@@ -323,7 +370,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
 
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
                      tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
-                     boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double") -> SolverResult:
+                     boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double",
+                     regions=None) -> SolverResult:
     """Power iteration for k_eff on the device.  ``cell_material``: material index per cell [n_cells] (or one index for all,
     or a dict region name -> index over ``tg.mesh.model.cell_region``).  ``polar``: a ``PolarQuadrature`` spec;
     ``azim_weights``: "exact", "equal" or an array.  Uses ``tg.device_tracks`` when ``segmentize(tg, fetch=False)`` has run,
@@ -336,25 +384,29 @@ def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar
     repeated run returns the same bits in every field, at the price of a delta buffer on the device and a slower sweep.
     ``precision="single"``: the sweep carries the angular flux in binary32 (``rt_solver_set_precision``; every sum, the fold, k and
     the residual stay FP64) — k then differs from the FP64 run's in about the seventh digit; not together with ``sigma_s1``,
-    ``scheme="linear"`` or ``reproducible=True`` (``RtError``)."""
+    ``scheme="linear"`` or ``reproducible=True`` (``RtError``).  ``regions``: an int array per cell (ids 0 .. R − 1, R <= 127) or
+    ``"material"`` (``cell_material``): every sweep tallies the partial currents between the regions (``rt_solver_set_regions``) and
+    the result carries ``region_current`` [R + 1, R + 1, G] and ``region_balance``; not together with ``reproducible=True`` or
+    ``precision="single"`` (``RtError``)."""
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible, precision)
+                  adjoint, boundary, reproducible, precision, regions)
 
 
 def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
                        tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
-                       boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double") -> SolverResult:
+                       boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double",
+                       regions=None) -> SolverResult:
     """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
     the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``; with ``adjoint=True`` ``source`` is the
     adjoint source S† (for instance a detector cross section) and ``phi`` the importance φ†: Σ V S† φ = Σ V S φ†.  ``boundary``: a
     ``SolverBoundary``, here also with an incoming flux per side and group (``source`` may then be zero: a run driven from the
-    boundary).  ``reproducible``, ``precision``: as for ``solve_eigenvalue``."""
+    boundary).  ``reproducible``, ``precision``, ``regions``: as for ``solve_eigenvalue``."""
     q = np.asarray(source, np.float64)
     G = xs.n_groups
     if q.ndim == 0 or q.shape == (G,):
         q = np.broadcast_to(q, (tg.mesh.num_cells, G))
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible, precision)
+                  adjoint, boundary, reproducible, precision, regions)
 
 
 # ---- adjoint-weighted integrals ------------------------------------------------------------------------------------------------

@@ -6,7 +6,8 @@ current tallies per iteration) under "albedo_*", with the leakage and the balanc
 forward figures first, then the same runs with the reproducible tallies (rt_solver_set_reproducible) under "reproducible_*", with the
 device memory the switch-on took — delta buffer and cell index — and whether the repeats returned the same bits; `--single`: the
 forward figures first, then the same runs with the single-precision sweep (rt_solver_set_precision) under "single_*", with the bare
-single-precision sweep beside the FP64 one and the deviation of k).
+single-precision sweep beside the FP64 one and the deviation of k; `--regions N`: the forward figures first, then the same runs with
+region currents (rt_solver_set_regions; N <= 3: regions by material, else by cell index modulo N) under "regions_*").
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
@@ -67,6 +68,9 @@ def main():
                     help="after the forward runs, the same runs with the reproducible tallies (rt_solver_set_reproducible)")
     ap.add_argument("--single", action="store_true",
                     help="after the forward runs, the same runs with the single-precision sweep (rt_solver_set_precision); not with --p1 / --linear")
+    ap.add_argument("--regions", type=int, default=0, metavar="N",
+                    help="after the forward runs, the same runs with region currents (rt_solver_set_regions): N = 2 .. 3 regions by material, "
+                         "more by cell index modulo N (N <= 127)")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -170,6 +174,25 @@ def main():
         out["single_k_eff"] = r["k_eff"]
         out["single_k_minus_double"] = r["k_eff"] - out["k_eff"]
         sv.set_precision("double")
+    if a.regions:  # (k_sweep_iface in place of k_sweep: one 4-byte gather per row, the LDS table's share, and the fold of S behind the sweep)
+        mat = _cell_material(tg, cm)
+        reg = np.minimum(mat, a.regions - 1) if a.regions <= 3 else np.arange(len(mat)) % a.regions
+        sv.set_regions(reg.astype(np.int32), a.regions)
+        sv.run(0, 3, 0.0, 0.0)
+        ev_ms, host_ms = [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            r = sv.run(0, a.iters, 0.0, 0.0)
+            host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+            ev_ms.append(r["device_ms"] / r["iterations"])
+        J = sv.fetch_regions()
+        out["regions"] = a.regions
+        out["regions_ms_per_iter_events"] = float(np.median(ev_ms))
+        out["regions_ms_per_iter_host"] = float(np.median(host_ms))
+        out["regions_over_plain_events"] = out["regions_ms_per_iter_events"] / out["ms_per_iter_events"]
+        out["regions_k_eff"] = r["k_eff"]
+        out["regions_net_current_0_to_1"] = float((J[0, 1] - J[1, 0]).sum()) if a.regions > 1 else 0.0
+        sv.set_regions(None)
     if a.steps:
         ev_ms, host_ms = [], []
         for _ in range(a.repeats):
