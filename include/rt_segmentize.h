@@ -602,6 +602,46 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              are those of the TRANSPOSED problem: ψ*(Ω) = ψ†(−Ω), so J†[a → b] = J*[b → a]
  * A solver without regions launches exactly what it always did.
  *
+ * Coarse-mesh acceleration (pCMFD), rt_solver_set_cmfd: off by default.  The regions of rt_solver_set_regions are the coarse cells —
+ * arbitrary cell sets, no Cartesian grid: the scheme works from the partial currents J alone, and an optional coupling D̂ only shapes
+ * its iteration.  All sums per group g; regions a, b < R; φ = φ^{n+½} and k = k^{n+½} as the fold of iteration n leaves them, J the
+ * last sweep's.
+ * Restriction  Φ_a = Σ_{e in a} V_e φ_e,  V_a = Σ_{e in a} V_e,  φ̄_a = Φ_a / V_a;  the coarse reaction rates, flux-volume weighted, from
+ *              the material table the solver holds (adjoint mode: the transposed one):
+ *                  T_a = Σ V_e Σt φ_e,   S_a[g'→g] = Σ V_e Σs[g'→g] φ_{e,g'},   P_a[g] = Σ V_e νΣf_g φ_{e,g},
+ *                  X_a[g'→g] = Σ V_e χ_g νΣf_g' φ_{e,g'}  (the χ-weighted production),   fixed-source runs: Q_a = Σ V_e S_e
+ *              Cells with V_e = 0 drop out.  Work items of at most 256 cells of one region, in ascending cell order, one thread per
+ *              sum; then one workgroup adds the items of a region in order: no atomics
+ * Coupling     D̂_ab[g] >= 0, symmetric, [R][R][G] from the caller (NULL: 0).  For b ≠ a
+ *                  c_ab = (J[a → b] + ½ D̂_ab (φ̄_a + φ̄_b)) / φ̄_a      (> 0 whenever φ̄ > 0, whatever D̂)
+ *                  ℓ_a  = (J[a → R] − J[R → a]) / φ̄_a                 (the net loss through track ends: ~0 under reflection)
+ * Balance      in the unknowns x_a (start value φ̄_a), with r = x / φ̄:
+ *                  (Σ_b c_ab + ℓ_a) x_a − Σ_b c_ba x_b + (T_a − S_a[g→g]) r_a − Σ_{g'≠g} S_a[g'→g] r_{a,g'} = (1/k) Σ_g' X_a[g'→g] r_{a,g'}
+ *              fixed-source runs: Q_a added to the right side, k = 1.  With x = φ̄ and the sweep's own source this is the per-region
+ *              balance above, so a converged iterate is a fixed point for any D̂
+ * Solve        A_g [R][R] of every group: row a holds Σ_b c_ab + ℓ_a + (T_a − S_a[g→g]) / φ̄_a on the diagonal and −c_ba in column b
+ *              (a column-dominant M-matrix when ℓ_a >= 0).  One LU factorisation per group without pivoting (row-wise elimination,
+ *              pivots p = 0 .. R − 1, all groups in step).  Then power iteration from x = φ̄, k: the fission source from the r of the
+ *              previous iteration, Gauss–Seidel over the groups in ascending order (the scattering from g' < g uses the new r), one
+ *              pair of triangular solves per group, k ← k P(r_new) / P(r_old) with P(r) = Σ_a Σ_g P_a[g] r_{a,g}.  It stops after
+ *              cmfd_max_iter iterations, or when |Δk| / k <= cmfd_tol and max |Δx| / max |x| <= 10 cmfd_tol
+ * Skipped      a region with V_a = 0 or a φ̄ that is not > 0 in some group is taken out (identity row and column, no coupling, r = 1)
+ *              and gets f = 1.  A pivot that is not > 0 and finite at step p takes region p out likewise, in all groups (the smallest
+ *              such p of a pass over all groups; the factorisation starts again without it).  A coarse k or an x that is not finite
+ *              and > 0 skips the whole step: f ≡ 1, k stays the fold's.  All three are counted (rt_solver_fetch_cmfd)
+ * Prolongation f_a[g] = 1 + θ (r_{a,g} − 1), θ = relax in (0, 1].  φ_e ← f φ_e; the first moments of the mode (J of first-moment
+ *              scattering, φ⃗ of the linear source) are scaled by the same factor; every ψ_in[(d, u)][g·P + p] is multiplied by the
+ *              f of the region of the traversal's first record (backward: the track's last record; a track without records is left
+ *              alone); k ← the coarse k.  F, the residual and |Δk| / k are formed as without the acceleration, from the prolonged φ
+ *              and the coarse k against the previous iteration's F_e, φ and k
+ * Kernels      rt_cmfd.hip, behind the fold's own: k_cmfd_restrict, k_cmfd_solve (one workgroup; the factors in LDS when all G
+ *              fit beside the vectors, else in global memory with one group's staged into LDS per pair of solves),
+ *              k_cmfd_prolong_cells, k_cmfd_prolong_psi, k_cmfd_finish.  Nothing more comes back to the host per iteration
+ * Refused      without regions, with a run open, together with an incoming boundary flux (from whichever is set second, or from
+ *              rt_solver_begin), for a D̂ that is negative, not finite or asymmetric, a relax outside (0, 1]: RT_ERR_INVALID, the
+ *              solver keeps its state.  Shards, the reproducible tallies and the single-precision sweep are excluded by the regions
+ * A solver without it launches exactly what it always did.
+ *
  * Reproducible tallies, rt_solver_set_reproducible.  The sweep's tallies T (and Tx, Ty) are the one sum of an iteration whose order
  * depends on timing: FP64 atomics into an LDS copy and from there into T.  With the option on, a run is bitwise reproducible:
  * Sweep        a lane neither folds with its neighbours nor adds anywhere: it stores the values w Δψ (w ξ Δψ − ..., as above) of its
@@ -835,6 +875,18 @@ int32_t rt_solver_fetch_regions(rt_solver *solver, double *J);
  * [(R + 1)²·G], valid while regions are set (NULL / 0 without them).  S is complete when the work rt_solver_step_sweep queued is
  * done: a stepwise caller reads it between step_sweep and step_fold.  Does not wait. */
 int32_t rt_solver_region_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
+/* Coarse-mesh acceleration (see above) for the following runs, with the regions that are set as coarse cells.  on = 0 switches it
+ * off (the other arguments are ignored): the solver then launches exactly what one that never had it does.  coupling: D̂ [R][R][G]
+ * (host memory, copied), finite, >= 0 and symmetric in a and b, or NULL for 0; relax: θ in (0, 1]; cmfd_max_iter >= 0 and cmfd_tol >= 0:
+ * the coarse power iteration's bounds.  RT_ERR_INVALID, with a message that names both sides, without regions, with a run open, while
+ * a boundary carries an incoming flux (rt_solver_set_boundary refuses likewise while the acceleration is on, and so does
+ * rt_solver_begin), for a bad D̂, relax or bound, and where the vectors and one group's factor of the coarse solve do not fit the LDS
+ * of a workgroup (R = 127: up to 7 groups); the solver then keeps what it had.  Every rt_solver_set_regions call switches it off. */
+int32_t rt_solver_set_cmfd(rt_solver *solver, int32_t on, const double *coupling, double relax, int32_t cmfd_max_iter, double cmfd_tol);
+/* The last coarse step: factors [R][G] (f_a[g]; NULL: not wanted) and info[3] (NULL: not wanted): the coarse iterations it took, the
+ * regions it left at f = 1, and the steps skipped whole since rt_solver_begin.  Waits for the step.  RT_ERR_INVALID without the
+ * acceleration, or before the first rt_solver_step_fold with it. */
+int32_t rt_solver_fetch_cmfd(rt_solver *solver, double *factors, int32_t *info);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

@@ -336,6 +336,29 @@ function solver_set_regions!(hs::Ptr{Cvoid}, n_regions::Integer, cell_region::Ve
     return nothing
 end
 
+# Coarse-mesh (pCMFD) acceleration over the regions that are set, for the following runs of `hs` (include/rt_segmentize.h,
+# "Coarse-mesh acceleration"): `coupling` is D̂ as a column-major Array{Float64,3} of size (n_groups, R, R) — the library's [a][b][g],
+# symmetric in a and b and >= 0 — or `nothing` for 0; `relax` in (0, 1].  `on = false` switches it off.  Refused without regions, with a
+# run open and together with an incoming boundary flux.
+function solver_set_cmfd!(hs::Ptr{Cvoid}, on::Bool; coupling::Union{Nothing,Array{Float64,3}}=nothing, relax::Float64=1.0,
+                          max_iter::Integer=200, tol::Float64=1e-10)
+    rc = coupling === nothing ?
+         ccall((:rt_solver_set_cmfd, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Int32, Float64), hs, on ? 1 : 0, C_NULL, relax, max_iter, tol) :
+         ccall((:rt_solver_set_cmfd, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}, Float64, Int32, Float64), hs, on ? 1 : 0, coupling, relax, max_iter, tol)
+    rc == 0 || error("rt_solver_set_cmfd failed: " * lasterror())
+    return nothing
+end
+
+# The last coarse step: the factors f[g, a] (column-major view of the library's [a][g]) and (coarse iterations, regions left at
+# f = 1, steps skipped since rt_solver_begin)
+function solver_fetch_cmfd(hs::Ptr{Cvoid}, n_regions::Integer, n_groups::Integer)
+    f = Array{Float64}(undef, n_groups, n_regions)
+    info = zeros(Int32, 3)
+    rc = ccall((:rt_solver_fetch_cmfd, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}), hs, f, info)
+    rc == 0 || error("rt_solver_fetch_cmfd failed: " * lasterror())
+    return f, (Int(info[1]), Int(info[2]), Int(info[3]))
+end
+
 # The last sweep's partial currents J[g, b, a] (column-major view of the library's [a][b][g]: from region a to region b, index
 # n_regions + 1: outside the track) of a solver with `n_regions` regions and `n_groups` groups
 function solver_fetch_regions(hs::Ptr{Cvoid}, n_regions::Integer, n_groups::Integer)

@@ -17,7 +17,7 @@ from .quadrature import AzimuthalQuadrature
 from .trackgenerator import (Backward, Forward, Segment, Track, TrackGenerator, bc_bwd, bc_fwd,
                              dir_next_track_bwd, dir_next_track_fwd, trace, track_end_sides)
 from .segmentize import RTOL_DEFAULT, SegmentStore, segmentize
-from .solver import (CrossSections, PolarQuadrature, SolverBoundary, SolverResult, azimuthal_weights, exact_azimuthal_weights,
+from .solver import (Cmfd, CrossSections, PolarQuadrature, SolverBoundary, SolverResult, azimuthal_weights, exact_azimuthal_weights, diffusion_coupling,
                      kinetics_parameters, perturbation_reactivity, solve_eigenvalue, solve_fixed_source)
 from .distributed import ShardedSolver
 
@@ -28,6 +28,6 @@ __all__ = [
     "Track", "Segment",
     "CrossSections", "PolarQuadrature", "SolverResult", "azimuthal_weights", "exact_azimuthal_weights",
     "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "ShardedSolver",
-    "SolverBoundary", "track_end_sides",
+    "SolverBoundary", "track_end_sides", "Cmfd", "diffusion_coupling",
     "Forward", "Backward", "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd",
 ]

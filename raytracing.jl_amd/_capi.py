@@ -35,6 +35,7 @@ SYMBOLS = (
     "rt_solver_set_adjoint", "rt_solver_bilinear", "rt_solver_set_reproducible", "rt_solver_set_precision",
     "rt_solver_set_boundary", "rt_solver_fetch_boundary", "rt_solver_boundary_pointers",
     "rt_solver_set_regions", "rt_solver_fetch_regions", "rt_solver_region_pointers",
+    "rt_solver_set_cmfd", "rt_solver_fetch_cmfd",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -291,6 +292,10 @@ def lib():
         L.rt_solver_fetch_regions.argtypes = [_vp, _dp]
         L.rt_solver_region_pointers.restype = C.c_int32
         L.rt_solver_region_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
+        L.rt_solver_set_cmfd.restype = C.c_int32
+        L.rt_solver_set_cmfd.argtypes = [_vp, C.c_int32, _dp, C.c_double, C.c_int32, C.c_double]
+        L.rt_solver_fetch_cmfd.restype = C.c_int32
+        L.rt_solver_fetch_cmfd.argtypes = [_vp, _dp, _ip]
     except AttributeError:
         if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
             raise
@@ -917,6 +922,33 @@ class DeviceSolver:
         out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
         out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
         return out
+
+    def set_cmfd(self, on=True, coupling=None, relax=1.0, max_iter=200, tol=1e-10):
+        """``rt_solver_set_cmfd`` for the following runs: the coarse-mesh (pCMFD) acceleration over the regions that are set.
+        ``coupling``: D̂ [R, R, G], symmetric and >= 0 (None: 0); ``relax``: θ in (0, 1]; ``max_iter``, ``tol``: the bounds of the
+        coarse power iteration.  ``on`` False: off."""
+        L = lib()
+        if not hasattr(L, "rt_solver_set_cmfd"):
+            raise RtError(f"{LIB_PATH} has no rt_solver_set_cmfd: the library is older than this binding")
+        if not on:
+            _check(L.rt_solver_set_cmfd(self._open(), 0, None, 1.0, 0, 0.0))
+            return
+        cp = None
+        if coupling is not None:
+            R = getattr(self, "n_regions", 0)
+            co = np.ascontiguousarray(coupling, np.float64)
+            if co.shape != (R, R, self.G):
+                raise ValueError(f"coupling must have shape [R, R, G] = {(R, R, self.G)}, got {co.shape}")
+            cp = co.ctypes.data_as(_dp)
+        _check(L.rt_solver_set_cmfd(self._open(), 1, cp, float(relax), int(max_iter), float(tol)))
+
+    def fetch_cmfd(self) -> dict:
+        """``rt_solver_fetch_cmfd``: ``factors`` [R, G] of the last coarse step, the coarse ``iterations`` it took, the
+        ``skipped_regions`` it left at f = 1 and the ``skipped_steps`` since ``begin``."""
+        R = getattr(self, "n_regions", 0)
+        f = np.empty((max(R, 1), self.G)); info = np.zeros(3, np.int32)
+        _check(lib().rt_solver_fetch_cmfd(self._open(), f.ctypes.data_as(_dp), info.ctypes.data_as(_ip)))
+        return dict(factors=f[:R], iterations=int(info[0]), skipped_regions=int(info[1]), skipped_steps=int(info[2]))
 
     def fetch_current(self) -> np.ndarray:
         """``rt_solver_fetch_current``: the net current [n_cells, G, 2] of the last run (with first-moment scattering)."""

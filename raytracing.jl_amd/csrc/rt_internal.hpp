@@ -324,6 +324,27 @@ struct DSweep {
     int32_t if_R, if_pad;
 };
 
+// The coarse-mesh step of rt_solver (rt_cmfd.hip; rt_solver_set_cmfd): what its five kernels read and write, by value.
+constexpr int kCmfdBlock = 256;   // threads of every kernel of the step
+constexpr int kCmfdChunk = 256;   // cells per work item of the restriction, at most
+constexpr int kCmfdLdsCap = 160 * 1024 - 1024;  // bytes of LDS k_cmfd_solve may ask for (the sweep's own cap on gfx950)
+struct DCmfd {
+    int32_t R, G, P, n_cells, eigen, max_iter, resident;
+    int64_t n;                                   // tracks
+    double theta, tol;
+    const int32_t *mat, *cell_region;            // [n_cells]
+    const double *tab, *vol, *ext;               // the solver's material table, V_e, the external source (fixed-source runs; or null)
+    double *phi, *prod, *mom, *psi_in;           // φ, F_e, the mode's first moments [n_cells][G][2] (or null), ψ_in [2][n][G·P]
+    const double *phi_old, *prod_old, *scal_prev;  // φ, F_e and the scalars of the previous iteration
+    double *scal, *partial;                      // the solver's scalars and the fold's block partials
+    const int32_t *cells, *item_begin, *item_end, *reg_first;  // the cells sorted by region; the work items; the items of a region
+    double *part, *coarse, *lu, *fac, *out;      // [items][NV], [R][NV], [G][R][R], f [R][G], [0]: k of the step
+    int32_t *info;                               // [0] coarse iterations, [1] regions with f = 1, [2] steps skipped so far
+    const double *J, *coupling;                  // the last sweep's J [(R + 1)²][G]; D̂ [R][R][G] (or null)
+    const int64_t *offsets;                      // the compact records: first record and count of every track, the records' cells
+    const int32_t *counts, *element;
+};
+
 }  // namespace rt
 
 // ------------------------------------------------------------------- handles -------------
@@ -598,6 +619,9 @@ int ensure_rows_from_compact(rt_tracks *t);  // rt_sweep.hip
 // rt_sweep_f32.hip: one pass of the single-precision sweep kernel over `gp` components from a.g0 (a.use_lds: the tallies' LDS copy)
 int launch_sweep_f32(const rt::DSweep &a, int gp, size_t smem, int waves, unsigned blocks, hipStream_t s);
 int launch_sweep_iface(const rt::DSweep &a, SweepMode mode, size_t smem, int waves, unsigned blocks, hipStream_t s);  // rt_sweep_iface.hip
+// rt_cmfd.hip: the LDS k_cmfd_solve asks for (0: does not fit; *resident: all G factors live there), and the coarse step of one fold
+size_t cmfd_solve_lds(int32_t R, int32_t G, bool *resident);
+int launch_cmfd_step(rt::DCmfd c, int32_t n_items, unsigned cblocks, hipStream_t s);
 // rt_sweep.hip: the row variant a solver's sweep (input 0) reads now, its rows made and the cell index built for it (once per
 // segmentation and variant); *slots: row slots of the variant.  RT_ERR_INVALID where the reproducible tallies cannot be served
 int sweep_repro_prepare(rt_tracks *t, int64_t *slots);

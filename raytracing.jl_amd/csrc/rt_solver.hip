@@ -573,6 +573,14 @@ struct rt_solver {
     bool reg_tallied = false, run_reg = false;  // reg_J holds a sweep of the last run; the open run tallies
     DevBuf<int32_t> reg_cell;
     DevBuf<double> reg_S, reg_J;
+    std::vector<int32_t> h_reg;  // the cells' regions as given (rt_solver_set_cmfd sorts the cells by them)
+    // coarse-mesh acceleration (rt_solver_set_cmfd): the regions' cell lists cut into work items, the step's workspaces (see
+    // rt::DCmfd), the previous iteration's φ, F_e and scalars, and what rt_solver_fetch_cmfd returns
+    bool cm_on = false, run_cm = false, cm_stepped = false, cm_has_coupling = false;
+    int32_t cm_items = 0, cm_max_iter = 0;
+    double cm_theta = 1.0, cm_tol = 0.0;
+    DevBuf<int32_t> cm_cells, cm_item_begin, cm_item_end, cm_reg_first, cm_info;
+    DevBuf<double> cm_part, cm_coarse, cm_lu, cm_fac, cm_out, cm_coupling, cm_phi_old, cm_prod_old, cm_prev;
     // reproducible tallies (rt_solver_set_reproducible): the sweep's per-pass delta buffer, 2 · row slots · NT · width doubles, held
     // from the switch-on to the switch-off (or rt_solver_destroy)
     bool repro = false;
@@ -883,6 +891,12 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
         RT_HIP(hipMemsetAsync(S->reg_J.p, 0, (size_t)(S->reg_R + 1) * (S->reg_R + 1) * G * sizeof(double), s));
     }
     S->reg_tallied = false;
+    const bool cm = reg && S->cm_on;
+    if (cm) {  // (the setters keep the two apart; a solver that got here with both is refused like them)
+        if (bnd && S->bnd_inc) { set_error("%s: the coarse-mesh acceleration is on (rt_solver_set_cmfd) and a boundary has an incoming flux (rt_solver_set_boundary): the two together are not supported", who); return RT_ERR_INVALID; }
+        RT_HIP(hipMemsetAsync(S->cm_info.p, 0, 4 * sizeof(int32_t), s));
+    }
+    S->cm_stepped = false;
     t->sw_loan = loan;
     S->bnd_tallied = false;
     if (bnd) RT_HIP(hipMemsetAsync(S->bnd_J.p, 0, (size_t)2 * S->bnd_S * G * sizeof(double), s));
@@ -891,7 +905,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
                            (const int8_t *)S->bnd_side_entry.p, (const double *)S->bnd_beta.p, (const double *)S->bnd_incv.p,
                            (const double *)nullptr, t->sw_psi_in.p, 2 * n, G, P, n);
     S->k_hist.clear();
-    S->run_eigen = eigen; S->run_mode = smode; S->run_bnd = bnd; S->run_reg = reg;
+    S->run_eigen = eigen; S->run_mode = smode; S->run_bnd = bnd; S->run_reg = reg; S->run_cm = cm;
     S->it = 0; S->last_k = 1.0; S->last_res = INFINITY; S->last_dk = INFINITY;
     // φ⁰ = 1, the components' Σt / sin θ, F⁰
     RT_HIP(hipMemsetAsync(S->prod.p, 0, (size_t)std::max(1, nc) * sizeof(double), s));
@@ -955,6 +969,12 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
     rt_tracks *t = S->t;
     hipStream_t s = t->mesh->stream;
     const int32_t G = d.G, P = d.P, nc = d.nc;
+    const bool cm = S->run_cm && nc > 0;
+    if (cm) {  // the previous iteration's φ, F_e and scalars: what the residual and |Δk| / k of the prolonged iterate refer to
+        RT_HIP(hipMemcpyAsync(S->cm_phi_old.p, S->phi.p, (size_t)d.ncg * sizeof(double), hipMemcpyDeviceToDevice, s));
+        RT_HIP(hipMemcpyAsync(S->cm_prod_old.p, S->prod.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, s));
+        RT_HIP(hipMemcpyAsync(S->cm_prev.p, S->scal.p, rt::kSolveScalars * sizeof(double), hipMemcpyDeviceToDevice, s));
+    }
     hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
                        (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P,
                        S->partial.p);
@@ -966,6 +986,22 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
                            (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->gr.p,
                            (const double *)S->cmat.p, (const double *)S->cinv.p, nc, G, P, S->mom.p);
     hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)d.cblocks, 0, S->run_eigen ? 1 : 0, S->scal.p);
+    if (cm) {  // the coarse step on φ^{n+½}, k^{n+½} and the last sweep's J: restriction, solve, prolongation, the scalars again
+        rt::DCmfd c{};
+        c.R = S->reg_R; c.G = G; c.P = P; c.n_cells = nc; c.eigen = S->run_eigen ? 1 : 0; c.max_iter = S->cm_max_iter;
+        c.n = t->n; c.theta = S->cm_theta; c.tol = S->cm_tol;
+        c.mat = S->mat.p; c.cell_region = S->reg_cell.p; c.tab = S->tab.p; c.vol = S->vol.p;
+        c.ext = (!S->run_eigen && S->has_ext) ? S->ext.p : nullptr;
+        c.phi = S->phi.p; c.prod = S->prod.p; c.psi_in = t->sw_psi_in.p;
+        c.mom = S->run_mode == SweepMode::P1 ? S->J.p : (S->run_mode == SweepMode::Linear ? S->mom.p : nullptr);
+        c.phi_old = S->cm_phi_old.p; c.prod_old = S->cm_prod_old.p; c.scal_prev = S->cm_prev.p; c.scal = S->scal.p; c.partial = S->partial.p;
+        c.cells = S->cm_cells.p; c.item_begin = S->cm_item_begin.p; c.item_end = S->cm_item_end.p; c.reg_first = S->cm_reg_first.p;
+        c.part = S->cm_part.p; c.coarse = S->cm_coarse.p; c.lu = S->cm_lu.p; c.fac = S->cm_fac.p; c.out = S->cm_out.p; c.info = S->cm_info.p;
+        c.J = S->reg_J.p; c.coupling = S->cm_has_coupling ? S->cm_coupling.p : nullptr;
+        c.offsets = t->offsets.p; c.counts = t->counts.p; c.element = t->element.p;
+        if (int rc = launch_cmfd_step(c, S->cm_items, d.cblocks, s)) return rc;
+        S->cm_stepped = true;
+    }
     RT_HIP(hipMemcpyAsync(S->h_scal, S->scal.p, rt::kSolveScalars * sizeof(double), hipMemcpyDeviceToHost, s));
     RT_HIP(hipStreamSynchronize(s));
     RT_HIP(hipGetLastError());
@@ -1223,6 +1259,7 @@ static int32_t solver_set_boundary_impl(rt_solver *S, int32_t n_sides, const int
         }
         any_inc = any_inc || (incoming && incoming[i] > 0.0);
     }
+    if (any_inc && S->cm_on) { set_error("%s: an incoming flux, and the coarse-mesh acceleration is on (rt_solver_set_cmfd): the two together are not supported", who); return RT_ERR_INVALID; }
     const size_t n2 = (size_t)(2 * n);
     std::vector<int8_t> side_end(std::max<size_t>(1, n2), -1), side_start(std::max<size_t>(1, n2), -1), side_entry(std::max<size_t>(1, n2), -1);
     std::vector<int32_t> src(std::max<size_t>(1, n2), -1);
@@ -1310,7 +1347,7 @@ static int32_t solver_set_regions_impl(rt_solver *S, int32_t n_regions, const in
     if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
     if (int rc = solver_check_epoch(S, who)) return rc;
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the regions cannot change under it", who); return RT_ERR_INVALID; }
-    if (n_regions == 0 || !cell_region) { S->reg_R = 0; S->reg_tallied = false; return RT_SUCCESS; }
+    if (n_regions == 0 || !cell_region) { S->reg_R = 0; S->reg_tallied = false; S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
     if (n_regions < 1 || n_regions > rtsweep::kMaxRegions) { set_error("%s: bad arguments (n_regions %d, need 1 .. %d)", who, n_regions, rtsweep::kMaxRegions); return RT_ERR_INVALID; }
     if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and region currents — an atomic sum — together with them are not supported", who); return RT_ERR_INVALID; }
     if (S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision: another kernel), and region currents together with it are not supported", who); return RT_ERR_INVALID; }
@@ -1330,6 +1367,7 @@ static int32_t solver_set_regions_impl(rt_solver *S, int32_t n_regions, const in
     DevBuf<double> d_S, d_J;
     const size_t pairs = (size_t)(n_regions + 1) * (n_regions + 1);
     std::vector<int32_t> one(1, 0);
+    std::vector<int32_t> keep(cell_region, cell_region + nc);
     if (int rc = upload(d_cell, nc ? cell_region : one.data(), std::max<size_t>(1, nc), s)) return rc;
     RT_HIP(d_S.reserve(pairs * S->G * S->P)); RT_HIP(d_J.reserve(pairs * S->G));
     RT_HIP(hipMemsetAsync(d_S.p, 0, pairs * S->G * S->P * sizeof(double), s));
@@ -1337,7 +1375,104 @@ static int32_t solver_set_regions_impl(rt_solver *S, int32_t n_regions, const in
     RT_HIP(hipStreamSynchronize(s));  // (the caller's array may go)
     S->reg_cell = std::move(d_cell); S->reg_S = std::move(d_S); S->reg_J = std::move(d_J);
     S->reg_R = n_regions; S->reg_tallied = false;
+    S->h_reg.swap(keep);
+    S->cm_on = false; S->cm_stepped = false;  // (the coarse cells have changed: rt_solver_set_cmfd comes again)
     return RT_SUCCESS;
+}
+
+// The coarse-mesh acceleration of the following runs: the regions' cell lists (cells ascending) cut into work items of at most
+// kCmfdChunk cells, and the step's workspaces.  Into fresh buffers: a refusal or a failure leaves the solver what it had.
+static int32_t solver_set_cmfd_impl(rt_solver *S, int32_t on, const double *coupling, double relax, int32_t max_iter, double tol) {
+    const char *who = "rt_solver_set_cmfd";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the acceleration cannot change under it", who); return RT_ERR_INVALID; }
+    if (!on) { S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
+    const int32_t R = S->reg_R, G = S->G, nc = S->n_cells;
+    if (R <= 0) { set_error("%s: no regions are set (rt_solver_set_regions comes first: its regions are the coarse cells)", who); return RT_ERR_INVALID; }
+    if (S->bnd_S > 0 && S->bnd_inc) { set_error("%s: a boundary has an incoming flux (rt_solver_set_boundary), and the coarse-mesh acceleration together with it is not supported", who); return RT_ERR_INVALID; }
+    if (!(relax > 0.0 && relax <= 1.0)) { set_error("%s: relax = %g (must lie in (0, 1])", who, relax); return RT_ERR_INVALID; }
+    if (max_iter < 0 || !(tol >= 0.0) || !std::isfinite(tol)) { set_error("%s: bad arguments (cmfd_max_iter %d, cmfd_tol %g)", who, max_iter, tol); return RT_ERR_INVALID; }
+    if (coupling)
+        for (int32_t a = 0; a < R; ++a)
+            for (int32_t b = 0; b < R; ++b)
+                for (int32_t g = 0; g < G; ++g) {
+                    const double v = coupling[((size_t)a * R + b) * G + g], w = coupling[((size_t)b * R + a) * G + g];
+                    if (!std::isfinite(v) || v < 0.0) { set_error("%s: coupling[%d][%d][%d] = %g (must be finite and >= 0)", who, a, b, g, v); return RT_ERR_INVALID; }
+                    if (v != w) { set_error("%s: coupling[%d][%d][%d] = %g but coupling[%d][%d][%d] = %g (must be symmetric)", who, a, b, g, v, b, a, g, w); return RT_ERR_INVALID; }
+                }
+    if (!cmfd_solve_lds(R, G, nullptr)) {
+        set_error("%s: %d regions and %d groups: the vectors and one group's factor of the coarse solve (%zu bytes) do not fit the LDS of a workgroup (%d bytes)",
+                  who, R, G, ((size_t)4 * R * G + 2 * (size_t)R + (size_t)R * R) * sizeof(double), rt::kCmfdLdsCap);
+        return RT_ERR_INVALID;
+    }
+    // the cells of every region, ascending, and the work items over them (a region without cells has none)
+    std::vector<int32_t> cells((size_t)std::max(1, nc)), first((size_t)R + 1, 0), ib, ie;
+    std::vector<int32_t> count((size_t)R + 1, 0);
+    for (int32_t e = 0; e < nc; ++e) ++count[(size_t)S->h_reg[(size_t)e] + 1];
+    for (int32_t a = 0; a < R; ++a) count[(size_t)a + 1] += count[(size_t)a];
+    {
+        std::vector<int32_t> at(count.begin(), count.end() - 1);
+        for (int32_t e = 0; e < nc; ++e) cells[(size_t)at[(size_t)S->h_reg[(size_t)e]]++] = e;
+    }
+    for (int32_t a = 0; a < R; ++a) {
+        first[(size_t)a] = (int32_t)ib.size();
+        for (int32_t b = count[(size_t)a]; b < count[(size_t)a + 1]; b += rt::kCmfdChunk) {
+            ib.push_back(b);
+            ie.push_back(std::min(b + rt::kCmfdChunk, count[(size_t)a + 1]));
+        }
+    }
+    first[(size_t)R] = (int32_t)ib.size();
+    const int32_t items = (int32_t)ib.size();
+    if (ib.empty()) { ib.push_back(0); ie.push_back(0); }
+    rt_tracks *t = S->t;
+    if (int rc = finish_call(t)) return rc;
+    RT_HIP(hipSetDevice(t->mesh->device));
+    hipStream_t s = t->mesh->stream;
+    const size_t NV = (size_t)4 * G + (size_t)2 * G * G + 1;
+    DevBuf<int32_t> d_cells, d_ib, d_ie, d_first, d_info;
+    DevBuf<double> d_part, d_coarse, d_lu, d_fac, d_out, d_coup, d_phi, d_prod, d_prev;
+    if (int rc = upload(d_cells, cells.data(), cells.size(), s)) return rc;
+    if (int rc = upload(d_ib, ib.data(), ib.size(), s)) return rc;
+    if (int rc = upload(d_ie, ie.data(), ie.size(), s)) return rc;
+    if (int rc = upload(d_first, first.data(), first.size(), s)) return rc;
+    if (coupling)
+        if (int rc = upload(d_coup, coupling, (size_t)R * R * G, s)) return rc;
+    RT_HIP(d_info.reserve(4));
+    RT_HIP(d_part.reserve(std::max<size_t>(1, (size_t)items) * NV)); RT_HIP(d_coarse.reserve((size_t)R * NV));
+    RT_HIP(d_lu.reserve((size_t)G * R * R)); RT_HIP(d_fac.reserve((size_t)R * G)); RT_HIP(d_out.reserve(rt::kSolveScalars));
+    RT_HIP(d_phi.reserve(std::max<size_t>(1, (size_t)nc * G))); RT_HIP(d_prod.reserve((size_t)std::max(1, nc))); RT_HIP(d_prev.reserve(rt::kSolveScalars));
+    RT_HIP(hipMemsetAsync(d_info.p, 0, 4 * sizeof(int32_t), s));
+    RT_HIP(hipStreamSynchronize(s));  // (the host vectors and the caller's array may go)
+    S->cm_cells = std::move(d_cells); S->cm_item_begin = std::move(d_ib); S->cm_item_end = std::move(d_ie); S->cm_reg_first = std::move(d_first);
+    S->cm_info = std::move(d_info); S->cm_part = std::move(d_part); S->cm_coarse = std::move(d_coarse); S->cm_lu = std::move(d_lu);
+    S->cm_fac = std::move(d_fac); S->cm_out = std::move(d_out); S->cm_phi_old = std::move(d_phi); S->cm_prod_old = std::move(d_prod);
+    S->cm_prev = std::move(d_prev);
+    if (coupling) S->cm_coupling = std::move(d_coup);
+    S->cm_has_coupling = coupling != nullptr;
+    S->cm_items = items; S->cm_theta = relax; S->cm_max_iter = max_iter; S->cm_tol = tol;
+    S->cm_on = true; S->cm_stepped = false;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_cmfd(rt_solver *solver, int32_t on, const double *coupling, double relax, int32_t cmfd_max_iter, double cmfd_tol) {
+    return guarded("rt_solver_set_cmfd", [&] { return solver_set_cmfd_impl(solver, on, coupling, relax, cmfd_max_iter, cmfd_tol); });
+}
+
+int32_t rt_solver_fetch_cmfd(rt_solver *solver, double *factors, int32_t *info) {
+    if (!solver) { set_error("rt_solver_fetch_cmfd: null solver"); return RT_ERR_INVALID; }
+    if (!solver->cm_on || !solver->cm_stepped) {
+        set_error("rt_solver_fetch_cmfd: no coarse step yet (rt_solver_set_cmfd, then a run or rt_solver_step_fold)");
+        return RT_ERR_INVALID;
+    }
+    return guarded("rt_solver_fetch_cmfd", [&]() -> int32_t {
+        RT_HIP(hipSetDevice(solver->device));
+        hipStream_t s = solver->t->mesh->stream;
+        if (factors) RT_HIP(hipMemcpyAsync(factors, solver->cm_fac.p, (size_t)solver->reg_R * solver->G * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (info) RT_HIP(hipMemcpyAsync(info, solver->cm_info.p, 3 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));
+        return RT_SUCCESS;
+    });
 }
 
 int32_t rt_solver_set_regions(rt_solver *solver, int32_t n_regions, const int32_t *cell_region) {

@@ -18,6 +18,9 @@ on that side, whatever ``trace`` linked there) and, in fixed-source runs, an iso
 carries the partial currents per side and group and the neutron balance (``rt_solver_set_boundary``).
 With ``regions=...`` (an int per cell, or ``"material"``) every sweep also tallies the partial currents between the cell regions
 (``rt_solver_set_regions``): ``SolverResult.region_current`` and the balance of every region, ``region_balance``.
+With ``cmfd=True`` (or a ``Cmfd``) on top of ``regions=...`` every iteration also solves the partial-current coarse-mesh balance
+over the regions and prolongs its solution onto φ, k and the boundary fluxes (``rt_solver_set_cmfd``): the same answer in fewer
+iterations; ``diffusion_coupling`` builds an optional coupling D̂ from the mesh.
 """
 from __future__ import annotations
 
@@ -30,7 +33,7 @@ import numpy as np
 from . import _capi
 from .trackgenerator import SIDE_NAMES, TrackGenerator, track_end_sides
 
-__all__ = ["CrossSections", "PolarQuadrature", "SolverBoundary", "SolverResult", "exact_azimuthal_weights", "azimuthal_weights",
+__all__ = ["CrossSections", "PolarQuadrature", "SolverBoundary", "SolverResult", "Cmfd", "diffusion_coupling", "exact_azimuthal_weights", "azimuthal_weights",
            "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "neutron_balance", "region_balance"]
 
 
@@ -239,6 +242,84 @@ def region_balance(xs, cell_material, cell_region, phi, volumes, k_eff, source, 
 
 
 @dataclass
+class Cmfd:
+    """The coarse-mesh (pCMFD) acceleration of ``include/rt_segmentize.h`` over ``regions=``: ``coupling`` D̂ [R, R, G], symmetric
+    and >= 0 (None: 0; ``diffusion_coupling`` builds one), ``relax`` θ in (0, 1], and the coarse power iteration's ``max_iter`` and
+    ``tol``."""
+    coupling: Optional[np.ndarray] = None
+    relax: float = 1.0
+    max_iter: int = 200
+    tol: float = 1e-10
+
+    def check(self, n_regions: int, n_groups: int):
+        """Raises ``ValueError`` for what ``rt_solver_set_cmfd`` would refuse in these fields."""
+        if not (0.0 < float(self.relax) <= 1.0):
+            raise ValueError("Cmfd.relax must lie in (0, 1]")
+        if int(self.max_iter) < 0 or not (float(self.tol) >= 0.0) or not math.isfinite(float(self.tol)):
+            raise ValueError("Cmfd.max_iter must be >= 0 and Cmfd.tol finite and >= 0")
+        if self.coupling is not None:
+            co = np.asarray(self.coupling, np.float64)
+            if co.shape != (n_regions, n_regions, n_groups):
+                raise ValueError(f"Cmfd.coupling must have shape [R, R, G] = {(n_regions, n_regions, n_groups)}, got {co.shape}")
+            if not np.all(np.isfinite(co)) or np.any(co < 0):
+                raise ValueError("every Cmfd.coupling entry must be finite and >= 0")
+            if not np.array_equal(co, co.transpose(1, 0, 2)):
+                raise ValueError("Cmfd.coupling must be symmetric in its two regions")
+
+
+def _as_cmfd(cmfd):
+    if cmfd is None or cmfd is False:
+        return None
+    if cmfd is True:
+        return Cmfd()
+    if isinstance(cmfd, Cmfd):
+        return cmfd
+    raise TypeError("cmfd must be True, False, None or a Cmfd")
+
+
+def diffusion_coupling(tg, cell_region, xs, cell_material) -> np.ndarray:
+    """A diffusion-like coupling D̂ [R, R, G] for ``Cmfd(coupling=...)``, on the host from the mesh: A_ab the summed length of the mesh
+    edges between cells of regions a and b, d_ab the distance of the volume-weighted (cell areas) region centroids, D_a the
+    volume-weighted 1 / (3 Σt) of the region, and D̂_ab = A_ab · 2 D_a D_b / ((D_a + D_b) d_ab); 0 for regions that share no edge
+    and on the diagonal.  It only shapes the coarse iteration (a preconditioner): the converged answer does not depend on it."""
+    mesh = tg.mesh
+    cn = np.asarray(mesh.cell_nodes, np.int64) - 1
+    nc = cn.shape[0]
+    reg = np.asarray(cell_region, np.int64)
+    mat = np.asarray(_cell_material(tg, cell_material), np.int64)
+    if reg.shape != (nc,) or mat.shape != (nc,):
+        raise ValueError("cell_region and cell_material must have one entry per cell")
+    if reg.size and reg.min() < 0:
+        raise ValueError("region ids must be >= 0")
+    R, G = int(reg.max(initial=-1)) + 1, xs.n_groups
+    x, y = mesh.x[cn], mesh.y[cn]
+    area = 0.5 * np.abs((x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (x[:, 2] - x[:, 0]) * (y[:, 1] - y[:, 0]))
+    Va = np.bincount(reg, weights=area, minlength=R)
+    Vs = np.where(Va > 0, Va, 1.0)
+    cen = np.stack([np.bincount(reg, weights=area * x.mean(1), minlength=R) / Vs, np.bincount(reg, weights=area * y.mean(1), minlength=R) / Vs], 1)
+    D = np.stack([np.bincount(reg, weights=area / (3.0 * xs.sigma_t[mat, g]), minlength=R) / Vs for g in range(G)], 1)  # [R, G]
+    # every edge (sorted node pair) with the cells on its two sides
+    ed = np.sort(np.concatenate([cn[:, [0, 1]], cn[:, [1, 2]], cn[:, [2, 0]]]), axis=1)
+    owner = np.tile(np.arange(nc), 3)
+    order = np.lexsort((ed[:, 1], ed[:, 0]))
+    ed, owner = ed[order], owner[order]
+    same = (ed[1:] == ed[:-1]).all(1)
+    c0, c1, e2 = owner[:-1][same], owner[1:][same], ed[:-1][same]
+    length = np.hypot(mesh.x[e2[:, 0]] - mesh.x[e2[:, 1]], mesh.y[e2[:, 0]] - mesh.y[e2[:, 1]])
+    cross = reg[c0] != reg[c1]
+    A = np.zeros((R, R))
+    np.add.at(A, (reg[c0][cross], reg[c1][cross]), length[cross])
+    A = A + A.T
+    out = np.zeros((R, R, G))
+    a, b = np.nonzero(A > 0)
+    dab = np.hypot(cen[a, 0] - cen[b, 0], cen[a, 1] - cen[b, 1])
+    ok = dab > 0
+    a, b, dab = a[ok], b[ok], dab[ok]
+    out[a, b] = A[a, b, None] * 2.0 * D[a] * D[b] / ((D[a] + D[b]) * dab[:, None])
+    return 0.5 * (out + out.transpose(1, 0, 2))  # (the two orders of a pair differ by rounding: exactly symmetric)
+
+
+@dataclass
 class SolverResult:
     k_eff: Optional[float]        # None in fixed-source mode
     phi: np.ndarray               # [n_cells, G]; eigenvalue mode: scaled to Σ_e V_e Σ_g νΣf φ = 1
@@ -262,6 +343,7 @@ class SolverResult:
     precision: str = "double"     # "single": the run swept the angular flux in binary32 (rt_solver_set_precision); sums, fold, k in FP64
     region_current: Optional[np.ndarray] = None  # regions=...: the last sweep's partial currents J [R + 1, R + 1, G], J[a, b] from a to b (R: outside)
     region_balance: Optional[dict] = None        # ... region_balance: gain, removal, leakage, net_inflow, defect [R, G]; both None without
+    cmfd: Optional[dict] = None   # cmfd=...: the last coarse step's factors [R, G], its iterations, skipped_regions, skipped_steps
 
 
 def _cell_material(tg, cell_material):
@@ -306,7 +388,10 @@ def _device_tracks(tg, device):
 
 
 def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat", adjoint=False,
-           boundary=None, reproducible=False, precision="double", regions=None):
+           boundary=None, reproducible=False, precision="double", regions=None, cmfd=None):
+    acc = _as_cmfd(cmfd)
+    if acc is not None and regions is None:
+        raise ValueError("cmfd needs regions= (its coarse cells)")
     if precision not in _capi.PRECISIONS:
         raise ValueError('precision must be "double" or "single"')
     if not isinstance(xs, CrossSections):
@@ -325,6 +410,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
     dt = _device_tracks(tg, device)
     cm = _cell_material(tg, cell_material)
     reg = None if regions is None else _cell_regions(cm, regions)
+    if acc is not None:
+        acc.check(int(reg.max(initial=-1)) + 1, xs.n_groups)
     sv = _capi.DeviceSolver(dt, cm, xs.sigma_t, xs.sigma_s, xs.nu_sigma_f, xs.chi,
                             pq.sin_theta, pq.weights, alpha)
     if source is not None:
@@ -339,6 +426,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         sv.set_boundary(boundary, track_end_sides(tg))
     if reg is not None:  # (refused by the library together with reproducible=True or precision="single")
         sv.set_regions(reg)
+    if acc is not None:  # (refused by the library together with an incoming boundary flux)
+        sv.set_cmfd(True, acc.coupling, acc.relax, acc.max_iter, acc.tol)
     if reproducible:  # (last: the delta buffer is sized for the mode set above)
         sv.set_reproducible(True)
     if precision != "double":  # (refused by the library together with sigma_s1, scheme="linear" or reproducible=True)
@@ -361,6 +450,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         bnd["region_current"] = sv.fetch_regions()
         bnd["region_balance"] = region_balance(xs, cm, reg, f["phi"], f["volumes"], r["k_eff"] if eigen else None, None if eigen else source,
                                                bnd["region_current"], adjoint=adjoint)
+    if acc is not None and it > 0:
+        bnd["cmfd"] = sv.fetch_cmfd()
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
@@ -371,7 +462,7 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
                      tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
                      boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double",
-                     regions=None) -> SolverResult:
+                     regions=None, cmfd=None) -> SolverResult:
     """Power iteration for k_eff on the device.  ``cell_material``: material index per cell [n_cells] (or one index for all,
     or a dict region name -> index over ``tg.mesh.model.cell_region``).  ``polar``: a ``PolarQuadrature`` spec;
     ``azim_weights``: "exact", "equal" or an array.  Uses ``tg.device_tracks`` when ``segmentize(tg, fetch=False)`` has run,
@@ -387,26 +478,29 @@ def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar
     ``scheme="linear"`` or ``reproducible=True`` (``RtError``).  ``regions``: an int array per cell (ids 0 .. R − 1, R <= 127) or
     ``"material"`` (``cell_material``): every sweep tallies the partial currents between the regions (``rt_solver_set_regions``) and
     the result carries ``region_current`` [R + 1, R + 1, G] and ``region_balance``; not together with ``reproducible=True`` or
-    ``precision="single"`` (``RtError``)."""
+    ``precision="single"`` (``RtError``).  ``cmfd``: True or a ``Cmfd`` — the partial-current coarse-mesh acceleration over the
+    regions (``rt_solver_set_cmfd``; needs ``regions``): the same converged k and φ in fewer iterations; the result carries the last
+    coarse step under ``cmfd``."""
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible, precision, regions)
+                  adjoint, boundary, reproducible, precision, regions, cmfd)
 
 
 def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
                        tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
                        boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double",
-                       regions=None) -> SolverResult:
+                       regions=None, cmfd=None) -> SolverResult:
     """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
     the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``; with ``adjoint=True`` ``source`` is the
     adjoint source S† (for instance a detector cross section) and ``phi`` the importance φ†: Σ V S† φ = Σ V S φ†.  ``boundary``: a
     ``SolverBoundary``, here also with an incoming flux per side and group (``source`` may then be zero: a run driven from the
-    boundary).  ``reproducible``, ``precision``, ``regions``: as for ``solve_eigenvalue``."""
+    boundary).  ``reproducible``, ``precision``, ``regions``, ``cmfd``: as for ``solve_eigenvalue`` (``cmfd`` not together with an
+    incoming flux)."""
     q = np.asarray(source, np.float64)
     G = xs.n_groups
     if q.ndim == 0 or q.shape == (G,):
         q = np.broadcast_to(q, (tg.mesh.num_cells, G))
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible, precision, regions)
+                  adjoint, boundary, reproducible, precision, regions, cmfd)
 
 
 # ---- adjoint-weighted integrals ------------------------------------------------------------------------------------------------

@@ -7,7 +7,10 @@ forward figures first, then the same runs with the reproducible tallies (rt_solv
 device memory the switch-on took — delta buffer and cell index — and whether the repeats returned the same bits; `--single`: the
 forward figures first, then the same runs with the single-precision sweep (rt_solver_set_precision) under "single_*", with the bare
 single-precision sweep beside the FP64 one and the deviation of k; `--regions N`: the forward figures first, then the same runs with
-region currents (rt_solver_set_regions; N <= 3: regions by material, else by cell index modulo N) under "regions_*").
+region currents (rt_solver_set_regions; N <= 3: regions by material, else by cell index modulo N; `--region-grid B`: a B x B grid of
+bands over the domain instead, N = B²) under "regions_*"; `--cmfd` (needs `--regions` or `--region-grid`): then the same runs with the
+coarse-mesh acceleration over those regions (rt_solver_set_cmfd) under "cmfd_*", and the iterations and device time to tol_k = tol_flux =
+`--tol` of the run with regions alone against the accelerated one).
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
@@ -71,9 +74,18 @@ def main():
     ap.add_argument("--regions", type=int, default=0, metavar="N",
                     help="after the forward runs, the same runs with region currents (rt_solver_set_regions): N = 2 .. 3 regions by material, "
                          "more by cell index modulo N (N <= 127)")
+    ap.add_argument("--region-grid", type=int, default=0, metavar="B", help="regions on a B x B grid of bands over the domain (B² <= 127) instead of --regions N")
+    ap.add_argument("--cmfd", action="store_true", help="after the runs with regions, the same runs with the coarse-mesh acceleration (rt_solver_set_cmfd)")
+    ap.add_argument("--cmfd-iters", type=int, default=200, help="cmfd_max_iter of --cmfd")
+    ap.add_argument("--cmfd-tol", type=float, default=1e-10, help="cmfd_tol of --cmfd")
+    ap.add_argument("--tol", type=float, default=1e-6, help="tol_k and tol_flux of the convergence runs of --cmfd")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
+    if a.region_grid:
+        a.regions = a.region_grid * a.region_grid
+    if a.cmfd and not a.regions:
+        ap.error("--cmfd needs --regions N or --region-grid B (its coarse cells)")
 
     import raytracing_jl_amd as rt
     from raytracing_jl_amd import _capi
@@ -177,6 +189,11 @@ def main():
     if a.regions:  # (k_sweep_iface in place of k_sweep: one 4-byte gather per row, the LDS table's share, and the fold of S behind the sweep)
         mat = _cell_material(tg, cm)
         reg = np.minimum(mat, a.regions - 1) if a.regions <= 3 else np.arange(len(mat)) % a.regions
+        if a.region_grid:
+            cn, Bg = tg.mesh.cell_nodes - 1, a.region_grid
+            cx, cy = tg.mesh.x[cn].mean(1), tg.mesh.y[cn].mean(1)
+            band = lambda v, lo, hi: np.minimum((Bg * (v - lo) / (hi - lo)).astype(np.int64), Bg - 1)
+            reg = Bg * band(cx, tg.mesh.x.min(), tg.mesh.x.max()) + band(cy, tg.mesh.y.min(), tg.mesh.y.max())
         sv.set_regions(reg.astype(np.int32), a.regions)
         sv.run(0, 3, 0.0, 0.0)
         ev_ms, host_ms = [], []
@@ -192,6 +209,27 @@ def main():
         out["regions_over_plain_events"] = out["regions_ms_per_iter_events"] / out["ms_per_iter_events"]
         out["regions_k_eff"] = r["k_eff"]
         out["regions_net_current_0_to_1"] = float((J[0, 1] - J[1, 0]).sum()) if a.regions > 1 else 0.0
+        if a.cmfd:  # (five more kernels behind the fold, the coarse solve in one workgroup; then what it buys: iterations to --tol)
+            conv = sv.run(0, 5000, a.tol, a.tol)
+            out["regions_iterations_to_tol"], out["regions_ms_to_tol"], out["regions_converged"] = conv["iterations"], conv["device_ms"], conv["converged"]
+            out["regions_k_eff_at_tol"] = conv["k_eff"]
+            sv.set_cmfd(True, None, 1.0, a.cmfd_iters, a.cmfd_tol)
+            sv.run(0, 3, 0.0, 0.0)
+            ev_ms, host_ms = [], []
+            for _ in range(a.repeats):
+                t0 = time.perf_counter()
+                r = sv.run(0, a.iters, 0.0, 0.0)
+                host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+                ev_ms.append(r["device_ms"] / r["iterations"])
+            out["cmfd_ms_per_iter_events"] = float(np.median(ev_ms))
+            out["cmfd_ms_per_iter_host"] = float(np.median(host_ms))
+            out["cmfd_over_regions_events"] = out["cmfd_ms_per_iter_events"] / out["regions_ms_per_iter_events"]
+            conv = sv.run(0, 5000, a.tol, a.tol)
+            info = sv.fetch_cmfd()
+            out["cmfd_iterations_to_tol"], out["cmfd_ms_to_tol"], out["cmfd_converged"] = conv["iterations"], conv["device_ms"], conv["converged"]
+            out["cmfd_k_eff_at_tol"] = conv["k_eff"]
+            out["cmfd_last_step"] = {k: v for k, v in info.items() if k != "factors"}
+            sv.set_cmfd(False)
         sv.set_regions(None)
     if a.steps:
         ev_ms, host_ms = [], []
