@@ -701,6 +701,38 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  * Speed        measured at the headline configuration: not faster than the FP64 sweep beyond noise; off by default
  * RT_PRECISION_DOUBLE (the default) launches exactly what a solver that never had the option launches.
  *
+ * Volume correction, rt_solver_set_volume_correction: off by default.  The chord lengths the solver's sweeps read are renormalised so
+ * that the tracked area of every cell equals its geometric area (the first-order error of the track spacing leaves the reaction
+ * rates and k).  rt_segmentize, fill_volumes, Segment.ℓ, the compact records and the handle's own (ℓ, cell) rows are never written:
+ * the solver owns a second ℓ array, and a bare rt_sweep is unaffected.
+ * Exact area   A_e = ½ |(x1 − x0)(y2 − y0) − (x2 − x0)(y1 − y0)| from the mesh's node coordinates, FP64, in that order
+ * Tracked      L[e][a] = Σ_{u: azim[u] = a} Σ_{rec of u in e} ℓ, a = 1 .. n_azim_2 as azim[u] gives it (supplementary angles are
+ *              separate columns), over the (ℓ, cell) rows the solver's sweeps read: an FP64 atomic sum (lanes of a wave-row with the
+ *              same (cell, angle) are summed first)
+ * "angle"      RT_VOLUME_CORRECTION_ANGLE: f[e][a] = A_e / (δ_a L[e][a]), δ_a the delta_s of the sweep's default weight; f = 1 where
+ *              L[e][a] = 0 (no chord of that angle crosses the cell: an unseen pair, counted) and where A_e = 0 (counted)
+ * "cell"       RT_VOLUME_CORRECTION_CELL: f[e][a] = f_e = A_e / V_e for every a, V_e = Σ_a w_a L[e][a] with the volumes' weights
+ *              w_a = 2 α_a δ_a; f = 1 where V_e = 0 (counted) and where A_e = 0.  The three counts do not depend on the mode
+ * Rows         ℓ'[slot] = ℓ[slot] · f[cell[slot]][azim of the slot's track]: one multiplication
+ * Volumes      V'_e = Σ_a w_a (f[e][a] L[e][a]), a ascending, one thread per cell, no atomics.  "angle": a cell that every angle sees
+ *              has V'_e = A_e Σ_a 2 α_a = A_e to rounding, a cell with unseen pairs A_e Σ_{a seen} 2 α_a; "cell": V'_e = A_e wherever
+ *              V_e > 0.  rt_solver_fetch returns V' as volumes
+ * Everything behind the rows uses ℓ' and V' and is otherwise what it was: τ, the tallies, the fold, F, k, the residual, the boundary
+ * currents, S and J of the regions, the coarse-mesh restriction, rt_solver_bilinear.
+ * When         once per segmentation and mode, inside rt_solver_begin (rt_solver_run), before anything else of the run is queued;
+ *              again only when the mode or the rows the sweep reads have changed since
+ * Works with   eigenvalue and fixed-source runs, first-moment scattering, adjoint mode (one ℓ' serves both directions),
+ *              rt_solver_set_boundary, rt_solver_set_regions, rt_solver_set_cmfd, the single-precision sweep, the stepwise calls
+ * Refused      (open) with the linear source — its sweep forms a record's midpoint from the running sum of ℓ ("Geometry" above), and
+ *              scaled chords would move the midpoints off the track —, with the reproducible tallies (L is an atomic sum) and on a
+ *              shard's track set (L would need a sum over the shards before the factors): RT_ERR_INVALID with a message that names
+ *              both sides, from whichever is switched on second; the solver keeps the state it had
+ * Rows' kind   ℓ' scales (ℓ, cell) rows: rt_sweep_rows_kind 1 or 2.  A run whose sweeps would read rows of kind 0 — "sweep_rows" 0,
+ *              "sweep_ell" 0, or the first pass over the 20-B rows of a march by exact steps — is refused by rt_solver_begin with
+ *              RT_ERR_INVALID before anything is queued, as the region currents are
+ * Off again    RT_VOLUME_CORRECTION_OFF restores the rows' own ℓ and the track-based volumes, bit-equal to a solver that never had
+ *              the option, and frees every buffer the correction held.  A solver without the option launches exactly what it always did.
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -760,6 +792,9 @@ typedef struct rt_solver rt_solver;
 #define RT_SOLVE_FIXED_SOURCE 1
 #define RT_PRECISION_DOUBLE 0
 #define RT_PRECISION_SINGLE 1
+#define RT_VOLUME_CORRECTION_OFF 0
+#define RT_VOLUME_CORRECTION_ANGLE 1
+#define RT_VOLUME_CORRECTION_CELL 2
 
 typedef struct rt_solver_result {
     double k_eff;       /* last k (1 in fixed-source mode)                                          */
@@ -887,6 +922,19 @@ int32_t rt_solver_set_cmfd(rt_solver *solver, int32_t on, const double *coupling
  * regions it left at f = 1, and the steps skipped whole since rt_solver_begin.  Waits for the step.  RT_ERR_INVALID without the
  * acceleration, or before the first rt_solver_step_fold with it. */
 int32_t rt_solver_fetch_cmfd(rt_solver *solver, double *factors, int32_t *info);
+/* Volume correction (see above) for the following runs: RT_VOLUME_CORRECTION_OFF, _ANGLE or _CELL.  Nothing is computed here: the
+ * next rt_solver_begin makes the tables.  Off: the track-based volumes are restored and the tables freed.  RT_ERR_INVALID for
+ * another value, while the linear source or the reproducible tallies are on (those setters refuse likewise while the correction is
+ * set), on a shard's track set, with a run open or after the tracks were segmentized again; the solver then keeps what it had. */
+int32_t rt_solver_set_volume_correction(rt_solver *solver, int32_t mode);
+/* The tables of the last rt_solver_begin with the correction: area [n_cells] (A_e), factor [n_cells][n_azim_2] (f), stats[2] (min f,
+ * max f over the table) and info[3] (unseen (cell, angle) pairs, cells with A = 0, cells with V = 0).  Any pointer may be NULL.
+ * RT_ERR_INVALID without the correction, or before the first rt_solver_begin with the mode that is set. */
+int32_t rt_solver_fetch_volume_correction(rt_solver *solver, double *area, double *factor, double *stats, int32_t *info);
+/* Device addresses ptrs_dev[3] and element counts lens[3] (either may be NULL) of [0] area [n_cells], [1] factor [n_cells·n_azim_2] and
+ * [2] ℓ' by row slot, valid from the rt_solver_begin that made them to the next change of the mode (NULL / 0 before, and without the
+ * correction); lens[1] / lens[0] is n_azim_2.  Does not wait. */
+int32_t rt_solver_volume_correction_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

@@ -349,6 +349,36 @@ function solver_set_cmfd!(hs::Ptr{Cvoid}, on::Bool; coupling::Union{Nothing,Arra
     return nothing
 end
 
+# Volume correction for the following runs of `hs` (include/rt_segmentize.h, "Volume correction"): `mode` 0 off, 1 "angle" (chord
+# lengths scaled per cell and azimuthal angle to the cells' exact areas), 2 "cell" (one factor per cell).  Refused together with the
+# linear source, the reproducible tallies and on a shard's track set.
+function solver_set_volume_correction!(hs::Ptr{Cvoid}, mode::Integer)
+    rc = ccall((:rt_solver_set_volume_correction, LIB), Int32, (Ptr{Cvoid}, Int32), hs, mode)
+    rc == 0 || error("rt_solver_set_volume_correction failed: " * lasterror())
+    return nothing
+end
+
+# The tables of the last begin with the correction: the areas A[e], the factors f[a, e] (column-major view of the library's [e][a]),
+# (min f, max f) and (unseen (cell, angle) pairs, cells with A = 0, cells with V = 0)
+function solver_fetch_volume_correction(hs::Ptr{Cvoid}, n_cells::Integer, n_azim_2::Integer)
+    area = Vector{Float64}(undef, n_cells)
+    f = Array{Float64}(undef, n_azim_2, n_cells)
+    stats = zeros(Float64, 2)
+    info = zeros(Int32, 3)
+    rc = ccall((:rt_solver_fetch_volume_correction, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), hs, area, f, stats, info)
+    rc == 0 || error("rt_solver_fetch_volume_correction failed: " * lasterror())
+    return area, f, (stats[1], stats[2]), (Int(info[1]), Int(info[2]), Int(info[3]))
+end
+
+# Device addresses (C_NULL before the first begin with the correction) and element counts of the areas, the factors and ℓ' by row slot
+function solver_volume_correction_pointers(hs::Ptr{Cvoid})
+    ptrs = fill(C_NULL, 3)
+    lens = zeros(Int64, 3)
+    rc = ccall((:rt_solver_volume_correction_pointers, LIB), Int32, (Ptr{Cvoid}, Ptr{Ptr{Cvoid}}, Ptr{Int64}), hs, ptrs, lens)
+    rc == 0 || error("rt_solver_volume_correction_pointers failed: " * lasterror())
+    return ptrs, lens
+end
+
 # The last coarse step: the factors f[g, a] (column-major view of the library's [a][g]) and (coarse iterations, regions left at
 # f = 1, steps skipped since rt_solver_begin)
 function solver_fetch_cmfd(hs::Ptr{Cvoid}, n_regions::Integer, n_groups::Integer)

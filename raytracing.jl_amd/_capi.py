@@ -36,6 +36,7 @@ SYMBOLS = (
     "rt_solver_set_boundary", "rt_solver_fetch_boundary", "rt_solver_boundary_pointers",
     "rt_solver_set_regions", "rt_solver_fetch_regions", "rt_solver_region_pointers",
     "rt_solver_set_cmfd", "rt_solver_fetch_cmfd",
+    "rt_solver_set_volume_correction", "rt_solver_fetch_volume_correction", "rt_solver_volume_correction_pointers",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -45,6 +46,7 @@ SYMBOLS_WITH_DIGITS = ("rt_solver_set_scatter_p1",)
 RT_PRECISION_DOUBLE = 0
 RT_PRECISION_SINGLE = 1
 PRECISIONS = {"double": RT_PRECISION_DOUBLE, "single": RT_PRECISION_SINGLE}
+VOLUME_CORRECTIONS = {None: 0, "angle": 1, "cell": 2}  # RT_VOLUME_CORRECTION_OFF, _ANGLE, _CELL
 
 RT_TRACK_OK = 0
 RT_TRACK_LOCATE_FAILED = 1
@@ -296,6 +298,16 @@ def lib():
         L.rt_solver_set_cmfd.argtypes = [_vp, C.c_int32, _dp, C.c_double, C.c_int32, C.c_double]
         L.rt_solver_fetch_cmfd.restype = C.c_int32
         L.rt_solver_fetch_cmfd.argtypes = [_vp, _dp, _ip]
+    except AttributeError:
+        if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
+            raise
+    try:
+        L.rt_solver_set_volume_correction.restype = C.c_int32
+        L.rt_solver_set_volume_correction.argtypes = [_vp, C.c_int32]
+        L.rt_solver_fetch_volume_correction.restype = C.c_int32
+        L.rt_solver_fetch_volume_correction.argtypes = [_vp, _dp, _dp, _dp, _ip]
+        L.rt_solver_volume_correction_pointers.restype = C.c_int32
+        L.rt_solver_volume_correction_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
     except AttributeError:
         if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
             raise
@@ -949,6 +961,45 @@ class DeviceSolver:
         f = np.empty((max(R, 1), self.G)); info = np.zeros(3, np.int32)
         _check(lib().rt_solver_fetch_cmfd(self._open(), f.ctypes.data_as(_dp), info.ctypes.data_as(_ip)))
         return dict(factors=f[:R], iterations=int(info[0]), skipped_regions=int(info[1]), skipped_steps=int(info[2]))
+
+    def set_volume_correction(self, mode="angle"):
+        """``rt_solver_set_volume_correction`` for the following runs: ``"angle"`` (chord lengths scaled per cell and azimuthal
+        angle so that every tracked area equals the cell's area), ``"cell"`` (one factor per cell, A_e / V_e), None: off — the
+        track-based volumes and the rows' own ℓ again.  Refused together with the linear source or the reproducible tallies, and on
+        a shard's track set."""
+        L = lib()
+        if mode is False:
+            mode = None
+        if mode not in VOLUME_CORRECTIONS:
+            raise ValueError('volume_correction must be None, "angle" or "cell"')
+        if not hasattr(L, "rt_solver_set_volume_correction"):
+            raise RtError(f"{LIB_PATH} has no rt_solver_set_volume_correction: the library is older than this binding")
+        _check(L.rt_solver_set_volume_correction(self._open(), VOLUME_CORRECTIONS[mode]))
+        self.volume_correction = mode
+
+    def fetch_volume_correction(self) -> dict:
+        """``rt_solver_fetch_volume_correction``: ``area`` [n_cells] (A_e), ``factor`` [n_cells, n_azim_2] (f), ``f_min``, ``f_max``
+        and the counts ``unseen_pairs``, ``zero_area_cells``, ``zero_volume_cells`` of the last ``begin`` with the correction."""
+        lens = self.volume_correction_pointers()["lens"]
+        if not lens["factor"]:
+            raise RtError("rt_solver_fetch_volume_correction: no run with the volume correction yet (set_volume_correction, then begin or run)")
+        n2 = lens["factor"] // max(1, lens["area"])  # (the library's own count of azimuthal indices)
+        area = np.empty(self.n_cells); f = np.empty((self.n_cells, n2)); st = np.zeros(2); info = np.zeros(3, np.int32)
+        _check(lib().rt_solver_fetch_volume_correction(self._open(), area.ctypes.data_as(_dp), f.ctypes.data_as(_dp), st.ctypes.data_as(_dp),
+                                                       info.ctypes.data_as(_ip)))
+        return dict(area=area, factor=f, f_min=float(st[0]), f_max=float(st[1]), unseen_pairs=int(info[0]), zero_area_cells=int(info[1]),
+                    zero_volume_cells=int(info[2]))
+
+    def volume_correction_pointers(self) -> dict:
+        """``rt_solver_volume_correction_pointers``: device addresses (0: no tables yet) of ``area`` [n_cells], ``factor``
+        [n_cells·n_azim_2] and ``ell_rows`` (ℓ' by row slot), and their element counts under ``lens``."""
+        ptrs = (_vp * 3)()
+        lens = (C.c_int64 * 3)()
+        _check(lib().rt_solver_volume_correction_pointers(self._open(), ptrs, lens))
+        names = ("area", "factor", "ell_rows")
+        out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
+        out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
+        return out
 
     def fetch_current(self) -> np.ndarray:
         """``rt_solver_fetch_current``: the net current [n_cells, G, 2] of the last run (with first-moment scattering)."""

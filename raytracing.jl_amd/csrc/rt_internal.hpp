@@ -5,6 +5,7 @@
 //   rt_materialise.hip k_materialise_lin: a two-phase call's records in output order
 //   rt_sweep.hip       rt_sweep: k_sweep, k_sweep_link, the sweep's host code and entry points
 //   rt_sweep_plan.hpp  what an rt_sweep call decides (rows, pass width and shape, refusals): host-only, a pure function
+//   rt_volcorr.hip     rt_solver's volume correction: tracked lengths, factors, corrected volumes, ℓ' (k_vc_tally / _factor / _apply)
 //   rt_solver.hip      rt_solver: source iteration (k_eff / fixed source) around rt_sweep, fold / source / reduction kernels
 //   rt_segmentize.hip  handles, rt_tracks_create, rt_segmentize (the call's host logic), fetches, statistics
 #pragma once
@@ -345,6 +346,23 @@ struct DCmfd {
     const int32_t *counts, *element;
 };
 
+// The volume correction of rt_solver (rt_volcorr.hip; rt_solver_set_volume_correction): what its kernels read and write, by value.
+constexpr int kVcPartials = 8;  // doubles per block partial of k_vc_factor: unseen pairs, cells with A = 0, cells with V = 0, min f, max f, (pad)
+struct DVolCorr {
+    int64_t n, slots;                        // tracks; row slots of the rows read (every slot index is checked against it)
+    int32_t n_waves, n_cells, N2, mode;      // march waves, cells, azimuthal indices, 1 "angle" / 2 "cell"
+    const int32_t *perm, *counts, *azim;     // march slot -> uid; records and azimuthal index (1-based) per uid
+    const int32_t *ctab, *cell_rows;         // the rows' chunk table [n_waves][kMaxChunks] and their cell words (|word| − 1: the cell)
+    const double *ell_rows;                  // ℓ of every row slot, as the sweep reads it
+    const double *x, *y;                     // the mesh's node coordinates ...
+    const int32_t *cn;                       // ... and the cells' nodes [n_cells][3], 0-based
+    const double *delta_s, *wvol;            // [N2]: δ_a, and the volumes' weights 2 α_a δ_a
+    double *L, *f;                           // [n_cells][N2]: tracked lengths, factors
+    double *area, *vol;                      // [n_cells]: A_e, V'_e
+    double *ell_out;                         // ℓ' of every row slot of a record
+    double *partial, *stats;                 // [blocks][kVcPartials]; [kVcPartials]: the three counts, min f, max f
+};
+
 }  // namespace rt
 
 // ------------------------------------------------------------------- handles -------------
@@ -360,6 +378,19 @@ struct SweepLoan {
     const int32_t *region = nullptr;  // region currents (rt_solver_set_regions): the cells' regions [n_cells] (DSweep if_region),
     double *iface_S = nullptr;        // the sweep's tally S [(R + 1)][(R + 1)][components], zeroed by every sweep (DSweep if_S),
     int32_t n_regions = 0;            // and R (0: off)
+    // volume correction (rt_solver_set_volume_correction): the solver's ℓ' of every row slot (DSweep ell_rows in place of sw_ell), made
+    const double *vc_ell = nullptr;   // from the rows `vc_rows` as they stood at generation `vc_gen` (rt_tracks::sw_rows_gen)
+    rtsweep::SweepRows vc_rows = rtsweep::SweepRows::Records;
+    uint64_t vc_gen = 0;
+};
+
+// rt_sweep.hip sweep_rows_for_loan: the (ℓ, cell) rows a sweep under a loan would read, made and described
+struct SweepRowsView {
+    rtsweep::SweepRows rows = rtsweep::SweepRows::Records;
+    const int32_t *ctab = nullptr, *cell_rows = nullptr;  // chunk table [n_waves][kMaxChunks]; cell words by row slot
+    const double *ell_rows = nullptr;                     // ℓ by row slot
+    int64_t slots = 0;                                    // row slots behind the two arrays
+    uint64_t gen = 0;                                     // rt_tracks::sw_rows_gen of these rows
 };
 
 struct rt_mesh {
@@ -555,6 +586,7 @@ struct rt_tracks {
     DevBuf<int32_t> sw_ctab, sw_plan;  // rows made from the COMPACT records (rt_sweep.hip ensure_rows_from_compact): their own chunk table
     bool sw_rowsc_valid = false;       // ... sw_ell / sw_cell hold those rows for the last rt_segmentize
     int64_t sw_rowsc_slots = 0;        // ... and their chunk table spans this many row slots
+    uint64_t sw_rows_gen = 0;          // counts every (re)making of sw_ell's content: a solver's ℓ' (SweepLoan::vc_ell) names the one it scaled
     // reproducible tallies (rt_solver_set_reproducible; rt_sweep.hip sweep_repro_prepare): the cell index of the last rt_segmentize
     // — CSR by cell, every cell's row slots in ascending (track uid, record index) — for the row variant `sw_ridx_kind` (0: none
     // built; 1 the staging pool's slots, 2 the rows made from the compact records, 3 the compact records where they lie)
@@ -622,6 +654,12 @@ int launch_sweep_iface(const rt::DSweep &a, SweepMode mode, size_t smem, int wav
 // rt_cmfd.hip: the LDS k_cmfd_solve asks for (0: does not fit; *resident: all G factors live there), and the coarse step of one fold
 size_t cmfd_solve_lds(int32_t R, int32_t G, bool *resident);
 int launch_cmfd_step(rt::DCmfd c, int32_t n_items, unsigned cblocks, hipStream_t s);
+// rt_volcorr.hip: L = 0, k_vc_tally, k_vc_factor (`cblocks` workgroups of kVcBlock cells), k_vc_reduce, k_vc_apply — queued on `s`
+int launch_volcorr(const rt::DVolCorr &a, unsigned cblocks, hipStream_t s);
+unsigned volcorr_blocks(int32_t n_cells);
+// rt_sweep.hip: what a sweep of `G` components with input 0 under `loan` would read — planned as rt_sweep plans it (refused with its
+// message), the rows made as rt_sweep makes them (once per segmentation) — for a solver that scales their ℓ before its first sweep
+int sweep_rows_for_loan(rt_tracks *t, int32_t G, const SweepLoan &loan, bool volcorr, SweepRowsView *out);
 // rt_sweep.hip: the row variant a solver's sweep (input 0) reads now, its rows made and the cell index built for it (once per
 // segmentation and variant); *slots: row slots of the variant.  RT_ERR_INVALID where the reproducible tallies cannot be served
 int sweep_repro_prepare(rt_tracks *t, int64_t *slots);

@@ -904,6 +904,7 @@ int ensure_rows(rt_tracks *t) {
     RT_HIP(hipGetLastError());
     t->sw_ell_valid = true;
     t->sw_rowsc_valid = false;  // (the same buffers)
+    ++t->sw_rows_gen;
     return RT_SUCCESS;
 }
 

@@ -971,6 +971,7 @@ struct SegmentizeCall {
         t->completion_order = false;
         t->sw_ell_valid = false;
         t->sw_rowsc_valid = false;
+        ++t->sw_rows_gen;
         t->sw_ridx_kind = 0;
         t->cplan = rt_tracks::CompactPlan{};
         t->last_split = 0;

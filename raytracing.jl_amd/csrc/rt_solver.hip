@@ -18,6 +18,10 @@
 // source's geometry are summed through the same cell index.  Without the option the solver launches what it always did.
 // With regions (rt_solver_set_regions) the sweep it queues runs k_sweep_iface (rt_sweep_iface.hip), which also tallies the partial
 // currents between the cell regions into S, and k_solver_iface_fold forms J from S behind it.  Without them: what it always did.
+// With the volume correction (rt_solver_set_volume_correction) rt_solver_begin runs the kernels of rt_volcorr.hip once per segmentation
+// and mode: the tracked lengths L[e][a] over the rows the sweep reads, the factors f, V' into `vol` (the track-based volumes are kept
+// aside) and ℓ' = f ℓ into a buffer of the solver's, which the run's sweeps read in place of the rows' ℓ (SweepLoan::vc_ell).  Without
+// it the solver launches what it always did.
 // Flat, first-moment scattering or linear source is one choice of three, a SweepMode (each setter switches only its own mode off and
 // refuses to switch it on over the other).  What a run's rt_sweep calls need to know — that mode, the linear source's geometry, the
 // reproducible tallies' delta buffer, single precision — goes to the handle as one SweepLoan (rt_internal.hpp) and comes back whole.
@@ -589,6 +593,16 @@ struct rt_solver {
     bool single = false;
     // ... and V_e as rt_solver_create summed it (FP64 atomics), kept while `vol` holds the sums in the index's order instead
     DevBuf<double> vol_atomic;
+    // volume correction (rt_solver_set_volume_correction): the mode as set (0 off, 1 "angle", 2 "cell") and the mode the tables hold
+    // (0: none), made from the rows `vc_rows` at generation `vc_gen`; L, f [n_cells][N2], A [n_cells], ℓ' by row slot, the factor
+    // kernel's block partials and its reduced counts / extremes; `vc_applied`: `vol` holds V', `vc_vol_track` the track-based V_e
+    int32_t vc_mode = 0, vc_done_mode = 0;
+    rtsweep::SweepRows vc_rows = rtsweep::SweepRows::Records;
+    uint64_t vc_gen = 0;
+    int64_t vc_slots = 0;  // row slots ℓ' covers
+    bool vc_applied = false;
+    DevBuf<double> vc_L, vc_f, vc_area, vc_ell, vc_vol_track, vc_part, vc_stats, vc_wvol, vc_delta;
+    double vc_h_stats[rt::kVcPartials] = {0, 0, 0, 1, 1, 0, 0, 0};
     std::vector<double> k_hist;
     // the run in progress (rt_solver_begin ... rt_solver_end): `open` while this solver holds the handle's sweep state
     // (rt_tracks::sw_loan.borrower points back here), `swept` between rt_solver_step_sweep and rt_solver_step_fold
@@ -828,6 +842,57 @@ int solver_repro_reserve(rt_solver *S, const char *who, int min_nv = 1) {
     return RT_SUCCESS;
 }
 
+// The volume correction of the run that begins: refused where the setters would have refused it (the links may have become a shard's
+// since), the rows the run's sweeps will read planned and made (rt_sweep's own refusals for rows without ℓ), and — when the mode, or
+// the rows, are not the ones the tables were made from — the kernels of rt_volcorr.hip queued.  `vol` holds V' from here on; the
+// track-based volumes go aside once.
+int solver_volcorr_prepare(rt_solver *S, const char *who) {
+    rt_tracks *t = S->t;
+    rt_mesh *m = t->mesh;
+    hipStream_t s = m->stream;
+    if (S->mode == SweepMode::Linear) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction) and the linear source is on (rt_solver_set_linear_source): the two together are not supported", who); return RT_ERR_INVALID; }
+    if (S->repro) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction) and the reproducible tallies are on (rt_solver_set_reproducible): the two together are not supported", who); return RT_ERR_INVALID; }
+    if (t->sw_shard) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction) and the track set is a shard (some next uid is 0): the tracked lengths of a shard are not the cells': not supported", who); return RT_ERR_INVALID; }
+    const int32_t nc = S->n_cells, N2 = S->N2;
+    if ((int64_t)nc * N2 >= (1ll << 31)) { set_error("%s: the volume correction's table of %d cells x %d azimuthal indices has 2^31 entries or more", who, nc, N2); return RT_ERR_INVALID; }
+    SweepLoan probe;
+    probe.mode = S->mode; probe.repro = S->repro; probe.f32 = S->single; probe.n_regions = S->reg_R;
+    SweepRowsView v;
+    if (int rc = sweep_rows_for_loan(t, S->G * S->P, probe, true, &v)) return rc;
+    if (S->vc_done_mode == S->vc_mode && S->vc_applied && S->vc_rows == v.rows && S->vc_gen == v.gen) return RT_SUCCESS;
+    S->vc_done_mode = 0;
+    const size_t ncs = (size_t)std::max<int32_t>(1, nc), tab = ncs * (size_t)N2;
+    const unsigned cblocks = volcorr_blocks(nc);
+    RT_HIP(S->vc_L.reserve(tab)); RT_HIP(S->vc_f.reserve(tab)); RT_HIP(S->vc_area.reserve(ncs));
+    RT_HIP(S->vc_part.reserve((size_t)cblocks * rt::kVcPartials)); RT_HIP(S->vc_stats.reserve(rt::kVcPartials));
+    RT_HIP(S->vc_vol_track.reserve(ncs));
+    if (S->vc_ell.reserve((size_t)std::max<int64_t>(1, v.slots)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: no device memory for the volume correction's ℓ' of %lld row slots (%lld bytes)", who, (long long)v.slots, (long long)v.slots * 8);
+        return RT_ERR_HIP;
+    }
+    if (int rc = upload(S->vc_wvol, S->h_wvol.data(), S->h_wvol.size(), s)) return rc;
+    if (int rc = upload(S->vc_delta, t->h_delta_s.data(), t->h_delta_s.size(), s)) return rc;
+    if (!S->vc_applied) {
+        RT_HIP(hipMemcpyAsync(S->vc_vol_track.p, S->vol.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, s));
+        S->vc_applied = true;
+    }
+    rt::DVolCorr a{};
+    a.n = t->n; a.slots = v.slots; a.n_waves = (int32_t)((t->n + 63) / 64); a.n_cells = nc; a.N2 = N2; a.mode = S->vc_mode;
+    a.perm = t->perm.p; a.counts = t->counts.p; a.azim = t->azim.p;
+    a.ctab = v.ctab; a.cell_rows = v.cell_rows; a.ell_rows = v.ell_rows;
+    a.x = m->x.p; a.y = m->y.p; a.cn = m->cn.p;
+    a.delta_s = S->vc_delta.p; a.wvol = S->vc_wvol.p;
+    a.L = S->vc_L.p; a.f = S->vc_f.p; a.area = S->vc_area.p; a.vol = S->vol.p; a.ell_out = S->vc_ell.p;
+    a.partial = S->vc_part.p; a.stats = S->vc_stats.p;
+    if (int rc = launch_volcorr(a, cblocks, s)) return rc;
+    RT_HIP(hipMemcpyAsync(S->vc_h_stats, S->vc_stats.p, rt::kVcPartials * sizeof(double), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));  // (the host vectors of the uploads may go; the counts are on the host)
+    RT_HIP(hipGetLastError());
+    S->vc_done_mode = S->vc_mode; S->vc_rows = v.rows; S->vc_gen = v.gen; S->vc_slots = v.slots;
+    return RT_SUCCESS;
+}
+
 int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
     if (S->open) solver_release(S);  // (a second begin starts afresh)
     rt_tracks *t = S->t;
@@ -850,6 +915,8 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
     const SolverDims d(S);
     const int32_t G = d.G, P = d.P, nc = d.nc, C = d.C;
     const int64_t n = t->n;
+    if (S->vc_mode)  // (refused, or ℓ' and V' made, before this run queues anything else: φ⁰'s F⁰ below already weighs with V')
+        if (int rc = solver_volcorr_prepare(S, who)) return rc;
     // the handle's sweep state: C components, zero boundary fluxes, the solver's track weights
     const size_t npsi = (size_t)std::max<int64_t>(1, 2 * n * C), nxs = std::max<size_t>(1, (size_t)nc * C);
     RT_HIP(t->sw_psi_in.reserve(npsi)); RT_HIP(t->sw_psi_out.reserve(npsi)); RT_HIP(t->sw_phi.reserve(nxs));
@@ -897,6 +964,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
         RT_HIP(hipMemsetAsync(S->cm_info.p, 0, 4 * sizeof(int32_t), s));
     }
     S->cm_stepped = false;
+    if (S->vc_mode) { loan.vc_ell = S->vc_ell.p; loan.vc_rows = S->vc_rows; loan.vc_gen = S->vc_gen; }
     t->sw_loan = loan;
     S->bnd_tallied = false;
     if (bnd) RT_HIP(hipMemsetAsync(S->bnd_J.p, 0, (size_t)2 * S->bnd_S * G * sizeof(double), s));
@@ -1616,6 +1684,7 @@ int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
     if (!on) { if (solver->mode == SweepMode::Linear) solver->mode = SweepMode::Flat; return RT_SUCCESS; }
     if (solver->mode == SweepMode::P1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
     if (solver->single) { set_error("rt_solver_set_linear_source: the single-precision sweep is set (rt_solver_set_precision), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
+    if (solver->vc_mode) { set_error("rt_solver_set_linear_source: the volume correction is set (rt_solver_set_volume_correction: scaled chords would move the linear source's midpoints off the track), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
     return guarded(who, [&]() -> int32_t {
         if (!solver->has_geom)
             for (int32_t stage = 0; stage < 3; ++stage)
@@ -1629,6 +1698,7 @@ int32_t rt_solver_ls_geometry(rt_solver *solver, int32_t stage) {
     const char *who = "rt_solver_ls_geometry";
     if (!solver) { set_error("rt_solver_ls_geometry: null solver"); return RT_ERR_INVALID; }
     if (stage < 0 || stage > 2) { set_error("rt_solver_ls_geometry: bad arguments (stage %d)", stage); return RT_ERR_INVALID; }
+    if (solver->vc_mode) { set_error("rt_solver_ls_geometry: the volume correction is set (rt_solver_set_volume_correction), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
     return guarded("rt_solver_ls_geometry", [&] { return solver_ls_geometry_stage(solver, stage, true, who); }, [&] { solver_ls_geometry_drop(solver); });
 }
 
@@ -1645,6 +1715,7 @@ static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
     if (want == S->repro) return RT_SUCCESS;
     if (want && S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
     if (want && S->reg_R > 0) { set_error("%s: region currents are set (rt_solver_set_regions: their tally is an atomic sum), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
+    if (want && S->vc_mode) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction: its tracked lengths are an atomic sum), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
     rt_tracks *t = S->t;
     if (int rc = finish_call(t)) return rc;
     RT_HIP(hipSetDevice(t->mesh->device));
@@ -1728,6 +1799,78 @@ int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision) {
         if (other) { set_error("%s: %s, and the single-precision sweep together with it is not supported", who, other); return RT_ERR_INVALID; }
     }
     S->single = precision == RT_PRECISION_SINGLE;
+    return RT_SUCCESS;
+}
+
+// The volume correction of the following runs.  On: the mode is noted, and rt_solver_begin makes L, f, V' and ℓ' (solver_volcorr_prepare).
+// Off: the track-based volumes go back into `vol`, bit for bit, and the tables and ℓ' are freed.
+static int32_t solver_set_volume_correction_impl(rt_solver *S, int32_t mode) {
+    const char *who = "rt_solver_set_volume_correction";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the chords cannot change under it", who); return RT_ERR_INVALID; }
+    if (mode != RT_VOLUME_CORRECTION_OFF && mode != RT_VOLUME_CORRECTION_ANGLE && mode != RT_VOLUME_CORRECTION_CELL) {
+        set_error("%s: mode %d (RT_VOLUME_CORRECTION_OFF = 0, RT_VOLUME_CORRECTION_ANGLE = 1 or RT_VOLUME_CORRECTION_CELL = 2)", who, mode);
+        return RT_ERR_INVALID;
+    }
+    if (mode == S->vc_mode) return RT_SUCCESS;
+    if (mode != RT_VOLUME_CORRECTION_OFF) {
+        if (S->mode == SweepMode::Linear || S->ls_stage != 0) { set_error("%s: the linear source is on (rt_solver_set_linear_source: scaled chords would move its midpoints off the track), and the volume correction together with it is not supported", who); return RT_ERR_INVALID; }
+        if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and the volume correction — its tracked lengths are an atomic sum — together with them is not supported", who); return RT_ERR_INVALID; }
+        if (S->t->sw_shard) { set_error("%s: the track set is a shard (some next uid is 0): the tracked lengths of a shard are not the cells', and the volume correction on sharded runs is not supported", who); return RT_ERR_INVALID; }
+        S->vc_mode = mode;
+        return RT_SUCCESS;
+    }
+    if (S->vc_applied) {
+        rt_tracks *t = S->t;
+        if (int rc = finish_call(t)) return rc;
+        RT_HIP(hipSetDevice(t->mesh->device));
+        hipStream_t s = t->mesh->stream;
+        RT_HIP(hipMemcpyAsync(S->vol.p, S->vc_vol_track.p, (size_t)S->n_cells * sizeof(double), hipMemcpyDeviceToDevice, s));
+        RT_HIP(hipStreamSynchronize(s));
+        S->vc_applied = false;
+    }
+    S->vc_mode = 0; S->vc_done_mode = 0;
+    S->vc_L.release(); S->vc_f.release(); S->vc_area.release(); S->vc_ell.release(); S->vc_vol_track.release(); S->vc_part.release();
+    S->vc_stats.release(); S->vc_wvol.release(); S->vc_delta.release();
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_volume_correction(rt_solver *solver, int32_t mode) {
+    return guarded("rt_solver_set_volume_correction", [&] { return solver_set_volume_correction_impl(solver, mode); });
+}
+
+int32_t rt_solver_fetch_volume_correction(rt_solver *solver, double *area, double *factor, double *stats, int32_t *info) {
+    if (!solver) { set_error("rt_solver_fetch_volume_correction: null solver"); return RT_ERR_INVALID; }
+    if (solver->vc_mode == 0 || solver->vc_done_mode != solver->vc_mode) {
+        set_error("rt_solver_fetch_volume_correction: no run with the volume correction yet (rt_solver_set_volume_correction, then a run or rt_solver_begin)");
+        return RT_ERR_INVALID;
+    }
+    return guarded("rt_solver_fetch_volume_correction", [&]() -> int32_t {
+        RT_HIP(hipSetDevice(solver->device));
+        hipStream_t s = solver->t->mesh->stream;
+        const size_t nc = (size_t)solver->n_cells;
+        if (area && nc) RT_HIP(hipMemcpyAsync(area, solver->vc_area.p, nc * sizeof(double), hipMemcpyDeviceToHost, s));
+        if (factor && nc) RT_HIP(hipMemcpyAsync(factor, solver->vc_f.p, nc * solver->N2 * sizeof(double), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));
+        if (stats) { stats[0] = solver->vc_h_stats[3]; stats[1] = solver->vc_h_stats[4]; }
+        if (info)
+            for (int i = 0; i < 3; ++i) info[i] = (int32_t)solver->vc_h_stats[i];
+        return RT_SUCCESS;
+    });
+}
+
+int32_t rt_solver_volume_correction_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
+    if (!solver) { set_error("rt_solver_volume_correction_pointers: null solver"); return RT_ERR_INVALID; }
+    // (no wait here: addresses and counts only)
+    const bool on = solver->vc_mode != 0 && solver->vc_done_mode == solver->vc_mode;
+    const int64_t nc = solver->n_cells;
+    void *p[3] = {on ? solver->vc_area.p : nullptr, on ? solver->vc_f.p : nullptr, on ? solver->vc_ell.p : nullptr};
+    const int64_t l[3] = {on ? nc : 0, on ? nc * solver->N2 : 0, on ? solver->vc_slots : 0};
+    for (int i = 0; i < 3; ++i) {
+        if (ptrs_dev) ptrs_dev[i] = p[i];
+        if (lens) lens[i] = l[i];
+    }
     return RT_SUCCESS;
 }
 

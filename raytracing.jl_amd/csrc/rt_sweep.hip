@@ -310,6 +310,7 @@ int ensure_rows_from_compact(rt_tracks *t) {
     RT_HIP(t->sw_ell.reserve(slots)); RT_HIP(t->sw_cell.reserve(slots));
     t->sw_rowsc_slots = (int64_t)slots;
     t->sw_ell_valid = false;  // (the buffers now hold rows in THIS chunk table's layout, not the staging pool's)
+    ++t->sw_rows_gen;
     hipLaunchKernelGGL(rt::k_rows_fill, dim3((unsigned)n_waves), dim3(256), 0, s, (const int32_t *)t->counts.p, (const int64_t *)t->offsets.p,
                        (const int32_t *)t->perm.p, n, (const double *)t->sell.p, (const int32_t *)t->element.p, (const int32_t *)first, (const int32_t *)nch,
                        t->sw_ctab.p, t->sw_ell.p, t->sw_cell.p);
@@ -403,6 +404,41 @@ using namespace rtx;
 using namespace rtsweep;
 
 // ---- rt_sweep -----------------------------------------------------------------------------------------------------
+// what a sweep of G components reads and how wide its passes may be: the handle's state, the options and an rt_solver's loan
+static SweepFacts sweep_facts(const rt_tracks *t, int32_t G, int32_t input, const SweepLoan &loan, bool volcorr) {
+    const rt_mesh *m = t->mesh;
+    return SweepFacts{.n = t->n, .n_cells = m->n_cells, .G = G, .input = input, .mode = loan.mode, .repro = loan.repro,
+                      .f32 = loan.f32 || m->sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
+                      .sw_ell_valid = t->sw_ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
+                      .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves, .regions = loan.n_regions,
+                      .volcorr = volcorr};
+}
+
+namespace rtx {
+int sweep_rows_for_loan(rt_tracks *t, int32_t G, const SweepLoan &loan, bool volcorr, SweepRowsView *out) {
+    const SweepPlan plan = plan_sweep(sweep_facts(t, G, 0, loan, volcorr));
+    if (plan.refusal) { set_error("%s", plan.message); return plan.refusal; }
+    if (!rows_read_ell(plan.rows)) { set_error("rt_sweep: this sweep would read rows of kind 0, which carry no ℓ"); return RT_ERR_INVALID; }
+    SweepRowsView v;
+    v.rows = plan.rows;
+    if (plan.rows == SweepRows::FromCompact) {
+        if (int rc = ensure_rows_from_compact(t)) return rc;
+        v.ctab = t->sw_ctab.p; v.cell_rows = t->sw_cell.p; v.slots = t->sw_rowsc_slots;
+    } else {
+        if (plan.rows == SweepRows::FromCodes)
+            if (int rc = ensure_rows(t)) return rc;
+        v.ctab = (const int32_t *)t->cplan.stg.ctab;
+        v.cell_rows = plan.rows == SweepRows::FromCodes ? (const int32_t *)t->sw_cell.p : (const int32_t *)t->cplan.stg.element;
+        v.slots = (int64_t)t->pool_chunks * rt::kChunkRows * 64;
+    }
+    v.ell_rows = t->sw_ell.p;
+    if ((int64_t)t->sw_ell.cap < v.slots || (t->n > 0 && (!v.ctab || !v.cell_rows))) { set_error("rt_sweep: the (ℓ, cell) rows of this segmentation are incomplete"); return RT_ERR_INVALID; }
+    v.gen = t->sw_rows_gen;
+    *out = v;
+    return RT_SUCCESS;
+}
+}  // namespace rtx
+
 static int32_t sweep_set_links_impl(rt_tracks *t, const int64_t *next_fwd, const int64_t *next_bwd, const int8_t *dir_fwd,
                                     const int8_t *dir_bwd, const int8_t *bc_fwd, const int8_t *bc_bwd) {
     if (!t || (t->n > 0 && (!next_fwd || !next_bwd || !dir_fwd || !dir_bwd || !bc_fwd || !bc_bwd))) { set_error("rt_sweep_set_links: null argument"); return RT_ERR_INVALID; }
@@ -525,12 +561,15 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     const SweepLoan &loan = t->sw_loan;
     const SweepMode mode = loan.mode;
     const bool moments = mode != SweepMode::Flat, repro = loan.repro;
-    const SweepFacts facts{.n = n, .n_cells = m->n_cells, .G = G, .input = input, .mode = mode, .repro = repro,
-                           .f32 = loan.f32 || m->sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
-                           .sw_ell_valid = t->sw_ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
-                           .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves, .regions = loan.n_regions};
+    const SweepFacts facts = sweep_facts(t, G, input, loan, loan.vc_ell != nullptr);
     SweepPlan plan = plan_sweep(facts);
     if (plan.refusal) { set_error("%s", plan.message); return plan.refusal; }
+    // the solver's ℓ' stands in for the rows' ℓ: it is the copy of THESE rows as they stand, or the sweep is refused here, with nothing
+    // queued (rows with ℓ exist already — the solver made them —, so nothing below makes them anew)
+    if (facts.volcorr && (!rows_read_ell(plan.rows) || plan.rows != loan.vc_rows || t->sw_rows_gen != loan.vc_gen)) {
+        set_error("rt_sweep: the volume correction (rt_solver_set_volume_correction) scaled other rows than this sweep reads (an option or the rows changed under the run): begin the run again");
+        return RT_ERR_INVALID;
+    }
     // the rows the plan names, made once per segmentation: from the compact records here, the staging's below (inside `ms`, as ever)
     if (!rows_staged(plan.rows) || plan.rows == SweepRows::FromCompact)
         if (int rc = ensure_compacted(t)) return rc;
@@ -588,6 +627,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         }
     }
     a.ell_rows = rows_kind(plan.rows) ? as_global(t->sw_ell.p) : nullptr;
+    if (facts.volcorr) a.ell_rows = as_global(const_cast<double *>(loan.vc_ell));  // (checked above; only read: no pass of these rows writes ℓ)
     int passes = 0;
     for (int g0 = 0; n > 0 && g0 < G; ++passes) {
         const int take = std::min(plan.gp, G - g0);
@@ -608,7 +648,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         } else {
             if (int rc = launch_sweep_f64(t, a, plan, shape, s)) return rc;
             if (plan.rows == SweepRows::Staged20WriteEll) {  // (the forward waves of this pass have written every row's ℓ)
-                t->sw_ell_valid = true; t->sw_rowsc_valid = false;
+                t->sw_ell_valid = true; t->sw_rowsc_valid = false; ++t->sw_rows_gen;
                 plan.rows = SweepRows::StagedEll;
             }
         }

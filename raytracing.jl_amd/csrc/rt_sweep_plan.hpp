@@ -50,6 +50,7 @@ struct SweepFacts {
     int lds_per_block = 0;
     int sweep_rows = 1, sweep_ell = 1, sweep_gp = 0, sweep_waves = 0;  // the options
     int regions = 0;           // R of the region currents (lent by a solver, rt_solver_set_regions); 0: off
+    bool volcorr = false;      // the rows' ℓ comes from a solver's corrected copy (rt_solver_set_volume_correction)
 };
 
 constexpr int kMaxRegions = 127;  // (R + 1)² doubles of one component fit the LDS of a workgroup: 128 KiB
@@ -95,6 +96,9 @@ struct SweepPlan {
 #define RT_IFACE_WITH(other) "rt_sweep: the region currents (rt_solver_set_regions) together with " other " — not supported"
 #define RT_IFACE_ROWS(why) "rt_sweep: the region currents (rt_solver_set_regions) are tallied over (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
 
+#define RT_VC_WITH(other) "rt_sweep: the volume correction (rt_solver_set_volume_correction) together with " other " — not supported"
+#define RT_VC_ROWS(why) "rt_sweep: the volume correction (rt_solver_set_volume_correction) scales the ℓ of (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
+
 inline SweepPlan plan_sweep(const SweepFacts &f) {
     SweepPlan p;
     p.f = f;
@@ -136,6 +140,18 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
             return refuse(RT_IFACE_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
                                         "sweep without regions first, or set option \"sweep_rows\" 2 and name the compact records"));
     }
+    // volume correction: the sweep reads ℓ' = f ℓ from the solver's copy of the (ℓ, cell) rows' ℓ — rows that carry no ℓ are refused like
+    // the region currents', before anything is queued; so are the linear source (its midpoints follow the running sum of ℓ) and the
+    // reproducible tallies (the tracked lengths are an atomic sum)
+    if (f.volcorr) {
+        if (f.mode == SweepMode::Linear) return refuse(RT_VC_WITH("the linear source (rt_solver_set_linear_source): scaled chords would move its midpoints off the track"));
+        if (f.repro) return refuse(RT_VC_WITH("the reproducible tallies (rt_solver_set_reproducible): the tracked lengths are an atomic sum"));
+        if (p.rows == SweepRows::Records) return refuse(RT_VC_ROWS("the compact records where they lie: option \"sweep_rows\" is 0"));
+        if (p.rows == SweepRows::Staged20) return refuse(RT_VC_ROWS("the staging's 20-B rows in every pass: option \"sweep_ell\" is 0"));
+        if (p.rows == SweepRows::Staged20WriteEll)
+            return refuse(RT_VC_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
+                                     "sweep without the correction first, or set option \"sweep_rows\" 2 and name the compact records"));
+    }
     // components per pass: as many as an LDS-private copy of their tallies allows (up to 4); none fits: global atomics.  The last
     // pass takes what is left with the kernel compiled for that many (7 groups = 4 + 3: a padded fourth group was an eighth of the
     // sweep's arithmetic).  First-moment scattering and the linear source: three tallies per component, so a mesh that fits 4
@@ -175,5 +191,7 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
 #undef RT_F32_ROWS
 #undef RT_IFACE_WITH
 #undef RT_IFACE_ROWS
+#undef RT_VC_WITH
+#undef RT_VC_ROWS
 
 }  // namespace rtsweep

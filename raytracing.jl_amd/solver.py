@@ -18,6 +18,8 @@ on that side, whatever ``trace`` linked there) and, in fixed-source runs, an iso
 carries the partial currents per side and group and the neutron balance (``rt_solver_set_boundary``).
 With ``regions=...`` (an int per cell, or ``"material"``) every sweep also tallies the partial currents between the cell regions
 (``rt_solver_set_regions``): ``SolverResult.region_current`` and the balance of every region, ``region_balance``.
+With ``volume_correction="angle"`` (or ``"cell"``) the chord lengths the sweeps read are renormalised so that every cell's tracked
+area equals its exact area (``rt_solver_set_volume_correction``); ``SolverResult.volumes`` are then the corrected ones.
 With ``cmfd=True`` (or a ``Cmfd``) on top of ``regions=...`` every iteration also solves the partial-current coarse-mesh balance
 over the regions and prolongs its solution onto φ, k and the boundary fluxes (``rt_solver_set_cmfd``): the same answer in fewer
 iterations; ``diffusion_coupling`` builds an optional coupling D̂ from the mesh.
@@ -344,6 +346,10 @@ class SolverResult:
     region_current: Optional[np.ndarray] = None  # regions=...: the last sweep's partial currents J [R + 1, R + 1, G], J[a, b] from a to b (R: outside)
     region_balance: Optional[dict] = None        # ... region_balance: gain, removal, leakage, net_inflow, defect [R, G]; both None without
     cmfd: Optional[dict] = None   # cmfd=...: the last coarse step's factors [R, G], its iterations, skipped_regions, skipped_steps
+    volume_correction: Optional[str] = None       # "angle" / "cell": chord lengths renormalised to the cells' areas; `volumes` are then V'
+    cell_area: Optional[np.ndarray] = None        # ... the cells' exact areas A_e [n_cells]
+    volume_factor: Optional[np.ndarray] = None    # ... f [n_cells, n_azim_2]
+    volume_correction_info: Optional[dict] = None  # ... unseen_pairs, zero_area_cells, zero_volume_cells, f_min, f_max; all None without
 
 
 def _cell_material(tg, cell_material):
@@ -387,9 +393,28 @@ def _device_tracks(tg, device):
     return dt
 
 
+def _volume_correction(tg, volume_correction):
+    """The mode of a solve: None is what the TrackGenerator says (``volume_correction=True`` there: "angle"), False is off."""
+    if volume_correction is None:
+        return "angle" if getattr(tg, "volume_correction", False) else None
+    if volume_correction is False:
+        return None
+    if volume_correction is True:
+        return "angle"
+    if volume_correction not in ("angle", "cell"):
+        raise ValueError('volume_correction must be None, "angle" or "cell"')
+    return volume_correction
+
+
 def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat", adjoint=False,
-           boundary=None, reproducible=False, precision="double", regions=None, cmfd=None):
+           boundary=None, reproducible=False, precision="double", regions=None, cmfd=None, volume_correction=None):
     acc = _as_cmfd(cmfd)
+    vc = _volume_correction(tg, volume_correction)
+    if vc is not None and scheme == "linear":
+        raise ValueError('volume_correction together with scheme="linear" is not supported (scaled chords would move the linear '
+                         "source's midpoints off the track)")
+    if vc is not None and reproducible:
+        raise ValueError("volume_correction together with reproducible=True is not supported (the tracked lengths are an atomic sum)")
     if acc is not None and regions is None:
         raise ValueError("cmfd needs regions= (its coarse cells)")
     if precision not in _capi.PRECISIONS:
@@ -432,6 +457,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         sv.set_reproducible(True)
     if precision != "double":  # (refused by the library together with sigma_s1, scheme="linear" or reproducible=True)
         sv.set_precision(precision)
+    if vc is not None:  # (refused by the library on a shard's track set)
+        sv.set_volume_correction(vc)
     r = sv.run(mode, int(max_iter), float(tol_k), float(tol_flux))
     f = sv.fetch(r["iterations"])
     mom = sv.fetch_moments() if linear else dict(flux_moments=None, flux_gradient=None)
@@ -452,6 +479,9 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
                                                bnd["region_current"], adjoint=adjoint)
     if acc is not None and it > 0:
         bnd["cmfd"] = sv.fetch_cmfd()
+    if vc is not None:
+        v = sv.fetch_volume_correction()
+        bnd.update(volume_correction=vc, cell_area=v.pop("area"), volume_factor=v.pop("factor"), volume_correction_info=v)
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
@@ -462,7 +492,7 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
                      tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
                      boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double",
-                     regions=None, cmfd=None) -> SolverResult:
+                     regions=None, cmfd=None, volume_correction=None) -> SolverResult:
     """Power iteration for k_eff on the device.  ``cell_material``: material index per cell [n_cells] (or one index for all,
     or a dict region name -> index over ``tg.mesh.model.cell_region``).  ``polar``: a ``PolarQuadrature`` spec;
     ``azim_weights``: "exact", "equal" or an array.  Uses ``tg.device_tracks`` when ``segmentize(tg, fetch=False)`` has run,
@@ -480,27 +510,31 @@ def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar
     the result carries ``region_current`` [R + 1, R + 1, G] and ``region_balance``; not together with ``reproducible=True`` or
     ``precision="single"`` (``RtError``).  ``cmfd``: True or a ``Cmfd`` — the partial-current coarse-mesh acceleration over the
     regions (``rt_solver_set_cmfd``; needs ``regions``): the same converged k and φ in fewer iterations; the result carries the last
-    coarse step under ``cmfd``."""
+    coarse step under ``cmfd``.  ``volume_correction``: ``"angle"`` or ``"cell"`` — the chord lengths the sweeps read are renormalised
+    so that every cell's tracked area equals its exact area, per azimuthal angle or with one factor per cell
+    (``rt_solver_set_volume_correction``); ``volumes`` are then the corrected V' and the result carries ``cell_area``,
+    ``volume_factor`` and ``volume_correction_info``; None: what ``tg.volume_correction`` says (True there: ``"angle"``), False: off.
+    Not together with ``scheme="linear"`` or ``reproducible=True`` (``ValueError``)."""
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible, precision, regions, cmfd)
+                  adjoint, boundary, reproducible, precision, regions, cmfd, volume_correction)
 
 
 def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
                        tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
                        boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double",
-                       regions=None, cmfd=None) -> SolverResult:
+                       regions=None, cmfd=None, volume_correction=None) -> SolverResult:
     """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
     the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``; with ``adjoint=True`` ``source`` is the
     adjoint source S† (for instance a detector cross section) and ``phi`` the importance φ†: Σ V S† φ = Σ V S φ†.  ``boundary``: a
     ``SolverBoundary``, here also with an incoming flux per side and group (``source`` may then be zero: a run driven from the
-    boundary).  ``reproducible``, ``precision``, ``regions``, ``cmfd``: as for ``solve_eigenvalue`` (``cmfd`` not together with an
-    incoming flux)."""
+    boundary).  ``reproducible``, ``precision``, ``regions``, ``cmfd``, ``volume_correction``: as for ``solve_eigenvalue`` (``cmfd``
+    not together with an incoming flux)."""
     q = np.asarray(source, np.float64)
     G = xs.n_groups
     if q.ndim == 0 or q.shape == (G,):
         q = np.broadcast_to(q, (tg.mesh.num_cells, G))
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible, precision, regions, cmfd)
+                  adjoint, boundary, reproducible, precision, regions, cmfd, volume_correction)
 
 
 # ---- adjoint-weighted integrals ------------------------------------------------------------------------------------------------

@@ -32,7 +32,10 @@ _RTOL = math.sqrt(np.finfo(np.float64).eps)  # Base.rtoldefault(Float64)
 
 class TrackGenerator:
     """``TrackGenerator(model, n_azim, δ; bcs, tiny_step=1e-8, volume_correction=false)``
-    (``src/trackgenerator.jl:80-125``)."""
+    (``src/trackgenerator.jl:80-125``).  ``volume_correction``: ``segmentize`` and ``fill_volumes`` ignore the flag, as the
+    reference does (its records and ``tg.volumes`` stay the track-based ones); the transport solver acts on it —
+    ``solve_eigenvalue`` / ``solve_fixed_source(..., volume_correction=None)`` take ``True`` here as ``"angle"``: chord lengths
+    renormalised per cell and azimuthal angle to the cells' exact areas (``rt_solver_set_volume_correction``)."""
 
     def __init__(self, model: DiscreteModel, n_azim: int, delta: float, *,
                  bcs: BoundaryConditions | None = None, tiny_step: float = 1e-8,
@@ -41,7 +44,7 @@ class TrackGenerator:
         self.bcs = bcs if bcs is not None else BoundaryConditions()
         self.azimuthal_quadrature = aq = AzimuthalQuadrature(n_azim, delta)
         self.tiny_step = float(tiny_step)
-        self.volume_correction = bool(volume_correction)  # stored, never acted on (as in the reference)
+        self.volume_correction = bool(volume_correction)  # (segmentize / fill_volumes ignore it, as in the reference; the solver acts on it)
 
         dx, dy = self.mesh.width(), self.mesh.height()
         n2, n4 = aq.n_azim_2, aq.n_azim_4

@@ -79,6 +79,9 @@ def main():
     ap.add_argument("--cmfd-iters", type=int, default=200, help="cmfd_max_iter of --cmfd")
     ap.add_argument("--cmfd-tol", type=float, default=1e-10, help="cmfd_tol of --cmfd")
     ap.add_argument("--tol", type=float, default=1e-6, help="tol_k and tol_flux of the convergence runs of --cmfd")
+    ap.add_argument("--volume-correction", choices=("angle", "cell"), default=None,
+                    help="after the forward runs, the same runs with the volume correction (rt_solver_set_volume_correction): the one-off time of "
+                         "its kernels (the first begin's host time minus a later one's) and the time per iteration; not with --linear")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -171,6 +174,29 @@ def main():
         out["reproducible_bytes_held"] = int(held)
         out["reproducible_bits_repeat"] = all(p == phis[0] for p in phis)
         sv.set_reproducible(False)
+    if a.volume_correction:  # (the sweep reads ℓ' through the pointer it read ℓ through: the time per iteration is expected equal)
+        sv.set_volume_correction(a.volume_correction)
+        t0 = time.perf_counter(); sv.begin(0); t_first = time.perf_counter() - t0; sv.end()  # (L, f, V', ℓ': once)
+        t0 = time.perf_counter(); sv.begin(0); t_again = time.perf_counter() - t0; sv.end()
+        sv.run(0, 3, 0.0, 0.0)
+        ev_ms, host_ms = [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            r = sv.run(0, a.iters, 0.0, 0.0)
+            host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+            ev_ms.append(r["device_ms"] / r["iterations"])
+        v = sv.fetch_volume_correction()
+        out["vc_mode"] = a.volume_correction
+        out["vc_ms_per_iter_events"] = float(np.median(ev_ms))
+        out["vc_ms_per_iter_host"] = float(np.median(host_ms))
+        out["vc_over_plain_events"] = out["vc_ms_per_iter_events"] / out["ms_per_iter_events"]
+        out["vc_k_eff"] = r["k_eff"]
+        out["vc_k_minus_plain"] = r["k_eff"] - out["k_eff"]
+        out["vc_one_off_ms"] = (t_first - t_again) * 1e3
+        out["vc_info"] = {k: v[k] for k in ("f_min", "f_max", "unseen_pairs", "zero_area_cells", "zero_volume_cells")}
+        out["vc_volume_sum"] = float(sv.volumes().sum())
+        out["vc_area_sum"] = float(v["area"].sum())
+        sv.set_volume_correction(None)
     if a.single:  # (k_sweep_f32 in place of k_sweep; everything else of the iteration is what it was)
         sv.set_precision("single")
         sv.run(0, 3, 0.0, 0.0)
