@@ -733,6 +733,36 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  * Off again    RT_VOLUME_CORRECTION_OFF restores the rows' own ℓ and the track-based volumes, bit-equal to a solver that never had
  *              the option, and frees every buffer the correction held.  A solver without the option launches exactly what it always did.
  *
+ * Source regions, rt_solver_set_source_regions: off by default.  Every flat-source region of the solver is then a set of mesh cells,
+ * and the rows its sweeps read are merged per region.  rt_segmentize, the compact records and the handle's own rows are never written:
+ * the solver owns a second row set (cell words, ℓ, counts, chunk table), and a bare rt_sweep is unaffected.
+ * Map          cell_source_region[e] ∈ [0, n_src) for every mesh cell e, 1 <= n_src <= n_cells; every region holds at least one cell, and
+ *              all cells of a region carry the same material (checked on the host: RT_ERR_INVALID otherwise)
+ * Run          for one track, a maximal sequence of consecutive records whose cells map to the same region; a region entered again
+ *              later starts a new run.  A record whose cell id is out of range belongs to no run and ends the one before it
+ * Merged row   of a run: region r and length ℓ' = the run's ℓ added left to right in record order (one defined order: a numpy twin
+ *              reproduces it to the bit); its word is r + 1, positive — the marked-record sign is dropped
+ * Volumes      V_r = Σ_{e ∈ r} V_e over the cells in ascending e, V_e the track-based volumes; no atomics; summed when the map is set
+ *              (V_r does not depend on the rows), so rt_solver_fetch returns V_r [n_src] from the setter on
+ * Everything behind the rows runs on n_src "cells" and is otherwise what it was: τ = Σt ℓ' (e^{−τ₁} e^{−τ₂} becomes e^{−(τ₁ + τ₂)}: the
+ * same number up to rounding for a region-wise flat source), the tallies, the fold, F, k, the residual, the boundary currents.  φ, the
+ * source of rt_solver_set_source, the current, rt_solver_pointers are [n_src]; cell_material stays per mesh cell.  Fewer rows shorten
+ * every wave's loop, and n_src · components · 8 B decides how many components a pass takes with an LDS copy of its tallies.
+ * When         the rows once per segmentation, inside rt_solver_begin (rt_solver_run), before anything else of the run is queued; again only
+ *              when the map or the rows the sweep reads have changed since.  A sweep that would read other rows than the merged ones
+ *              were made from is refused before anything is queued
+ * Works with   eigenvalue and fixed-source runs, first-moment scattering, adjoint mode, rt_solver_set_boundary, the single-precision
+ *              sweep, the stepwise calls
+ * Refused      RT_ERR_INVALID with a message that names both sides, from whichever is switched on second (the solver keeps the state
+ *              it had), together with: the linear source — centroids and the C matrices are per cell; the reproducible tallies — the
+ *              tally index is per original row slot; rt_solver_set_regions / rt_solver_set_cmfd — the coarse-mesh prolongation
+ *              reads the compact records' cells; the volume correction — its factors are per cell; rows of kind 0 — they carry no
+ *              ℓ to add (refused by rt_solver_begin, as for the volume correction); a shard's track set — a run would end at the
+ *              shard's edge (all open)
+ * Switching    on, off or to another map drops the external source of rt_solver_set_source (its shape changes) and the last run's
+ *              result.  Off restores the cells' materials and the track-based V_e, bit-equal to a solver that never had the option,
+ *              and frees every buffer.  A solver without the option launches exactly what it always did.
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -935,6 +965,26 @@ int32_t rt_solver_fetch_volume_correction(rt_solver *solver, double *area, doubl
  * [2] ℓ' by row slot, valid from the rt_solver_begin that made them to the next change of the mode (NULL / 0 before, and without the
  * correction); lens[1] / lens[0] is n_azim_2.  Does not wait. */
 int32_t rt_solver_volume_correction_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
+/* Source regions (see above) for the following runs: cell_source_region [n_cells] with every entry in [0, n_src); NULL: off.  V_r is
+ * summed here; nothing is merged: the next rt_solver_begin makes the rows.  RT_ERR_INVALID for an entry out of range, a region without a cell, a region
+ * that mixes materials, n_src outside [1, n_cells], while the linear source, the reproducible tallies, region currents, the coarse-mesh
+ * acceleration or the volume correction are on (those setters refuse likewise while source regions are set), on a shard's track set,
+ * with a run open or after the tracks were segmentized again; the solver then keeps what it had. */
+int32_t rt_solver_set_source_regions(rt_solver *solver, const int32_t *cell_source_region, int32_t n_src);
+/* out[8]: [0] n_src, [1] rows before and [2] after the merge, [3] the largest count of a track before and [4] after, [5] 32-row chunks
+ * before (Σ over the march waves of ⌈largest count / 32⌉) and [6] after, [7] 0.  [1..6] are 0 before the first rt_solver_begin with
+ * the map that is set; all 0 without source regions.  Does not wait. */
+int32_t rt_solver_source_region_info(rt_solver *solver, int64_t *out);
+/* Device addresses ptrs_dev[6] and element counts lens[6] (either may be NULL) of [0] the merged rows' chunk table [waves][313] (a
+ * wave's entries below its chunk count are written), [1] their words (region + 1; 0: no row), [2] ℓ' by row slot, [3] the runs per
+ * track uid, [4] V_r [n_src] and [5] int32 [waves][4] per march wave: the largest count of a track before and after the merge, the
+ * rows before and after — valid from the rt_solver_begin that made the rows to the next change of the map (NULL / 0 before, and
+ * without source regions).  Does not wait. */
+int32_t rt_solver_source_region_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
+/* The merged rows of the last rt_solver_begin in uid-CSR order: offsets [n + 1], and — either may be NULL — ell and region (0-based)
+ * with room for `cap` rows each.  RT_ERR_INVALID without source regions, before the first rt_solver_begin with them, or when the
+ * rows exceed `cap` (offsets are filled all the same: offsets[n] is the room needed).  Waits. */
+int32_t rt_solver_fetch_source_rows(rt_solver *solver, int64_t *offsets, double *ell, int32_t *region, int64_t cap);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

@@ -37,6 +37,7 @@ SYMBOLS = (
     "rt_solver_set_regions", "rt_solver_fetch_regions", "rt_solver_region_pointers",
     "rt_solver_set_cmfd", "rt_solver_fetch_cmfd",
     "rt_solver_set_volume_correction", "rt_solver_fetch_volume_correction", "rt_solver_volume_correction_pointers",
+    "rt_solver_set_source_regions", "rt_solver_source_region_info", "rt_solver_source_region_pointers", "rt_solver_fetch_source_rows",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -308,6 +309,18 @@ def lib():
         L.rt_solver_fetch_volume_correction.argtypes = [_vp, _dp, _dp, _dp, _ip]
         L.rt_solver_volume_correction_pointers.restype = C.c_int32
         L.rt_solver_volume_correction_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
+    except AttributeError:
+        if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
+            raise
+    try:
+        L.rt_solver_set_source_regions.restype = C.c_int32
+        L.rt_solver_set_source_regions.argtypes = [_vp, _ip, C.c_int32]
+        L.rt_solver_source_region_info.restype = C.c_int32
+        L.rt_solver_source_region_info.argtypes = [_vp, _lp]
+        L.rt_solver_source_region_pointers.restype = C.c_int32
+        L.rt_solver_source_region_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
+        L.rt_solver_fetch_source_rows.restype = C.c_int32
+        L.rt_solver_fetch_source_rows.argtypes = [_vp, _lp, _dp, _ip, C.c_int64]
     except AttributeError:
         if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
             raise
@@ -772,6 +785,7 @@ class DeviceSolver:
         self.reproducible = False
         if reproducible:
             self.set_reproducible(True)
+        self.source_region = None  # (set_source_regions: the map while it is on; n_cells is then n_src)
         self.precision = "double"
         if precision != "double":
             self.set_precision(precision)
@@ -1000,6 +1014,58 @@ class DeviceSolver:
         out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
         out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
         return out
+
+    SOURCE_REGION_INFO = ("n_src", "rows_before", "rows_after", "max_count_before", "max_count_after", "chunks_before", "chunks_after")
+
+    def set_source_regions(self, cell_source_region=None, n_src=None):
+        """``rt_solver_set_source_regions`` for the following runs: ``cell_source_region`` int [mesh cells], every entry in
+        0 .. ``n_src`` − 1 (``n_src`` None: the largest entry + 1); every region's cells carry one material.  The solver then runs on
+        ``n_src`` flat-source regions — ``n_cells`` here, ``set_source``, ``fetch`` and ``pointers`` are per region — over rows merged
+        per run of cells of one region.  None: off, per mesh cell again.  Switching drops the external source.  Refused together with
+        the linear source, the reproducible tallies, regions / cmfd and the volume correction, and on a shard's track set."""
+        L = lib()
+        if not hasattr(L, "rt_solver_set_source_regions"):
+            raise RtError(f"{LIB_PATH} has no rt_solver_set_source_regions: the library is older than this binding")
+        nm = self.dtracks.dmesh.n_cells
+        if cell_source_region is None:
+            _check(L.rt_solver_set_source_regions(self._open(), None, 0))
+            self.n_cells, self.source_region = nm, None
+            return
+        sr, srp = _i32(cell_source_region)
+        if sr.shape != (nm,):
+            raise ValueError("cell_source_region must have one entry per mesh cell")
+        n = int(sr.max()) + 1 if n_src is None else int(n_src)
+        _check(L.rt_solver_set_source_regions(self._open(), srp, n))
+        self.n_cells, self.source_region = n, sr.copy()
+
+    def source_region_info(self) -> dict:
+        """``rt_solver_source_region_info``: n_src, rows, the largest count of a track and 32-row chunks before and after the merge
+        (zeros before the first ``begin`` with the map)."""
+        out = (C.c_int64 * 8)()
+        _check(lib().rt_solver_source_region_info(self._open(), out))
+        return {k: int(out[i]) for i, k in enumerate(self.SOURCE_REGION_INFO)}
+
+    def source_region_pointers(self) -> dict:
+        """``rt_solver_source_region_pointers``: device addresses (0: none yet) of ``ctab``, ``words`` (region + 1 by merged row slot),
+        ``ell_rows``, ``counts`` (runs per uid), ``volumes`` (V_r) and ``wave_stats`` (int32 [waves, 4]: largest count before / after,
+        rows before / after per march wave), and their element counts under ``lens``."""
+        ptrs = (_vp * 6)()
+        lens = (C.c_int64 * 6)()
+        _check(lib().rt_solver_source_region_pointers(self._open(), ptrs, lens))
+        names = ("ctab", "words", "ell_rows", "counts", "volumes", "wave_stats")
+        out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
+        out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
+        return out
+
+    def fetch_source_rows(self) -> dict:
+        """``rt_solver_fetch_source_rows``: the merged rows of the last ``begin`` in uid-CSR order — ``offsets`` [n + 1], ``ell`` and
+        ``region`` (0-based) per row."""
+        n = self.dtracks.n
+        off = np.zeros(n + 1, np.int64)
+        _check(lib().rt_solver_fetch_source_rows(self._open(), off.ctypes.data_as(_lp), None, None, 0))
+        ell = np.empty(int(off[-1])); reg = np.empty(int(off[-1]), np.int32)
+        _check(lib().rt_solver_fetch_source_rows(self._open(), off.ctypes.data_as(_lp), ell.ctypes.data_as(_dp), reg.ctypes.data_as(_ip), len(ell)))
+        return dict(offsets=off, ell=ell, region=reg)
 
     def fetch_current(self) -> np.ndarray:
         """``rt_solver_fetch_current``: the net current [n_cells, G, 2] of the last run (with first-moment scattering)."""

@@ -6,6 +6,7 @@
 //   rt_sweep.hip       rt_sweep: k_sweep, k_sweep_link, the sweep's host code and entry points
 //   rt_sweep_plan.hpp  what an rt_sweep call decides (rows, pass width and shape, refusals): host-only, a pure function
 //   rt_volcorr.hip     rt_solver's volume correction: tracked lengths, factors, corrected volumes, ℓ' (k_vc_tally / _factor / _apply)
+//   rt_srcreg.hip      rt_solver's source regions: the sweep's rows merged per run of cells of one region (k_sr_count / _plan / _fill / _volumes)
 //   rt_solver.hip      rt_solver: source iteration (k_eff / fixed source) around rt_sweep, fold / source / reduction kernels
 //   rt_segmentize.hip  handles, rt_tracks_create, rt_segmentize (the call's host logic), fetches, statistics
 #pragma once
@@ -363,6 +364,25 @@ struct DVolCorr {
     double *partial, *stats;                 // [blocks][kVcPartials]; [kVcPartials]: the three counts, min f, max f
 };
 
+// The source regions of rt_solver (rt_srcreg.hip; rt_solver_set_source_regions): what its kernels read and write, by value.
+constexpr int kSrWaveStats = 4;  // int32 per march wave: largest count before, after; rows before, after
+struct DSrcReg {
+    int64_t n, slots_in, slots_out;          // tracks; row slots of the rows read and of the merged rows (every slot index is checked)
+    int32_t n_waves, n_cells, n_src;         // march waves, mesh cells, source regions
+    const int32_t *perm, *counts;            // march slot -> uid; records per uid
+    const int32_t *ctab, *cell_rows;         // the rows' chunk table [n_waves][kMaxChunks] and their cell words (|word| − 1: the cell)
+    const double *ell_rows;                  // ℓ of every row slot, as the sweep reads it
+    const int32_t *map;                      // cell_source_region [n_cells]
+    int32_t *counts_out;                     // runs per uid [n]
+    int32_t *nch, *first, *total;            // chunks a wave's merged rows need [n_waves], their exclusive scan, total[0]: chunks in all
+    int32_t *wstats;                         // [n_waves][kSrWaveStats]
+    int32_t *ctab_out, *cell_out;            // the merged rows' chunk table [n_waves][kMaxChunks] and words (region + 1)
+    double *ell_out;                         // ℓ' by merged row slot
+    const int32_t *reg_first, *reg_cells;    // [n_src + 1], [n_cells]: the cells sorted by region, ascending cell inside a region
+    const double *vol_cells;                 // V_e [n_cells]
+    double *vol;                             // V_r [n_src]
+};
+
 }  // namespace rt
 
 // ------------------------------------------------------------------- handles -------------
@@ -382,6 +402,13 @@ struct SweepLoan {
     const double *vc_ell = nullptr;   // from the rows `vc_rows` as they stood at generation `vc_gen` (rt_tracks::sw_rows_gen)
     rtsweep::SweepRows vc_rows = rtsweep::SweepRows::Records;
     uint64_t vc_gen = 0;
+    // source regions (rt_solver_set_source_regions): n_src (0: off) and the solver's merged rows — chunk table, words (region + 1), ℓ',
+    // runs per uid — in place of DSweep stg.ctab, stg.element, ell_rows and counts, made from the rows `sr_rows` at generation `sr_gen`
+    int32_t sr_n_src = 0;
+    const int32_t *sr_ctab = nullptr, *sr_cell = nullptr, *sr_counts = nullptr;
+    const double *sr_ell = nullptr;
+    rtsweep::SweepRows sr_rows = rtsweep::SweepRows::Records;
+    uint64_t sr_gen = 0;
 };
 
 // rt_sweep.hip sweep_rows_for_loan: the (ℓ, cell) rows a sweep under a loan would read, made and described
@@ -657,6 +684,11 @@ int launch_cmfd_step(rt::DCmfd c, int32_t n_items, unsigned cblocks, hipStream_t
 // rt_volcorr.hip: L = 0, k_vc_tally, k_vc_factor (`cblocks` workgroups of kVcBlock cells), k_vc_reduce, k_vc_apply — queued on `s`
 int launch_volcorr(const rt::DVolCorr &a, unsigned cblocks, hipStream_t s);
 unsigned volcorr_blocks(int32_t n_cells);
+// rt_srcreg.hip: k_sr_count and k_sr_plan (the merged rows' counts, chunk needs and their scan), then — the buffers sized from
+// total[0] — k_sr_fill, and k_sr_volumes; queued on `s`
+int launch_srcreg_count(const rt::DSrcReg &a, hipStream_t s);
+int launch_srcreg_fill(const rt::DSrcReg &a, hipStream_t s);
+int launch_srcreg_volumes(const rt::DSrcReg &a, hipStream_t s);
 // rt_sweep.hip: what a sweep of `G` components with input 0 under `loan` would read — planned as rt_sweep plans it (refused with its
 // message), the rows made as rt_sweep makes them (once per segmentation) — for a solver that scales their ℓ before its first sweep
 int sweep_rows_for_loan(rt_tracks *t, int32_t G, const SweepLoan &loan, bool volcorr, SweepRowsView *out);

@@ -22,6 +22,10 @@
 // and mode: the tracked lengths L[e][a] over the rows the sweep reads, the factors f, V' into `vol` (the track-based volumes are kept
 // aside) and ℓ' = f ℓ into a buffer of the solver's, which the run's sweeps read in place of the rows' ℓ (SweepLoan::vc_ell).  Without
 // it the solver launches what it always did.
+// With source regions (rt_solver_set_source_regions) every flat-source region is a set of mesh cells: the solver's own n_cells is n_src,
+// its material table's index and `vol` are per region, and rt_solver_begin runs the kernels of rt_srcreg.hip once per segmentation —
+// the rows the sweep reads merged per run of cells of one region, into rows, counts and a chunk table of the solver's, which the run's
+// sweeps read in place of the handle's (SweepLoan::sr_*).  Without them the solver launches what it always did.
 // Flat, first-moment scattering or linear source is one choice of three, a SweepMode (each setter switches only its own mode off and
 // refuses to switch it on over the other).  What a run's rt_sweep calls need to know — that mode, the linear source's geometry, the
 // reproducible tallies' delta buffer, single precision — goes to the handle as one SweepLoan (rt_internal.hpp) and comes back whole.
@@ -603,6 +607,19 @@ struct rt_solver {
     bool vc_applied = false;
     DevBuf<double> vc_L, vc_f, vc_area, vc_ell, vc_vol_track, vc_part, vc_stats, vc_wvol, vc_delta;
     double vc_h_stats[rt::kVcPartials] = {0, 0, 0, 1, 1, 0, 0, 0};
+    // source regions (rt_solver_set_source_regions): while on, `n_cells` is n_src, `mat` the regions' materials and `vol` V_r, the
+    // track-based V_e kept in `sr_vol_cells` (`sr_applied`).  `n_mesh` is the mesh's cell count,
+    // `h_mat` / `h_sr` the cells' materials and regions as given.  `sr_done`: the merged rows (sr_ctab, sr_cell, sr_ell, sr_counts) were
+    // made from the rows `sr_rows` at generation `sr_gen`; `sr_info`: what rt_solver_source_region_info reports
+    bool sr_on = false, sr_done = false, sr_applied = false;
+    int32_t n_mesh = 0;
+    std::vector<int32_t> h_mat, h_sr;
+    rtsweep::SweepRows sr_rows = rtsweep::SweepRows::Records;
+    uint64_t sr_gen = 0;
+    int64_t sr_slots = 0;
+    int64_t sr_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DevBuf<int32_t> sr_map, sr_counts, sr_plan, sr_wstats, sr_ctab, sr_cell, sr_first, sr_cells;
+    DevBuf<double> sr_ell, sr_vol_cells;
     std::vector<double> k_hist;
     // the run in progress (rt_solver_begin ... rt_solver_end): `open` while this solver holds the handle's sweep state
     // (rt_tracks::sw_loan.borrower points back here), `swept` between rt_solver_step_sweep and rt_solver_step_fold
@@ -735,6 +752,7 @@ int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_m
     struct Guard { rt_solver *&p; ~Guard() { free_solver(p); } } guard{S};
     S->h_st.assign(sigma_t, sigma_t + mg); S->h_ss.assign(sigma_s, sigma_s + mg * G);
     S->t = t; S->device = m->device; S->epoch = t->seg_epoch; S->G = G; S->M = M; S->P = P; S->N2 = N2; S->n_cells = nc;
+    S->n_mesh = nc; S->h_mat.assign(cell_material, cell_material + nc);
     S->h_nf.assign(nu_sigma_f, nu_sigma_f + mg); S->h_chi.assign(chi, chi + mg);
     const std::vector<double> tab = solver_table(S, false);
     std::vector<double> pol((size_t)2 * P);
@@ -893,6 +911,69 @@ int solver_volcorr_prepare(rt_solver *S, const char *who) {
     return RT_SUCCESS;
 }
 
+// The source regions of the run that begins: refused where the setter would have refused them (the links may have become a shard's
+// since), the rows the run's sweeps would read planned and made (rt_sweep's own refusals for rows without ℓ), and — when the merged rows
+// are not made from those rows as they stand — the row kernels of rt_srcreg.hip queued (V_r is made by the setter: it does not depend
+// on the rows).
+int solver_srcreg_prepare(rt_solver *S, const char *who) {
+    rt_tracks *t = S->t;
+    hipStream_t s = t->mesh->stream;
+    if (S->mode == SweepMode::Linear) { set_error("%s: source regions are set (rt_solver_set_source_regions) and the linear source is on (rt_solver_set_linear_source): the two together are not supported", who); return RT_ERR_INVALID; }
+    if (S->repro) { set_error("%s: source regions are set (rt_solver_set_source_regions) and the reproducible tallies are on (rt_solver_set_reproducible): the two together are not supported", who); return RT_ERR_INVALID; }
+    if (S->reg_R > 0 || S->vc_mode) { set_error("%s: source regions are set (rt_solver_set_source_regions) together with region currents or the volume correction: not supported", who); return RT_ERR_INVALID; }
+    if (t->sw_shard) { set_error("%s: source regions are set (rt_solver_set_source_regions) and the track set is a shard (some next uid is 0): not supported", who); return RT_ERR_INVALID; }
+    const int32_t nsrc = S->n_cells, nm = S->n_mesh;
+    SweepLoan probe;
+    probe.mode = S->mode; probe.repro = S->repro; probe.f32 = S->single; probe.n_regions = S->reg_R; probe.sr_n_src = nsrc;
+    SweepRowsView v;
+    if (int rc = sweep_rows_for_loan(t, S->G * S->P, probe, false, &v)) return rc;
+    if (S->sr_done && S->sr_rows == v.rows && S->sr_gen == v.gen) return RT_SUCCESS;
+    S->sr_done = false;
+    const int64_t n = t->n;
+    const int32_t n_waves = (int32_t)((n + 63) / 64);
+    const size_t nw = (size_t)std::max(1, n_waves);
+    RT_HIP(S->sr_counts.reserve((size_t)std::max<int64_t>(1, n)));
+    RT_HIP(S->sr_plan.reserve(2 * nw + 8));
+    RT_HIP(S->sr_wstats.reserve(nw * rt::kSrWaveStats));
+    RT_HIP(S->sr_ctab.reserve(nw * rt::kMaxChunks));
+    rt::DSrcReg a{};
+    a.n = n; a.slots_in = v.slots; a.n_waves = n_waves; a.n_cells = nm; a.n_src = nsrc;
+    a.perm = t->perm.p; a.counts = t->counts.p; a.ctab = v.ctab; a.cell_rows = v.cell_rows; a.ell_rows = v.ell_rows;
+    a.map = S->sr_map.p; a.counts_out = S->sr_counts.p;
+    a.nch = S->sr_plan.p; a.first = a.nch + nw; a.total = a.first + nw; a.wstats = S->sr_wstats.p;
+    a.ctab_out = S->sr_ctab.p;
+    if (int rc = launch_srcreg_count(a, s)) return rc;
+    int32_t h_total = 0;
+    std::vector<int32_t> ws(nw * rt::kSrWaveStats, 0), nch(nw, 0);
+    RT_HIP(hipMemcpyAsync(&h_total, a.total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (n_waves > 0) {
+        RT_HIP(hipMemcpyAsync(ws.data(), a.wstats, (size_t)n_waves * rt::kSrWaveStats * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipMemcpyAsync(nch.data(), a.nch, (size_t)n_waves * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    RT_HIP(hipStreamSynchronize(s));
+    RT_HIP(hipGetLastError());
+    const int64_t slots = (int64_t)std::max(1, h_total) * rt::kChunkRows * 64;
+    if (S->sr_ell.reserve((size_t)slots) != hipSuccess || S->sr_cell.reserve((size_t)slots) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("%s: no device memory for the source regions' merged rows of %lld row slots (%lld bytes)", who, (long long)slots, (long long)slots * 12);
+        return RT_ERR_HIP;
+    }
+    a.slots_out = slots; a.ell_out = S->sr_ell.p; a.cell_out = S->sr_cell.p;
+    if (int rc = launch_srcreg_fill(a, s)) return rc;
+    RT_HIP(hipStreamSynchronize(s));
+    RT_HIP(hipGetLastError());
+    int64_t *I = S->sr_info;
+    I[0] = nsrc; I[1] = I[2] = I[3] = I[4] = I[5] = 0; I[6] = h_total; I[7] = 0;
+    for (int32_t w = 0; w < n_waves; ++w) {
+        const int32_t *x = ws.data() + (size_t)w * rt::kSrWaveStats;
+        I[1] += x[2]; I[2] += x[3];
+        I[3] = std::max<int64_t>(I[3], x[0]); I[4] = std::max<int64_t>(I[4], x[1]);
+        I[5] += (x[0] + rt::kChunkRows - 1) >> rt::kChunkLog2;
+    }
+    S->sr_done = true; S->sr_rows = v.rows; S->sr_gen = v.gen; S->sr_slots = slots;
+    return RT_SUCCESS;
+}
+
 int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
     if (S->open) solver_release(S);  // (a second begin starts afresh)
     rt_tracks *t = S->t;
@@ -917,8 +998,10 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
     const int64_t n = t->n;
     if (S->vc_mode)  // (refused, or ℓ' and V' made, before this run queues anything else: φ⁰'s F⁰ below already weighs with V')
         if (int rc = solver_volcorr_prepare(S, who)) return rc;
+    if (S->sr_on)  // (refused, or the merged rows made, before this run queues anything else)
+        if (int rc = solver_srcreg_prepare(S, who)) return rc;
     // the handle's sweep state: C components, zero boundary fluxes, the solver's track weights
-    const size_t npsi = (size_t)std::max<int64_t>(1, 2 * n * C), nxs = std::max<size_t>(1, (size_t)nc * C);
+    const size_t npsi = (size_t)std::max<int64_t>(1, 2 * n * C), nxs = std::max<size_t>(1, (size_t)std::max(nc, m->n_cells) * C);  // (rt_sweep clears the mesh's cells' worth)
     RT_HIP(t->sw_psi_in.reserve(npsi)); RT_HIP(t->sw_psi_out.reserve(npsi)); RT_HIP(t->sw_phi.reserve(nxs));
     RT_HIP(t->sw_xs.reserve(2 * nxs));
     RT_HIP(hipMemsetAsync(t->sw_psi_in.p, 0, npsi * sizeof(double), s));
@@ -965,6 +1048,10 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
     }
     S->cm_stepped = false;
     if (S->vc_mode) { loan.vc_ell = S->vc_ell.p; loan.vc_rows = S->vc_rows; loan.vc_gen = S->vc_gen; }
+    if (S->sr_on) {
+        loan.sr_n_src = nc; loan.sr_ctab = S->sr_ctab.p; loan.sr_cell = S->sr_cell.p; loan.sr_ell = S->sr_ell.p; loan.sr_counts = S->sr_counts.p;
+        loan.sr_rows = S->sr_rows; loan.sr_gen = S->sr_gen;
+    }
     t->sw_loan = loan;
     S->bnd_tallied = false;
     if (bnd) RT_HIP(hipMemsetAsync(S->bnd_J.p, 0, (size_t)2 * S->bnd_S * G * sizeof(double), s));
@@ -1416,6 +1503,7 @@ static int32_t solver_set_regions_impl(rt_solver *S, int32_t n_regions, const in
     if (int rc = solver_check_epoch(S, who)) return rc;
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the regions cannot change under it", who); return RT_ERR_INVALID; }
     if (n_regions == 0 || !cell_region) { S->reg_R = 0; S->reg_tallied = false; S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
+    if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the coarse-mesh prolongation reads the compact records' cells), and region currents together with them are not supported", who); return RT_ERR_INVALID; }
     if (n_regions < 1 || n_regions > rtsweep::kMaxRegions) { set_error("%s: bad arguments (n_regions %d, need 1 .. %d)", who, n_regions, rtsweep::kMaxRegions); return RT_ERR_INVALID; }
     if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and region currents — an atomic sum — together with them are not supported", who); return RT_ERR_INVALID; }
     if (S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision: another kernel), and region currents together with it are not supported", who); return RT_ERR_INVALID; }
@@ -1456,6 +1544,7 @@ static int32_t solver_set_cmfd_impl(rt_solver *S, int32_t on, const double *coup
     if (int rc = solver_check_epoch(S, who)) return rc;
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the acceleration cannot change under it", who); return RT_ERR_INVALID; }
     if (!on) { S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
+    if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the prolongation reads the compact records' cells), and the coarse-mesh acceleration together with them is not supported", who); return RT_ERR_INVALID; }
     const int32_t R = S->reg_R, G = S->G, nc = S->n_cells;
     if (R <= 0) { set_error("%s: no regions are set (rt_solver_set_regions comes first: its regions are the coarse cells)", who); return RT_ERR_INVALID; }
     if (S->bnd_S > 0 && S->bnd_inc) { set_error("%s: a boundary has an incoming flux (rt_solver_set_boundary), and the coarse-mesh acceleration together with it is not supported", who); return RT_ERR_INVALID; }
@@ -1684,6 +1773,7 @@ int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
     if (!on) { if (solver->mode == SweepMode::Linear) solver->mode = SweepMode::Flat; return RT_SUCCESS; }
     if (solver->mode == SweepMode::P1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
     if (solver->single) { set_error("rt_solver_set_linear_source: the single-precision sweep is set (rt_solver_set_precision), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
+    if (solver->sr_on) { set_error("rt_solver_set_linear_source: source regions are set (rt_solver_set_source_regions: the centroids and C matrices are per cell), and the linear source together with them is not supported"); return RT_ERR_INVALID; }
     if (solver->vc_mode) { set_error("rt_solver_set_linear_source: the volume correction is set (rt_solver_set_volume_correction: scaled chords would move the linear source's midpoints off the track), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
     return guarded(who, [&]() -> int32_t {
         if (!solver->has_geom)
@@ -1698,6 +1788,7 @@ int32_t rt_solver_ls_geometry(rt_solver *solver, int32_t stage) {
     const char *who = "rt_solver_ls_geometry";
     if (!solver) { set_error("rt_solver_ls_geometry: null solver"); return RT_ERR_INVALID; }
     if (stage < 0 || stage > 2) { set_error("rt_solver_ls_geometry: bad arguments (stage %d)", stage); return RT_ERR_INVALID; }
+    if (solver->sr_on) { set_error("rt_solver_ls_geometry: source regions are set (rt_solver_set_source_regions), and the linear source together with them is not supported"); return RT_ERR_INVALID; }
     if (solver->vc_mode) { set_error("rt_solver_ls_geometry: the volume correction is set (rt_solver_set_volume_correction), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
     return guarded("rt_solver_ls_geometry", [&] { return solver_ls_geometry_stage(solver, stage, true, who); }, [&] { solver_ls_geometry_drop(solver); });
 }
@@ -1715,6 +1806,7 @@ static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
     if (want == S->repro) return RT_SUCCESS;
     if (want && S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
     if (want && S->reg_R > 0) { set_error("%s: region currents are set (rt_solver_set_regions: their tally is an atomic sum), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
+    if (want && S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the tally index is per original row slot), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
     if (want && S->vc_mode) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction: its tracked lengths are an atomic sum), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
     rt_tracks *t = S->t;
     if (int rc = finish_call(t)) return rc;
@@ -1815,6 +1907,7 @@ static int32_t solver_set_volume_correction_impl(rt_solver *S, int32_t mode) {
     }
     if (mode == S->vc_mode) return RT_SUCCESS;
     if (mode != RT_VOLUME_CORRECTION_OFF) {
+        if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions), and the volume correction — its factors are per cell — together with them is not supported", who); return RT_ERR_INVALID; }
         if (S->mode == SweepMode::Linear || S->ls_stage != 0) { set_error("%s: the linear source is on (rt_solver_set_linear_source: scaled chords would move its midpoints off the track), and the volume correction together with it is not supported", who); return RT_ERR_INVALID; }
         if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and the volume correction — its tracked lengths are an atomic sum — together with them is not supported", who); return RT_ERR_INVALID; }
         if (S->t->sw_shard) { set_error("%s: the track set is a shard (some next uid is 0): the tracked lengths of a shard are not the cells', and the volume correction on sharded runs is not supported", who); return RT_ERR_INVALID; }
@@ -1872,6 +1965,145 @@ int32_t rt_solver_volume_correction_pointers(rt_solver *solver, void **ptrs_dev,
         if (lens) lens[i] = l[i];
     }
     return RT_SUCCESS;
+}
+
+// The source regions of the following runs.  On: every cell's region is checked, the regions' materials derived (a mixed region is
+// refused), the cells sorted by region; the solver's n_cells becomes n_src, `mat` the regions' materials; rt_solver_begin makes the
+// merged rows (solver_srcreg_prepare); V_r is summed here, from the cells' V_e kept aside.  Off: n_cells, `mat` and `vol` are the cells' again, bit for bit, and every buffer is freed.
+static int32_t solver_set_source_regions_impl(rt_solver *S, const int32_t *map, int32_t n_src) {
+    const char *who = "rt_solver_set_source_regions";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the regions cannot change under it", who); return RT_ERR_INVALID; }
+    rt_tracks *t = S->t;
+    const int32_t nm = S->n_mesh;
+    if (!map) {
+        if (!S->sr_on) return RT_SUCCESS;
+        if (int rc = finish_call(t)) return rc;
+        RT_HIP(hipSetDevice(t->mesh->device));
+        hipStream_t s = t->mesh->stream;
+        if (S->sr_applied) RT_HIP(hipMemcpyAsync(S->vol.p, S->sr_vol_cells.p, (size_t)nm * sizeof(double), hipMemcpyDeviceToDevice, s));
+        if (int rc = upload(S->mat, S->h_mat.data(), (size_t)nm, s)) return rc;
+        RT_HIP(hipStreamSynchronize(s));
+        S->sr_on = false; S->sr_done = false; S->sr_applied = false; S->n_cells = nm; S->has_ext = false; S->ran = false;
+        S->h_sr.clear();
+        for (int i = 0; i < 8; ++i) S->sr_info[i] = 0;
+        S->sr_map.release(); S->sr_counts.release(); S->sr_plan.release(); S->sr_wstats.release(); S->sr_ctab.release(); S->sr_cell.release();
+        S->sr_first.release(); S->sr_cells.release(); S->sr_ell.release(); S->sr_vol_cells.release();
+        return RT_SUCCESS;
+    }
+    if (n_src < 1 || n_src > nm) { set_error("%s: bad arguments (n_src %d, need 1 .. the mesh's %d cells)", who, n_src, nm); return RT_ERR_INVALID; }
+    if (S->mode == SweepMode::Linear || S->ls_stage != 0) { set_error("%s: the linear source is on (rt_solver_set_linear_source: its centroids and C matrices are per cell), and source regions together with it are not supported", who); return RT_ERR_INVALID; }
+    if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible: their tally index is per original row slot), and source regions together with them are not supported", who); return RT_ERR_INVALID; }
+    if (S->reg_R > 0 || S->cm_on) { set_error("%s: region currents are set (rt_solver_set_regions, rt_solver_set_cmfd: the coarse-mesh prolongation reads the compact records' cells), and source regions together with them are not supported", who); return RT_ERR_INVALID; }
+    if (S->vc_mode) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction: its factors are per cell), and source regions together with it are not supported", who); return RT_ERR_INVALID; }
+    if (t->sw_shard) { set_error("%s: the track set is a shard (some next uid is 0): source regions on sharded runs are not supported", who); return RT_ERR_INVALID; }
+    std::vector<int32_t> rmat((size_t)n_src, -1), first((size_t)n_src + 1, 0), cells((size_t)nm);
+    for (int32_t e = 0; e < nm; ++e) {
+        const int32_t g = map[e];
+        if (g < 0 || g >= n_src) { set_error("%s: cell_source_region[%d] = %d is not a region in [0, %d)", who, e, g, n_src); return RT_ERR_INVALID; }
+        if (rmat[(size_t)g] < 0) rmat[(size_t)g] = S->h_mat[(size_t)e];
+        else if (rmat[(size_t)g] != S->h_mat[(size_t)e]) {
+            set_error("%s: source region %d mixes materials (cell %d has material %d, an earlier cell of the region %d): every cell of a region must carry the same material", who, g, e, S->h_mat[(size_t)e], rmat[(size_t)g]);
+            return RT_ERR_INVALID;
+        }
+        ++first[(size_t)g + 1];
+    }
+    for (int32_t g = 0; g < n_src; ++g) {
+        if (first[(size_t)g + 1] == 0) { set_error("%s: source region %d has no cell (every region in [0, %d) needs one: its material is its cells')", who, g, n_src); return RT_ERR_INVALID; }
+        first[(size_t)g + 1] += first[(size_t)g];
+    }
+    {
+        std::vector<int32_t> at(first.begin(), first.end() - 1);
+        for (int32_t e = 0; e < nm; ++e) cells[(size_t)at[(size_t)map[e]]++] = e;  // (ascending e inside every region)
+    }
+    if (int rc = finish_call(t)) return rc;
+    RT_HIP(hipSetDevice(t->mesh->device));
+    hipStream_t s = t->mesh->stream;
+    if (int rc = upload(S->sr_map, map, (size_t)nm, s)) return rc;
+    if (int rc = upload(S->sr_first, first.data(), first.size(), s)) return rc;
+    if (int rc = upload(S->sr_cells, cells.data(), cells.size(), s)) return rc;
+    if (int rc = upload(S->mat, rmat.data(), rmat.size(), s)) return rc;
+    // V_r from the cells' track-based V_e, which go aside once (another map while the option is on sums them again)
+    RT_HIP(S->sr_vol_cells.reserve((size_t)std::max<int32_t>(1, nm)));
+    if (!S->sr_applied) {
+        RT_HIP(hipMemcpyAsync(S->sr_vol_cells.p, S->vol.p, (size_t)nm * sizeof(double), hipMemcpyDeviceToDevice, s));
+        S->sr_applied = true;
+    }
+    rt::DSrcReg a{};
+    a.n_cells = nm; a.n_src = n_src;
+    a.reg_first = S->sr_first.p; a.reg_cells = S->sr_cells.p; a.vol_cells = S->sr_vol_cells.p; a.vol = S->vol.p;
+    if (int rc = launch_srcreg_volumes(a, s)) return rc;
+    RT_HIP(hipStreamSynchronize(s));  // (the host vectors die here)
+    RT_HIP(hipGetLastError());
+    S->h_sr.assign(map, map + nm);
+    S->sr_on = true; S->sr_done = false; S->n_cells = n_src; S->has_ext = false; S->ran = false;
+    for (int i = 0; i < 8; ++i) S->sr_info[i] = 0;
+    S->sr_info[0] = n_src;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_source_regions(rt_solver *solver, const int32_t *cell_source_region, int32_t n_src) {
+    return guarded("rt_solver_set_source_regions", [&] { return solver_set_source_regions_impl(solver, cell_source_region, n_src); });
+}
+
+int32_t rt_solver_source_region_info(rt_solver *solver, int64_t *out) {
+    if (!solver || !out) { set_error("rt_solver_source_region_info: null argument"); return RT_ERR_INVALID; }
+    for (int i = 0; i < 8; ++i) out[i] = solver->sr_on ? solver->sr_info[i] : 0;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_source_region_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
+    if (!solver) { set_error("rt_solver_source_region_pointers: null solver"); return RT_ERR_INVALID; }
+    // (no wait here: addresses and counts only)
+    const bool on = solver->sr_on && solver->sr_done;
+    const int64_t nw = (solver->t->n + 63) / 64;
+    void *p[6] = {solver->sr_ctab.p, solver->sr_cell.p, solver->sr_ell.p, solver->sr_counts.p, solver->vol.p, solver->sr_wstats.p};
+    const int64_t l[6] = {nw * rt::kMaxChunks, solver->sr_slots, solver->sr_slots, solver->t->n, solver->n_cells, nw * rt::kSrWaveStats};
+    for (int i = 0; i < 6; ++i) {
+        if (ptrs_dev) ptrs_dev[i] = on ? p[i] : nullptr;
+        if (lens) lens[i] = on ? l[i] : 0;
+    }
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_fetch_source_rows(rt_solver *solver, int64_t *offsets, double *ell, int32_t *region, int64_t cap) {
+    const char *who = "rt_solver_fetch_source_rows";
+    if (!solver || !offsets) { set_error("%s: null argument", who); return RT_ERR_INVALID; }
+    if (!solver->sr_on || !solver->sr_done) { set_error("%s: no run with source regions yet (rt_solver_set_source_regions, then a run or rt_solver_begin)", who); return RT_ERR_INVALID; }
+    return guarded(who, [&]() -> int32_t {
+        rt_tracks *t = solver->t;
+        if (int rc = finish_call(t)) return rc;
+        RT_HIP(hipSetDevice(solver->device));
+        hipStream_t s = t->mesh->stream;
+        const int64_t n = t->n, nw = (n + 63) / 64, slots = solver->sr_slots;
+        std::vector<int32_t> perm((size_t)n), cnt((size_t)n), ctab((size_t)nw * rt::kMaxChunks), word((size_t)slots);
+        std::vector<double> l((size_t)slots);
+        if (n > 0) {
+            RT_HIP(hipMemcpyAsync(perm.data(), t->perm.p, perm.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            RT_HIP(hipMemcpyAsync(cnt.data(), solver->sr_counts.p, cnt.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            RT_HIP(hipMemcpyAsync(ctab.data(), solver->sr_ctab.p, ctab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            RT_HIP(hipMemcpyAsync(word.data(), solver->sr_cell.p, word.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            RT_HIP(hipMemcpyAsync(l.data(), solver->sr_ell.p, l.size() * sizeof(double), hipMemcpyDeviceToHost, s));
+        }
+        RT_HIP(hipStreamSynchronize(s));
+        offsets[0] = 0;
+        for (int64_t u = 0; u < n; ++u) offsets[u + 1] = offsets[u] + cnt[(size_t)u];
+        if (!ell && !region) return RT_SUCCESS;
+        if (offsets[n] > cap) { set_error("%s: %lld merged rows, room for %lld", who, (long long)offsets[n], (long long)cap); return RT_ERR_INVALID; }
+        for (int64_t slot = 0; slot < n; ++slot) {  // (march slot -> uid; the row slot as stage_slot forms it)
+            const int64_t u = perm[(size_t)slot], w = slot >> 6, lane = slot & 63;
+            if (u < 0 || u >= n) { set_error("%s: the march order names uid %lld", who, (long long)u); return RT_ERR_INVALID; }
+            for (int32_t r = 0; r < cnt[(size_t)u]; ++r) {
+                const int64_t c = ctab[(size_t)(w * rt::kMaxChunks + (r >> rt::kChunkLog2))];
+                const int64_t sl = ((c * 4 + (lane >> 4)) * rt::kChunkRows + (r & (rt::kChunkRows - 1))) * 16 + (lane & 15);
+                if (sl < 0 || sl >= slots) { set_error("%s: a merged row lies outside its buffer", who); return RT_ERR_INVALID; }
+                if (ell) ell[offsets[u] + r] = l[(size_t)sl];
+                if (region) region[offsets[u] + r] = word[(size_t)sl] - 1;
+            }
+        }
+        return RT_SUCCESS;
+    });
 }
 
 int32_t rt_solver_ls_geometry_pointer(rt_solver *solver, void **acc_dev, int64_t *len) {

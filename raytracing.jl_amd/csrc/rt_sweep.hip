@@ -407,11 +407,12 @@ using namespace rtsweep;
 // what a sweep of G components reads and how wide its passes may be: the handle's state, the options and an rt_solver's loan
 static SweepFacts sweep_facts(const rt_tracks *t, int32_t G, int32_t input, const SweepLoan &loan, bool volcorr) {
     const rt_mesh *m = t->mesh;
-    return SweepFacts{.n = t->n, .n_cells = m->n_cells, .G = G, .input = input, .mode = loan.mode, .repro = loan.repro,
+    // (source regions: the solver's n_src stands in for the mesh's cells — the LDS copy of a pass holds n_src tallies per component)
+    return SweepFacts{.n = t->n, .n_cells = loan.sr_n_src > 0 ? loan.sr_n_src : m->n_cells, .G = G, .input = input, .mode = loan.mode, .repro = loan.repro,
                       .f32 = loan.f32 || m->sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
                       .sw_ell_valid = t->sw_ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
                       .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves, .regions = loan.n_regions,
-                      .volcorr = volcorr};
+                      .volcorr = volcorr, .srcreg = loan.sr_n_src > 0};
 }
 
 namespace rtx {
@@ -570,6 +571,13 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         set_error("rt_sweep: the volume correction (rt_solver_set_volume_correction) scaled other rows than this sweep reads (an option or the rows changed under the run): begin the run again");
         return RT_ERR_INVALID;
     }
+    // the solver's merged rows stand in for the rows: they were made from THESE rows as they stand, or the sweep is refused here, with
+    // nothing queued
+    if (facts.srcreg && (!rows_read_ell(plan.rows) || plan.rows != loan.sr_rows || t->sw_rows_gen != loan.sr_gen || !loan.sr_ctab || !loan.sr_cell ||
+                         !loan.sr_ell || !loan.sr_counts)) {
+        set_error("rt_sweep: the source regions (rt_solver_set_source_regions) merged other rows than this sweep reads (an option or the rows changed under the run): begin the run again");
+        return RT_ERR_INVALID;
+    }
     // the rows the plan names, made once per segmentation: from the compact records here, the staging's below (inside `ms`, as ever)
     if (!rows_staged(plan.rows) || plan.rows == SweepRows::FromCompact)
         if (int rc = ensure_compacted(t)) return rc;
@@ -628,6 +636,11 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     }
     a.ell_rows = rows_kind(plan.rows) ? as_global(t->sw_ell.p) : nullptr;
     if (facts.volcorr) a.ell_rows = as_global(const_cast<double *>(loan.vc_ell));  // (checked above; only read: no pass of these rows writes ℓ)
+    if (facts.srcreg) {  // (checked above; only read) the merged rows, their chunk table and counts, n_src "cells"
+        a.stg.ctab = as_global(const_cast<int32_t *>(loan.sr_ctab)); a.stg.element = as_global(const_cast<int32_t *>(loan.sr_cell));
+        a.ell_rows = as_global(const_cast<double *>(loan.sr_ell)); a.counts = as_global(loan.sr_counts);
+        a.n_cells = loan.sr_n_src;
+    }
     int passes = 0;
     for (int g0 = 0; n > 0 && g0 < G; ++passes) {
         const int take = std::min(plan.gp, G - g0);

@@ -51,6 +51,7 @@ struct SweepFacts {
     int sweep_rows = 1, sweep_ell = 1, sweep_gp = 0, sweep_waves = 0;  // the options
     int regions = 0;           // R of the region currents (lent by a solver, rt_solver_set_regions); 0: off
     bool volcorr = false;      // the rows' ℓ comes from a solver's corrected copy (rt_solver_set_volume_correction)
+    bool srcreg = false;       // the rows are a solver's merged rows and n_cells its n_src (rt_solver_set_source_regions)
 };
 
 constexpr int kMaxRegions = 127;  // (R + 1)² doubles of one component fit the LDS of a workgroup: 128 KiB
@@ -98,6 +99,9 @@ struct SweepPlan {
 
 #define RT_VC_WITH(other) "rt_sweep: the volume correction (rt_solver_set_volume_correction) together with " other " — not supported"
 #define RT_VC_ROWS(why) "rt_sweep: the volume correction (rt_solver_set_volume_correction) scales the ℓ of (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
+
+#define RT_SR_WITH(other) "rt_sweep: the source regions (rt_solver_set_source_regions) together with " other " — not supported"
+#define RT_SR_ROWS(why) "rt_sweep: the source regions (rt_solver_set_source_regions) merge (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
 
 inline SweepPlan plan_sweep(const SweepFacts &f) {
     SweepPlan p;
@@ -152,6 +156,20 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
             return refuse(RT_VC_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
                                      "sweep without the correction first, or set option \"sweep_rows\" 2 and name the compact records"));
     }
+    // source regions: the sweep reads the solver's merged rows and tallies into n_src "cells" (f.n_cells is n_src here, so the passes
+    // below widen by themselves) — rows that carry no ℓ are refused like the volume correction's, before anything is queued; so is
+    // everything that is per mesh cell or per original row slot
+    if (f.srcreg) {
+        if (f.mode == SweepMode::Linear) return refuse(RT_SR_WITH("the linear source (rt_solver_set_linear_source): its centroids and C matrices are per cell"));
+        if (f.repro) return refuse(RT_SR_WITH("the reproducible tallies (rt_solver_set_reproducible): their tally index is per original row slot"));
+        if (f.regions > 0) return refuse(RT_SR_WITH("the region currents (rt_solver_set_regions, rt_solver_set_cmfd): the coarse-mesh prolongation reads the compact records' cells"));
+        if (f.volcorr) return refuse(RT_SR_WITH("the volume correction (rt_solver_set_volume_correction): its factors are per cell"));
+        if (p.rows == SweepRows::Records) return refuse(RT_SR_ROWS("the compact records where they lie: option \"sweep_rows\" is 0"));
+        if (p.rows == SweepRows::Staged20) return refuse(RT_SR_ROWS("the staging's 20-B rows in every pass: option \"sweep_ell\" is 0"));
+        if (p.rows == SweepRows::Staged20WriteEll)
+            return refuse(RT_SR_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
+                                     "sweep without source regions first, or set option \"sweep_rows\" 2 and name the compact records"));
+    }
     // components per pass: as many as an LDS-private copy of their tallies allows (up to 4); none fits: global atomics.  The last
     // pass takes what is left with the kernel compiled for that many (7 groups = 4 + 3: a padded fourth group was an eighth of the
     // sweep's arithmetic).  First-moment scattering and the linear source: three tallies per component, so a mesh that fits 4
@@ -193,5 +211,7 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
 #undef RT_IFACE_ROWS
 #undef RT_VC_WITH
 #undef RT_VC_ROWS
+#undef RT_SR_WITH
+#undef RT_SR_ROWS
 
 }  // namespace rtsweep

@@ -20,6 +20,9 @@ With ``regions=...`` (an int per cell, or ``"material"``) every sweep also talli
 (``rt_solver_set_regions``): ``SolverResult.region_current`` and the balance of every region, ``region_balance``.
 With ``volume_correction="angle"`` (or ``"cell"``) the chord lengths the sweeps read are renormalised so that every cell's tracked
 area equals its exact area (``rt_solver_set_volume_correction``); ``SolverResult.volumes`` are then the corrected ones.
+With ``source_regions=...`` (an int per cell, or ``"material"``) every flat-source region is a set of cells and the sweeps read rows
+merged per region (``rt_solver_set_source_regions``): ``phi``, ``volumes``, ``current`` and ``source`` are then per source region, and
+``SolverResult.to_cells`` spreads such an array over the mesh's cells.
 With ``cmfd=True`` (or a ``Cmfd``) on top of ``regions=...`` every iteration also solves the partial-current coarse-mesh balance
 over the regions and prolongs its solution onto φ, k and the boundary fluxes (``rt_solver_set_cmfd``): the same answer in fewer
 iterations; ``diffusion_coupling`` builds an optional coupling D̂ from the mesh.
@@ -350,6 +353,13 @@ class SolverResult:
     cell_area: Optional[np.ndarray] = None        # ... the cells' exact areas A_e [n_cells]
     volume_factor: Optional[np.ndarray] = None    # ... f [n_cells, n_azim_2]
     volume_correction_info: Optional[dict] = None  # ... unseen_pairs, zero_area_cells, zero_volume_cells, f_min, f_max; all None without
+    source_region: Optional[np.ndarray] = None     # source_regions=...: the cells' regions [mesh cells]; phi, volumes, current are then [n_src, ...]
+    source_region_info: Optional[dict] = None      # ... n_src, rows / largest count / chunks before and after the merge; both None without
+
+    def to_cells(self, a):
+        """An array per source region (``phi``, ``volumes``, ``current``) spread over the mesh's cells: ``a[source_region]``; ``a``
+        itself without source regions."""
+        return np.asarray(a) if self.source_region is None else np.asarray(a)[self.source_region]
 
 
 def _cell_material(tg, cell_material):
@@ -381,6 +391,30 @@ def _cell_regions(cm, regions):
     return np.ascontiguousarray(reg, np.int32)
 
 
+def _source_regions(cm, source_regions):
+    """``source_regions`` as (int32 array per cell, n_src): ``"material"`` is ``cell_material``'s distinct values, numbered in
+    ascending order.  A region whose cells carry different materials raises ``ValueError``."""
+    if isinstance(source_regions, str):
+        if source_regions != "material":
+            raise ValueError(f'unknown source_regions {source_regions!r} ("material" or an int array per cell)')
+        sr = np.unique(cm, return_inverse=True)[1].reshape(-1)
+    else:
+        sr = np.asarray(source_regions)
+        if sr.shape != np.shape(cm) or not np.issubdtype(sr.dtype, np.integer):
+            raise ValueError("source_regions must be an int array with one entry per cell")
+    sr = np.ascontiguousarray(sr, np.int32)
+    if sr.size == 0 or sr.min() < 0:
+        raise ValueError("source region ids must be >= 0, one per cell")
+    n_src = int(sr.max()) + 1
+    lo = np.full(n_src, np.iinfo(np.int64).max); hi = np.full(n_src, -1)
+    np.minimum.at(lo, sr, cm); np.maximum.at(hi, sr, cm)
+    if (hi < 0).any():
+        raise ValueError(f"source region {int(np.flatnonzero(hi < 0)[0])} has no cell (the ids must be 0 .. n_src - 1 without gaps)")
+    if (lo != hi).any():
+        raise ValueError(f"source region {int(np.flatnonzero(lo != hi)[0])} mixes materials: every cell of a region must carry the same one")
+    return sr, n_src
+
+
 def _device_tracks(tg, device):
     """The tracks' device handle after ``segmentize`` (run here with ``fetch=False`` if it has not run), links set."""
     from .segmentize import segmentize
@@ -407,9 +441,16 @@ def _volume_correction(tg, volume_correction):
 
 
 def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat", adjoint=False,
-           boundary=None, reproducible=False, precision="double", regions=None, cmfd=None, volume_correction=None):
+           boundary=None, reproducible=False, precision="double", regions=None, cmfd=None, volume_correction=None, source_regions=None):
     acc = _as_cmfd(cmfd)
     vc = _volume_correction(tg, volume_correction)
+    if source_regions is not None:
+        for on, what in ((scheme == "linear", 'scheme="linear" (centroids and the C matrices are per cell)'),
+                         (reproducible, "reproducible=True (the tally index is per original row slot)"),
+                         (regions is not None or acc is not None, "regions= / cmfd= (the coarse-mesh prolongation reads the compact records' cells)"),
+                         (vc is not None, "volume_correction (its factors are per cell)")):
+            if on:
+                raise ValueError(f"source_regions together with {what} is not supported")
     if vc is not None and scheme == "linear":
         raise ValueError('volume_correction together with scheme="linear" is not supported (scaled chords would move the linear '
                          "source's midpoints off the track)")
@@ -435,10 +476,21 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
     dt = _device_tracks(tg, device)
     cm = _cell_material(tg, cell_material)
     reg = None if regions is None else _cell_regions(cm, regions)
+    sr, cm_r = None, cm  # (cm_r: the material of every flat-source region — of every cell without source regions)
+    if source_regions is not None:
+        sr, n_src = _source_regions(cm, source_regions)
+        cm_r = np.zeros(n_src, cm.dtype)
+        cm_r[sr] = cm
+        if source is not None and (np.ndim(source) == 0 or np.shape(source) == (xs.n_groups,)):
+            source = np.broadcast_to(source, (n_src, xs.n_groups))
+        if source is not None and np.shape(source) != (n_src, xs.n_groups):
+            raise ValueError("source must have shape [n_src, G] with source_regions")
     if acc is not None:
         acc.check(int(reg.max(initial=-1)) + 1, xs.n_groups)
     sv = _capi.DeviceSolver(dt, cm, xs.sigma_t, xs.sigma_s, xs.nu_sigma_f, xs.chi,
                             pq.sin_theta, pq.weights, alpha)
+    if sr is not None:  # (first: the source below is per region; refused by the library on a shard's track set)
+        sv.set_source_regions(sr, n_src)
     if source is not None:
         sv.set_source(source)
     if xs.sigma_s1 is not None:
@@ -470,7 +522,7 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         bnd.update(sv.fetch_boundary())
         bnd["leakage"] = bnd["current_out"] - bnd["current_in"]
         eigen = mode == _capi.DeviceSolver.EIGENVALUE
-        bnd["balance"] = neutron_balance(xs, cm, f["phi"], f["volumes"], r["k_eff"] if eigen else None, None if eigen else source,
+        bnd["balance"] = neutron_balance(xs, cm_r, f["phi"], f["volumes"], r["k_eff"] if eigen else None, None if eigen else source,
                                          bnd["current_out"], bnd["current_in"], adjoint=adjoint)
     if reg is not None:
         eigen = mode == _capi.DeviceSolver.EIGENVALUE
@@ -482,6 +534,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
     if vc is not None:
         v = sv.fetch_volume_correction()
         bnd.update(volume_correction=vc, cell_area=v.pop("area"), volume_factor=v.pop("factor"), volume_correction_info=v)
+    if sr is not None:
+        bnd.update(source_region=sr, source_region_info=sv.source_region_info())
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
@@ -492,7 +546,7 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
                      tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
                      boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double",
-                     regions=None, cmfd=None, volume_correction=None) -> SolverResult:
+                     regions=None, cmfd=None, volume_correction=None, source_regions=None) -> SolverResult:
     """Power iteration for k_eff on the device.  ``cell_material``: material index per cell [n_cells] (or one index for all,
     or a dict region name -> index over ``tg.mesh.model.cell_region``).  ``polar``: a ``PolarQuadrature`` spec;
     ``azim_weights``: "exact", "equal" or an array.  Uses ``tg.device_tracks`` when ``segmentize(tg, fetch=False)`` has run,
@@ -514,27 +568,32 @@ def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar
     so that every cell's tracked area equals its exact area, per azimuthal angle or with one factor per cell
     (``rt_solver_set_volume_correction``); ``volumes`` are then the corrected V' and the result carries ``cell_area``,
     ``volume_factor`` and ``volume_correction_info``; None: what ``tg.volume_correction`` says (True there: ``"angle"``), False: off.
-    Not together with ``scheme="linear"`` or ``reproducible=True`` (``ValueError``)."""
+    Not together with ``scheme="linear"`` or ``reproducible=True`` (``ValueError``).  ``source_regions``: an int array per cell or
+    ``"material"`` — every flat-source region a set of cells of one material, the sweeps over rows merged per region
+    (``rt_solver_set_source_regions``); ``cell_material`` stays per mesh cell (a mixed region: ``ValueError``), ``phi``, ``volumes``
+    and ``current`` are per source region, the result carries ``source_region`` and ``source_region_info``, and
+    ``result.to_cells(a)`` spreads an array over the cells.  Not together with ``scheme="linear"``, ``reproducible=True``,
+    ``regions`` / ``cmfd`` or ``volume_correction`` (``ValueError``)."""
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.EIGENVALUE, None, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible, precision, regions, cmfd, volume_correction)
+                  adjoint, boundary, reproducible, precision, regions, cmfd, volume_correction, source_regions)
 
 
 def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
                        tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
                        boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double",
-                       regions=None, cmfd=None, volume_correction=None) -> SolverResult:
+                       regions=None, cmfd=None, volume_correction=None, source_regions=None) -> SolverResult:
     """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
     the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``; with ``adjoint=True`` ``source`` is the
     adjoint source S† (for instance a detector cross section) and ``phi`` the importance φ†: Σ V S† φ = Σ V S φ†.  ``boundary``: a
     ``SolverBoundary``, here also with an incoming flux per side and group (``source`` may then be zero: a run driven from the
-    boundary).  ``reproducible``, ``precision``, ``regions``, ``cmfd``, ``volume_correction``: as for ``solve_eigenvalue`` (``cmfd``
-    not together with an incoming flux)."""
+    boundary).  ``reproducible``, ``precision``, ``regions``, ``cmfd``, ``volume_correction``, ``source_regions``: as for ``solve_eigenvalue``
+    (``cmfd`` not together with an incoming flux; with ``source_regions`` the ``source`` is [n_src, G])."""
     q = np.asarray(source, np.float64)
     G = xs.n_groups
-    if q.ndim == 0 or q.shape == (G,):
+    if (q.ndim == 0 or q.shape == (G,)) and source_regions is None:  # (with source_regions: _solve broadcasts over its n_src)
         q = np.broadcast_to(q, (tg.mesh.num_cells, G))
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible, precision, regions, cmfd, volume_correction)
+                  adjoint, boundary, reproducible, precision, regions, cmfd, volume_correction, source_regions)
 
 
 # ---- adjoint-weighted integrals ------------------------------------------------------------------------------------------------
@@ -561,6 +620,8 @@ def _fission_form(xs):
 
 
 def _check_pair(forward, adjoint):
+    if getattr(forward, "source_region", None) is not None or getattr(adjoint, "source_region", None) is not None:
+        raise ValueError("the adjoint-weighted integrals are per mesh cell: results of a run with source_regions= are not supported")
     if getattr(forward, "adjoint", False) or not getattr(adjoint, "adjoint", True):
         raise ValueError("forward must be a forward result and adjoint an adjoint one (solve_eigenvalue(..., adjoint=True))")
     if forward.k_eff is None:

@@ -10,7 +10,10 @@ single-precision sweep beside the FP64 one and the deviation of k; `--regions N`
 region currents (rt_solver_set_regions; N <= 3: regions by material, else by cell index modulo N; `--region-grid B`: a B x B grid of
 bands over the domain instead, N = B²) under "regions_*"; `--cmfd` (needs `--regions` or `--region-grid`): then the same runs with the
 coarse-mesh acceleration over those regions (rt_solver_set_cmfd) under "cmfd_*", and the iterations and device time to tol_k = tol_flux =
-`--tol` of the run with regions alone against the accelerated one).
+`--tol` of the run with regions alone against the accelerated one; `--source-regions material` or `--source-regions rings:K,S`: the
+forward figures first, then the same runs on source regions (rt_solver_set_source_regions) under "sr_*" — by material, or K equal-area
+rings inside each material times S sectors about the mesh's centre, binned by cell centroid — with the rows, the mean over the march
+waves of the largest count before and after the merge, the chunks, `gp` and the passes of the sweep, the one-off host time and k).
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
@@ -53,6 +56,37 @@ def xs_groups(rt, G, seed=1):
     return rt.CrossSections(st, ss, nf, chi)
 
 
+def source_region_map(tg, mat, spec):
+    """`material`, or `rings:K,S`: inside each material K rings of equal cell area about the mesh's centre (cells sorted by their
+    centroid's distance, cut where the running area passes 1/K, 2/K, ... of the material's) times S sectors of equal angle; only the
+    regions that hold a cell are numbered.  int32 [cells], n_src."""
+    mat = np.asarray(mat, np.int64)
+    if spec == "material":
+        sr = mat
+    else:
+        if not spec.startswith("rings:"):
+            raise SystemExit('--source-regions: "material" or "rings:K,S"')
+        K, S = (int(v) for v in spec[6:].split(","))
+        if K < 1 or S < 1:
+            raise SystemExit("--source-regions rings:K,S needs K >= 1 and S >= 1")
+        m = tg.mesh
+        cn = np.asarray(m.cell_nodes, np.int64).reshape(-1, 3) - 1
+        x, y = np.asarray(m.x, np.float64)[cn], np.asarray(m.y, np.float64)[cn]
+        area = 0.5 * np.abs((x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (x[:, 2] - x[:, 0]) * (y[:, 1] - y[:, 0]))
+        cx, cy = x.mean(1) - 0.5 * (m.x.min() + m.x.max()), y.mean(1) - 0.5 * (m.y.min() + m.y.max())
+        r = np.hypot(cx, cy)
+        sector = np.minimum((S * (np.arctan2(cy, cx) + np.pi) / (2.0 * np.pi)).astype(np.int64), S - 1)
+        ring = np.zeros(len(mat), np.int64)
+        for mm in np.unique(mat):
+            idx = np.flatnonzero(mat == mm)
+            idx = idx[np.argsort(r[idx], kind="stable")]
+            run = np.cumsum(area[idx]) - 0.5 * area[idx]  # (the running area at the cell's middle)
+            ring[idx] = np.minimum((K * run / area[idx].sum()).astype(np.int64), K - 1)
+        sr = (mat * K + ring) * S + sector
+    sr = np.unique(sr, return_inverse=True)[1].reshape(-1).astype(np.int32)
+    return sr, int(sr.max()) + 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mesh", default="pincell.msh")
@@ -82,6 +116,9 @@ def main():
     ap.add_argument("--volume-correction", choices=("angle", "cell"), default=None,
                     help="after the forward runs, the same runs with the volume correction (rt_solver_set_volume_correction): the one-off time of "
                          "its kernels (the first begin's host time minus a later one's) and the time per iteration; not with --linear")
+    ap.add_argument("--source-regions", default=None, metavar="MAP",
+                    help='after the forward runs, the same runs on source regions (rt_solver_set_source_regions): "material", or "rings:K,S" — K '
+                         "equal-area rings inside each material and S sectors, by cell centroid; not with --linear / --reproducible / --regions / --volume-correction")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -121,7 +158,11 @@ def main():
         ks.append(r["k_eff"])
     out = dict(config=dict(mesh=a.mesh, n_azim=a.n_azim, delta=a.delta, groups=a.groups, polar=a.polar, components=a.groups * pq.n_polar,
                            p1=bool(a.p1), linear=bool(a.linear), tracks=int(tg.n_total_tracks), records=int(dt.total), cells=int(tg.mesh.num_cells), iters=a.iters),
-               ms_per_iter_events=float(np.median(ev_ms)), ms_per_iter_host=float(np.median(host_ms)), k_eff=ks[-1])
+               ms_per_iter_events=float(np.median(ev_ms)), ms_per_iter_host=float(np.median(host_ms)), k_eff=ks[-1],
+               ms_per_iter_events_runs=[float(v) for v in ev_ms])
+    swi = (_capi.C.c_int32 * 4)()
+    _capi._check(_capi.lib().rt_sweep_info(dt._h, None, swi))
+    out["sweep_gp"], out["sweep_passes"] = int(swi[1]), int(swi[2])
     if a.adjoint:  # (the same kernels on the transposed tables: the time per iteration is expected to equal the forward one)
         sv.set_adjoint(True)
         sv.run(0, 3, 0.0, 0.0)
@@ -197,6 +238,40 @@ def main():
         out["vc_volume_sum"] = float(sv.volumes().sum())
         out["vc_area_sum"] = float(v["area"].sum())
         sv.set_volume_correction(None)
+    if a.source_regions:  # (the sweep reads the solver's merged rows through the pointers it read rows through, and tallies into n_src "cells")
+        sr, n_src = source_region_map(tg, _cell_material(tg, cm), a.source_regions)
+        sv.set_source_regions(sr, n_src)
+        t0 = time.perf_counter(); sv.begin(0); t_first = time.perf_counter() - t0; sv.end()  # (count, plan, fill: once)
+        t0 = time.perf_counter(); sv.begin(0); t_again = time.perf_counter() - t0; sv.end()
+        sv.run(0, 3, 0.0, 0.0)
+        ev_ms, host_ms = [], []
+        for _ in range(a.repeats):
+            t0 = time.perf_counter()
+            r = sv.run(0, a.iters, 0.0, 0.0)
+            host_ms.append((time.perf_counter() - t0) * 1e3 / a.iters)
+            ev_ms.append(r["device_ms"] / r["iterations"])
+        info = sv.source_region_info()
+        swi = (_capi.C.c_int32 * 4)()
+        _capi._check(_capi.lib().rt_sweep_info(dt._h, None, swi))
+        import torch
+        from raytracing_jl_amd.distributed import DevArray
+
+        p = sv.source_region_pointers()
+        ws = torch.as_tensor(DevArray(p["wave_stats"], p["lens"]["wave_stats"], "<i4", sv), device=torch.device("cuda", 0)).cpu().numpy().reshape(-1, 4)
+        out["sr_map"] = a.source_regions
+        out["sr_info"] = info
+        out["sr_waves"] = int(len(ws))
+        out["sr_mean_wave_max_before"] = float(ws[:, 0].mean())
+        out["sr_mean_wave_max_after"] = float(ws[:, 1].mean())
+        out["sr_sweep_gp"] = int(swi[1])  # (components per pass with an LDS copy; 0: global atomics)
+        out["sr_sweep_passes"] = int(swi[2])
+        out["sr_ms_per_iter_events"] = float(np.median(ev_ms))
+        out["sr_ms_per_iter_host"] = float(np.median(host_ms))
+        out["sr_over_plain_events"] = out["sr_ms_per_iter_events"] / out["ms_per_iter_events"]
+        out["sr_k_eff"] = r["k_eff"]
+        out["sr_k_minus_plain"] = r["k_eff"] - out["k_eff"]
+        out["sr_one_off_ms"] = (t_first - t_again) * 1e3
+        sv.set_source_regions(None)
     if a.single:  # (k_sweep_f32 in place of k_sweep; everything else of the iteration is what it was)
         sv.set_precision("single")
         sv.run(0, 3, 0.0, 0.0)
