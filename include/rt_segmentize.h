@@ -444,9 +444,9 @@ void rt_msh_free(rt_msh *msh);
 int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
 
 /* ---------------------------------------------------------------------------------------
- * MOC source-iteration solver on the device (power-iteration k_eff and fixed source) over the
- * records of the last rt_segmentize, built on rt_sweep.  Only a few scalars come back to the
- * host per iteration.
+ * MOC source-iteration solver on the device (power-iteration k_eff, fixed source, and implicit-Euler
+ * transients with delayed neutrons) over the records of the last rt_segmentize, built on rt_sweep.
+ * Only a few scalars come back to the host per iteration.
  *
  * Notation: G groups, P polar angles per half space (sin θ_p, weights ω_p, Σ_p ω_p = 1), M
  * materials (0-based ids) with sigma_t[m][g], sigma_s[m][g'][g] (from g' to g), nu_sigma_f[m][g],
@@ -763,6 +763,42 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              result.  Off restores the cells' materials and the track-based V_e, bit-equal to a solver that never had the option,
  *              and frees every buffer.  A solver without the option launches exactly what it always did.
  *
+ * Transient, rt_solver_transient_begin / _step / _set_xs / _fetch / _pointers / _end: implicit Euler in time with the isotropic
+ * approximation of the time derivative, ∂ψ/∂t ≈ (1/4π) ∂φ/∂t, and D families of delayed-neutron precursors.  Every time step is a
+ * fixed-source problem of the iteration above (k ≡ 1), started from the previous step's φ and boundary fluxes.
+ * Data         λ_d [D] (decay constants), β [M][D], χd [M][D][G] (delayed spectra), 1/v [M][G]; k0: the k_eff of the solver's last
+ *              completed eigenvalue run, whose φ (scaled to F(φ) = 1) is the initial flux — the production F(t) is the relative power
+ * Prompt part  χ̃_{m,g} = χ_{m,g} − Σ_d β_{m,d} χd_{m,d,g} must be >= −1e-14 (RT_ERR_INVALID names the material and the group)
+ * Precursors   per (cell, family): dC/dt = β_d F_e / k0 − λ_d C, F_e = Σ_g νΣf_g φ_{e,g};  C⁰ = β_d F_e⁰ / (λ_d k0);
+ *              C^{n+1} = (C^n + Δt β_d F_e^{n+1} / k0) / (1 + λ_d Δt)
+ * Step         n → n+1 with Δt: Σt unchanged (the sweep's Σt / sin θ and the fold's Σt carry no time term), and a material table with
+ *                  Σs'[g→g] = Σs[g→g] − 1/(v_g Δt)   (the lagged −φ^{n+1} / (4π v Δt); off-diagonal entries as they are)
+ *                  νΣf'     = νΣf / k0
+ *                  χ'_g     = χ_g − Σ_d β_d χd_{d,g} / (1 + λ_d Δt)   (the delayed emission implicit in F^{n+1}; clamped at 0)
+ *              and the external source S_{e,g} = φ^n_{e,g} / (v_g Δt) + Σ_d χd_{m(e),d,g} λ_d C^n_{e,d} / (1 + λ_d Δt)
+ * Inner        one inner iteration is the source update, one sweep and the fold, unchanged; from φ^n and the boundary fluxes the last
+ *              sweep handed on, until the fixed-source residual < tol or max_inner iterations; then the precursor update from the
+ *              last fold's F_e.  With unchanged cross sections φ^{n+1} = φ^n is an exact fixed point of the step
+ * Settling     the boundary fluxes belong to the handle and may have been overwritten since the eigenvalue run:
+ *              rt_solver_transient_begin opens a fixed-source run that keeps φ, zeroes ψ_in and iterates the steady table (νΣf / k0,
+ *              χ, Σs; no time terms, no source) until the residual < settle_tol or settle_max_iter; it reports both numbers.  φ is
+ *              the converged one and only ψ has to settle — and a free iteration of a critical table would let the amplitude drift
+ *              (the zeroed ψ_in are neutrons lost) — so every settling iteration sweeps the source of φ⁰, folds, and puts φ⁰ back:
+ *              the residual is ‖fold − φ⁰‖₂ / ‖fold‖₂, and φ(0) = φ⁰, F(0) = 1 to the bit
+ * Changes      rt_solver_transient_set_xs replaces the [M]-tables (Σt, Σs, νΣf, χ; the checks of rt_solver_create) from the next step
+ *              on and rewrites the sweep's Σt / sin θ; cell_material and k0 stay (a moving rod: declare the rodded material up front).
+ *              The step table is rebuilt on the host only when Δt differs from the previous step's, or by this call
+ * State        a transient is an open run: every setter refuses ("a run is open"), rt_solver_step_sweep / _step_fold / rt_solver_end
+ *              refuse ("a transient is open"), rt_solver_begin / rt_solver_run end it as a second begin ends a run, rt_tracks_destroy
+ *              and rt_segmentize void it.  The solver's own tables and the source of rt_solver_set_source are never written:
+ *              rt_solver_transient_end only hands the sweep state back; rt_solver_fetch then returns the last φ (not normalised), and
+ *              a later rt_solver_run is what it always was.  The next transient needs an eigenvalue run again
+ * Works with   the flat source, isotropic scattering, FP64, rt_solver_set_boundary albedos
+ * Refused      RT_ERR_INVALID from rt_solver_transient_begin, with a message that names both sides: adjoint mode, the linear source,
+ *              first-moment scattering (the current's time derivative is not modelled), the reproducible tallies, region currents /
+ *              the coarse-mesh acceleration, an incoming boundary flux, the single-precision sweep, the volume correction, source
+ *              regions, a shard's track set.  A solver that never starts a transient launches exactly what it always did.
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -985,6 +1021,29 @@ int32_t rt_solver_source_region_pointers(rt_solver *solver, void **ptrs_dev, int
  * with room for `cap` rows each.  RT_ERR_INVALID without source regions, before the first rt_solver_begin with them, or when the
  * rows exceed `cap` (offsets are filled all the same: offsets[n] is the room needed).  Waits. */
 int32_t rt_solver_fetch_source_rows(rt_solver *solver, int64_t *offsets, double *ell, int32_t *region, int64_t cap);
+/* A transient (see "Transient" above), from the flux and k_eff of this solver's last completed forward eigenvalue run.  All arrays are
+ * host memory and copied: inv_velocity [M][G] (1/v, > 0), beta [M][D] (>= 0), lambda [D] (> 0), chi_delayed [M][D][G] (>= 0), D =
+ * n_families in 1 .. 64.  Builds the tables, settles the boundary fluxes with at most settle_max_iter iterations of the steady table
+ * (stopped once the flux residual < settle_tol) and computes C⁰.  out (may be NULL): iterations and residual of the settling, k_eff =
+ * k0, converged 1 when the residual got below settle_tol.  RT_ERR_INVALID without such a run, with a run open, for bad data (a
+ * negative prompt spectrum names the material and the group) and in the modes listed under "Refused"; the solver keeps what it had. */
+int32_t rt_solver_transient_begin(rt_solver *solver, int32_t n_families, const double *inv_velocity, const double *beta, const double *lambda,
+                                  const double *chi_delayed, int32_t settle_max_iter, double settle_tol, rt_solver_result *out);
+/* One implicit-Euler step of dt (finite, > 0): at most max_inner (>= 1) inner iterations, stopped once the flux residual < tol; then
+ * the precursor update.  out (may be NULL): iterations = the inner iterations of this step, residual = the last one's, k_eff = the
+ * PRODUCTION F(φ^{n+1}) = Σ_e V_e Σ_g νΣf φ (1 at t = 0: the relative power; not an eigenvalue), dk 0, device_ms of the step,
+ * converged 1 when the residual got below tol.  A step that produces a non-finite flux ends the transient. */
+int32_t rt_solver_transient_step(rt_solver *solver, double dt, int32_t max_inner, double tol, rt_solver_result *out);
+/* New [M]-tables (shapes and checks of rt_solver_create) from the next step on; cell_material and k0 stay.  Waits for its kernels. */
+int32_t rt_solver_transient_set_xs(rt_solver *solver, const double *sigma_t, const double *sigma_s, const double *nu_sigma_f, const double *chi);
+/* The state of an open transient: phi [n_cells][G], precursors [n_cells][D], *time = Σ dt so far; any may be NULL. */
+int32_t rt_solver_transient_fetch(rt_solver *solver, double *phi, double *precursors, double *time);
+/* Device addresses and element counts of [0] phi and [1] phi_prev (φ^n of the last step) [n_cells·G], [2] precursors [n_cells·D] and
+ * [3] the step's external source S [n_cells·G], valid while a transient is open (NULL / 0 outside).  Does not wait. */
+int32_t rt_solver_transient_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
+/* Ends the transient: the handle gets its sweep state back, rt_solver_fetch returns the last φ (not normalised), and the solver's own
+ * tables and source are what they were before rt_solver_transient_begin.  RT_ERR_INVALID when none is open. */
+int32_t rt_solver_transient_end(rt_solver *solver);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

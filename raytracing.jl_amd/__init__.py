@@ -9,7 +9,8 @@ without a GPU it raises.  ``solve_eigenvalue`` / ``solve_fixed_source`` run a MO
 source iteration on the device over the records of the last ``segmentize``, forward or
 adjoint; ``perturbation_reactivity`` / ``kinetics_parameters`` weigh with the adjoint flux.
 ``SolverBoundary`` puts albedos and an incoming flux on the four sides and makes a run
-return the partial currents per side and the neutron balance.
+return the partial currents per side and the neutron balance.  ``solve_transient`` continues
+an eigenvalue result in time with ``Kinetics`` data (implicit Euler, delayed neutrons).
 """
 from .boundary import BoundaryConditions, BoundaryType, Periodic, Reflective, Vacuum
 from .mesh import DiscreteModel, DiscreteModelFromFile, GmshDiscreteModel, Mesh, data_path
@@ -18,7 +19,7 @@ from .trackgenerator import (Backward, Forward, Segment, Track, TrackGenerator, 
                              dir_next_track_bwd, dir_next_track_fwd, trace, track_end_sides)
 from .segmentize import RTOL_DEFAULT, SegmentStore, segmentize
 from .solver import (Cmfd, CrossSections, PolarQuadrature, SolverBoundary, SolverResult, azimuthal_weights, exact_azimuthal_weights, diffusion_coupling,
-                     kinetics_parameters, perturbation_reactivity, solve_eigenvalue, solve_fixed_source)
+                     kinetics_parameters, perturbation_reactivity, solve_eigenvalue, solve_fixed_source, Kinetics, TransientResult, solve_transient)
 from .distributed import ShardedSolver
 
 __all__ = [
@@ -28,6 +29,6 @@ __all__ = [
     "Track", "Segment",
     "CrossSections", "PolarQuadrature", "SolverResult", "azimuthal_weights", "exact_azimuthal_weights",
     "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "ShardedSolver",
-    "SolverBoundary", "track_end_sides", "Cmfd", "diffusion_coupling",
+    "SolverBoundary", "track_end_sides", "Cmfd", "diffusion_coupling", "Kinetics", "TransientResult", "solve_transient",
     "Forward", "Backward", "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd",
 ]

@@ -38,6 +38,8 @@ SYMBOLS = (
     "rt_solver_set_cmfd", "rt_solver_fetch_cmfd",
     "rt_solver_set_volume_correction", "rt_solver_fetch_volume_correction", "rt_solver_volume_correction_pointers",
     "rt_solver_set_source_regions", "rt_solver_source_region_info", "rt_solver_source_region_pointers", "rt_solver_fetch_source_rows",
+    "rt_solver_transient_begin", "rt_solver_transient_step", "rt_solver_transient_set_xs", "rt_solver_transient_fetch",
+    "rt_solver_transient_pointers", "rt_solver_transient_end",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -321,6 +323,22 @@ def lib():
         L.rt_solver_source_region_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
         L.rt_solver_fetch_source_rows.restype = C.c_int32
         L.rt_solver_fetch_source_rows.argtypes = [_vp, _lp, _dp, _ip, C.c_int64]
+    except AttributeError:
+        if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
+            raise
+    try:
+        L.rt_solver_transient_begin.restype = C.c_int32
+        L.rt_solver_transient_begin.argtypes = [_vp, C.c_int32, _dp, _dp, _dp, _dp, C.c_int32, C.c_double, C.POINTER(SolverResult)]
+        L.rt_solver_transient_step.restype = C.c_int32
+        L.rt_solver_transient_step.argtypes = [_vp, C.c_double, C.c_int32, C.c_double, C.POINTER(SolverResult)]
+        L.rt_solver_transient_set_xs.restype = C.c_int32
+        L.rt_solver_transient_set_xs.argtypes = [_vp, _dp, _dp, _dp, _dp]
+        L.rt_solver_transient_fetch.restype = C.c_int32
+        L.rt_solver_transient_fetch.argtypes = [_vp, _dp, _dp, _dp]
+        L.rt_solver_transient_pointers.restype = C.c_int32
+        L.rt_solver_transient_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
+        L.rt_solver_transient_end.restype = C.c_int32
+        L.rt_solver_transient_end.argtypes = [_vp]
     except AttributeError:
         if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
             raise
@@ -1139,6 +1157,65 @@ class DeviceSolver:
         r = SolverResult()
         _check(lib().rt_solver_end(self._open(), C.byref(r)))
         return self._result(r)
+
+    # ---- a transient (see "Transient" in include/rt_segmentize.h): begin, (set_xs, step) as often as wanted, end
+    def _transient(self, name):
+        L = lib()
+        if not hasattr(L, name):
+            raise RtError(f"{LIB_PATH} has no {name}: the library is older than this binding")
+        return getattr(L, name)
+
+    def transient_begin(self, inv_velocity, beta, decay, chi_delayed, settle_max_iter=500, settle_tol=1e-9) -> dict:
+        """``rt_solver_transient_begin`` from this solver's last forward eigenvalue run: ``inv_velocity`` [M, G], ``beta`` [M, D],
+        ``decay`` [D], ``chi_delayed`` [M, D, G].  Returns the settling's ``iterations`` and ``residual``, and ``k_eff`` = k0."""
+        f = self._transient("rt_solver_transient_begin")
+        lam = np.ascontiguousarray(decay, np.float64).reshape(-1)
+        D = len(lam)
+        iv, be, cd = (np.ascontiguousarray(a, np.float64) for a in (inv_velocity, beta, chi_delayed))
+        if iv.shape != (self.M, self.G) or be.shape != (self.M, D) or cd.shape != (self.M, D, self.G):
+            raise ValueError(f"inv_velocity must be [M, G] = {(self.M, self.G)}, beta [M, D] = {(self.M, D)} and chi_delayed [M, D, G]")
+        r = SolverResult()
+        _check(f(self._open(), D, iv.ctypes.data_as(_dp), be.ctypes.data_as(_dp), lam.ctypes.data_as(_dp), cd.ctypes.data_as(_dp),
+                 int(settle_max_iter), float(settle_tol), C.byref(r)))
+        self.n_families = D
+        return self._result(r)
+
+    def transient_step(self, dt, max_inner=200, tol=1e-8) -> dict:
+        """``rt_solver_transient_step``: one time step of ``dt``.  ``production`` F(φ^{n+1}) (the relative power), the step's inner
+        ``iterations``, the last ``residual``, ``converged`` and ``device_ms``."""
+        r = SolverResult()
+        _check(self._transient("rt_solver_transient_step")(self._open(), float(dt), int(max_inner), float(tol), C.byref(r)))
+        return dict(production=r.k_eff, residual=r.residual, device_ms=r.device_ms, iterations=int(r.iterations), converged=bool(r.converged))
+
+    def transient_set_xs(self, sigma_t, sigma_s, nu_sigma_f, chi):
+        """``rt_solver_transient_set_xs``: the [M]-tables from the next step on (shapes as at construction)."""
+        st, ss, nf, ch = (np.ascontiguousarray(a, np.float64) for a in (sigma_t, sigma_s, nu_sigma_f, chi))
+        M, G = self.M, self.G
+        if st.shape != (M, G) or ss.shape != (M, G, G) or nf.shape != (M, G) or ch.shape != (M, G):
+            raise ValueError(f"sigma_t, nu_sigma_f, chi must be [M, G] = {(M, G)} and sigma_s [M, G, G]")
+        _check(self._transient("rt_solver_transient_set_xs")(self._open(), st.ctypes.data_as(_dp), ss.ctypes.data_as(_dp), nf.ctypes.data_as(_dp),
+                                                             ch.ctypes.data_as(_dp)))
+
+    def transient_fetch(self) -> dict:
+        """``rt_solver_transient_fetch``: ``phi`` [n_cells, G], ``precursors`` [n_cells, D] and ``time``."""
+        phi = np.empty((self.n_cells, self.G)); c = np.empty((self.n_cells, getattr(self, "n_families", 0))); t = C.c_double(0.0)
+        _check(self._transient("rt_solver_transient_fetch")(self._open(), phi.ctypes.data_as(_dp), c.ctypes.data_as(_dp) if c.size else None, C.byref(t)))
+        return dict(phi=phi, precursors=c, time=t.value)
+
+    def transient_pointers(self) -> dict:
+        """``rt_solver_transient_pointers``: device addresses (0: no transient open) of ``phi``, ``phi_prev`` [n_cells, G],
+        ``precursors`` [n_cells, D] and ``source`` [n_cells, G], and their element counts under ``lens``."""
+        ptrs = (_vp * 4)()
+        lens = (C.c_int64 * 4)()
+        _check(self._transient("rt_solver_transient_pointers")(self._open(), ptrs, lens))
+        names = ("phi", "phi_prev", "precursors", "source")
+        out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
+        out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
+        return out
+
+    def transient_end(self):
+        """``rt_solver_transient_end``: the handle gets its sweep state back; ``fetch`` then returns the last φ."""
+        _check(self._transient("rt_solver_transient_end")(self._open()))
 
     def pointers(self) -> dict:
         """``rt_solver_pointers``: device addresses (0: none) of ``volumes`` [n_cells], ``tally`` [n_cells, G·P], ``tally1``

@@ -383,6 +383,19 @@ struct DSrcReg {
     double *vol;                             // V_r [n_src]
 };
 
+// A transient of rt_solver (rt_transient.hip; rt_solver_transient_*): what its kernels read and write, by value.
+struct DTransient {
+    int32_t n_cells, G, P, D;
+    int32_t ktab_lds;                        // doubles of the kinetics table to copy into LDS (0: read it where it lies)
+    double dt;                               // Δt of the step
+    const int32_t *mat;                      // the cells' materials
+    const double *ktab;                      // λ[D], then per material β[D], χd[D][G], 1/v[G]
+    const double *tab, *pol;                 // the material table that holds now (mat_row); sin θ_p [P]
+    const double *phi, *prod;                // φ [n_cells][G]; F_e [n_cells] as the last fold left it
+    double *phi_prev, *C, *ext;              // φ^n [n_cells][G], C [n_cells][D], S [n_cells][G]
+    double *xs, *prod_out;                   // the sweep's cross sections [n_cells][G·P][2]; F_e written by k_tr_production
+};
+
 }  // namespace rt
 
 // ------------------------------------------------------------------- handles -------------
@@ -689,6 +702,9 @@ unsigned volcorr_blocks(int32_t n_cells);
 int launch_srcreg_count(const rt::DSrcReg &a, hipStream_t s);
 int launch_srcreg_fill(const rt::DSrcReg &a, hipStream_t s);
 int launch_srcreg_volumes(const rt::DSrcReg &a, hipStream_t s);
+// rt_transient.hip: one of a transient's small kernels, queued on `s`
+enum class TransientKernel { PrecursorsInit, Precursors, Source, SigmaT, Production };
+int launch_transient(TransientKernel which, const rt::DTransient &a, hipStream_t s);
 // rt_sweep.hip: what a sweep of `G` components with input 0 under `loan` would read — planned as rt_sweep plans it (refused with its
 // message), the rows made as rt_sweep makes them (once per segmentation) — for a solver that scales their ℓ before its first sweep
 int sweep_rows_for_loan(rt_tracks *t, int32_t G, const SweepLoan &loan, bool volcorr, SweepRowsView *out);

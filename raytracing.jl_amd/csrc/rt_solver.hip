@@ -26,6 +26,10 @@
 // its material table's index and `vol` are per region, and rt_solver_begin runs the kernels of rt_srcreg.hip once per segmentation —
 // the rows the sweep reads merged per run of cells of one region, into rows, counts and a chunk table of the solver's, which the run's
 // sweeps read in place of the handle's (SweepLoan::sr_*).  Without them the solver launches what it always did.
+// A transient (rt_solver_transient_*) is an open fixed-source run that keeps the φ of the last eigenvalue run: every time step queues
+// k_tr_source (rt_transient.hip: φ^n aside, the step's external source), the iteration above on the step's own material table until
+// the flux residual is small, and k_tr_precursors.  The solver's own table and source are never written; without a transient the
+// solver launches what it always did.
 // Flat, first-moment scattering or linear source is one choice of three, a SweepMode (each setter switches only its own mode off and
 // refuses to switch it on over the other).  What a run's rt_sweep calls need to know — that mode, the linear source's geometry, the
 // reproducible tallies' delta buffer, single precision — goes to the handle as one SweepLoan (rt_internal.hpp) and comes back whole.
@@ -628,6 +632,19 @@ struct rt_solver {
     double last_k = 1.0, last_res = INFINITY, last_dk = INFINITY;
     double *h_scal = nullptr;  // pinned, kSolveScalars
     hipEvent_t ev[2] = {nullptr, nullptr};
+    // what the last completed run was (rt_solver_transient_begin starts from a forward eigenvalue run's φ and k)
+    bool ran_eigen = false, ran_adjoint = false;
+    double ran_k = 1.0;
+    // transient (rt_solver_transient_*): `tr_open` from rt_solver_transient_begin to whatever ends the run (`open` is true as well:
+    // the transient is an open fixed-source run).  The solver's own tables and external source are never written: the run's kernels
+    // read `tr_tab` (the steady table νΣf / k0, χ, Σs, or a step's, made for `tr_dt_tab`; 0: the steady one) and, once a step has
+    // made it (`tr_src`), S in `tr_ext`.  `tr_h_*`: the [M]-tables that hold now (rt_solver_transient_set_xs replaces them) and
+    // the kinetics data as given; `tr_h_tab`: the host copy the last upload reads
+    bool tr_open = false, tr_src = false;
+    int32_t tr_D = 0, tr_steps = 0;
+    double tr_k0 = 1.0, tr_time = 0.0, tr_dt_tab = 0.0;
+    std::vector<double> tr_h_st, tr_h_ss, tr_h_nf, tr_h_chi, tr_h_iv, tr_h_beta, tr_h_lambda, tr_h_chid, tr_h_tab;
+    DevBuf<double> tr_tab, tr_ktab, tr_C, tr_phi_prev, tr_ext;
 };
 
 namespace rtx {
@@ -639,6 +656,7 @@ void solver_release(rt_solver *S) {
     S->t->sw_loan = SweepLoan{};  // (an open run is the handle's borrower: solver_begin_impl ends every other one)
     S->t->sw_has_w = false;
     S->open = false; S->swept = false;
+    S->tr_open = false; S->tr_src = false;  // (a transient ends with its run: the solver's own tables were never written)
 }
 
 }  // namespace rtx
@@ -830,6 +848,7 @@ int solver_check_tracks(const rt_solver *S, const char *who) {
 int solver_step_enter(const rt_solver *S, bool want_swept, const char *who) {
     if (int rc = solver_check_epoch(S, who)) return rc;
     if (!S->open) { set_error("%s: no run is open (rt_solver_begin has not run, or the run has ended)", who); return RT_ERR_INVALID; }
+    if (S->tr_open) { set_error("%s: a transient is open (rt_solver_transient_step makes its own sweeps and folds; rt_solver_transient_end ends it)", who); return RT_ERR_INVALID; }
     if (want_swept && !S->swept) { set_error("%s: there is no sweep to fold (rt_solver_step_sweep comes first)", who); return RT_ERR_INVALID; }
     if (!want_swept && S->swept) { set_error("%s: the last sweep has not been folded yet (rt_solver_step_fold comes between two sweeps)", who); return RT_ERR_INVALID; }
     return RT_SUCCESS;
@@ -974,8 +993,10 @@ int solver_srcreg_prepare(rt_solver *S, const char *who) {
     return RT_SUCCESS;
 }
 
-int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
-    if (S->open) solver_release(S);  // (a second begin starts afresh)
+// keep_phi (rt_solver_transient_begin): the run starts from the φ the solver holds instead of φ⁰ = 1; the caller queues the components'
+// Σt / sin θ, F_e and the scalars itself, from the table its run reads
+int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi = false) {
+    if (S->open) solver_release(S);  // (a second begin starts afresh; a transient ends here as well)
     rt_tracks *t = S->t;
     if (int rc = solver_check_tracks(S, who)) return rc;
     const bool bnd = S->bnd_S > 0;
@@ -1063,10 +1084,12 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who) {
     S->run_eigen = eigen; S->run_mode = smode; S->run_bnd = bnd; S->run_reg = reg; S->run_cm = cm;
     S->it = 0; S->last_k = 1.0; S->last_res = INFINITY; S->last_dk = INFINITY;
     // φ⁰ = 1, the components' Σt / sin θ, F⁰
-    RT_HIP(hipMemsetAsync(S->prod.p, 0, (size_t)std::max(1, nc) * sizeof(double), s));
-    hipLaunchKernelGGL(rt::k_solver_fold<true>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
-                       (const double *)S->vol.p, (const double *)S->pol.p, (const double *)nullptr, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P, S->partial.p);
-    hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)d.cblocks, 1, eigen ? 1 : 0, S->scal.p);
+    if (!keep_phi) {
+        RT_HIP(hipMemsetAsync(S->prod.p, 0, (size_t)std::max(1, nc) * sizeof(double), s));
+        hipLaunchKernelGGL(rt::k_solver_fold<true>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)nullptr, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P, S->partial.p);
+        hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)d.cblocks, 1, eigen ? 1 : 0, S->scal.p);
+    }
     RT_HIP(hipGetLastError());
     RT_HIP(hipEventRecord(S->ev[0], s));
     abort_run.ok = true;
@@ -1078,9 +1101,11 @@ int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
     rt_tracks *t = S->t;
     hipStream_t s = t->mesh->stream;
     const int32_t G = d.G, P = d.P, nc = d.nc, eig = S->run_eigen ? 1 : 0;
-    const double *ext = (!S->run_eigen && S->has_ext) ? S->ext.p : nullptr;
+    // (a transient reads its own table and, from its first step on, its own S: the solver's table and source are left as they are)
+    const double *ext = S->tr_open ? (S->tr_src ? S->tr_ext.p : nullptr) : ((!S->run_eigen && S->has_ext) ? S->ext.p : nullptr);
+    const double *tab = S->tr_open ? S->tr_tab.p : S->tab.p;
     hipLaunchKernelGGL(rt::k_solver_source, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
-                       (const double *)S->tab.p, d.lds_len, (const double *)S->phi.p, (const double *)S->prod.p, ext, (const double *)S->scal.p, eig,
+                       tab, d.lds_len, (const double *)S->phi.p, (const double *)S->prod.p, ext, (const double *)S->scal.p, eig,
                        nc, G, P, t->sw_xs.p);
     if (S->run_mode == SweepMode::P1)
         hipLaunchKernelGGL(rt::k_solver_source_p1, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds1_len * sizeof(double), s, (const int32_t *)S->mat.p,
@@ -1130,7 +1155,7 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
         RT_HIP(hipMemcpyAsync(S->cm_prod_old.p, S->prod.p, (size_t)nc * sizeof(double), hipMemcpyDeviceToDevice, s));
         RT_HIP(hipMemcpyAsync(S->cm_prev.p, S->scal.p, rt::kSolveScalars * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
-    hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
+    hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)(S->tr_open ? S->tr_tab.p : S->tab.p),
                        (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P,
                        S->partial.p);
     if (S->run_mode == SweepMode::P1)
@@ -1188,6 +1213,7 @@ int solver_step_impl(rt_solver *S, bool fold, rt_solver_result *res, const char 
 int solver_end_impl(rt_solver *S, rt_solver_result *res, const char *who) {
     if (int rc = solver_check_epoch(S, who)) return rc;
     if (!S->open) { set_error("%s: no run is open (rt_solver_begin has not run, or the run has ended)", who); return RT_ERR_INVALID; }
+    if (S->tr_open) { set_error("%s: a transient is open (rt_solver_transient_end ends it)", who); return RT_ERR_INVALID; }
     AbortRun abort_run{S};
     rt_tracks *t = S->t;
     RT_HIP(hipSetDevice(t->mesh->device));
@@ -1213,6 +1239,7 @@ int solver_end_impl(rt_solver *S, rt_solver_result *res, const char *who) {
     RT_HIP(hipEventElapsedTime(&f, S->ev[0], S->ev[1]));
     t->in_flight = false;
     S->ran = true; S->ran_mode = S->run_mode;
+    S->ran_eigen = eigen; S->ran_adjoint = S->adjoint; S->ran_k = S->last_k;
     if (res) {
         res->k_eff = eigen ? S->last_k : 1.0; res->residual = S->last_res; res->dk = S->last_dk; res->device_ms = f;
         res->iterations = S->it; res->converged = 0;
@@ -1245,6 +1272,281 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
     }
     if (int rc = solver_end_impl(S, res, who)) return rc;
     if (res) res->converged = converged ? 1 : 0;
+    return RT_SUCCESS;
+}
+
+// ---- transient (rt_solver_transient_*; "Transient" in include/rt_segmentize.h) ------------------------------------------------------
+constexpr int32_t kMaxFamilies = 64;
+
+// The [M]-tables of a solver as rt_solver_create checks them.
+int solver_check_xs(const char *who, int32_t M, int32_t G, const double *sigma_t, const double *sigma_s, const double *nu_sigma_f, const double *chi) {
+    const size_t mg = (size_t)M * G;
+    for (size_t i = 0; i < mg; ++i)
+        if (!(sigma_t[i] > 0.0) || !std::isfinite(sigma_t[i])) {
+            set_error("%s: sigma_t[%zu][%zu] = %g (every Σt must be finite and > 0; void materials are not supported)", who, i / G, i % G, sigma_t[i]);
+            return RT_ERR_INVALID;
+        }
+    size_t bad = 0;
+    if (!finite_nonneg(sigma_s, mg * G, &bad)) { set_error("%s: sigma_s[%zu] = %g (must be finite and >= 0)", who, bad, sigma_s[bad]); return RT_ERR_INVALID; }
+    if (!finite_nonneg(nu_sigma_f, mg, &bad)) { set_error("%s: nu_sigma_f[%zu] = %g (must be finite and >= 0)", who, bad, nu_sigma_f[bad]); return RT_ERR_INVALID; }
+    if (!finite_nonneg(chi, mg, &bad)) { set_error("%s: chi[%zu] = %g (must be finite and >= 0)", who, bad, chi[bad]); return RT_ERR_INVALID; }
+    return RT_SUCCESS;
+}
+
+// χ̃_{m,g} = χ_{m,g} − Σ_d β_{m,d} χd_{m,d,g} for the given tables: >= −1e-14 everywhere, or the material and group named
+int transient_check_prompt(const rt_solver *S, const double *chi, int32_t D, const double *beta, const double *chi_delayed, const char *who) {
+    const int32_t G = S->G, M = S->M;
+    for (int32_t m = 0; m < M; ++m)
+        for (int32_t g = 0; g < G; ++g) {
+            double v = chi[(size_t)m * G + g];
+            for (int32_t d = 0; d < D; ++d) v -= beta[(size_t)m * D + d] * chi_delayed[((size_t)m * D + d) * G + g];
+            if (!(v >= -1e-14)) {
+                set_error("%s: the prompt spectrum chi - sum_d beta_d chi_delayed_d of material %d, group %d is %g (must be >= 0: the delayed part exceeds chi there)", who, m, g, v);
+                return RT_ERR_INVALID;
+            }
+        }
+    return RT_SUCCESS;
+}
+
+// The material table (mat_row) a transient's kernels read, into tr_h_tab: dt = 0 the steady one (Σt, νΣf / k0, χ, Σs), dt > 0 a
+// step's (Σs'[g→g] = Σs[g→g] − 1/(v_g Δt), χ'_g = χ_g − Σ_d β_d χd_{d,g} / (1 + λ_d Δt) clamped at 0).  Σt is never touched.
+void transient_table(rt_solver *S, double dt) {
+    const int32_t G = S->G, M = S->M, D = S->tr_D;
+    S->tr_h_tab.resize((size_t)M * G * (3 + G));
+    for (int32_t m = 0; m < M; ++m) {
+        double *X = S->tr_h_tab.data() + (size_t)m * G * (3 + G);
+        for (int32_t g = 0; g < G; ++g) {
+            X[g] = S->tr_h_st[(size_t)m * G + g];
+            X[G + g] = S->tr_h_nf[(size_t)m * G + g] / S->tr_k0;
+            double c = S->tr_h_chi[(size_t)m * G + g];
+            if (dt > 0.0) {
+                for (int32_t d = 0; d < D; ++d)
+                    c -= S->tr_h_beta[(size_t)m * D + d] * S->tr_h_chid[((size_t)m * D + d) * G + g] / (1.0 + S->tr_h_lambda[(size_t)d] * dt);
+                c = c > 0.0 ? c : 0.0;
+            }
+            X[2 * G + g] = c;
+        }
+        for (int32_t a = 0; a < G; ++a)
+            for (int32_t b = 0; b < G; ++b) {
+                double v = S->tr_h_ss[((size_t)m * G + a) * G + b];
+                if (dt > 0.0 && a == b) v -= S->tr_h_iv[(size_t)m * G + a] / dt;
+                X[3 * G + a * G + b] = v;
+            }
+    }
+    S->tr_dt_tab = dt;
+}
+
+rt::DTransient transient_args(const rt_solver *S, double dt) {
+    rt::DTransient a{};
+    a.n_cells = S->n_cells; a.G = S->G; a.P = S->P; a.D = S->tr_D; a.dt = dt;
+    const size_t klen = (size_t)S->tr_D + (size_t)S->M * ((size_t)S->tr_D * (1 + S->G) + S->G);
+    a.ktab_lds = klen * sizeof(double) <= 32 * 1024 ? (int32_t)klen : 0;  // (else read where it lies: L2-resident)
+    a.mat = S->mat.p; a.ktab = S->tr_ktab.p; a.tab = S->tr_tab.p; a.pol = S->pol.p;
+    a.phi = S->phi.p; a.prod = S->prod.p;
+    a.phi_prev = S->tr_phi_prev.p; a.C = S->tr_C.p; a.ext = S->tr_ext.p;
+    a.xs = S->t->sw_xs.p; a.prod_out = S->prod.p;
+    return a;
+}
+
+// tr_h_tab to the device (the host copy stays until the next one replaces it, behind a wait)
+int transient_upload_table(rt_solver *S, hipStream_t s) {
+    RT_HIP(S->tr_tab.reserve(S->tr_h_tab.size()));
+    RT_HIP(hipMemcpyAsync(S->tr_tab.p, S->tr_h_tab.data(), S->tr_h_tab.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    RT_HIP(hipStreamSynchronize(s));
+    return RT_SUCCESS;
+}
+
+// inner iterations of an open transient: sweep + fold until the flux residual < tol or `max_iter` of them
+int transient_iterate(rt_solver *S, int32_t max_iter, double tol, const char *who) {
+    const SolverDims d(S);
+    S->it = 0; S->k_hist.clear();
+    while (S->it < max_iter) {
+        if (int rc = solver_queue_sweep(S, d)) return rc;
+        if (int rc = solver_queue_fold(S, d, nullptr, who)) return rc;
+        if (S->last_res < tol) break;
+    }
+    return RT_SUCCESS;
+}
+
+int transient_begin_impl(rt_solver *S, int32_t D, const double *inv_velocity, const double *beta, const double *lambda, const double *chi_delayed,
+                         int32_t settle_max_iter, double settle_tol, rt_solver_result *res) {
+    const char *who = "rt_solver_transient_begin";
+    if (!S || !inv_velocity || !beta || !lambda || !chi_delayed) { set_error("%s: null argument", who); return RT_ERR_INVALID; }
+    if (D < 1 || D > kMaxFamilies || settle_max_iter < 0 || !(settle_tol >= 0.0)) {
+        set_error("%s: bad arguments (%d precursor families, need 1 .. %d; settle_max_iter %d, settle_tol %g)", who, D, kMaxFamilies, settle_max_iter, settle_tol);
+        return RT_ERR_INVALID;
+    }
+    if (int rc = solver_check_tracks(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end, or a transient): end it first", who); return RT_ERR_INVALID; }
+    if (!S->ran || !S->ran_eigen) {
+        set_error("%s: no completed eigenvalue run of this solver (rt_solver_run with RT_SOLVE_EIGENVALUE comes first: its flux and k_eff are the initial state)", who);
+        return RT_ERR_INVALID;
+    }
+    if (S->ran_adjoint) { set_error("%s: the last completed run was an adjoint run (rt_solver_set_adjoint): a transient starts from a forward eigenvalue run", who); return RT_ERR_INVALID; }
+    // the modes a transient does not run in: the message names both sides
+    const char *other = S->adjoint ? "adjoint mode is set (rt_solver_set_adjoint)"
+        : S->mode == SweepMode::Linear ? "the linear source is on (rt_solver_set_linear_source)"
+        : S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1: the time derivative of the current is not modelled)"
+        : S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
+        : (S->reg_R > 0 || S->cm_on) ? "region currents are set (rt_solver_set_regions, rt_solver_set_cmfd)"
+        : (S->bnd_S > 0 && S->bnd_inc) ? "a boundary has an incoming flux (rt_solver_set_boundary)"
+        : S->single ? "the single-precision sweep is set (rt_solver_set_precision)"
+        : S->vc_mode ? "the volume correction is set (rt_solver_set_volume_correction)"
+        : S->sr_on ? "source regions are set (rt_solver_set_source_regions)"
+        : S->t->sw_shard ? "the track set is a shard (some next uid is 0)" : nullptr;
+    if (other) { set_error("%s: %s, and a transient together with it is not supported", who, other); return RT_ERR_INVALID; }
+    const int32_t G = S->G, M = S->M, nc = S->n_cells;
+    const size_t mg = (size_t)M * G, md = (size_t)M * D;
+    for (size_t i = 0; i < mg; ++i)
+        if (!(inv_velocity[i] > 0.0) || !std::isfinite(inv_velocity[i])) { set_error("%s: inv_velocity[%zu][%zu] = %g (must be finite and > 0)", who, i / G, i % G, inv_velocity[i]); return RT_ERR_INVALID; }
+    for (int32_t d = 0; d < D; ++d)
+        if (!(lambda[d] > 0.0) || !std::isfinite(lambda[d])) { set_error("%s: lambda[%d] = %g (must be finite and > 0)", who, d, lambda[d]); return RT_ERR_INVALID; }
+    size_t bad = 0;
+    if (!finite_nonneg(beta, md, &bad)) { set_error("%s: beta[%zu][%zu] = %g (must be finite and >= 0)", who, bad / D, bad % D, beta[bad]); return RT_ERR_INVALID; }
+    if (!finite_nonneg(chi_delayed, md * G, &bad)) { set_error("%s: chi_delayed[%zu] = %g (must be finite and >= 0)", who, bad, chi_delayed[bad]); return RT_ERR_INVALID; }
+    if (!(S->ran_k > 0.0) || !std::isfinite(S->ran_k)) { set_error("%s: the eigenvalue run left k_eff = %g", who, S->ran_k); return RT_ERR_INVALID; }
+    if (int rc = transient_check_prompt(S, S->h_chi.data(), D, beta, chi_delayed, who)) return rc;
+    // (nothing refuses from here on but the device: the solver keeps what it had until now)
+    S->tr_D = D; S->tr_k0 = S->ran_k;
+    S->tr_h_iv.assign(inv_velocity, inv_velocity + mg); S->tr_h_beta.assign(beta, beta + md); S->tr_h_lambda.assign(lambda, lambda + D);
+    S->tr_h_chid.assign(chi_delayed, chi_delayed + md * G);
+    S->tr_h_st = S->h_st; S->tr_h_ss = S->h_ss; S->tr_h_nf = S->h_nf; S->tr_h_chi = S->h_chi;
+    // the kinetics table of the kernels: λ[D], then per material β[D], χd[D][G], 1/v[G]
+    std::vector<double> kt((size_t)D + (size_t)M * ((size_t)D * (1 + G) + G));
+    for (int32_t d = 0; d < D; ++d) kt[(size_t)d] = lambda[d];
+    for (int32_t m = 0; m < M; ++m) {
+        double *K = kt.data() + D + (size_t)m * ((size_t)D * (1 + G) + G);
+        for (int32_t d = 0; d < D; ++d) K[d] = beta[(size_t)m * D + d];
+        for (size_t i = 0; i < (size_t)D * G; ++i) K[D + i] = chi_delayed[(size_t)m * D * G + i];
+        for (int32_t g = 0; g < G; ++g) K[(size_t)D * (1 + G) + g] = inv_velocity[(size_t)m * G + g];
+    }
+    // a fixed-source run that keeps φ: zero boundary fluxes, the handle's sweep state borrowed
+    if (int rc = solver_begin_impl(S, RT_SOLVE_FIXED_SOURCE, who, true)) return rc;
+    AbortRun abort_run{S};
+    S->tr_open = true; S->tr_src = false; S->tr_time = 0.0; S->tr_steps = 0;
+    hipStream_t s = S->t->mesh->stream;
+    const size_t ncg = std::max<size_t>(1, (size_t)nc * G);
+    RT_HIP(S->tr_C.reserve(std::max<size_t>(1, (size_t)nc * D))); RT_HIP(S->tr_phi_prev.reserve(ncg)); RT_HIP(S->tr_ext.reserve(ncg));
+    if (int rc = upload(S->tr_ktab, kt.data(), kt.size(), s)) return rc;
+    transient_table(S, 0.0);
+    if (int rc = transient_upload_table(S, s)) return rc;  // (waits: `kt` may go)
+    S->h_scal[0] = 1.0; S->h_scal[1] = 1.0 / S->tr_k0; S->h_scal[2] = INFINITY; S->h_scal[3] = INFINITY;
+    RT_HIP(hipMemcpyAsync(S->scal.p, S->h_scal, rt::kSolveScalars * sizeof(double), hipMemcpyHostToDevice, s));
+    const rt::DTransient a = transient_args(S, 0.0);
+    if (int rc = launch_transient(TransientKernel::SigmaT, a, s)) return rc;
+    if (int rc = launch_transient(TransientKernel::Production, a, s)) return rc;
+    RT_HIP(hipMemcpyAsync(S->tr_phi_prev.p, S->phi.p, (size_t)nc * G * sizeof(double), hipMemcpyDeviceToDevice, s));
+    RT_HIP(hipStreamSynchronize(s));  // (h_scal is the fold's again)
+    S->last_res = INFINITY;
+    // only ψ has to settle: φ is the converged one, and an iteration of the critical steady table would let its amplitude drift
+    // (the zeroed boundary fluxes are neutrons lost).  So every settling iteration sweeps the source of φ⁰, folds — the residual
+    // is the distance of that fold from φ⁰ — and puts φ⁰ and its F_e back
+    {
+        const SolverDims d(S);
+        S->it = 0; S->k_hist.clear();
+        while (S->it < settle_max_iter) {
+            if (int rc = solver_queue_sweep(S, d)) return rc;
+            if (int rc = solver_queue_fold(S, d, nullptr, who)) return rc;
+            RT_HIP(hipMemcpyAsync(S->phi.p, S->tr_phi_prev.p, (size_t)nc * G * sizeof(double), hipMemcpyDeviceToDevice, s));
+            if (int rc = launch_transient(TransientKernel::Production, a, s)) return rc;
+            if (S->last_res < settle_tol) break;
+        }
+    }
+    if (int rc = launch_transient(TransientKernel::PrecursorsInit, a, s)) return rc;
+    RT_HIP(hipEventRecord(S->ev[1], s));
+    RT_HIP(hipStreamSynchronize(s));
+    RT_HIP(hipGetLastError());
+    float f = 0.0f;
+    RT_HIP(hipEventElapsedTime(&f, S->ev[0], S->ev[1]));
+    if (res) {
+        res->k_eff = S->tr_k0; res->residual = S->last_res; res->dk = 0.0; res->device_ms = f; res->iterations = S->it;
+        res->converged = S->last_res < settle_tol ? 1 : 0;
+    }
+    abort_run.ok = true;
+    return RT_SUCCESS;
+}
+
+// what every call of an open transient checks first: the tracks' epoch (rt_segmentize ends the run: the stale solver is the error to
+// report), then that a transient is open
+int transient_enter(const rt_solver *S, const char *who) {
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (!S->tr_open) { set_error("%s: no transient is open (rt_solver_transient_begin has not run, or the transient has ended)", who); return RT_ERR_INVALID; }
+    return RT_SUCCESS;
+}
+
+int transient_step_impl(rt_solver *S, double dt, int32_t max_inner, double tol, rt_solver_result *res) {
+    const char *who = "rt_solver_transient_step";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = transient_enter(S, who)) return rc;
+    if (!(dt > 0.0) || !std::isfinite(dt) || max_inner < 1 || !(tol >= 0.0)) {
+        set_error("%s: bad arguments (dt %g: must be finite and > 0; max_inner %d: at least 1; tol %g)", who, dt, max_inner, tol);
+        return RT_ERR_INVALID;
+    }
+    AbortRun abort_run{S};
+    RT_HIP(hipSetDevice(S->t->mesh->device));
+    hipStream_t s = S->t->mesh->stream;
+    if (dt != S->tr_dt_tab) {  // (rt_solver_transient_set_xs rebuilds the table it finds: the same Δt again reads it as it is)
+        transient_table(S, dt);
+        if (int rc = transient_upload_table(S, s)) return rc;
+    }
+    RT_HIP(hipEventRecord(S->ev[0], s));
+    const rt::DTransient a = transient_args(S, dt);
+    if (int rc = launch_transient(TransientKernel::Source, a, s)) return rc;  // φ^n aside and S from it and C^n
+    S->tr_src = true;
+    if (int rc = transient_iterate(S, max_inner, tol, who)) return rc;
+    if (int rc = launch_transient(TransientKernel::Precursors, a, s)) return rc;  // from the last fold's F_e
+    RT_HIP(hipEventRecord(S->ev[1], s));
+    RT_HIP(hipStreamSynchronize(s));
+    RT_HIP(hipGetLastError());
+    float f = 0.0f;
+    RT_HIP(hipEventElapsedTime(&f, S->ev[0], S->ev[1]));
+    S->tr_time += dt; ++S->tr_steps;
+    if (res) {
+        res->k_eff = S->tr_k0 * S->h_scal[1]; res->residual = S->last_res; res->dk = 0.0; res->device_ms = f; res->iterations = S->it;
+        res->converged = S->last_res < tol ? 1 : 0;
+    }
+    abort_run.ok = true;
+    return RT_SUCCESS;
+}
+
+int transient_set_xs_impl(rt_solver *S, const double *sigma_t, const double *sigma_s, const double *nu_sigma_f, const double *chi) {
+    const char *who = "rt_solver_transient_set_xs";
+    if (!S || !sigma_t || !sigma_s || !nu_sigma_f || !chi) { set_error("%s: null argument", who); return RT_ERR_INVALID; }
+    if (int rc = transient_enter(S, who)) return rc;
+    const int32_t G = S->G, M = S->M;
+    if (int rc = solver_check_xs(who, M, G, sigma_t, sigma_s, nu_sigma_f, chi)) return rc;
+    if (int rc = transient_check_prompt(S, chi, S->tr_D, S->tr_h_beta.data(), S->tr_h_chid.data(), who)) return rc;
+    const size_t mg = (size_t)M * G;
+    S->tr_h_st.assign(sigma_t, sigma_t + mg); S->tr_h_ss.assign(sigma_s, sigma_s + mg * G);
+    S->tr_h_nf.assign(nu_sigma_f, nu_sigma_f + mg); S->tr_h_chi.assign(chi, chi + mg);
+    AbortRun abort_run{S};
+    RT_HIP(hipSetDevice(S->t->mesh->device));
+    hipStream_t s = S->t->mesh->stream;
+    transient_table(S, S->tr_dt_tab);
+    if (int rc = transient_upload_table(S, s)) return rc;
+    // the sweep's Σt / sin θ of every component, and F_e of the φ that is kept with the νΣf that holds from now on
+    const rt::DTransient a = transient_args(S, S->tr_dt_tab);
+    if (int rc = launch_transient(TransientKernel::SigmaT, a, s)) return rc;
+    if (int rc = launch_transient(TransientKernel::Production, a, s)) return rc;
+    RT_HIP(hipStreamSynchronize(s));
+    RT_HIP(hipGetLastError());
+    abort_run.ok = true;
+    return RT_SUCCESS;
+}
+
+int transient_end_impl(rt_solver *S) {
+    const char *who = "rt_solver_transient_end";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = transient_enter(S, who)) return rc;
+    AbortRun abort_run{S};
+    RT_HIP(hipSetDevice(S->t->mesh->device));
+    RT_HIP(hipStreamSynchronize(S->t->mesh->stream));
+    RT_HIP(hipGetLastError());
+    S->t->in_flight = false;
+    // the last φ is what rt_solver_fetch returns (no normalisation); the next transient needs an eigenvalue run again
+    S->ran = true; S->ran_mode = SweepMode::Flat; S->ran_eigen = false; S->k_hist.clear();
+    solver_release(S);
+    abort_run.ok = true;
     return RT_SUCCESS;
 }
 
@@ -2179,6 +2481,53 @@ int32_t rt_solver_step_fold(rt_solver *solver, rt_solver_result *out) {
 int32_t rt_solver_end(rt_solver *solver, rt_solver_result *out) {
     if (!solver) { set_error("rt_solver_end: null solver"); return RT_ERR_INVALID; }
     return guarded("rt_solver_end", [&] { return solver_end_impl(solver, out, "rt_solver_end"); });
+}
+
+int32_t rt_solver_transient_begin(rt_solver *solver, int32_t n_families, const double *inv_velocity, const double *beta, const double *lambda,
+                                  const double *chi_delayed, int32_t settle_max_iter, double settle_tol, rt_solver_result *out) {
+    return guarded("rt_solver_transient_begin", [&] {
+        return transient_begin_impl(solver, n_families, inv_velocity, beta, lambda, chi_delayed, settle_max_iter, settle_tol, out);
+    }, [&] { if (solver) solver_release(solver); });
+}
+
+int32_t rt_solver_transient_step(rt_solver *solver, double dt, int32_t max_inner, double tol, rt_solver_result *out) {
+    return guarded("rt_solver_transient_step", [&] { return transient_step_impl(solver, dt, max_inner, tol, out); }, [&] { if (solver) solver_release(solver); });
+}
+
+int32_t rt_solver_transient_set_xs(rt_solver *solver, const double *sigma_t, const double *sigma_s, const double *nu_sigma_f, const double *chi) {
+    return guarded("rt_solver_transient_set_xs", [&] { return transient_set_xs_impl(solver, sigma_t, sigma_s, nu_sigma_f, chi); },
+                   [&] { if (solver) solver_release(solver); });
+}
+
+int32_t rt_solver_transient_fetch(rt_solver *solver, double *phi, double *precursors, double *time) {
+    if (!solver) { set_error("rt_solver_transient_fetch: null solver"); return RT_ERR_INVALID; }
+    if (int rc = transient_enter(solver, "rt_solver_transient_fetch")) return rc;
+    RT_HIP(hipSetDevice(solver->device));
+    hipStream_t s = solver->t->mesh->stream;
+    const size_t nc = (size_t)solver->n_cells;
+    if (phi && nc) RT_HIP(hipMemcpyAsync(phi, solver->phi.p, nc * solver->G * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (precursors && nc) RT_HIP(hipMemcpyAsync(precursors, solver->tr_C.p, nc * solver->tr_D * sizeof(double), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    if (time) *time = solver->tr_time;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_transient_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
+    if (!solver) { set_error("rt_solver_transient_pointers: null solver"); return RT_ERR_INVALID; }
+    // (no wait here: addresses and counts only)
+    const bool on = solver->tr_open;
+    const int64_t nc = solver->n_cells, ncg = nc * solver->G;
+    void *p[4] = {solver->phi.p, solver->tr_phi_prev.p, solver->tr_C.p, solver->tr_ext.p};
+    const int64_t l[4] = {ncg, ncg, nc * solver->tr_D, ncg};
+    for (int i = 0; i < 4; ++i) {
+        if (ptrs_dev) ptrs_dev[i] = on ? p[i] : nullptr;
+        if (lens) lens[i] = on ? l[i] : 0;
+    }
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_transient_end(rt_solver *solver) {
+    return guarded("rt_solver_transient_end", [&] { return transient_end_impl(solver); });
 }
 
 int32_t rt_solver_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {

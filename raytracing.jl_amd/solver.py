@@ -26,6 +26,9 @@ merged per region (``rt_solver_set_source_regions``): ``phi``, ``volumes``, ``cu
 With ``cmfd=True`` (or a ``Cmfd``) on top of ``regions=...`` every iteration also solves the partial-current coarse-mesh balance
 over the regions and prolongs its solution onto φ, k and the boundary fluxes (``rt_solver_set_cmfd``): the same answer in fewer
 iterations; ``diffusion_coupling`` builds an optional coupling D̂ from the mesh.
+``solve_transient`` continues an eigenvalue result in time (``rt_solver_transient_*``): implicit Euler with ``Kinetics`` data (1/v, delayed
+fractions, decay constants and spectra), every step a fixed-source problem started from the previous step's flux, cross sections
+changed between steps by ``events``; the result carries the relative power ``production`` over ``times``.
 """
 from __future__ import annotations
 
@@ -39,7 +42,8 @@ from . import _capi
 from .trackgenerator import SIDE_NAMES, TrackGenerator, track_end_sides
 
 __all__ = ["CrossSections", "PolarQuadrature", "SolverBoundary", "SolverResult", "Cmfd", "diffusion_coupling", "exact_azimuthal_weights", "azimuthal_weights",
-           "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "neutron_balance", "region_balance"]
+           "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "neutron_balance", "region_balance",
+           "Kinetics", "TransientResult", "solve_transient"]
 
 
 class CrossSections:
@@ -355,6 +359,7 @@ class SolverResult:
     volume_correction_info: Optional[dict] = None  # ... unseen_pairs, zero_area_cells, zero_volume_cells, f_min, f_max; all None without
     source_region: Optional[np.ndarray] = None     # source_regions=...: the cells' regions [mesh cells]; phi, volumes, current are then [n_src, ...]
     source_region_info: Optional[dict] = None      # ... n_src, rows / largest count / chunks before and after the merge; both None without
+    xs: Optional["CrossSections"] = None           # the cross sections of the run (what ``solve_transient`` starts from)
 
     def to_cells(self, a):
         """An array per source region (``phi``, ``volumes``, ``current``) spread over the mesh's cells: ``a[source_region]``; ``a``
@@ -540,7 +545,7 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
                         flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids, adjoint=bool(adjoint),
-                        reproducible=bool(reproducible), precision=precision, **bnd)
+                        reproducible=bool(reproducible), precision=precision, xs=xs, **bnd)
 
 
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
@@ -677,3 +682,141 @@ def kinetics_parameters(forward, adjoint, xs: CrossSections, inv_velocity, beta,
     A = np.concatenate([np.stack([_fission_form(xs), V]), Ad.transpose(1, 0, 2, 3)])
     b = _bilinear(forward, adjoint, A, cell_material)
     return dict(Lambda=float(b[1] / b[0]), beta_eff=np.asarray(b[2:] / b[0]), B_F=float(b[0]))
+
+
+# ---- transients -----------------------------------------------------------------------------------------------------------------
+class Kinetics:
+    """Kinetics data of a transient, in the conventions of ``kinetics_parameters`` plus the decay constants: ``inv_velocity`` [G] or
+    [M, G] (1/v, > 0), ``beta`` [M, D] (delayed fractions per material and family; [D] for one material), ``decay`` [D] (λ_d, > 0),
+    ``chi_delayed`` [M, D, G] (delayed spectra; any array of M·D·G values).  ``arrays(xs)`` returns them shaped for ``xs`` and checks
+    the prompt spectrum χ − Σ_d β_d χd_d >= −1e-14 in every material and group."""
+
+    def __init__(self, inv_velocity, beta, decay, chi_delayed):
+        self.inv_velocity = np.asarray(inv_velocity, np.float64)
+        self.beta = np.asarray(beta, np.float64)
+        self.decay = np.ascontiguousarray(decay, np.float64).reshape(-1)
+        self.chi_delayed = np.asarray(chi_delayed, np.float64)
+        D = len(self.decay)
+        if D < 1 or not np.all(np.isfinite(self.decay)) or np.any(self.decay <= 0):
+            raise ValueError("decay must hold at least one decay constant, every one finite and > 0")
+        if self.beta.ndim not in (1, 2) or self.beta.shape[-1] != D:
+            raise ValueError(f"beta must have shape [M, D] with D = {D} families (the length of decay), got {self.beta.shape}")
+        if not np.all(np.isfinite(self.beta)) or np.any(self.beta < 0):
+            raise ValueError("every beta must be finite and >= 0")
+        if not np.all(np.isfinite(self.inv_velocity)) or np.any(self.inv_velocity <= 0) or self.inv_velocity.ndim not in (1, 2):
+            raise ValueError("inv_velocity must have shape [G] or [M, G], every entry finite and > 0")
+        if not np.all(np.isfinite(self.chi_delayed)) or np.any(self.chi_delayed < 0):
+            raise ValueError("every chi_delayed must be finite and >= 0")
+
+    @property
+    def n_families(self) -> int:
+        return len(self.decay)
+
+    def arrays(self, xs: "CrossSections"):
+        """``(inv_velocity [M, G], beta [M, D], decay [D], chi_delayed [M, D, G])`` for ``xs``; ``ValueError`` for a shape that
+        does not fit or a negative prompt spectrum."""
+        M, G = xs.sigma_t.shape
+        D = self.n_families
+        iv = np.broadcast_to(self.inv_velocity, (M, G)) if self.inv_velocity.shape == (G,) else self.inv_velocity
+        be = self.beta.reshape(1, -1) if self.beta.ndim == 1 and M == 1 else self.beta
+        if iv.shape != (M, G) or be.shape != (M, D):
+            raise ValueError(f"inv_velocity must have shape [G] or [M, G] = {(M, G)} and beta [M, D] = {(M, D)}")
+        cd = self.chi_delayed.reshape(M, D, G) if self.chi_delayed.size == M * D * G else self.chi_delayed
+        if cd.shape != (M, D, G):
+            raise ValueError(f"chi_delayed must have shape [M, D, G] = {(M, D, G)}")
+        iv, be, cd = (np.ascontiguousarray(a, np.float64) for a in (iv, be, cd))
+        self.check_prompt(xs, be, cd)
+        return iv, be, self.decay, cd
+
+    @staticmethod
+    def check_prompt(xs, beta, chi_delayed):
+        prompt = xs.chi - np.einsum("md,mdg->mg", beta, chi_delayed)
+        if np.any(prompt < -1e-14):
+            m, g = (int(i) for i in np.argwhere(prompt < -1e-14)[0])
+            raise ValueError(f"the prompt spectrum chi - sum_d beta_d chi_delayed_d of material {m}, group {g} is {prompt[m, g]:g} "
+                             "(must be >= 0: the delayed part exceeds chi there)")
+
+
+@dataclass
+class TransientResult:
+    times: np.ndarray             # [n_steps + 1], times[0] = 0
+    production: np.ndarray        # [n_steps + 1]: F(φ(t)) = Σ_e V_e Σ_g νΣf φ, the relative power; production[0] = 1
+    inner_iterations: np.ndarray  # [n_steps]: inner iterations of every step
+    residual: np.ndarray          # [n_steps]: the last inner iteration's flux residual
+    converged: np.ndarray         # [n_steps] bool: the step's residual got below tol within max_inner iterations
+    phi: np.ndarray               # [n_cells, G] at the last time
+    precursors: np.ndarray        # [n_cells, D] at the last time
+    settle_iterations: int        # iterations the boundary fluxes took to settle before the first step
+    settle_residual: float
+    k_eff: float                  # k0: the eigenvalue the transient is normalised with
+    ms_per_step: np.ndarray       # [n_steps]: HIP-event time of every step
+    phi_history: Optional[np.ndarray] = None  # keep_flux=True: [n_steps + 1, n_cells, G]
+
+
+def solve_transient(result: SolverResult, kinetics: Kinetics, dt, n_steps: int, events=(), tol=1e-8, max_inner=200, settle_tol=1e-9,
+                    settle_max_iter=500, keep_flux=False) -> TransientResult:
+    """Continues the eigenvalue ``result`` (``solve_eigenvalue``; its device solver does the work) in time: ``n_steps`` implicit-Euler
+    steps of ``dt`` (a float, or a sequence of ``n_steps`` values) with the delayed-neutron data ``kinetics``.  ``events``: a sequence of
+    ``(step_index, CrossSections)`` — the cross sections (same materials and groups) that hold from that step on, applied before it.
+    Every step iterates until the flux residual < ``tol`` or ``max_inner`` iterations; before the first one the boundary fluxes settle
+    (``settle_tol``, ``settle_max_iter``).  The scheme and what it does not run with: "Transient" in ``include/rt_segmentize.h``.
+    A step that stops at ``max_inner`` is not an error: ``TransientResult.converged`` says which steps met ``tol`` (near critical, a
+    step after a reactivity change can take thousands of unaccelerated iterations).  A cell that no track crosses (``volumes == 0``)
+    enters no sum and iterates on its own — in a fissile material without bound over many steps — so ``phi``, ``phi_history`` and
+    ``precursors`` may hold inf there: mask with ``result.volumes > 0``.
+    ``ValueError`` for an adjoint result, a fixed-source result, a host result without a device solver, a result without its cross
+    sections, data that does not fit."""
+    if not isinstance(kinetics, Kinetics):
+        raise TypeError("kinetics must be a Kinetics")
+    if getattr(result, "adjoint", False):
+        raise ValueError("result is an adjoint result (adjoint=True): a transient starts from a forward eigenvalue result")
+    if result.k_eff is None:
+        raise ValueError("result is a fixed-source result: a transient starts from an eigenvalue result (solve_eigenvalue)")
+    n_steps = int(n_steps)
+    dts = np.full(n_steps, float(dt)) if np.ndim(dt) == 0 else np.asarray(dt, np.float64).reshape(-1)
+    if n_steps < 0 or dts.shape != (n_steps,) or not np.all(np.isfinite(dts)) or np.any(dts <= 0):
+        raise ValueError("dt must be a positive float or a sequence of n_steps positive floats")
+    xs = getattr(result, "xs", None)
+    ev = {}
+    for step, x in events:
+        if not isinstance(x, CrossSections) or not (0 <= int(step) < max(n_steps, 1)):
+            raise ValueError("events must be (step_index in 0 .. n_steps - 1, CrossSections) pairs")
+        if xs is not None and x.sigma_t.shape != xs.sigma_t.shape:
+            raise ValueError("the CrossSections of an event must have the materials and groups of the result's")
+        ev[int(step)] = x
+    if xs is not None:
+        arrays = kinetics.arrays(xs)
+        for x in ev.values():
+            kinetics.check_prompt(x, arrays[1], arrays[3])
+    sv = getattr(result, "solver", None)
+    if sv is None:
+        raise ValueError("result carries no device solver (a host twin's result): solve_transient runs on the device")
+    if xs is None:
+        raise ValueError("result carries no cross sections (result.xs is None: it was not made by solve_eigenvalue of this version): "
+                         "set result.xs to the CrossSections of its run")
+    if getattr(result, "source_region", None) is not None:
+        raise ValueError("source_regions together with a transient is not supported")
+    r0 = sv.transient_begin(*arrays, settle_max_iter=settle_max_iter, settle_tol=settle_tol)
+    times, prod, inner, res, ms, conv = [0.0], [1.0], [], [], [], []
+    hist = [np.array(result.phi, np.float64)] if keep_flux else None
+    try:
+        for n in range(n_steps):
+            if n in ev:
+                x = ev[n]
+                sv.transient_set_xs(x.sigma_t, x.sigma_s, x.nu_sigma_f, x.chi)
+            r = sv.transient_step(dts[n], max_inner, tol)
+            times.append(times[-1] + float(dts[n])); prod.append(r["production"]); inner.append(r["iterations"]); res.append(r["residual"])
+            ms.append(r["device_ms"]); conv.append(r["converged"])
+            if keep_flux:
+                hist.append(sv.transient_fetch()["phi"])
+        f = sv.transient_fetch()
+    finally:
+        if getattr(sv, "_h", None):
+            try:
+                sv.transient_end()
+            except _capi.RtError:
+                pass  # (a failed step has ended the transient already)
+    return TransientResult(times=np.asarray(times), production=np.asarray(prod), inner_iterations=np.asarray(inner, np.int64),
+                           residual=np.asarray(res), converged=np.asarray(conv, bool), phi=f["phi"], precursors=f["precursors"], settle_iterations=r0["iterations"],
+                           settle_residual=r0["residual"], k_eff=r0["k_eff"], ms_per_step=np.asarray(ms),
+                           phi_history=np.stack(hist) if keep_flux else None)

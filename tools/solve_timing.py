@@ -13,7 +13,10 @@ coarse-mesh acceleration over those regions (rt_solver_set_cmfd) under "cmfd_*",
 `--tol` of the run with regions alone against the accelerated one; `--source-regions material` or `--source-regions rings:K,S`: the
 forward figures first, then the same runs on source regions (rt_solver_set_source_regions) under "sr_*" — by material, or K equal-area
 rings inside each material times S sectors about the mesh's centre, binned by cell centroid — with the rows, the mean over the march
-waves of the largest count before and after the merge, the chunks, `gp` and the passes of the sweep, the one-off host time and k).
+waves of the largest count before and after the merge, the chunks, `gp` and the passes of the sweep, the one-off host time and k;
+`--transient N`: the forward figures first, then a converged eigenvalue run and, for every Δt of `--transient-dt`, the settling and N time
+steps (rt_solver_transient_*) after the fuel's νΣf rose by 5e-4 (below prompt critical) under "transient": ms per time step, inner iterations per step, ms per
+inner iteration — beside "fixed_source_ms_per_iter_events", the fixed-source iteration of the same build — and the settle cost).
 
 Prints one JSON line: ms per outer iteration from HIP events (rt_solver_result.device_ms / iterations) and from a host clock
 around a synchronised run, the bare sweep of the same G·P components (rt_sweep's own events), and the non-sweep share
@@ -119,6 +122,10 @@ def main():
     ap.add_argument("--source-regions", default=None, metavar="MAP",
                     help='after the forward runs, the same runs on source regions (rt_solver_set_source_regions): "material", or "rings:K,S" — K '
                          "equal-area rings inside each material and S sectors, by cell centroid; not with --linear / --reproducible / --regions / --volume-correction")
+    ap.add_argument("--transient", type=int, default=0, metavar="N",
+                    help="after the forward runs, N time steps of a transient (rt_solver_transient_*) per --transient-dt value")
+    ap.add_argument("--transient-dt", default="1e-3,1e-2,1e-1", help="the Δt values of --transient, in seconds")
+    ap.add_argument("--transient-tol", type=float, default=1e-8, help="the inner tolerance of --transient")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -193,6 +200,34 @@ def main():
         out["albedo_k_eff"] = r["k_eff"]
         out["albedo_leakage"] = float((J["current_out"] - J["current_in"]).sum())
         sv.set_boundary()
+    if a.transient:  # (a converged eigenvalue run, the settling, then per Δt: N steps after the fuel's νΣf rose by 5e-4)
+        G, D = a.groups, 6
+        beta = np.tile([0.000215, 0.001424, 0.001274, 0.002568, 0.000748, 0.000273], (3, 1))
+        lam = np.array([0.0124, 0.0305, 0.111, 0.301, 1.14, 3.01])
+        iv = np.tile(np.geomspace(5e-10, 4.5e-6, G), (3, 1))  # 1/v from fast to thermal, s/cm
+        chid = np.repeat(xs.chi[:, None, :], D, axis=1)
+        t0 = time.perf_counter()
+        re = sv.run(0, 20000, 1e-10, 1e-9)
+        out["transient_eigen_iterations"], out["transient_eigen_ms"] = re["iterations"], (time.perf_counter() - t0) * 1e3
+        rf = sv.run(1, a.iters, 0.0, 0.0)  # the fixed-source iteration of the same build, for comparison
+        out["fixed_source_ms_per_iter_events"] = rf["device_ms"] / rf["iterations"]
+        nf2 = xs.nu_sigma_f.copy(); nf2[0] *= 1.0 + 5e-4  # (below prompt critical: Σβ = 6.5e-3)
+        rows = []
+        for dt_s in (float(v) for v in a.transient_dt.split(",")):
+            sv.run(0, 20000, 1e-10, 1e-9)
+            t0 = time.perf_counter()
+            r0 = sv.transient_begin(iv, beta, lam, chid, settle_max_iter=500, settle_tol=1e-9)
+            settle_host = (time.perf_counter() - t0) * 1e3
+            sv.transient_set_xs(xs.sigma_t, xs.sigma_s, nf2, xs.chi)
+            inner, ms, prod = [], [], []
+            for _ in range(a.transient):
+                r = sv.transient_step(dt_s, 20000, a.transient_tol)
+                inner.append(r["iterations"]); ms.append(r["device_ms"]); prod.append(r["production"])
+            sv.transient_end()
+            rows.append(dict(dt=dt_s, settle_iterations=r0["iterations"], settle_ms_events=r0["device_ms"], settle_ms_host=settle_host,
+                             ms_per_step=float(np.mean(ms)), inner_per_step=float(np.mean(inner)), inner=inner,
+                             ms_per_inner=float(np.sum(ms) / max(1, np.sum(inner))), production_last=prod[-1]))
+        out["transient"] = rows
     if a.reproducible:  # (the delta buffer written and read once per pass, and k_sweep_reduce behind every pass)
         import torch
 
