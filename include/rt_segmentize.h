@@ -799,6 +799,35 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              the coarse-mesh acceleration, an incoming boundary flux, the single-precision sweep, the volume correction, source
  *              regions, a shard's track set.  A solver that never starts a transient launches exactly what it always did.
  *
+ * Krylov, rt_solver_set_krylov / _step_krylov / _fetch_krylov / _krylov_pointers: restarted GMRES(m) for fixed-source runs and the
+ * steps of a transient.  With its table held fixed, one iteration is an affine map x ↦ A x + b on the state x = (φ [n_cells·G], ψ_in
+ * [2·n·G·P] as the sweep's hand-over leaves it), N entries in all; b is what the external source (a transient: the step's S) adds.
+ * Evaluation   F(x): the source update, one sweep and the fold, unchanged.  A v: the same kernels with no external source (F_e is
+ *              recomputed from φ whenever a vector kernel has written φ)
+ * Cycle        1. x₀ aside; r₀ = F(x₀) − x₀ by one plain iteration, whose residual ‖Δφ‖₂ / ‖φ‖₂ is the run's stopping test: tol means
+ *                 what it means without the option.  Below tol the cycle ends with x = F(x₀) and no Krylov vector
+ *              2. v₀ = r₀ / β, β = ‖r₀‖₂ (over all N entries); for k = 0 .. m − 1: w = v_k − A v_k, orthogonalised against v₀ .. v_k by
+ *                 classical Gram–Schmidt applied twice (h_{j,k} = the sum of the two passes' coefficients), h_{k+1,k} = ‖w‖₂; the host
+ *                 extends the Givens-rotated Hessenberg system and reads the GMRES residual norm ρ_{k+1} = min_y ‖β e₁ − H y‖₂
+ *              3. stop after m vectors, at ρ_{k+1} < tol_lin β, or at a breakdown h_{k+1,k} <= 1e-14 β (the solve is then exact;
+ *                 nothing is divided by it)
+ *              4. x = x₀ + V y, F_e from its φ
+ * Counting     every Krylov vector is a sweep and counts as an iteration: rt_solver_result::iterations, max_iter of rt_solver_run and
+ *              max_inner of rt_solver_transient_step bound the sweeps (k_history holds 1 for every one).  A run that counts always
+ *              ends on a plain iteration — a cycle takes at most as many vectors as leave one sweep over — so its residual, F and
+ *              the boundary currents are those of a plain iteration's fold
+ * Sums         the Euclidean inner product over the N entries, in a fixed order (lanes, waves, blocks; no atomics): for the same
+ *              sweeps the Krylov arithmetic repeats its bits.  The sweeps' own FP64 atomics still vary in their last bits
+ * Memory       the basis, (m + 1)·Ns doubles (Ns = N rounded up to even), and x₀, held from the first cycle to the switch-off
+ *              (m = 0) or rt_solver_destroy; a failed allocation returns RT_ERR_HIP and names the size
+ * Works with   fixed-source runs (rt_solver_run, and rt_solver_step_krylov in an open run, freely mixed with rt_solver_step_sweep /
+ *              _step_fold), transient steps, the flat source, isotropic scattering, FP64, rt_solver_set_boundary albedos, adjoint mode
+ * Refused      RT_ERR_INVALID with a message that names both sides, whichever of the two setters comes second: first-moment
+ *              scattering, the linear source, the single-precision sweep, the reproducible tallies, region currents / the coarse-mesh
+ *              acceleration, source regions, the volume correction, an incoming boundary flux (without its source the iteration is then
+ *              not its linear part), a shard's track set (also by rt_solver_begin, whose links may have changed since) — all open
+ * Unaffected   eigenvalue runs launch what they launch without the option; so does every run of a solver that never sets it
+ *
  * The solver borrows the handle's sweep state (rt_sweep's cross sections, boundary fluxes, tallies and group count):
  * after rt_solver_run, rt_sweep_fetch returns its last sweep (components G·P) and the handle's per-track weights are
  * back to the default δ_s.  A later rt_segmentize of the tracks voids the solver: rt_solver_run then fails with
@@ -1044,6 +1073,25 @@ int32_t rt_solver_transient_pointers(rt_solver *solver, void **ptrs_dev, int64_t
 /* Ends the transient: the handle gets its sweep state back, rt_solver_fetch returns the last φ (not normalised), and the solver's own
  * tables and source are what they were before rt_solver_transient_begin.  RT_ERR_INVALID when none is open. */
 int32_t rt_solver_transient_end(rt_solver *solver);
+/* Restarted GMRES (see "Krylov" above) for the following fixed-source runs and transients: m Krylov vectors per cycle at most, 1 .. 64
+ * (0 switches it off and frees the basis), and the relative GMRES residual tol_lin in [0, 1) at which a cycle stops early.  Allocates
+ * nothing (the first cycle does).  RT_ERR_INVALID with a run open, for bad arguments and in the modes listed under "Refused". */
+int32_t rt_solver_set_krylov(rt_solver *solver, int32_t m, double tol_lin);
+/* One cycle of an open fixed-source run (rt_solver_begin; not a transient), with up to m Krylov vectors whatever the plain iteration's
+ * residual: where rt_solver_step_sweep may come, and in its place.  out (may be NULL): residual = the plain iteration's, iterations =
+ * the sweeps so far.  After a cycle that made Krylov vectors the last sweep was a vector's, not the state's: rt_solver_fetch_boundary
+ * refuses ("no sweep with a boundary yet") and the handle's sweep tallies and ψ_out are that vector's until the next
+ * rt_solver_step_sweep / _step_fold (rt_solver_run and a transient's step always end on one).  Waits. */
+int32_t rt_solver_step_krylov(rt_solver *solver, rt_solver_result *out);
+/* info [8] (may be NULL): since the last rt_solver_begin / rt_solver_transient_begin [0] cycles, [1] Krylov vectors, [2] sweeps (cycles +
+ * vectors), [3] the last cycle's vectors, [4] the cycles that ended in a breakdown; [5] m, [6] N, [7] the doubles of the basis held.
+ * resnorm (may be NULL; room for m + 1): of the last cycle β, then the GMRES residual norm after every vector — info[3] + 1 values,
+ * none when the cycle made no vector. */
+int32_t rt_solver_fetch_krylov(rt_solver *solver, int64_t *info, double *resnorm);
+/* Device addresses and element counts of [0] the basis [(m + 1)][Ns] (row j: v_j; the row behind the last vector: what was left of w)
+ * and [1] H [m][m + 1] as the device left it (column k: h_{0,k} .. h_{k+1,k}), valid in an open run after its first cycle with Krylov
+ * vectors (NULL / 0 otherwise).  Does not wait. */
+int32_t rt_solver_krylov_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

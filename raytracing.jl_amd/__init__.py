@@ -19,7 +19,7 @@ from .trackgenerator import (Backward, Forward, Segment, Track, TrackGenerator, 
                              dir_next_track_bwd, dir_next_track_fwd, trace, track_end_sides)
 from .segmentize import RTOL_DEFAULT, SegmentStore, segmentize
 from .solver import (Cmfd, CrossSections, PolarQuadrature, SolverBoundary, SolverResult, azimuthal_weights, exact_azimuthal_weights, diffusion_coupling,
-                     kinetics_parameters, perturbation_reactivity, solve_eigenvalue, solve_fixed_source, Kinetics, TransientResult, solve_transient)
+                     kinetics_parameters, perturbation_reactivity, solve_eigenvalue, solve_fixed_source, Kinetics, TransientResult, solve_transient, Krylov)
 from .distributed import ShardedSolver
 
 __all__ = [
@@ -29,6 +29,6 @@ __all__ = [
     "Track", "Segment",
     "CrossSections", "PolarQuadrature", "SolverResult", "azimuthal_weights", "exact_azimuthal_weights",
     "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "ShardedSolver",
-    "SolverBoundary", "track_end_sides", "Cmfd", "diffusion_coupling", "Kinetics", "TransientResult", "solve_transient",
+    "SolverBoundary", "track_end_sides", "Cmfd", "diffusion_coupling", "Kinetics", "TransientResult", "solve_transient", "Krylov",
     "Forward", "Backward", "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd",
 ]

@@ -40,6 +40,7 @@ SYMBOLS = (
     "rt_solver_set_source_regions", "rt_solver_source_region_info", "rt_solver_source_region_pointers", "rt_solver_fetch_source_rows",
     "rt_solver_transient_begin", "rt_solver_transient_step", "rt_solver_transient_set_xs", "rt_solver_transient_fetch",
     "rt_solver_transient_pointers", "rt_solver_transient_end",
+    "rt_solver_set_krylov", "rt_solver_step_krylov", "rt_solver_fetch_krylov", "rt_solver_krylov_pointers",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -339,6 +340,18 @@ def lib():
         L.rt_solver_transient_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
         L.rt_solver_transient_end.restype = C.c_int32
         L.rt_solver_transient_end.argtypes = [_vp]
+    except AttributeError:
+        if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
+            raise
+    try:
+        L.rt_solver_set_krylov.restype = C.c_int32
+        L.rt_solver_set_krylov.argtypes = [_vp, C.c_int32, C.c_double]
+        L.rt_solver_step_krylov.restype = C.c_int32
+        L.rt_solver_step_krylov.argtypes = [_vp, C.POINTER(SolverResult)]
+        L.rt_solver_fetch_krylov.restype = C.c_int32
+        L.rt_solver_fetch_krylov.argtypes = [_vp, _lp, _dp]
+        L.rt_solver_krylov_pointers.restype = C.c_int32
+        L.rt_solver_krylov_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
     except AttributeError:
         if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
             raise
@@ -1216,6 +1229,43 @@ class DeviceSolver:
     def transient_end(self):
         """``rt_solver_transient_end``: the handle gets its sweep state back; ``fetch`` then returns the last φ."""
         _check(self._transient("rt_solver_transient_end")(self._open()))
+
+    # ---- restarted GMRES (see "Krylov" in include/rt_segmentize.h)
+    def set_krylov(self, m=20, tol_lin=1e-2):
+        """``rt_solver_set_krylov``: fixed-source runs and transient steps take GMRES cycles of at most ``m`` Krylov vectors (1 .. 64),
+        stopped early at the relative GMRES residual ``tol_lin``; ``m`` = 0 (or None / False) switches it off and frees the basis."""
+        _check(self._transient("rt_solver_set_krylov")(self._open(), int(m or 0), float(tol_lin)))
+
+    def step_krylov(self) -> dict:
+        """``rt_solver_step_krylov``: one cycle of an open fixed-source run; ``residual`` is its plain iteration's, ``iterations`` the
+        sweeps so far."""
+        r = SolverResult()
+        _check(self._transient("rt_solver_step_krylov")(self._open(), C.byref(r)))
+        return self._result(r)
+
+    def krylov_info(self) -> dict:
+        """``rt_solver_fetch_krylov``: ``cycles``, ``vectors`` and ``sweeps`` since the run began, ``breakdown`` (some cycle ended in one), of the
+        last cycle ``last_vectors`` and ``resnorm`` (β, then the GMRES residual norm after every vector), and ``m``, ``n`` (the vectors' length) and
+        ``basis_doubles`` (what the basis holds on the device)."""
+        info = (C.c_int64 * 8)()
+        res = np.zeros(66)
+        _check(self._transient("rt_solver_fetch_krylov")(self._open(), info, res.ctypes.data_as(_dp)))
+        lv = int(info[3])
+        return dict(cycles=int(info[0]), vectors=int(info[1]), sweeps=int(info[2]), last_vectors=lv, breakdown=bool(info[4]),
+                    m=int(info[5]), n=int(info[6]), basis_doubles=int(info[7]), resnorm=res[:lv + 1].copy() if lv else res[:0].copy())
+
+    def krylov_pointers(self) -> dict:
+        """``rt_solver_krylov_pointers``: device addresses (0: none) of ``basis`` [(m + 1), row_stride] and ``H`` [m, m + 1] (column k:
+        h[0 .. k + 1]), their element counts under ``lens``, and ``row_stride``."""
+        ptrs = (_vp * 2)()
+        lens = (C.c_int64 * 2)()
+        _check(self._transient("rt_solver_krylov_pointers")(self._open(), ptrs, lens))
+        out = dict(basis=ptrs[0] or 0, H=ptrs[1] or 0, lens=dict(basis=int(lens[0]), H=int(lens[1])))
+        info = (C.c_int64 * 8)()
+        _check(self._transient("rt_solver_fetch_krylov")(self._open(), info, None))
+        m = int(info[5]) if out["lens"]["H"] else 0
+        out["m"], out["row_stride"] = m, out["lens"]["basis"] // (m + 1) if m else 0
+        return out
 
     def pointers(self) -> dict:
         """``rt_solver_pointers``: device addresses (0: none) of ``volumes`` [n_cells], ``tally`` [n_cells, G·P], ``tally1``

@@ -7,6 +7,7 @@
 //   rt_sweep_plan.hpp  what an rt_sweep call decides (rows, pass width and shape, refusals): host-only, a pure function
 //   rt_volcorr.hip     rt_solver's volume correction: tracked lengths, factors, corrected volumes, ℓ' (k_vc_tally / _factor / _apply)
 //   rt_srcreg.hip      rt_solver's source regions: the sweep's rows merged per run of cells of one region (k_sr_count / _plan / _fill / _volumes)
+//   rt_krylov.hip      rt_solver's restarted GMRES: the Krylov vector kernels (k_kry_residual / _dots / _reduce / _update / _scale_store / _combine)
 //   rt_solver.hip      rt_solver: source iteration (k_eff / fixed source) around rt_sweep, fold / source / reduction kernels
 //   rt_segmentize.hip  handles, rt_tracks_create, rt_segmentize (the call's host logic), fetches, statistics
 #pragma once
@@ -396,6 +397,20 @@ struct DTransient {
     double *xs, *prod_out;                   // the sweep's cross sections [n_cells][G·P][2]; F_e written by k_tr_production
 };
 
+// The Krylov vectors of rt_solver (rt_krylov.hip; rt_solver_set_krylov): a vector is the solver's φ [nphi] followed by the handle's
+// ψ_in [N − nphi].  The basis holds m + 1 of them, row stride Ns = N rounded up to even (a row starts on 16 bytes; the pad stays 0).
+struct DKrylov {
+    int64_t nphi, N, Ns;
+    int32_t m, blocks;                       // workgroups of the vector kernels (partials per reduction)
+    double *basis, *x0;                      // [(m + 1)·Ns], [Ns]
+    double *part, *npart;                    // block partials: the dots [blocks][kKryStride], a squared norm [blocks]
+    double *coef;                            // the coefficients of one Gram–Schmidt pass, then y [m + 1]
+    double *H, *beta;                        // H [m][m + 1] (column k: h_{0..k+1,k}), ‖r₀‖
+    double *phi, *psi;                       // the live pieces: rt_solver::phi, rt_tracks::sw_psi_in
+};
+constexpr int kKryStride = 72;               // doubles per block partial row of the dots (up to 65 of them)
+constexpr int kKryMaxBlocks = 1024;
+
 }  // namespace rt
 
 // ------------------------------------------------------------------- handles -------------
@@ -705,6 +720,15 @@ int launch_srcreg_volumes(const rt::DSrcReg &a, hipStream_t s);
 // rt_transient.hip: one of a transient's small kernels, queued on `s`
 enum class TransientKernel { PrecursorsInit, Precursors, Source, SigmaT, Production };
 int launch_transient(TransientKernel which, const rt::DTransient &a, hipStream_t s);
+// rt_krylov.hip: the vector kernels of the restarted GMRES, queued on `s` (every reduction in a fixed order).  `slot`: a basis row.
+// residual: out = pieces − ref (neg: ref − pieces) and ‖out‖ into *norm_dst;  orthogonalise: classical Gram–Schmidt twice of row
+// `slot` against rows 0 .. nvec − 1, the summed coefficients into hcol [nvec] and the norm of what is left into hcol[nvec];
+// scale_store: row `slot` /= *div, also into the pieces;  combine: pieces = x0 + Σ_j coef[j] · row j, j < nvec
+unsigned krylov_blocks(int64_t N);
+int launch_kry_residual(const rt::DKrylov &a, bool neg, const double *ref, double *out, double *norm_dst, hipStream_t s);
+int launch_kry_orthogonalise(const rt::DKrylov &a, int32_t slot, int32_t nvec, double *hcol, hipStream_t s);
+int launch_kry_scale_store(const rt::DKrylov &a, int32_t slot, const double *div, hipStream_t s);
+int launch_kry_combine(const rt::DKrylov &a, int32_t nvec, hipStream_t s);
 // rt_sweep.hip: what a sweep of `G` components with input 0 under `loan` would read — planned as rt_sweep plans it (refused with its
 // message), the rows made as rt_sweep makes them (once per segmentation) — for a solver that scales their ℓ before its first sweep
 int sweep_rows_for_loan(rt_tracks *t, int32_t G, const SweepLoan &loan, bool volcorr, SweepRowsView *out);

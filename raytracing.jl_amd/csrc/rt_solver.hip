@@ -30,10 +30,15 @@
 // k_tr_source (rt_transient.hip: φ^n aside, the step's external source), the iteration above on the step's own material table until
 // the flux residual is small, and k_tr_precursors.  The solver's own table and source are never written; without a transient the
 // solver launches what it always did.
+// With restarted GMRES (rt_solver_set_krylov) a fixed-source run and a transient's steps take cycles (solver_krylov_cycle) in place of
+// plain iterations: one plain iteration, then up to m applications of the iteration's linear part — the same sweep and fold with the
+// external source left out — with the vector kernels of rt_krylov.hip between them and the least-squares solve of rt_krylov_host.hpp
+// on the host.  Eigenvalue runs, and a solver without the option, launch what they always did.
 // Flat, first-moment scattering or linear source is one choice of three, a SweepMode (each setter switches only its own mode off and
 // refuses to switch it on over the other).  What a run's rt_sweep calls need to know — that mode, the linear source's geometry, the
 // reproducible tallies' delta buffer, single precision — goes to the handle as one SweepLoan (rt_internal.hpp) and comes back whole.
 #include "rt_internal.hpp"
+#include "rt_krylov_host.hpp"
 
 namespace rt {
 
@@ -645,6 +650,19 @@ struct rt_solver {
     double tr_k0 = 1.0, tr_time = 0.0, tr_dt_tab = 0.0;
     std::vector<double> tr_h_st, tr_h_ss, tr_h_nf, tr_h_chi, tr_h_iv, tr_h_beta, tr_h_lambda, tr_h_chid, tr_h_tab;
     DevBuf<double> tr_tab, tr_ktab, tr_C, tr_phi_prev, tr_ext;
+    // restarted GMRES (rt_solver_set_krylov): m (0: off) and the linear tolerance; the basis [(m + 1)·Ns], x₀, the block partials,
+    // one pass's coefficients / y, H and ‖r₀‖ on the device (made by the first cycle for `kry_alloc_m` and `kry_N`, freed by the
+    // switch-off and rt_solver_destroy); `kry_lin`: the sweep being queued applies the linear part (no external source);
+    // `kry_h`: pinned, a column of H / y; `kry_info`, `kry_res`: what rt_solver_fetch_krylov reports
+    int32_t kry_m = 0, kry_alloc_m = 0;
+    double kry_tol_lin = 0.0;
+    bool kry_lin = false;
+    int64_t kry_N = 0, kry_Ns = 0;
+    DevBuf<double> kry_basis, kry_x0, kry_part, kry_npart, kry_coef, kry_H, kry_beta;
+    double *kry_h = nullptr;
+    int64_t kry_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<double> kry_res;
+    rtkry::Hessenberg kry_lsq;
 };
 
 namespace rtx {
@@ -657,6 +675,7 @@ void solver_release(rt_solver *S) {
     S->t->sw_has_w = false;
     S->open = false; S->swept = false;
     S->tr_open = false; S->tr_src = false;  // (a transient ends with its run: the solver's own tables were never written)
+    S->kry_lin = false;
 }
 
 }  // namespace rtx
@@ -673,6 +692,7 @@ bool finite_nonneg(const double *a, size_t n, size_t *bad) {
 void free_solver(rt_solver *s) {
     if (!s) return;
     if (s->h_scal) (void)hipHostFree(s->h_scal);
+    if (s->kry_h) (void)hipHostFree(s->kry_h);
     for (hipEvent_t &e : s->ev)
         if (e) (void)hipEventDestroy(e);
     delete s;
@@ -993,6 +1013,8 @@ int solver_srcreg_prepare(rt_solver *S, const char *who) {
     return RT_SUCCESS;
 }
 
+const char *krylov_conflict(const rt_solver *S);  // (below, with the cycles)
+
 // keep_phi (rt_solver_transient_begin): the run starts from the φ the solver holds instead of φ⁰ = 1; the caller queues the components'
 // Σt / sin θ, F_e and the scalars itself, from the table its run reads
 int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi = false) {
@@ -1008,8 +1030,13 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
         set_error("%s: an incoming boundary flux is set (rt_solver_set_boundary), and an eigenvalue run has no fixed source", who);
         return RT_ERR_INVALID;
     }
-    if (t->sw_loan.borrower) solver_release(t->sw_loan.borrower);  // (another solver's unfinished run on this handle ends here)
     const bool eigen = mode == RT_SOLVE_EIGENVALUE;
+    if (!eigen && S->kry_m > 0)  // (the setters keep the combinations apart; the links may have become a shard's since)
+        if (const char *other = krylov_conflict(S)) {
+            set_error("%s: restarted GMRES is set (rt_solver_set_krylov) and %s: the two together are not supported", who, other);
+            return RT_ERR_INVALID;
+        }
+    if (t->sw_loan.borrower) solver_release(t->sw_loan.borrower);  // (another solver's unfinished run on this handle ends here)
     rt_mesh *m = t->mesh;
     if (int rc = finish_call(t)) return rc;
     RT_HIP(hipSetDevice(m->device));
@@ -1081,6 +1108,8 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
                            (const int8_t *)S->bnd_side_entry.p, (const double *)S->bnd_beta.p, (const double *)S->bnd_incv.p,
                            (const double *)nullptr, t->sw_psi_in.p, 2 * n, G, P, n);
     S->k_hist.clear();
+    for (int i = 0; i < 5; ++i) S->kry_info[i] = 0;
+    S->kry_res.clear(); S->kry_lin = false;
     S->run_eigen = eigen; S->run_mode = smode; S->run_bnd = bnd; S->run_reg = reg; S->run_cm = cm;
     S->it = 0; S->last_k = 1.0; S->last_res = INFINITY; S->last_dk = INFINITY;
     // φ⁰ = 1, the components' Σt / sin θ, F⁰
@@ -1102,7 +1131,8 @@ int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
     hipStream_t s = t->mesh->stream;
     const int32_t G = d.G, P = d.P, nc = d.nc, eig = S->run_eigen ? 1 : 0;
     // (a transient reads its own table and, from its first step on, its own S: the solver's table and source are left as they are)
-    const double *ext = S->tr_open ? (S->tr_src ? S->tr_ext.p : nullptr) : ((!S->run_eigen && S->has_ext) ? S->ext.p : nullptr);
+    // (a Krylov vector takes the linear part of the iteration: the same kernels without the source)
+    const double *ext = S->kry_lin ? nullptr : S->tr_open ? (S->tr_src ? S->tr_ext.p : nullptr) : ((!S->run_eigen && S->has_ext) ? S->ext.p : nullptr);
     const double *tab = S->tr_open ? S->tr_tab.p : S->tab.p;
     hipLaunchKernelGGL(rt::k_solver_source, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
                        tab, d.lds_len, (const double *)S->phi.p, (const double *)S->prod.p, ext, (const double *)S->scal.p, eig,
@@ -1200,6 +1230,140 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
     return RT_SUCCESS;
 }
 
+// ---- restarted GMRES (rt_solver_set_krylov; "Krylov" in include/rt_segmentize.h) -----------------------------------------------------
+// What a solver with the option set cannot run together with, for the messages that name both sides; nullptr: nothing.
+const char *krylov_conflict(const rt_solver *S) {
+    return S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
+        : (S->mode == SweepMode::Linear || S->ls_stage != 0) ? "the linear source is on (rt_solver_set_linear_source)"
+        : S->single ? "the single-precision sweep is set (rt_solver_set_precision)"
+        : S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
+        : (S->reg_R > 0 || S->cm_on) ? "region currents are set (rt_solver_set_regions, rt_solver_set_cmfd)"
+        : S->sr_on ? "source regions are set (rt_solver_set_source_regions)"
+        : S->vc_mode ? "the volume correction is set (rt_solver_set_volume_correction)"
+        : (S->bnd_S > 0 && S->bnd_inc) ? "a boundary has an incoming flux (rt_solver_set_boundary: the iteration without its source is then not its linear part)"
+        : S->t->sw_shard ? "the track set is a shard (some next uid is 0)" : nullptr;
+}
+
+void krylov_free(rt_solver *S) {
+    S->kry_basis.release(); S->kry_x0.release(); S->kry_part.release(); S->kry_npart.release(); S->kry_coef.release(); S->kry_H.release();
+    S->kry_beta.release();
+    S->kry_alloc_m = 0; S->kry_N = 0; S->kry_Ns = 0;
+}
+
+// The buffers of the cycles for the m that is set and the open run's vector length: exactly (m + 1)·Ns doubles of basis, zeroed once
+// (the pad of an odd N stays 0: no kernel writes it).  A failed allocation frees what was held and names the size.
+int krylov_reserve(rt_solver *S, const char *who) {
+    rt_tracks *t = S->t;
+    const int32_t m = S->kry_m;
+    const int64_t nphi = (int64_t)S->n_cells * S->G, N = nphi + 2 * t->n * (int64_t)S->G * S->P, Ns = (N + 1) & ~(int64_t)1;
+    if (S->kry_basis.p && S->kry_alloc_m == m && S->kry_N == N) return RT_SUCCESS;
+    krylov_free(S);
+    if (N < 1) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov) on a problem without cells and tracks", who); return RT_ERR_INVALID; }
+    const size_t need = (size_t)(m + 1) * (size_t)Ns;
+    DevBuf<double> b;
+    if (hipMalloc((void **)&b.p, need * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        b.p = nullptr;
+        set_error("%s: no device memory for the Krylov basis: %zu bytes ((%d + 1) vectors x %lld doubles x 8)", who, need * sizeof(double), m, (long long)Ns);
+        return RT_ERR_HIP;
+    }
+    b.cap = need;
+    S->kry_basis = std::move(b);
+    hipStream_t s = t->mesh->stream;
+    RT_HIP(hipMemsetAsync(S->kry_basis.p, 0, need * sizeof(double), s));
+    const unsigned blocks = krylov_blocks(N);
+    RT_HIP(S->kry_x0.reserve((size_t)Ns)); RT_HIP(S->kry_part.reserve((size_t)blocks * rt::kKryStride)); RT_HIP(S->kry_npart.reserve(blocks));
+    RT_HIP(S->kry_coef.reserve(rt::kKryStride)); RT_HIP(S->kry_H.reserve((size_t)m * (m + 1))); RT_HIP(S->kry_beta.reserve(8));
+    RT_HIP(hipMemsetAsync(S->kry_H.p, 0, (size_t)m * (m + 1) * sizeof(double), s));
+    if (!S->kry_h) RT_HIP(hipHostMalloc((void **)&S->kry_h, rt::kKryStride * sizeof(double), hipHostMallocDefault));
+    S->kry_alloc_m = m; S->kry_N = N; S->kry_Ns = Ns;
+    return RT_SUCCESS;
+}
+
+// F_e of the φ that a vector kernel has written, from the table the run reads (k_tr_production reads nothing else of its arguments)
+int krylov_production(rt_solver *S, hipStream_t s) {
+    rt::DTransient a{};
+    a.n_cells = S->n_cells; a.G = S->G; a.P = S->P;
+    a.mat = S->mat.p; a.tab = S->tr_open ? S->tr_tab.p : S->tab.p; a.phi = S->phi.p; a.prod_out = S->prod.p;
+    return launch_transient(TransientKernel::Production, a, s);
+}
+
+// One cycle of an open fixed-source run (a transient's step included): x₀ aside, one plain iteration — its residual, against `tol`,
+// is the run's stopping test — and, unless that has converged, up to min(m, budget − 2) Krylov vectors (every one a sweep and a
+// fold of the linear part, counted as an iteration) and x = x₀ + V y.  `budget`: the sweeps the caller has left; a cycle leaves at
+// least one of them, so that a run that counts its sweeps always ends on a plain iteration, with the scalars of its fold.
+int solver_krylov_cycle(rt_solver *S, const SolverDims &d, int32_t budget, double tol, rt_solver_result *res, const char *who) {
+    rt_tracks *t = S->t;
+    hipStream_t s = t->mesh->stream;
+    if (int rc = krylov_reserve(S, who)) return rc;
+    const int32_t m = S->kry_m;
+    rt::DKrylov a{};
+    a.nphi = d.ncg; a.N = S->kry_N; a.Ns = S->kry_Ns; a.m = m; a.blocks = (int32_t)krylov_blocks(S->kry_N);
+    a.basis = S->kry_basis.p; a.x0 = S->kry_x0.p; a.part = S->kry_part.p; a.npart = S->kry_npart.p; a.coef = S->kry_coef.p;
+    a.H = S->kry_H.p; a.beta = S->kry_beta.p; a.phi = S->phi.p; a.psi = t->sw_psi_in.p;
+    const int64_t npsi = a.N - a.nphi;
+    if (a.nphi > 0) RT_HIP(hipMemcpyAsync(a.x0, a.phi, (size_t)a.nphi * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (npsi > 0) RT_HIP(hipMemcpyAsync(a.x0 + a.nphi, a.psi, (size_t)npsi * sizeof(double), hipMemcpyDeviceToDevice, s));
+    if (int rc = solver_queue_sweep(S, d)) return rc;
+    if (int rc = solver_queue_fold(S, d, res, who)) return rc;
+    int64_t *I = S->kry_info;
+    ++I[0]; ++I[2]; I[3] = 0;
+    S->kry_res.clear();
+    const int32_t mk = std::min<int64_t>(m, (int64_t)budget - 2);
+    if (S->last_res < tol || mk < 1) return RT_SUCCESS;
+    // r₀ = F(x₀) − x₀ into row 0, v₀ = r₀ / ‖r₀‖ there and into the pieces
+    if (int rc = launch_kry_residual(a, false, a.x0, a.basis, a.beta, s)) return rc;
+    RT_HIP(hipMemcpyAsync(S->kry_h, a.beta, sizeof(double), hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    const double beta = S->kry_h[0];
+    if (!std::isfinite(beta)) { set_error("%s: the residual of a Krylov cycle has the norm %g", who, beta); return RT_ERR_INVALID; }
+    if (!(beta > 0.0)) return RT_SUCCESS;  // (x₀ is the fixed point to the bit: F(x₀) stands)
+    S->kry_res.push_back(beta);
+    S->kry_lsq.reset(m, beta);
+    if (int rc = launch_kry_scale_store(a, 0, a.beta, s)) return rc;
+    if (int rc = krylov_production(S, s)) return rc;
+    struct Linear { rt_solver *S; ~Linear() { S->kry_lin = false; } } linear{S};
+    S->kry_lin = true;
+    int32_t kdone = 0;
+    for (int32_t k = 0; k < mk; ++k) {
+        // A v_k: the sweep and the fold of the iteration without its source (no scalars, no history: they mean nothing here)
+        if (int rc = solver_queue_sweep(S, d)) return rc;
+        hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)(S->tr_open ? S->tr_tab.p : S->tab.p),
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, d.nc, d.G, d.P,
+                           S->partial.p);
+        S->swept = false;
+        ++S->it; S->k_hist.push_back(1.0);
+        ++I[1]; ++I[2]; ++I[3];
+        // w = v_k − A v_k into row k + 1, orthogonalised against the rows 0 .. k; the column comes to the host
+        double *hcol = a.H + (size_t)k * (m + 1);
+        if (int rc = launch_kry_residual(a, true, a.basis + (int64_t)k * a.Ns, a.basis + (int64_t)(k + 1) * a.Ns, nullptr, s)) return rc;
+        if (int rc = launch_kry_orthogonalise(a, k + 1, k + 1, hcol, s)) return rc;
+        RT_HIP(hipMemcpyAsync(S->kry_h, hcol, (size_t)(k + 2) * sizeof(double), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));
+        for (int32_t j = 0; j <= k + 1; ++j)
+            if (!std::isfinite(S->kry_h[j])) { set_error("%s: Krylov vector %d of the cycle produced h[%d] = %g", who, k + 1, j, S->kry_h[j]); return RT_ERR_INVALID; }
+        const bool breakdown = S->kry_h[k + 1] <= 1e-14 * beta;  // (the solve is then exact, and nothing is divided by it)
+        const double rn = S->kry_lsq.append(S->kry_h);
+        S->kry_res.push_back(rn);
+        kdone = k + 1;
+        if (breakdown) { ++I[4]; break; }
+        if (rn < S->kry_tol_lin * beta || kdone == mk) break;
+        if (int rc = launch_kry_scale_store(a, k + 1, hcol + k + 1, s)) return rc;
+        if (int rc = krylov_production(S, s)) return rc;
+    }
+    // x = x₀ + V y, F_e of its φ
+    S->kry_lsq.solve(S->kry_h);
+    RT_HIP(hipMemcpyAsync(a.coef, S->kry_h, (size_t)kdone * sizeof(double), hipMemcpyHostToDevice, s));
+    if (int rc = launch_kry_combine(a, kdone, s)) return rc;
+    if (int rc = krylov_production(S, s)) return rc;
+    // (the last sweep was a Krylov vector's: its boundary and region currents are not those of x; the next plain sweep tallies anew)
+    S->bnd_tallied = false; S->reg_tallied = false;
+    RT_HIP(hipStreamSynchronize(s));  // (kry_h is the next column's again)
+    RT_HIP(hipGetLastError());
+    if (res) res->iterations = S->it;
+    return RT_SUCCESS;
+}
+
 // one step call: the sweep (fold = false; res unused) or the fold of an open run
 int solver_step_impl(rt_solver *S, bool fold, rt_solver_result *res, const char *who) {
     if (int rc = solver_step_enter(S, fold, who)) return rc;
@@ -1263,9 +1427,14 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
     {   // (begin has checked the tracks and set the device, and nothing comes between the steps here)
         AbortRun abort_run{S};
         const SolverDims d(S);
+        const bool krylov = S->kry_m > 0 && !S->run_eigen;
         while (S->it < max_iter) {
-            if (int rc = solver_queue_sweep(S, d)) return rc;
-            if (int rc = solver_queue_fold(S, d, nullptr, who)) return rc;
+            if (krylov) {
+                if (int rc = solver_krylov_cycle(S, d, max_iter - S->it, tol_flux, nullptr, who)) return rc;
+            } else {
+                if (int rc = solver_queue_sweep(S, d)) return rc;
+                if (int rc = solver_queue_fold(S, d, nullptr, who)) return rc;
+            }
             if (S->last_dk < tol_k && S->last_res < tol_flux) { converged = true; break; }
         }
         abort_run.ok = true;
@@ -1361,8 +1530,12 @@ int transient_iterate(rt_solver *S, int32_t max_iter, double tol, const char *wh
     const SolverDims d(S);
     S->it = 0; S->k_hist.clear();
     while (S->it < max_iter) {
-        if (int rc = solver_queue_sweep(S, d)) return rc;
-        if (int rc = solver_queue_fold(S, d, nullptr, who)) return rc;
+        if (S->kry_m > 0) {  // (a cycle ends on x₀ + V y: the loop comes back for the plain iteration that tests it)
+            if (int rc = solver_krylov_cycle(S, d, max_iter - S->it, tol, nullptr, who)) return rc;
+        } else {
+            if (int rc = solver_queue_sweep(S, d)) return rc;
+            if (int rc = solver_queue_fold(S, d, nullptr, who)) return rc;
+        }
         if (S->last_res < tol) break;
     }
     return RT_SUCCESS;
@@ -1587,6 +1760,7 @@ static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) 
     if (S->open) { set_error("rt_solver_set_scatter_p1: a run is open (rt_solver_begin without rt_solver_end): the tables cannot change under it"); return RT_ERR_INVALID; }
     if (!sigma_s1) { if (S->mode == SweepMode::P1) S->mode = SweepMode::Flat; return RT_SUCCESS; }
     if (S->mode == SweepMode::Linear) { set_error("rt_solver_set_scatter_p1: the linear source is on, and the two together are not supported"); return RT_ERR_INVALID; }
+    if (S->kry_m > 0) { set_error("rt_solver_set_scatter_p1: restarted GMRES is set (rt_solver_set_krylov), and first-moment scattering together with it is not supported"); return RT_ERR_INVALID; }
     if (S->single) { set_error("rt_solver_set_scatter_p1: the single-precision sweep is set (rt_solver_set_precision), and first-moment scattering together with it is not supported"); return RT_ERR_INVALID; }
     const int32_t G = S->G, M = S->M;
     const size_t n1 = (size_t)M * G * G;
@@ -1716,6 +1890,7 @@ static int32_t solver_set_boundary_impl(rt_solver *S, int32_t n_sides, const int
         }
         any_inc = any_inc || (incoming && incoming[i] > 0.0);
     }
+    if (any_inc && S->kry_m > 0) { set_error("%s: an incoming flux, and restarted GMRES is set (rt_solver_set_krylov) (the iteration without its source is then not its linear part): the two together are not supported", who); return RT_ERR_INVALID; }
     if (any_inc && S->cm_on) { set_error("%s: an incoming flux, and the coarse-mesh acceleration is on (rt_solver_set_cmfd): the two together are not supported", who); return RT_ERR_INVALID; }
     const size_t n2 = (size_t)(2 * n);
     std::vector<int8_t> side_end(std::max<size_t>(1, n2), -1), side_start(std::max<size_t>(1, n2), -1), side_entry(std::max<size_t>(1, n2), -1);
@@ -1806,6 +1981,7 @@ static int32_t solver_set_regions_impl(rt_solver *S, int32_t n_regions, const in
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the regions cannot change under it", who); return RT_ERR_INVALID; }
     if (n_regions == 0 || !cell_region) { S->reg_R = 0; S->reg_tallied = false; S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
     if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the coarse-mesh prolongation reads the compact records' cells), and region currents together with them are not supported", who); return RT_ERR_INVALID; }
+    if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and region currents together with it are not supported", who); return RT_ERR_INVALID; }
     if (n_regions < 1 || n_regions > rtsweep::kMaxRegions) { set_error("%s: bad arguments (n_regions %d, need 1 .. %d)", who, n_regions, rtsweep::kMaxRegions); return RT_ERR_INVALID; }
     if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and region currents — an atomic sum — together with them are not supported", who); return RT_ERR_INVALID; }
     if (S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision: another kernel), and region currents together with it are not supported", who); return RT_ERR_INVALID; }
@@ -1847,6 +2023,7 @@ static int32_t solver_set_cmfd_impl(rt_solver *S, int32_t on, const double *coup
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the acceleration cannot change under it", who); return RT_ERR_INVALID; }
     if (!on) { S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
     if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the prolongation reads the compact records' cells), and the coarse-mesh acceleration together with them is not supported", who); return RT_ERR_INVALID; }
+    if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the coarse-mesh acceleration together with it is not supported", who); return RT_ERR_INVALID; }
     const int32_t R = S->reg_R, G = S->G, nc = S->n_cells;
     if (R <= 0) { set_error("%s: no regions are set (rt_solver_set_regions comes first: its regions are the coarse cells)", who); return RT_ERR_INVALID; }
     if (S->bnd_S > 0 && S->bnd_inc) { set_error("%s: a boundary has an incoming flux (rt_solver_set_boundary), and the coarse-mesh acceleration together with it is not supported", who); return RT_ERR_INVALID; }
@@ -2002,6 +2179,7 @@ static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged
         return RT_ERR_INVALID;
     }
     if (S->mode == SweepMode::P1) { set_error("%s: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported", who); return RT_ERR_INVALID; }
+    if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the linear source together with it is not supported", who); return RT_ERR_INVALID; }
     if (staged && S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the geometry cannot change under it", who); return RT_ERR_INVALID; }
     if (stage != 0 && stage != S->ls_stage) {
         set_error("%s: stage %d out of order (%s)", who, stage,
@@ -2074,6 +2252,7 @@ int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
     if (solver->open) { set_error("rt_solver_set_linear_source: a run is open (rt_solver_begin without rt_solver_end): the source's shape cannot change under it"); return RT_ERR_INVALID; }
     if (!on) { if (solver->mode == SweepMode::Linear) solver->mode = SweepMode::Flat; return RT_SUCCESS; }
     if (solver->mode == SweepMode::P1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
+    if (solver->kry_m > 0) { set_error("rt_solver_set_linear_source: restarted GMRES is set (rt_solver_set_krylov), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
     if (solver->single) { set_error("rt_solver_set_linear_source: the single-precision sweep is set (rt_solver_set_precision), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
     if (solver->sr_on) { set_error("rt_solver_set_linear_source: source regions are set (rt_solver_set_source_regions: the centroids and C matrices are per cell), and the linear source together with them is not supported"); return RT_ERR_INVALID; }
     if (solver->vc_mode) { set_error("rt_solver_set_linear_source: the volume correction is set (rt_solver_set_volume_correction: scaled chords would move the linear source's midpoints off the track), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
@@ -2106,6 +2285,7 @@ static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
     if (S->ls_stage != 0) { set_error("%s: the linear source's geometry is between two stages (rt_solver_ls_geometry)", who); return RT_ERR_INVALID; }
     const bool want = on != 0;
     if (want == S->repro) return RT_SUCCESS;
+    if (want && S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
     if (want && S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
     if (want && S->reg_R > 0) { set_error("%s: region currents are set (rt_solver_set_regions: their tally is an atomic sum), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
     if (want && S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the tally index is per original row slot), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
@@ -2189,7 +2369,8 @@ int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision) {
         const char *other = S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
                                   : (S->mode == SweepMode::Linear ? "the linear source is on (rt_solver_set_linear_source)"
                                            : (S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
-                                                       : (S->reg_R > 0 ? "region currents are set (rt_solver_set_regions: another kernel)" : nullptr)));
+                                                       : (S->reg_R > 0 ? "region currents are set (rt_solver_set_regions: another kernel)"
+                                                                       : (S->kry_m > 0 ? "restarted GMRES is set (rt_solver_set_krylov)" : nullptr))));
         if (other) { set_error("%s: %s, and the single-precision sweep together with it is not supported", who, other); return RT_ERR_INVALID; }
     }
     S->single = precision == RT_PRECISION_SINGLE;
@@ -2209,6 +2390,7 @@ static int32_t solver_set_volume_correction_impl(rt_solver *S, int32_t mode) {
     }
     if (mode == S->vc_mode) return RT_SUCCESS;
     if (mode != RT_VOLUME_CORRECTION_OFF) {
+        if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the volume correction together with it is not supported", who); return RT_ERR_INVALID; }
         if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions), and the volume correction — its factors are per cell — together with them is not supported", who); return RT_ERR_INVALID; }
         if (S->mode == SweepMode::Linear || S->ls_stage != 0) { set_error("%s: the linear source is on (rt_solver_set_linear_source: scaled chords would move its midpoints off the track), and the volume correction together with it is not supported", who); return RT_ERR_INVALID; }
         if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and the volume correction — its tracked lengths are an atomic sum — together with them is not supported", who); return RT_ERR_INVALID; }
@@ -2295,6 +2477,7 @@ static int32_t solver_set_source_regions_impl(rt_solver *S, const int32_t *map, 
         return RT_SUCCESS;
     }
     if (n_src < 1 || n_src > nm) { set_error("%s: bad arguments (n_src %d, need 1 .. the mesh's %d cells)", who, n_src, nm); return RT_ERR_INVALID; }
+    if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and source regions together with it are not supported", who); return RT_ERR_INVALID; }
     if (S->mode == SweepMode::Linear || S->ls_stage != 0) { set_error("%s: the linear source is on (rt_solver_set_linear_source: its centroids and C matrices are per cell), and source regions together with it are not supported", who); return RT_ERR_INVALID; }
     if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible: their tally index is per original row slot), and source regions together with them are not supported", who); return RT_ERR_INVALID; }
     if (S->reg_R > 0 || S->cm_on) { set_error("%s: region currents are set (rt_solver_set_regions, rt_solver_set_cmfd: the coarse-mesh prolongation reads the compact records' cells), and source regions together with them are not supported", who); return RT_ERR_INVALID; }
@@ -2481,6 +2664,74 @@ int32_t rt_solver_step_fold(rt_solver *solver, rt_solver_result *out) {
 int32_t rt_solver_end(rt_solver *solver, rt_solver_result *out) {
     if (!solver) { set_error("rt_solver_end: null solver"); return RT_ERR_INVALID; }
     return guarded("rt_solver_end", [&] { return solver_end_impl(solver, out, "rt_solver_end"); });
+}
+
+// Restarted GMRES for the following fixed-source runs and transients.  Nothing is allocated here: the first cycle makes the basis.
+int32_t rt_solver_set_krylov(rt_solver *solver, int32_t m, double tol_lin) {
+    const char *who = "rt_solver_set_krylov";
+    rt_solver *S = solver;
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (int rc = solver_check_epoch(S, who)) return rc;
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the iteration cannot change under it", who); return RT_ERR_INVALID; }
+    if (m < 0 || m > 64 || (m > 0 && (!(tol_lin >= 0.0) || !(tol_lin < 1.0)))) {
+        set_error("%s: bad arguments (m %d: 0 switches it off, else 1 .. 64; tol_lin %g: in [0, 1))", who, m, tol_lin);
+        return RT_ERR_INVALID;
+    }
+    if (m == 0) {
+        return guarded(who, [&]() -> int32_t {
+            if (S->kry_basis.p) {  // (nothing of a cycle is on the stream any more: no run is open)
+                if (int rc = finish_call(S->t)) return rc;
+                RT_HIP(hipSetDevice(S->t->mesh->device));
+                RT_HIP(hipStreamSynchronize(S->t->mesh->stream));
+            }
+            krylov_free(S);
+            S->kry_m = 0; S->kry_tol_lin = 0.0;
+            return RT_SUCCESS;
+        });
+    }
+    if (const char *other = krylov_conflict(S)) { set_error("%s: %s, and restarted GMRES together with it is not supported", who, other); return RT_ERR_INVALID; }
+    S->kry_m = m; S->kry_tol_lin = tol_lin;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_step_krylov(rt_solver *solver, rt_solver_result *out) {
+    const char *who = "rt_solver_step_krylov";
+    if (!solver) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    return guarded(who, [&]() -> int32_t {
+        rt_solver *S = solver;
+        if (int rc = solver_step_enter(S, false, who)) return rc;
+        if (S->kry_m <= 0) { set_error("%s: restarted GMRES is not set (rt_solver_set_krylov comes before rt_solver_begin)", who); return RT_ERR_INVALID; }
+        if (S->run_eigen) { set_error("%s: the open run is an eigenvalue run: a Krylov cycle needs a fixed-source run", who); return RT_ERR_INVALID; }
+        AbortRun abort_run{S};
+        RT_HIP(hipSetDevice(S->t->mesh->device));
+        if (int rc = solver_krylov_cycle(S, SolverDims(S), INT32_MAX, 0.0, out, who)) return rc;
+        abort_run.ok = true;
+        return RT_SUCCESS;
+    });
+}
+
+int32_t rt_solver_fetch_krylov(rt_solver *solver, int64_t *info, double *resnorm) {
+    if (!solver) { set_error("rt_solver_fetch_krylov: null solver"); return RT_ERR_INVALID; }
+    if (info) {
+        for (int i = 0; i < 5; ++i) info[i] = solver->kry_info[i];
+        info[5] = solver->kry_m; info[6] = solver->kry_N; info[7] = (int64_t)solver->kry_basis.cap;
+    }
+    if (resnorm)
+        for (size_t i = 0; i < solver->kry_res.size(); ++i) resnorm[i] = solver->kry_res[i];
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_krylov_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
+    if (!solver) { set_error("rt_solver_krylov_pointers: null solver"); return RT_ERR_INVALID; }
+    // (no wait here: addresses and counts only)
+    const bool on = solver->open && solver->kry_basis.p != nullptr;
+    void *p[2] = {solver->kry_basis.p, solver->kry_H.p};
+    const int64_t l[2] = {(int64_t)(solver->kry_alloc_m + 1) * solver->kry_Ns, (int64_t)solver->kry_alloc_m * (solver->kry_alloc_m + 1)};
+    for (int i = 0; i < 2; ++i) {
+        if (ptrs_dev) ptrs_dev[i] = on ? p[i] : nullptr;
+        if (lens) lens[i] = on ? l[i] : 0;
+    }
+    return RT_SUCCESS;
 }
 
 int32_t rt_solver_transient_begin(rt_solver *solver, int32_t n_families, const double *inv_velocity, const double *beta, const double *lambda,

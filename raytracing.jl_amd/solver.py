@@ -29,6 +29,10 @@ iterations; ``diffusion_coupling`` builds an optional coupling D̂ from the mesh
 ``solve_transient`` continues an eigenvalue result in time (``rt_solver_transient_*``): implicit Euler with ``Kinetics`` data (1/v, delayed
 fractions, decay constants and spectra), every step a fixed-source problem started from the previous step's flux, cross sections
 changed between steps by ``events``; the result carries the relative power ``production`` over ``times``.
+With ``krylov=True`` (or a ``Krylov``) ``solve_fixed_source`` and ``solve_transient`` take restarted-GMRES cycles in place of plain
+iterations (``rt_solver_set_krylov``): the iteration is an affine map on (φ, ψ_in), every Krylov vector costs one unchanged sweep and
+counts as an iteration, and a scattering ratio (or a transient's 1 − β) near one no longer sets the number of sweeps;
+``SolverResult.krylov`` and ``TransientResult.krylov_vectors`` say what the cycles did.
 """
 from __future__ import annotations
 
@@ -43,7 +47,7 @@ from .trackgenerator import SIDE_NAMES, TrackGenerator, track_end_sides
 
 __all__ = ["CrossSections", "PolarQuadrature", "SolverBoundary", "SolverResult", "Cmfd", "diffusion_coupling", "exact_azimuthal_weights", "azimuthal_weights",
            "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "neutron_balance", "region_balance",
-           "Kinetics", "TransientResult", "solve_transient"]
+           "Kinetics", "TransientResult", "solve_transient", "Krylov"]
 
 
 class CrossSections:
@@ -276,6 +280,32 @@ class Cmfd:
                 raise ValueError("Cmfd.coupling must be symmetric in its two regions")
 
 
+@dataclass
+class Krylov:
+    """Restarted GMRES of ``include/rt_segmentize.h`` ("Krylov") for fixed-source runs and transient steps: at most ``m`` Krylov
+    vectors per cycle (1 .. 64; the basis holds (m + 1) vectors of n_cells·G + 2·n_tracks·G·P doubles on the device) and the
+    relative GMRES residual ``tol_lin`` at which a cycle stops early."""
+    m: int = 20
+    tol_lin: float = 1e-2
+
+    def check(self):
+        if not (1 <= int(self.m) <= 64):
+            raise ValueError("Krylov.m must lie in 1 .. 64")
+        if not (0.0 <= float(self.tol_lin) < 1.0):
+            raise ValueError("Krylov.tol_lin must lie in [0, 1)")
+
+
+def _as_krylov(krylov):
+    if krylov is None or krylov is False:
+        return None
+    if krylov is True:
+        return Krylov()
+    if isinstance(krylov, Krylov):
+        krylov.check()
+        return krylov
+    raise TypeError("krylov must be True, False, None or a Krylov")
+
+
 def _as_cmfd(cmfd):
     if cmfd is None or cmfd is False:
         return None
@@ -360,6 +390,7 @@ class SolverResult:
     source_region: Optional[np.ndarray] = None     # source_regions=...: the cells' regions [mesh cells]; phi, volumes, current are then [n_src, ...]
     source_region_info: Optional[dict] = None      # ... n_src, rows / largest count / chunks before and after the merge; both None without
     xs: Optional["CrossSections"] = None           # the cross sections of the run (what ``solve_transient`` starts from)
+    krylov: Optional[dict] = None                  # krylov=...: cycles, vectors, sweeps, the last cycle's vectors / breakdown / resnorm; None without
 
     def to_cells(self, a):
         """An array per source region (``phi``, ``volumes``, ``current``) spread over the mesh's cells: ``a[source_region]``; ``a``
@@ -446,8 +477,10 @@ def _volume_correction(tg, volume_correction):
 
 
 def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme="flat", adjoint=False,
-           boundary=None, reproducible=False, precision="double", regions=None, cmfd=None, volume_correction=None, source_regions=None):
+           boundary=None, reproducible=False, precision="double", regions=None, cmfd=None, volume_correction=None, source_regions=None,
+           krylov=None):
     acc = _as_cmfd(cmfd)
+    kry = _as_krylov(krylov)
     vc = _volume_correction(tg, volume_correction)
     if source_regions is not None:
         for on, what in ((scheme == "linear", 'scheme="linear" (centroids and the C matrices are per cell)'),
@@ -516,6 +549,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         sv.set_precision(precision)
     if vc is not None:  # (refused by the library on a shard's track set)
         sv.set_volume_correction(vc)
+    if kry is not None:  # (last: refused by the library, in a message that names both, together with what it does not run with)
+        sv.set_krylov(kry.m, kry.tol_lin)
     r = sv.run(mode, int(max_iter), float(tol_k), float(tol_flux))
     f = sv.fetch(r["iterations"])
     mom = sv.fetch_moments() if linear else dict(flux_moments=None, flux_gradient=None)
@@ -541,6 +576,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         bnd.update(volume_correction=vc, cell_area=v.pop("area"), volume_factor=v.pop("factor"), volume_correction_info=v)
     if sr is not None:
         bnd.update(source_region=sr, source_region_info=sv.source_region_info())
+    if kry is not None:
+        bnd["krylov"] = sv.krylov_info()
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
@@ -586,19 +623,23 @@ def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar
 def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, source, polar="TY3", azim_weights="exact",
                        tol_k=1e-8, tol_flux=1e-7, max_iter=1000, device: int = 0, scheme: str = "flat", adjoint: bool = False,
                        boundary: Optional["SolverBoundary"] = None, reproducible: bool = False, precision: str = "double",
-                       regions=None, cmfd=None, volume_correction=None, source_regions=None) -> SolverResult:
+                       regions=None, cmfd=None, volume_correction=None, source_regions=None, krylov=None) -> SolverResult:
     """Source iteration with the external volumetric source ``source`` [n_cells, G] (k ≡ 1; fission multiplies).  Stops when
     the relative L2 change of φ is below ``tol_flux``.  Arguments as ``solve_eigenvalue``; with ``adjoint=True`` ``source`` is the
     adjoint source S† (for instance a detector cross section) and ``phi`` the importance φ†: Σ V S† φ = Σ V S φ†.  ``boundary``: a
     ``SolverBoundary``, here also with an incoming flux per side and group (``source`` may then be zero: a run driven from the
     boundary).  ``reproducible``, ``precision``, ``regions``, ``cmfd``, ``volume_correction``, ``source_regions``: as for ``solve_eigenvalue``
-    (``cmfd`` not together with an incoming flux; with ``source_regions`` the ``source`` is [n_src, G])."""
+    (``cmfd`` not together with an incoming flux; with ``source_regions`` the ``source`` is [n_src, G]).  ``krylov``: True or a
+    ``Krylov`` — restarted GMRES cycles in place of plain iterations (``rt_solver_set_krylov``): the same fixed point in fewer sweeps
+    where the scattering ratio is near one; ``iterations`` and ``max_iter`` count sweeps, Krylov vectors included, and the result
+    carries ``krylov``.  Not together with ``sigma_s1``, ``scheme="linear"``, ``precision="single"``, ``reproducible=True``, ``regions``
+    / ``cmfd``, ``source_regions``, ``volume_correction`` or an incoming boundary flux (``RtError``)."""
     q = np.asarray(source, np.float64)
     G = xs.n_groups
     if (q.ndim == 0 or q.shape == (G,)) and source_regions is None:  # (with source_regions: _solve broadcasts over its n_src)
         q = np.broadcast_to(q, (tg.mesh.num_cells, G))
     return _solve(tg, xs, cell_material, _capi.DeviceSolver.FIXED_SOURCE, q, polar, azim_weights, tol_k, tol_flux, max_iter, device, scheme,
-                  adjoint, boundary, reproducible, precision, regions, cmfd, volume_correction, source_regions)
+                  adjoint, boundary, reproducible, precision, regions, cmfd, volume_correction, source_regions, krylov)
 
 
 # ---- adjoint-weighted integrals ------------------------------------------------------------------------------------------------
@@ -751,10 +792,11 @@ class TransientResult:
     k_eff: float                  # k0: the eigenvalue the transient is normalised with
     ms_per_step: np.ndarray       # [n_steps]: HIP-event time of every step
     phi_history: Optional[np.ndarray] = None  # keep_flux=True: [n_steps + 1, n_cells, G]
+    krylov_vectors: Optional[np.ndarray] = None  # krylov=...: [n_steps], the Krylov vectors among every step's inner iterations; None without
 
 
 def solve_transient(result: SolverResult, kinetics: Kinetics, dt, n_steps: int, events=(), tol=1e-8, max_inner=200, settle_tol=1e-9,
-                    settle_max_iter=500, keep_flux=False) -> TransientResult:
+                    settle_max_iter=500, keep_flux=False, krylov=None) -> TransientResult:
     """Continues the eigenvalue ``result`` (``solve_eigenvalue``; its device solver does the work) in time: ``n_steps`` implicit-Euler
     steps of ``dt`` (a float, or a sequence of ``n_steps`` values) with the delayed-neutron data ``kinetics``.  ``events``: a sequence of
     ``(step_index, CrossSections)`` — the cross sections (same materials and groups) that hold from that step on, applied before it.
@@ -763,7 +805,9 @@ def solve_transient(result: SolverResult, kinetics: Kinetics, dt, n_steps: int, 
     A step that stops at ``max_inner`` is not an error: ``TransientResult.converged`` says which steps met ``tol`` (near critical, a
     step after a reactivity change can take thousands of unaccelerated iterations).  A cell that no track crosses (``volumes == 0``)
     enters no sum and iterates on its own — in a fissile material without bound over many steps — so ``phi``, ``phi_history`` and
-    ``precursors`` may hold inf there: mask with ``result.volumes > 0``.
+    ``precursors`` may hold inf there: mask with ``result.volumes > 0``.  ``krylov``: True or a ``Krylov`` — every step's inner
+    iterations are restarted-GMRES cycles (``rt_solver_set_krylov``; ``inner_iterations`` and ``max_inner`` count sweeps, Krylov vectors
+    included, ``krylov_vectors`` how many of them were); None: plain iterations, whatever an earlier call left set.
     ``ValueError`` for an adjoint result, a fixed-source result, a host result without a device solver, a result without its cross
     sections, data that does not fit."""
     if not isinstance(kinetics, Kinetics):
@@ -796,8 +840,13 @@ def solve_transient(result: SolverResult, kinetics: Kinetics, dt, n_steps: int, 
                          "set result.xs to the CrossSections of its run")
     if getattr(result, "source_region", None) is not None:
         raise ValueError("source_regions together with a transient is not supported")
+    kry = _as_krylov(krylov)
+    if kry is not None:
+        sv.set_krylov(kry.m, kry.tol_lin)
+    elif hasattr(_capi.lib(), "rt_solver_fetch_krylov") and sv.krylov_info()["m"]:  # (an earlier call's: a solver without it takes no new call)
+        sv.set_krylov(0)
     r0 = sv.transient_begin(*arrays, settle_max_iter=settle_max_iter, settle_tol=settle_tol)
-    times, prod, inner, res, ms, conv = [0.0], [1.0], [], [], [], []
+    times, prod, inner, res, ms, conv, kv = [0.0], [1.0], [], [], [], [], []
     hist = [np.array(result.phi, np.float64)] if keep_flux else None
     try:
         for n in range(n_steps):
@@ -807,6 +856,8 @@ def solve_transient(result: SolverResult, kinetics: Kinetics, dt, n_steps: int, 
             r = sv.transient_step(dts[n], max_inner, tol)
             times.append(times[-1] + float(dts[n])); prod.append(r["production"]); inner.append(r["iterations"]); res.append(r["residual"])
             ms.append(r["device_ms"]); conv.append(r["converged"])
+            if kry is not None:
+                kv.append(sv.krylov_info()["vectors"])
             if keep_flux:
                 hist.append(sv.transient_fetch()["phi"])
         f = sv.transient_fetch()
@@ -819,4 +870,5 @@ def solve_transient(result: SolverResult, kinetics: Kinetics, dt, n_steps: int, 
     return TransientResult(times=np.asarray(times), production=np.asarray(prod), inner_iterations=np.asarray(inner, np.int64),
                            residual=np.asarray(res), converged=np.asarray(conv, bool), phi=f["phi"], precursors=f["precursors"], settle_iterations=r0["iterations"],
                            settle_residual=r0["residual"], k_eff=r0["k_eff"], ms_per_step=np.asarray(ms),
-                           phi_history=np.stack(hist) if keep_flux else None)
+                           phi_history=np.stack(hist) if keep_flux else None,
+                           krylov_vectors=np.diff(np.asarray([0] + kv, np.int64)) if kry is not None else None)

@@ -126,6 +126,9 @@ def main():
                     help="after the forward runs, N time steps of a transient (rt_solver_transient_*) per --transient-dt value")
     ap.add_argument("--transient-dt", default="1e-3,1e-2,1e-1", help="the Δt values of --transient, in seconds")
     ap.add_argument("--transient-tol", type=float, default=1e-8, help="the inner tolerance of --transient")
+    ap.add_argument("--krylov", type=int, default=0, metavar="M",
+                    help="with --transient: every step in restarted-GMRES cycles of at most M Krylov vectors (rt_solver_set_krylov)")
+    ap.add_argument("--krylov-tol", type=float, default=1e-2, help="tol_lin of --krylov")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -215,18 +218,28 @@ def main():
         rows = []
         for dt_s in (float(v) for v in a.transient_dt.split(",")):
             sv.run(0, 20000, 1e-10, 1e-9)
+            if a.krylov:
+                sv.set_krylov(a.krylov, a.krylov_tol)
             t0 = time.perf_counter()
             r0 = sv.transient_begin(iv, beta, lam, chid, settle_max_iter=500, settle_tol=1e-9)
             settle_host = (time.perf_counter() - t0) * 1e3
             sv.transient_set_xs(xs.sigma_t, xs.sigma_s, nf2, xs.chi)
-            inner, ms, prod = [], [], []
+            inner, ms, prod, vectors = [], [], [], []
             for _ in range(a.transient):
                 r = sv.transient_step(dt_s, 20000, a.transient_tol)
                 inner.append(r["iterations"]); ms.append(r["device_ms"]); prod.append(r["production"])
+                if a.krylov:
+                    vectors.append(sv.krylov_info()["vectors"])
+            ki = sv.krylov_info() if a.krylov else None
             sv.transient_end()
+            if a.krylov:
+                sv.set_krylov(0)
             rows.append(dict(dt=dt_s, settle_iterations=r0["iterations"], settle_ms_events=r0["device_ms"], settle_ms_host=settle_host,
                              ms_per_step=float(np.mean(ms)), inner_per_step=float(np.mean(inner)), inner=inner,
                              ms_per_inner=float(np.sum(ms) / max(1, np.sum(inner))), production_last=prod[-1]))
+            if a.krylov:  # (the Krylov vectors among every step's sweeps; the basis held, in bytes)
+                rows[-1].update(krylov_m=a.krylov, krylov_vectors=np.diff([0] + vectors).tolist(), krylov_cycles=ki["cycles"],
+                                krylov_vector_length=ki["n"], krylov_basis_bytes=8 * ki["basis_doubles"])
         out["transient"] = rows
     if a.reproducible:  # (the delta buffer written and read once per pass, and k_sweep_reduce behind every pass)
         import torch
