@@ -489,6 +489,33 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              with the continuous value 4π/3 of ∫ Ωx² dΩ, as the scalar term uses 4π
  * Iteration    J⁰ = 0; k, residual, stopping rule and normalisation are unchanged (eigenvalue mode scales J with φ)
  *
+ * P2 / P3 scattering, rt_solver_set_scatter_pn.  sigma_sl[l − 1][m][g'][g], l = 1 .. L with L = 2 or 3, continues the convention:
+ * Σs(g'→g, μ0) = (1/4π) Σ_{l=0..L} (2l+1) Σs_l[g'→g] P_l(μ0), Σs_0 = sigma_s, Σs_1 = the sigma_s1 above.  Every entry must be finite
+ * with |Σs_l[g'→g]| <= Σs0[g'→g].  Fission and the external source stay isotropic.  All state and arithmetic are FP64.
+ * Harmonics    real spherical harmonics, Schmidt semi-normalised: Σ_m R_lm(Ω) R_lm(Ω') = P_l(Ω·Ω').  The 2-D angular flux is even
+ *              in cos θ, so only those with l + m even survive: NM = 6 up to l = 2, 10 up to l = 3.  With s = sin θ, μ² = 1 − s²,
+ *              R_lm = a_lm(θ) · az(φ), az of azimuthal order k = |m|: cos kφ (m >= 0) or sin kφ (m < 0), in this order:
+ *                (l, m)  (0,0)  (1,±1)  (2,0)        (2,±2)      (3,±1)             (3,±3)
+ *                a_lm    1      s       (3μ² − 1)/2  (√3/2) s²   √(3/8) s (5μ² − 1)  √(5/8) s³
+ *                k       0      1       0            2           1                  3
+ * Moments      φ_lm = ∫ R_lm ψ dΩ;  φ_00 = φ,  (φ_11, φ_1−1) = (Jx, Jy)
+ * Source       q_{e,g}(Ω) = Σ_lm R_lm(Ω) q_lm,{e,g}: q_00 the isotropic q_{e,g} above, and for l >= 1
+ *              q_lm,{e,g} = ((2l+1)/4π) Σ_g' Σs_l[g'→g] φ_lm,{e,g'}
+ * Ratios       per cell, component c = g·P + p and azimuthal index j = 0 .. 2L (j = 0: "1", j = 2k − 1: cos k, j = 2k: sin k):
+ *              h_j[e][c] = Σ_{(l,m) on j} a_lm(θ_p) q_lm,{e,g} / Σt_g   (h_0 depends on p through (2, 0))
+ * Sweep        traversal (track u, d = ±1): the same recurrence with the source ratio h_0 + Σ_{j>=1} d^k f_j(u) h_j, f_j(u) = cos kφ_u
+ *              or sin kφ_u; it tallies T_j[e][c] = Σ w d^k f_j(u) Δψ over both directions (T_0 = T, T_1 = Tx, T_2 = Ty)
+ * Fold         φ_lm,{e,g} = (4π/(2l+1)) q_lm,{e,g} / Σt_g + Σ_p ω_p sin θ_p a_lm(θ_p) T_j(l,m)[e][g·P + p] / (Σt_g V_e)
+ *              (V_e = 0: first term only), with the continuous value 4π/(2l+1) of ∫ R_lm² dΩ, as the scalar and P1 folds use
+ * Iteration    φ⁰_lm = 0 for l >= 1; k, residual, stopping rule and normalisation use φ only (eigenvalue mode scales every moment
+ *              with φ).  P1 is the L = 1 case of exactly this: order 1 takes rt_solver_set_scatter_p1's path unchanged
+ * Works with   eigenvalue and fixed-source runs, adjoint mode (every Σs_l transposed), rt_solver_set_boundary, the stepwise calls
+ *              (rt_solver_pn_pointers), both polar families, every call that leaves (ℓ, cell) rows (kinds 1 and 2)
+ * Refused      (RT_ERR_INVALID, by whichever setter comes second, in a message that names both) the linear source, the
+ *              single-precision sweep, the reproducible tallies, region currents and the coarse-mesh acceleration, source regions,
+ *              the volume correction, restarted GMRES, transients, a shard's track set; a sweep that would read rows of kind 0
+ *              is refused by rt_sweep.  rt_solver_bilinear keeps its scalar-only meaning
+ *
  * Linear source (LS-MOC), rt_solver_set_linear_source.  The source of cell e is Q(r) = q_{e,g} + q⃗_{e,g}·(r − r_c,e) instead of
  * the flat q_{e,g}, and the characteristic equation is still solved exactly along every segment.  A traversal is
  * (track u, d = ±1) and moves along d (cs, sn) = d (cos φ_u, sin φ_u); lengths ℓ are 2-D, Σ_c = Σt_g / sin θ_p.
@@ -918,6 +945,21 @@ int32_t rt_solver_fetch(rt_solver *solver, double *phi, double *volumes, double 
  * isotropic scattering, which runs exactly the kernels of a solver that never had any.  RT_ERR_INVALID when an entry is not
  * finite or exceeds Σs0 in magnitude, or with a run open (the solver keeps what it had). */
 int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1);
+/* Scattering up to Legendre order `order` (see "P2 / P3 scattering" above) for the following runs: sigma_sl [order][M][G][G] (host
+ * memory, copied), l = 1 .. order.  order 0 or a NULL table: back to isotropic scattering; order 1: rt_solver_set_scatter_p1 with
+ * sigma_sl[0], unchanged; order 2 or 3: the P2 / P3 sweep.  A solver that never sets an order >= 2 launches exactly what it always
+ * did.  RT_ERR_INVALID for another order, an entry that is not finite or exceeds Σs0 in magnitude, with a run open, or together
+ * with an option of the list above (the solver keeps what it had). */
+int32_t rt_solver_set_scatter_pn(rt_solver *solver, int32_t order, const double *sigma_sl);
+/* After a run with order 2 or 3: the angular moments out [n_cells][G][NM] (NM = 6 or 10; slot 0 is φ) and their (l, m) as
+ * lm [NM][2]; either may be NULL.  (rt_solver_fetch_moments is the linear source's.)  RT_ERR_INVALID before a run, or when that
+ * run had an order below 2. */
+int32_t rt_solver_fetch_angular_moments(rt_solver *solver, double *out, int32_t *lm);
+/* Device addresses ptrs_dev[3] and element counts lens[3] (doubles; either may be NULL) of an open run with order 2 or 3, beside
+ * rt_solver_pointers ([2] there is NULL in such a run): [0] the moments [n_cells·G·NM] (slot 0 of every (cell, group) unused: φ is
+ * rt_solver_pointers' [3]), [1] the sweep's ratios h [n_cells·G·P·(2L + 1)], [2] the tallies T_1 .. T_2L [n_cells·G·P·2L] (T_0 is
+ * rt_solver_pointers' [1]).  NULL / 0 outside such a run.  Does not wait. */
+int32_t rt_solver_pn_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
 /* Adjoint mode (see above) on (non-zero) or off for the following runs: rebuilds the device material table, and the first-moment
  * table when first-moment scattering is set, from host copies.  Off restores the forward tables; a solver that never had it on
  * launches exactly what it always did.  RT_ERR_INVALID with a run open (rt_solver_begin without rt_solver_end) or after the
@@ -941,8 +983,8 @@ int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision);
  * completed a run and have none open, be bound to the same tracks at the same segmentation and agree in G, M and the number of
  * cells; `adjoint == forward` is allowed (plain ⟨φ, Aφ⟩).  RT_ERR_INVALID otherwise, or when an entry of A is not finite. */
 int32_t rt_solver_bilinear(rt_solver *adjoint, rt_solver *forward, int32_t n_forms, const double *A, double *out, double *out_cell);
-/* The net current J [n_cells][G][2] (x, y) of the last run.  RT_ERR_INVALID before a run, or when that run had no
- * first-moment scattering. */
+/* The net current J [n_cells][G][2] (x, y) of the last run — with order 2 or 3 the (1, ±1) moments.  RT_ERR_INVALID before a run,
+ * or when that run had no first-moment scattering. */
 int32_t rt_solver_fetch_current(rt_solver *solver, double *J);
 /* Linear source (see above) on (non-zero) or off for the following runs.  Off runs exactly the kernels of a solver that never
  * had it on.  The first switching-on computes the cells' geometry on the device.  RT_ERR_INVALID while first-moment scattering

@@ -326,6 +326,29 @@ function solver_set_precision!(hs::Ptr{Cvoid}, single::Bool=true)
     return nothing
 end
 
+# Scattering up to Legendre order `order` for the following runs of an `rt_solver` handle `hs` (include/rt_segmentize.h, "P2 / P3
+# scattering"): `sigma_sl` is a column-major Array{Float64,4} of size (n_groups, n_groups, n_materials, order) — the library's
+# [l − 1][m][g'][g] — for l = 1 .. order; order 0 (or `nothing`) is isotropic scattering again, 1 the first-moment path, 2 and 3 the
+# P2 / P3 sweep.  Refused together with the linear source, the single-precision sweep, the reproducible tallies, regions, source
+# regions, the volume correction, restarted GMRES and on a shard's track set.
+function solver_set_scatter_pn!(hs::Ptr{Cvoid}, order::Integer, sigma_sl::Union{Nothing,Array{Float64,4}}=nothing)
+    rc = (order == 0 || sigma_sl === nothing) ? ccall((:rt_solver_set_scatter_pn, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}), hs, 0, C_NULL) :
+                                                 ccall((:rt_solver_set_scatter_pn, LIB), Int32, (Ptr{Cvoid}, Int32, Ptr{Float64}), hs, order, sigma_sl)
+    rc == 0 || error("rt_solver_set_scatter_pn failed: " * lasterror())
+    return nothing
+end
+
+# After a run of `hs` with order 2 or 3: the angular moments as a column-major Array{Float64,3} of size (NM, n_groups, n_cells) —
+# the library's [cell][group][NM], NM = 6 or 10, slot 1 is φ — and their (l, m) as an Array{Int32,2} of size (2, NM).
+function solver_fetch_angular_moments(hs::Ptr{Cvoid}, n_cells::Integer, n_groups::Integer, order::Integer)
+    nm = order == 2 ? 6 : 10
+    out = Array{Float64,3}(undef, nm, n_groups, n_cells)
+    lm = Array{Int32,2}(undef, 2, nm)
+    rc = ccall((:rt_solver_fetch_angular_moments, LIB), Int32, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Int32}), hs, out, lm)
+    rc == 0 || error("rt_solver_fetch_angular_moments failed: " * lasterror())
+    return out, lm
+end
+
 # Region currents for the following runs of an `rt_solver` handle `hs` (include/rt_segmentize.h, "Regions"): `cell_region` holds a
 # 0-based region id below `n_regions` <= 127 for every cell; an empty vector switches them off.  Refused together with the
 # reproducible tallies, the single-precision sweep and on a shard's track set.

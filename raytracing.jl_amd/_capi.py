@@ -31,6 +31,7 @@ SYMBOLS = (
     "rt_solver_set_linear_source", "rt_solver_fetch_geometry", "rt_solver_fetch_moments",
     "rt_solver_ls_geometry", "rt_solver_ls_geometry_pointer",
     "rt_solver_fetch_current",
+    "rt_solver_set_scatter_pn", "rt_solver_fetch_angular_moments", "rt_solver_pn_pointers",
     "rt_solver_begin", "rt_solver_step_sweep", "rt_solver_step_fold", "rt_solver_end", "rt_solver_pointers",
     "rt_solver_set_adjoint", "rt_solver_bilinear", "rt_solver_set_reproducible", "rt_solver_set_precision",
     "rt_solver_set_boundary", "rt_solver_fetch_boundary", "rt_solver_boundary_pointers",
@@ -291,6 +292,16 @@ def lib():
     L.rt_solver_boundary_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
     L.rt_solver_pointers.restype = C.c_int32
     L.rt_solver_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
+    try:
+        L.rt_solver_set_scatter_pn.restype = C.c_int32
+        L.rt_solver_set_scatter_pn.argtypes = [_vp, C.c_int32, _dp]
+        L.rt_solver_fetch_angular_moments.restype = C.c_int32
+        L.rt_solver_fetch_angular_moments.argtypes = [_vp, _dp, _ip]
+        L.rt_solver_pn_pointers.restype = C.c_int32
+        L.rt_solver_pn_pointers.argtypes = [_vp, C.POINTER(_vp), _lp]
+    except AttributeError:
+        if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
+            raise
     try:
         L.rt_solver_set_regions.restype = C.c_int32
         L.rt_solver_set_regions.argtypes = [_vp, C.c_int32, _ip]
@@ -862,6 +873,41 @@ class DeviceSolver:
         if s1.shape != (self.M, self.G, self.G):
             raise ValueError("sigma_s1 must have shape [M, G, G]")
         _check(lib().rt_solver_set_scatter_p1(self._h, s1.ctypes.data_as(_dp)))
+
+    def set_scatter_pn(self, order, sigma_sl=None):
+        """``rt_solver_set_scatter_pn``: scattering up to Legendre order ``order`` for the following runs, ``sigma_sl`` [order, M, G, G]
+        (l = 1 .. order, from g' to g).  Order 0 or None: isotropic again; 1: ``set_scatter_p1``'s path; 2, 3: the P2 / P3 sweep."""
+        order = int(order)
+        if order == 0 or sigma_sl is None:
+            _check(lib().rt_solver_set_scatter_pn(self._h, 0, None))
+            self.pn_order = 0
+            return
+        sl = np.ascontiguousarray(sigma_sl, np.float64)
+        if sl.shape != (order, self.M, self.G, self.G):
+            raise ValueError("sigma_sl must have shape [order, M, G, G]")
+        _check(lib().rt_solver_set_scatter_pn(self._h, order, sl.ctypes.data_as(_dp)))
+        self.pn_order = order
+
+    def fetch_angular_moments(self) -> dict:
+        """``rt_solver_fetch_angular_moments``: after a run with order 2 or 3 ``angular_moments`` [n_cells, G, NM] (slot 0 is φ) and
+        ``moment_lm`` [NM, 2], the (l, m) of every slot (NM = 6 or 10).  (``fetch_moments`` is the linear source's.)"""
+        lm = np.zeros((10, 2), np.int32)
+        _check(lib().rt_solver_fetch_angular_moments(self._h, None, lm.ctypes.data_as(_ip)))
+        nm = 6 if not lm[6:].any() else 10
+        out = np.empty((self.n_cells, self.G, nm))
+        _check(lib().rt_solver_fetch_angular_moments(self._h, out.ctypes.data_as(_dp), None))
+        return dict(angular_moments=out, moment_lm=lm[:nm].copy())
+
+    def pn_pointers(self) -> dict:
+        """``rt_solver_pn_pointers``: device addresses (0: none) of ``moments`` [n_cells, G, NM], ``ratios`` [n_cells, G·P, 2L + 1] and
+        ``tallies`` [n_cells, G·P, 2L] of an open run with order 2 or 3, and their element counts under ``lens``."""
+        ptrs = (_vp * 3)()
+        lens = (C.c_int64 * 3)()
+        _check(lib().rt_solver_pn_pointers(self._open(), ptrs, lens))
+        names = ("moments", "ratios", "tallies")
+        out = {k: ptrs[i] or 0 for i, k in enumerate(names)}
+        out["lens"] = {k: int(lens[i]) for i, k in enumerate(names)}
+        return out
 
     def set_adjoint(self, on=True):
         """``rt_solver_set_adjoint``: the adjoint (transposed) problem for the following runs (False: the forward one again)."""

@@ -325,6 +325,11 @@ struct DSweep {
     const RT_G int32_t *if_region;    // [n_cells] region of every cell, 0 .. if_R − 1
     RT_G double *if_S;                // [(if_R + 1)][(if_R + 1)][G]; index if_R: outside the track
     int32_t if_R, if_pad;
+    // P2 / P3 scattering (k_sweep_pn, rt_sweep_pn.hip; rt_solver with rt_solver_set_scatter_pn): M = the order, NT = 2M + 1 ratios per
+    // (cell, component) — h_0, then (cos k, sin k) of k = 1 .. M — and the 2M tallies beside T_0 (which goes to `phi`)
+    const RT_G double *pn_h;          // [n_cells * G][2M + 1]
+    RT_G double *pn_t;                // [n_cells * G][2M]
+    int32_t pn_M, pn_pad;
 };
 
 // The coarse-mesh step of rt_solver (rt_cmfd.hip; rt_solver_set_cmfd): what its five kernels read and write, by value.
@@ -426,6 +431,9 @@ struct SweepLoan {
     const int32_t *region = nullptr;  // region currents (rt_solver_set_regions): the cells' regions [n_cells] (DSweep if_region),
     double *iface_S = nullptr;        // the sweep's tally S [(R + 1)][(R + 1)][components], zeroed by every sweep (DSweep if_S),
     int32_t n_regions = 0;            // and R (0: off)
+    int32_t pn_M = 0;                 // PN: the order (2, 3), the solver's ratios [n_cells · G][2M + 1] and higher tallies [n_cells · G][2M]
+    const double *pn_h = nullptr;     // (DSweep pn_h, pn_t)
+    double *pn_t = nullptr;
     // volume correction (rt_solver_set_volume_correction): the solver's ℓ' of every row slot (DSweep ell_rows in place of sw_ell), made
     const double *vc_ell = nullptr;   // from the rows `vc_rows` as they stood at generation `vc_gen` (rt_tracks::sw_rows_gen)
     rtsweep::SweepRows vc_rows = rtsweep::SweepRows::Records;
@@ -706,6 +714,7 @@ int ensure_rows_from_compact(rt_tracks *t);  // rt_sweep.hip
 // rt_sweep_f32.hip: one pass of the single-precision sweep kernel over `gp` components from a.g0 (a.use_lds: the tallies' LDS copy)
 int launch_sweep_f32(const rt::DSweep &a, int gp, size_t smem, int waves, unsigned blocks, hipStream_t s);
 int launch_sweep_iface(const rt::DSweep &a, SweepMode mode, size_t smem, int waves, unsigned blocks, hipStream_t s);  // rt_sweep_iface.hip
+int launch_sweep_pn(const rt::DSweep &a, size_t smem, int waves, unsigned blocks, hipStream_t s);  // rt_sweep_pn.hip
 // rt_cmfd.hip: the LDS k_cmfd_solve asks for (0: does not fit; *resident: all G factors live there), and the coarse step of one fold
 size_t cmfd_solve_lds(int32_t R, int32_t G, bool *resident);
 int launch_cmfd_step(rt::DCmfd c, int32_t n_items, unsigned cblocks, hipStream_t s);

@@ -8,6 +8,10 @@
 // mode: k_solver_source_p1 (q1/Σt from the net current J, and its sin θ_p multiple of every component into the sweep's xs1
 // array) after k_solver_source, and k_solver_fold_p1 (J from the first-moment tallies) after k_solver_fold.  Without it the
 // solver launches what it always did.
+// With P2 / P3 scattering (rt_solver_set_scatter_pn, order 2 or 3) likewise two more kernels, and the sweep runs k_sweep_pn
+// (rt_sweep_pn.hip): k_solver_source_pn (q_lm/Σt of the surviving moments from a {Σt, Σs_l} table, and the 2L + 1 ratios of every
+// component into an array of the solver's) after k_solver_source, and k_solver_fold_pn (the higher moments from the 2L + 1 tallies)
+// after k_solver_fold.  The moments, ratios and tallies exist only while the option is set; order 1 is the path above, unchanged.
 // With the linear source (rt_solver_set_linear_source) likewise two more kernels, and the sweep runs in its linear-source mode:
 // k_solver_source_ls (q⃗ = C⁻¹ s⃗ from the flux moments φ⃗, and q⃗ / (Σt_g Σ_c) of every component into the sweep's xs1 array) and
 // k_solver_fold_ls (φ⃗ from the moment tallies).  The cells' geometry (centroids, C, C⁻¹, the tracks' end points) is computed once,
@@ -161,6 +165,83 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_fold_p1(const int32_t *_
     }
     J[2 * i] = kFourPiOverThree * q1r[2 * i] + (V > 0.0 ? ax / (st * V) : 0.0);
     J[2 * i + 1] = kFourPiOverThree * q1r[2 * i + 1] + (V > 0.0 ? ay / (st * V) : 0.0);
+}
+
+// ---- P2 / P3 scattering (rt_solver_set_scatter_pn) ----------------------------------------------------------------------------------
+// The moments with l + m even in the header's order, NM = 6 up to l = 2 and 10 up to l = 3:
+//   i       0      1      2       3      4      5       6      7       8      9
+//   (l, m)  (0,0)  (1,1)  (1,−1)  (2,0)  (2,2)  (2,−2)  (3,1)  (3,−1)  (3,3)  (3,−3)
+//   j       0      1      2       0      3      4       1      2       5      6        (the sweep's azimuthal index)
+__device__ __forceinline__ int pn_l(int i) { return i == 0 ? 0 : (i < 3 ? 1 : (i < 6 ? 2 : 3)); }
+__device__ __forceinline__ int pn_j(int i) { return i < 3 ? i : (i == 3 ? 0 : (i < 6 ? i - 1 : (i < 8 ? i - 5 : i - 3))); }
+// a_lm(θ) of moment i from s = sin θ (μ² = 1 − s²)
+__device__ __forceinline__ double pn_a(int i, double s) {
+    const double mu2 = 1.0 - s * s;
+    switch (i) {
+    case 0: return 1.0;
+    case 1: case 2: return s;
+    case 3: return 0.5 * (3.0 * mu2 - 1.0);
+    case 4: case 5: return 0.8660254037844386 * (s * s);            // √3 / 2
+    case 6: case 7: return 0.6123724356957945 * s * (5.0 * mu2 - 1.0);  // √(3/8)
+    default: return 0.7905694150420949 * (s * s * s);               // √(5/8)
+    }
+}
+// higher-moment table: per material, stride G·(1 + L·G) doubles — Σt[G], then Σs_l[G][G] (from g' to g) for l = 1 .. L
+__device__ __forceinline__ const double *mat_row_pn(const double *tab, int32_t m, int32_t G, int32_t L) { return tab + (int64_t)m * G * (1 + L * G); }
+
+// q_lm/Σt = ((2l+1)/4π) Σ_g' Σs_l[g'→g] φ_lm,g' / Σt_g of every (cell, group) (one thread each) into `qr` [n_cells][G][NM] (slot 0
+// unused), and the sweep's 2L + 1 ratios of every component into `h` [n_cells][G·P][2L + 1]: h_0 = the isotropic q/Σt that
+// k_solver_source left in `xs` plus the (2, 0) term, h_j = Σ_{(l,m) on j} a_lm(θ_p) q_lm/Σt.
+__global__ __launch_bounds__(kSolveBlock) void k_solver_source_pn(const int32_t *__restrict__ mat, const double *__restrict__ tab, const double *__restrict__ mom,
+                                                                  const double *__restrict__ pol, const double *__restrict__ xs, int32_t n_cells,
+                                                                  int32_t G, int32_t P, int32_t L, double *__restrict__ qr, double *__restrict__ h) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n_cells * G) return;
+    const int64_t e = i / G;
+    const int32_t g = (int32_t)(i - e * G);
+    const int32_t NM = L == 2 ? 6 : 10, NT = 2 * L + 1;
+    const double *X = mat_row_pn(tab, mat[e], G, L);
+    const double *me = mom + e * G * NM;
+    double r[10];
+    for (int32_t k = 1; k < NM; ++k) {
+        const int32_t l = pn_l(k);
+        const double *sl = X + G + (int64_t)(l - 1) * G * G;
+        double s = 0.0;
+        for (int32_t gp = 0; gp < G; ++gp) s += sl[gp * G + g] * me[gp * NM + k];
+        r[k] = (2 * l + 1) / kFourPi * s / X[g];
+        qr[i * NM + k] = r[k];
+    }
+    for (int32_t p = 0; p < P; ++p) {
+        const int64_t c = e * G * P + (int64_t)g * P + p;
+        double hv[7] = {xs[2 * c + 1], 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int32_t k = 1; k < NM; ++k) hv[pn_j(k)] += pn_a(k, pol[p]) * r[k];
+        for (int32_t j = 0; j < NT; ++j) h[c * NT + j] = hv[j];
+    }
+}
+
+// φ_lm of every (cell, group) (one thread each), l >= 1, from the sweep's tallies — T_0 in `t0` [n_cells][G·P], T_1 .. T_2L in `tj`
+// [n_cells][G·P][2L] —: φ_lm = (4π/(2l+1)) q_lm/Σt + Σ_p ω_p sin θ_p a_lm(θ_p) T_j(l,m) / (Σt V); the first term alone where V = 0
+__global__ __launch_bounds__(kSolveBlock) void k_solver_fold_pn(const int32_t *__restrict__ mat, const double *__restrict__ tab, const double *__restrict__ vol,
+                                                                const double *__restrict__ pol, const double *__restrict__ t0, const double *__restrict__ tj,
+                                                                const double *__restrict__ qr, int32_t n_cells, int32_t G, int32_t P, int32_t L,
+                                                                double *__restrict__ mom) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n_cells * G) return;
+    const int64_t e = i / G;
+    const int32_t g = (int32_t)(i - e * G);
+    const int32_t NM = L == 2 ? 6 : 10, NF = 2 * L;
+    const double V = vol[e];
+    const double st = mat_row_pn(tab, mat[e], G, L)[g];
+    const int64_t c0 = e * G * P + (int64_t)g * P;
+    for (int32_t k = 1; k < NM; ++k) {
+        const int32_t l = pn_l(k), j = pn_j(k);
+        double acc = 0.0;
+        for (int32_t p = 0; p < P; ++p) {
+            const double T = j == 0 ? t0[c0 + p] : tj[(c0 + p) * NF + (j - 1)];
+            acc += pol[P + p] * pn_a(k, pol[p]) * T;  // (pol[P + p]: ω_p sin θ_p)
+        }
+        mom[i * NM + k] = kFourPi / (2 * l + 1) * qr[i * NM + k] + (V > 0.0 ? acc / (st * V) : 0.0);
+    }
 }
 
 // ---- linear source ---------------------------------------------------------------------------------------------------------
@@ -562,6 +643,13 @@ struct rt_solver {
     std::vector<double> h_nf, h_chi, h_s1;
     bool adjoint = false;
     DevBuf<double> tab1, J, q1r;     // table (see mat_row_p1); net current and q1/Σt [n_cells][G][2]
+    // P2 / P3 scattering (rt_solver_set_scatter_pn): the order L while mode == PN (the open run's: run_pn, the last completed one's:
+    // ran_pn), Σs_l as given [L][M][G][G] (the adjoint's transposes are made from it), the table (see mat_row_pn); made by
+    // rt_solver_begin while the option is set: the moments φ_lm and q_lm/Σt [n_cells][G][NM], the sweep's ratios [n_cells][G·P][2L + 1]
+    // and its higher tallies [n_cells][G·P][2L]
+    int32_t pn_order = 0, run_pn = 0, ran_pn = 0;
+    std::vector<double> h_sl;
+    DevBuf<double> pn_tab, pn_mom, pn_qr, pn_h, pn_t;
     // the source's shape as the setters leave it, of the open run, of the last completed run (a mode switched off keeps its table / geometry)
     SweepMode mode = SweepMode::Flat, run_mode = SweepMode::Flat, ran_mode = SweepMode::Flat;
     // linear source (rt_solver_set_linear_source)
@@ -731,6 +819,32 @@ std::vector<double> solver_table_p1(const rt_solver *S, const double *sigma_s1, 
             for (int32_t b = 0; b < G; ++b) X[G + a * G + b] = adjoint ? s1[b * G + a] : s1[a * G + b];
     }
     return tab;
+}
+
+// The higher-moment table (see mat_row_pn) from the host copies, sigma_sl [L][M][G][G]; adjoint: every Σs_l transposed.
+std::vector<double> solver_table_pn(const rt_solver *S, int32_t L, const double *sigma_sl, bool adjoint) {
+    const int32_t G = S->G, M = S->M;
+    const size_t stride = (size_t)G * (1 + (size_t)L * G);
+    std::vector<double> tab((size_t)M * stride);
+    for (int32_t mm = 0; mm < M; ++mm) {
+        double *X = tab.data() + (size_t)mm * stride;
+        for (int32_t g = 0; g < G; ++g) X[g] = S->h_st[(size_t)mm * G + g];
+        for (int32_t l = 0; l < L; ++l) {
+            const double *sl = sigma_sl + ((size_t)l * M + mm) * G * G;
+            double *Y = X + G + (size_t)l * G * G;
+            for (int32_t a = 0; a < G; ++a)
+                for (int32_t b = 0; b < G; ++b) Y[a * G + b] = adjoint ? sl[b * G + a] : sl[a * G + b];
+        }
+    }
+    return tab;
+}
+
+// What a solver with P2 / P3 scattering set cannot run together with: every setter of such an option asks here, and the message
+// names both sides.
+bool pn_refuses(const rt_solver *S, const char *who, const char *other) {
+    if (S->mode != SweepMode::PN) return false;
+    set_error("%s: P%d scattering is set (rt_solver_set_scatter_pn), and %s together with it is not supported", who, S->pn_order, other);
+    return true;
 }
 
 int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_material, const double *sigma_t, const double *sigma_s,
@@ -1064,7 +1178,22 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
     S->ran = false; S->ran_mode = SweepMode::Flat;
     const SweepMode smode = S->mode;
     if (smode == SweepMode::Linear && !S->has_geom) { set_error("%s: the linear source has no geometry", who); return RT_ERR_INVALID; }
-    if (smode != SweepMode::Flat) {  // J⁰ = 0 (P1), φ⃗⁰ = 0 (Linear); the sweep's ratios xs1 and its moment tallies, the same buffers for both
+    if (smode == SweepMode::PN) {  // φ⁰_lm = 0 for l >= 1; the sweep's ratios and higher tallies, lent for the run
+        if (S->repro || S->single || S->reg_R > 0 || S->vc_mode || S->sr_on || t->sw_shard) {  // (the setters keep the combinations apart; the links may have become a shard's since)
+            set_error("%s: P%d scattering is set (rt_solver_set_scatter_pn) and %s: the two together are not supported", who, S->pn_order,
+                      S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)" : S->single ? "the single-precision sweep is set (rt_solver_set_precision)"
+                      : S->reg_R > 0 ? "region currents are set (rt_solver_set_regions, rt_solver_set_cmfd)" : S->vc_mode ? "the volume correction is set (rt_solver_set_volume_correction)"
+                      : S->sr_on ? "source regions are set (rt_solver_set_source_regions)" : "the track set is a shard (some next uid is 0)");
+            return RT_ERR_INVALID;
+        }
+        const int32_t L = S->pn_order, NM = L == 2 ? 6 : 10;
+        const size_t nm = (size_t)NM * std::max<size_t>(1, (size_t)nc * G);
+        RT_HIP(S->pn_mom.reserve(nm)); RT_HIP(S->pn_qr.reserve(nm));
+        RT_HIP(S->pn_h.reserve((size_t)(2 * L + 1) * nxs)); RT_HIP(S->pn_t.reserve((size_t)(2 * L) * nxs));
+        RT_HIP(hipMemsetAsync(S->pn_mom.p, 0, nm * sizeof(double), s));
+        RT_HIP(hipMemsetAsync(S->pn_qr.p, 0, nm * sizeof(double), s));
+        loan.pn_M = L; loan.pn_h = S->pn_h.p; loan.pn_t = S->pn_t.p;
+    } else if (smode != SweepMode::Flat) {  // J⁰ = 0 (P1), φ⃗⁰ = 0 (Linear); the sweep's ratios xs1 and its moment tallies, the same buffers for both
         const bool p1 = smode == SweepMode::P1;
         DevBuf<double> &mom0 = p1 ? S->J : S->mom, &ratio = p1 ? S->q1r : S->gr;
         const size_t nj = 2 * std::max<size_t>(1, (size_t)nc * G);
@@ -1110,6 +1239,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
     S->k_hist.clear();
     for (int i = 0; i < 5; ++i) S->kry_info[i] = 0;
     S->kry_res.clear(); S->kry_lin = false;
+    S->run_pn = smode == SweepMode::PN ? S->pn_order : 0;
     S->run_eigen = eigen; S->run_mode = smode; S->run_bnd = bnd; S->run_reg = reg; S->run_cm = cm;
     S->it = 0; S->last_k = 1.0; S->last_res = INFINITY; S->last_dk = INFINITY;
     // φ⁰ = 1, the components' Σt / sin θ, F⁰
@@ -1140,6 +1270,9 @@ int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
     if (S->run_mode == SweepMode::P1)
         hipLaunchKernelGGL(rt::k_solver_source_p1, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds1_len * sizeof(double), s, (const int32_t *)S->mat.p,
                            (const double *)S->tab1.p, d.lds1_len, (const double *)S->J.p, (const double *)S->pol.p, nc, G, P, S->q1r.p, t->sw_xs1.p);
+    if (S->run_mode == SweepMode::PN)
+        hipLaunchKernelGGL(rt::k_solver_source_pn, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->pn_tab.p,
+                           (const double *)S->pn_mom.p, (const double *)S->pol.p, (const double *)t->sw_xs.p, nc, G, P, S->run_pn, S->pn_qr.p, S->pn_h.p);
     if (S->run_mode == SweepMode::Linear)
         hipLaunchKernelGGL(rt::k_solver_source_ls, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
                            (const double *)S->tab.p, d.lds_len, (const double *)S->mom.p, (const double *)S->cinv.p, (const double *)S->pol.p,
@@ -1191,6 +1324,10 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
     if (S->run_mode == SweepMode::P1)
         hipLaunchKernelGGL(rt::k_solver_fold_p1, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab1.p,
                            (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->q1r.p, nc, G, P, S->J.p);
+    if (S->run_mode == SweepMode::PN)
+        hipLaunchKernelGGL(rt::k_solver_fold_pn, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->pn_tab.p,
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, (const double *)S->pn_t.p,
+                           (const double *)S->pn_qr.p, nc, G, P, S->run_pn, S->pn_mom.p);
     if (S->run_mode == SweepMode::Linear)
         hipLaunchKernelGGL(rt::k_solver_fold_ls, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
                            (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->gr.p,
@@ -1234,6 +1371,7 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
 // What a solver with the option set cannot run together with, for the messages that name both sides; nullptr: nothing.
 const char *krylov_conflict(const rt_solver *S) {
     return S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
+        : S->mode == SweepMode::PN ? "P2 / P3 scattering is set (rt_solver_set_scatter_pn)"
         : (S->mode == SweepMode::Linear || S->ls_stage != 0) ? "the linear source is on (rt_solver_set_linear_source)"
         : S->single ? "the single-precision sweep is set (rt_solver_set_precision)"
         : S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
@@ -1387,7 +1525,10 @@ int solver_end_impl(rt_solver *S, rt_solver_result *res, const char *who) {
     RT_HIP(hipEventRecord(S->ev[1], s));
     if (eigen && d.nc > 0)
         hipLaunchKernelGGL(rt::k_solver_scale, dim3(d.sblocks), dim3(256), 0, s, S->phi.p, d.ncg, (const double *)S->scal.p);
-    if (eigen && d.nc > 0 && S->run_mode != SweepMode::Flat)  // (the moments of the mode, scaled with φ)
+    if (eigen && d.nc > 0 && S->run_mode == SweepMode::PN) {  // (every moment, scaled with φ)
+        const int64_t nm = (int64_t)(S->run_pn == 2 ? 6 : 10) * d.ncg;
+        hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((nm + 255) / 256)), dim3(256), 0, s, S->pn_mom.p, nm, (const double *)S->scal.p);
+    } else if (eigen && d.nc > 0 && S->run_mode != SweepMode::Flat)  // (the moments of the mode, scaled with φ)
         hipLaunchKernelGGL(rt::k_solver_scale, dim3((unsigned)((2 * d.ncg + 255) / 256)), dim3(256), 0, s,
                            S->run_mode == SweepMode::P1 ? S->J.p : S->mom.p, 2 * d.ncg, (const double *)S->scal.p);
     if (eigen && S->run_bnd && S->bnd_tallied)  // (the currents of the last sweep, scaled with φ)
@@ -1402,7 +1543,7 @@ int solver_end_impl(rt_solver *S, rt_solver_result *res, const char *who) {
     float f = 0.0f;
     RT_HIP(hipEventElapsedTime(&f, S->ev[0], S->ev[1]));
     t->in_flight = false;
-    S->ran = true; S->ran_mode = S->run_mode;
+    S->ran = true; S->ran_mode = S->run_mode; S->ran_pn = S->run_pn;
     S->ran_eigen = eigen; S->ran_adjoint = S->adjoint; S->ran_k = S->last_k;
     if (res) {
         res->k_eff = eigen ? S->last_k : 1.0; res->residual = S->last_res; res->dk = S->last_dk; res->device_ms = f;
@@ -1560,6 +1701,7 @@ int transient_begin_impl(rt_solver *S, int32_t D, const double *inv_velocity, co
     const char *other = S->adjoint ? "adjoint mode is set (rt_solver_set_adjoint)"
         : S->mode == SweepMode::Linear ? "the linear source is on (rt_solver_set_linear_source)"
         : S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1: the time derivative of the current is not modelled)"
+        : S->mode == SweepMode::PN ? "P2 / P3 scattering is set (rt_solver_set_scatter_pn: the time derivative of the higher moments is not modelled)"
         : S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
         : (S->reg_R > 0 || S->cm_on) ? "region currents are set (rt_solver_set_regions, rt_solver_set_cmfd)"
         : (S->bnd_S > 0 && S->bnd_inc) ? "a boundary has an incoming flux (rt_solver_set_boundary)"
@@ -1760,6 +1902,7 @@ static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) 
     if (S->open) { set_error("rt_solver_set_scatter_p1: a run is open (rt_solver_begin without rt_solver_end): the tables cannot change under it"); return RT_ERR_INVALID; }
     if (!sigma_s1) { if (S->mode == SweepMode::P1) S->mode = SweepMode::Flat; return RT_SUCCESS; }
     if (S->mode == SweepMode::Linear) { set_error("rt_solver_set_scatter_p1: the linear source is on, and the two together are not supported"); return RT_ERR_INVALID; }
+    if (pn_refuses(S, "rt_solver_set_scatter_p1", "first-moment scattering of its own (rt_solver_set_scatter_pn carries Σs1; order 0 switches it off)")) return RT_ERR_INVALID;
     if (S->kry_m > 0) { set_error("rt_solver_set_scatter_p1: restarted GMRES is set (rt_solver_set_krylov), and first-moment scattering together with it is not supported"); return RT_ERR_INVALID; }
     if (S->single) { set_error("rt_solver_set_scatter_p1: the single-precision sweep is set (rt_solver_set_precision), and first-moment scattering together with it is not supported"); return RT_ERR_INVALID; }
     const int32_t G = S->G, M = S->M;
@@ -1784,6 +1927,97 @@ int32_t rt_solver_set_scatter_p1(rt_solver *solver, const double *sigma_s1) {
     return guarded("rt_solver_set_scatter_p1", [&] { return solver_set_scatter_p1_impl(solver, sigma_s1); });
 }
 
+// Scattering up to the order given: 0 (or no table) switches every anisotropic order off, 1 is rt_solver_set_scatter_p1 with the first
+// matrix, 2 and 3 upload the higher-moment table and make PN the solver's mode.  A refusal leaves the solver what it had.
+static int32_t solver_set_scatter_pn_impl(rt_solver *S, int32_t order, const double *sigma_sl) {
+    const char *who = "rt_solver_set_scatter_pn";
+    if (!S) { set_error("%s: null solver", who); return RT_ERR_INVALID; }
+    if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the tables cannot change under it", who); return RT_ERR_INVALID; }
+    if (order < 0 || order > 3) { set_error("%s: order %d (0: off, 1: first-moment scattering, 2 or 3: P2 / P3)", who, order); return RT_ERR_INVALID; }
+    if (order == 0 || !sigma_sl) {
+        if (S->mode == SweepMode::PN) { S->mode = SweepMode::Flat; S->pn_order = 0; }
+        return solver_set_scatter_p1_impl(S, nullptr);
+    }
+    if (order == 1) {
+        const SweepMode was = S->mode;
+        const int32_t was_order = S->pn_order;
+        if (was == SweepMode::PN) { S->mode = SweepMode::Flat; S->pn_order = 0; }
+        const int32_t rc = solver_set_scatter_p1_impl(S, sigma_sl);
+        if (rc && was == SweepMode::PN) { S->mode = was; S->pn_order = was_order; }
+        return rc;
+    }
+    // what the P2 / P3 sweep does not run with: the message names both sides
+    const char *other = (S->mode == SweepMode::Linear || S->ls_stage != 0) ? "the linear source is on (rt_solver_set_linear_source)"
+        : S->single ? "the single-precision sweep is set (rt_solver_set_precision)"
+        : S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
+        : (S->reg_R > 0 || S->cm_on) ? "region currents are set (rt_solver_set_regions, rt_solver_set_cmfd)"
+        : S->sr_on ? "source regions are set (rt_solver_set_source_regions)"
+        : S->vc_mode ? "the volume correction is set (rt_solver_set_volume_correction)"
+        : S->kry_m > 0 ? "restarted GMRES is set (rt_solver_set_krylov)"
+        : S->t->sw_shard ? "the track set is a shard (some next uid is 0)" : nullptr;
+    if (other) { set_error("%s: %s, and P%d scattering together with it is not supported", who, other, order); return RT_ERR_INVALID; }
+    const int32_t G = S->G, M = S->M;
+    const size_t n1 = (size_t)M * G * G;
+    for (int32_t l = 0; l < order; ++l)
+        for (size_t i = 0; i < n1; ++i) {
+            const double v = sigma_sl[(size_t)l * n1 + i];
+            if (!std::isfinite(v) || !(std::fabs(v) <= S->h_ss[i])) {
+                set_error("%s: sigma_s%d[%zu] = %g against sigma_s = %g (must be finite with |Σs_l| <= Σs0)", who, l + 1, i, v, S->h_ss[i]);
+                return RT_ERR_INVALID;
+            }
+        }
+    const std::vector<double> tab = solver_table_pn(S, order, sigma_sl, S->adjoint);
+    std::vector<double> keep(sigma_sl, sigma_sl + (size_t)order * n1);  // (rt_solver_set_adjoint rebuilds the table from it)
+    if (int rc = finish_call(S->t)) return rc;
+    RT_HIP(hipSetDevice(S->t->mesh->device));
+    if (int rc = upload(S->pn_tab, tab.data(), tab.size(), S->t->mesh->stream)) return rc;
+    RT_HIP(hipStreamSynchronize(S->t->mesh->stream));
+    S->h_sl.swap(keep);
+    S->mode = SweepMode::PN; S->pn_order = order;
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_set_scatter_pn(rt_solver *solver, int32_t order, const double *sigma_sl) {
+    return guarded("rt_solver_set_scatter_pn", [&] { return solver_set_scatter_pn_impl(solver, order, sigma_sl); });
+}
+
+int32_t rt_solver_fetch_angular_moments(rt_solver *solver, double *out, int32_t *lm) {
+    const char *who = "rt_solver_fetch_angular_moments";
+    if (!solver || (!out && !lm)) { set_error("%s: null argument", who); return RT_ERR_INVALID; }
+    if (!solver->ran || solver->ran_mode != SweepMode::PN) {
+        set_error("%s: no completed rt_solver_run with P2 / P3 scattering (rt_solver_set_scatter_pn, order 2 or 3)", who);
+        return RT_ERR_INVALID;
+    }
+    static const int32_t kLm[10][2] = {{0, 0}, {1, 1}, {1, -1}, {2, 0}, {2, 2}, {2, -2}, {3, 1}, {3, -1}, {3, 3}, {3, -3}};
+    const size_t NM = solver->ran_pn == 2 ? 6 : 10, ncg = (size_t)solver->n_cells * solver->G;
+    if (lm) std::memcpy(lm, kLm, NM * 2 * sizeof(int32_t));
+    if (!out) return RT_SUCCESS;
+    RT_HIP(hipSetDevice(solver->t->mesh->device));
+    hipStream_t s = solver->t->mesh->stream;
+    std::vector<double> phi(std::max<size_t>(1, ncg));
+    if (ncg) {
+        RT_HIP(hipMemcpyAsync(out, solver->pn_mom.p, NM * ncg * sizeof(double), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipMemcpyAsync(phi.data(), solver->phi.p, ncg * sizeof(double), hipMemcpyDeviceToHost, s));
+    }
+    RT_HIP(hipStreamSynchronize(s));
+    for (size_t i = 0; i < ncg; ++i) out[NM * i] = phi[i];  // (φ_00 = φ: the iteration keeps it in its own array)
+    return RT_SUCCESS;
+}
+
+int32_t rt_solver_pn_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
+    if (!solver) { set_error("rt_solver_pn_pointers: null solver"); return RT_ERR_INVALID; }
+    // (no wait here: addresses and counts only; all null outside an open run with P2 / P3 scattering)
+    const bool on = solver->open && solver->run_mode == SweepMode::PN;
+    const int64_t L = solver->run_pn, NM = L == 2 ? 6 : 10, ncg = (int64_t)solver->n_cells * solver->G, nC = ncg * solver->P;
+    void *p[3] = {solver->pn_mom.p, solver->pn_h.p, solver->pn_t.p};
+    const int64_t l[3] = {NM * ncg, (2 * L + 1) * nC, 2 * L * nC};
+    for (int i = 0; i < 3; ++i) {
+        if (ptrs_dev) ptrs_dev[i] = on ? p[i] : nullptr;
+        if (lens) lens[i] = on ? l[i] : 0;
+    }
+    return RT_SUCCESS;
+}
+
 // Adjoint mode: the device tables of the transposed problem (solver_table, solver_table_p1), or the forward ones again.  The
 // kernels of the iteration read the tables they always read.
 static int32_t solver_set_adjoint_impl(rt_solver *S, int32_t on) {
@@ -1797,12 +2031,16 @@ static int32_t solver_set_adjoint_impl(rt_solver *S, int32_t on) {
     std::vector<double> tab1;
     const bool p1 = S->mode == SweepMode::P1;
     if (p1) tab1 = solver_table_p1(S, S->h_s1.data(), adj);
+    const bool pn = S->mode == SweepMode::PN;
+    if (pn) tab1 = solver_table_pn(S, S->pn_order, S->h_sl.data(), adj);
     if (int rc = finish_call(S->t)) return rc;
     RT_HIP(hipSetDevice(S->t->mesh->device));
     hipStream_t s = S->t->mesh->stream;
     if (int rc = upload(S->tab, tab.data(), tab.size(), s)) return rc;
     if (p1)
         if (int rc = upload(S->tab1, tab1.data(), tab1.size(), s)) return rc;
+    if (pn)
+        if (int rc = upload(S->pn_tab, tab1.data(), tab1.size(), s)) return rc;
     RT_HIP(hipStreamSynchronize(s));  // (the host vectors die here)
     S->adjoint = adj;
     return RT_SUCCESS;
@@ -1982,6 +2220,7 @@ static int32_t solver_set_regions_impl(rt_solver *S, int32_t n_regions, const in
     if (n_regions == 0 || !cell_region) { S->reg_R = 0; S->reg_tallied = false; S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
     if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the coarse-mesh prolongation reads the compact records' cells), and region currents together with them are not supported", who); return RT_ERR_INVALID; }
     if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and region currents together with it are not supported", who); return RT_ERR_INVALID; }
+    if (pn_refuses(S, who, "region currents (rt_solver_set_regions: another kernel)")) return RT_ERR_INVALID;
     if (n_regions < 1 || n_regions > rtsweep::kMaxRegions) { set_error("%s: bad arguments (n_regions %d, need 1 .. %d)", who, n_regions, rtsweep::kMaxRegions); return RT_ERR_INVALID; }
     if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and region currents — an atomic sum — together with them are not supported", who); return RT_ERR_INVALID; }
     if (S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision: another kernel), and region currents together with it are not supported", who); return RT_ERR_INVALID; }
@@ -2024,6 +2263,7 @@ static int32_t solver_set_cmfd_impl(rt_solver *S, int32_t on, const double *coup
     if (!on) { S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
     if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the prolongation reads the compact records' cells), and the coarse-mesh acceleration together with them is not supported", who); return RT_ERR_INVALID; }
     if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the coarse-mesh acceleration together with it is not supported", who); return RT_ERR_INVALID; }
+    if (pn_refuses(S, who, "the coarse-mesh acceleration (rt_solver_set_cmfd: it needs the region currents)")) return RT_ERR_INVALID;
     const int32_t R = S->reg_R, G = S->G, nc = S->n_cells;
     if (R <= 0) { set_error("%s: no regions are set (rt_solver_set_regions comes first: its regions are the coarse cells)", who); return RT_ERR_INVALID; }
     if (S->bnd_S > 0 && S->bnd_inc) { set_error("%s: a boundary has an incoming flux (rt_solver_set_boundary), and the coarse-mesh acceleration together with it is not supported", who); return RT_ERR_INVALID; }
@@ -2149,13 +2389,21 @@ int32_t rt_solver_region_pointers(rt_solver *solver, void **ptrs_dev, int64_t *l
 
 int32_t rt_solver_fetch_current(rt_solver *solver, double *J) {
     if (!solver || !J) { set_error("rt_solver_fetch_current: null argument"); return RT_ERR_INVALID; }
-    if (!solver->ran || solver->ran_mode != SweepMode::P1) {
-        set_error("rt_solver_fetch_current: no completed rt_solver_run with first-moment scattering (rt_solver_set_scatter_p1)");
+    if (!solver->ran || (solver->ran_mode != SweepMode::P1 && solver->ran_mode != SweepMode::PN)) {
+        set_error("rt_solver_fetch_current: no completed rt_solver_run with first-moment scattering (rt_solver_set_scatter_p1, rt_solver_set_scatter_pn)");
         return RT_ERR_INVALID;
     }
     RT_HIP(hipSetDevice(solver->t->mesh->device));
     hipStream_t s = solver->t->mesh->stream;
     const size_t nj = (size_t)solver->n_cells * solver->G * 2;
+    if (solver->ran_mode == SweepMode::PN) {  // the (1, ±1) moments: slots 1 and 2 of every (cell, group)
+        const size_t NM = solver->ran_pn == 2 ? 6 : 10, ncg = nj / 2;
+        std::vector<double> mom(std::max<size_t>(1, NM * ncg));
+        if (ncg) RT_HIP(hipMemcpyAsync(mom.data(), solver->pn_mom.p, NM * ncg * sizeof(double), hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));
+        for (size_t i = 0; i < ncg; ++i) { J[2 * i] = mom[NM * i + 1]; J[2 * i + 1] = mom[NM * i + 2]; }
+        return RT_SUCCESS;
+    }
     if (nj) RT_HIP(hipMemcpyAsync(J, solver->J.p, nj * sizeof(double), hipMemcpyDeviceToHost, s));
     RT_HIP(hipStreamSynchronize(s));
     return RT_SUCCESS;
@@ -2179,6 +2427,7 @@ static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged
         return RT_ERR_INVALID;
     }
     if (S->mode == SweepMode::P1) { set_error("%s: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported", who); return RT_ERR_INVALID; }
+    if (pn_refuses(S, who, "the linear source (rt_solver_set_linear_source)")) return RT_ERR_INVALID;
     if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the linear source together with it is not supported", who); return RT_ERR_INVALID; }
     if (staged && S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the geometry cannot change under it", who); return RT_ERR_INVALID; }
     if (stage != 0 && stage != S->ls_stage) {
@@ -2252,6 +2501,7 @@ int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
     if (solver->open) { set_error("rt_solver_set_linear_source: a run is open (rt_solver_begin without rt_solver_end): the source's shape cannot change under it"); return RT_ERR_INVALID; }
     if (!on) { if (solver->mode == SweepMode::Linear) solver->mode = SweepMode::Flat; return RT_SUCCESS; }
     if (solver->mode == SweepMode::P1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
+    if (pn_refuses(solver, who, "the linear source (rt_solver_set_linear_source)")) return RT_ERR_INVALID;
     if (solver->kry_m > 0) { set_error("rt_solver_set_linear_source: restarted GMRES is set (rt_solver_set_krylov), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
     if (solver->single) { set_error("rt_solver_set_linear_source: the single-precision sweep is set (rt_solver_set_precision), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
     if (solver->sr_on) { set_error("rt_solver_set_linear_source: source regions are set (rt_solver_set_source_regions: the centroids and C matrices are per cell), and the linear source together with them is not supported"); return RT_ERR_INVALID; }
@@ -2286,6 +2536,7 @@ static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
     const bool want = on != 0;
     if (want == S->repro) return RT_SUCCESS;
     if (want && S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
+    if (want && pn_refuses(S, who, "the reproducible tallies (rt_solver_set_reproducible: its tallies are an atomic sum)")) return RT_ERR_INVALID;
     if (want && S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
     if (want && S->reg_R > 0) { set_error("%s: region currents are set (rt_solver_set_regions: their tally is an atomic sum), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
     if (want && S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the tally index is per original row slot), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
@@ -2366,6 +2617,7 @@ int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision) {
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the sweep cannot change under it", who); return RT_ERR_INVALID; }
     if (precision != RT_PRECISION_DOUBLE && precision != RT_PRECISION_SINGLE) { set_error("%s: precision %d (RT_PRECISION_DOUBLE = 0 or RT_PRECISION_SINGLE = 1)", who, precision); return RT_ERR_INVALID; }
     if (precision == RT_PRECISION_SINGLE) {
+        if (pn_refuses(S, who, "the single-precision sweep (rt_solver_set_precision: another kernel)")) return RT_ERR_INVALID;
         const char *other = S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
                                   : (S->mode == SweepMode::Linear ? "the linear source is on (rt_solver_set_linear_source)"
                                            : (S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
@@ -2391,6 +2643,7 @@ static int32_t solver_set_volume_correction_impl(rt_solver *S, int32_t mode) {
     if (mode == S->vc_mode) return RT_SUCCESS;
     if (mode != RT_VOLUME_CORRECTION_OFF) {
         if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the volume correction together with it is not supported", who); return RT_ERR_INVALID; }
+        if (pn_refuses(S, who, "the volume correction (rt_solver_set_volume_correction)")) return RT_ERR_INVALID;
         if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions), and the volume correction — its factors are per cell — together with them is not supported", who); return RT_ERR_INVALID; }
         if (S->mode == SweepMode::Linear || S->ls_stage != 0) { set_error("%s: the linear source is on (rt_solver_set_linear_source: scaled chords would move its midpoints off the track), and the volume correction together with it is not supported", who); return RT_ERR_INVALID; }
         if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and the volume correction — its tracked lengths are an atomic sum — together with them is not supported", who); return RT_ERR_INVALID; }
@@ -2478,6 +2731,7 @@ static int32_t solver_set_source_regions_impl(rt_solver *S, const int32_t *map, 
     }
     if (n_src < 1 || n_src > nm) { set_error("%s: bad arguments (n_src %d, need 1 .. the mesh's %d cells)", who, n_src, nm); return RT_ERR_INVALID; }
     if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and source regions together with it are not supported", who); return RT_ERR_INVALID; }
+    if (pn_refuses(S, who, "source regions (rt_solver_set_source_regions)")) return RT_ERR_INVALID;
     if (S->mode == SweepMode::Linear || S->ls_stage != 0) { set_error("%s: the linear source is on (rt_solver_set_linear_source: its centroids and C matrices are per cell), and source regions together with it are not supported", who); return RT_ERR_INVALID; }
     if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible: their tally index is per original row slot), and source regions together with them are not supported", who); return RT_ERR_INVALID; }
     if (S->reg_R > 0 || S->cm_on) { set_error("%s: region currents are set (rt_solver_set_regions, rt_solver_set_cmfd: the coarse-mesh prolongation reads the compact records' cells), and source regions together with them are not supported", who); return RT_ERR_INVALID; }
@@ -2785,7 +3039,7 @@ int32_t rt_solver_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
     if (!solver) { set_error("rt_solver_pointers: null solver"); return RT_ERR_INVALID; }
     // (no wait here: addresses and counts only)
     const int64_t nc = solver->n_cells, C = (int64_t)solver->G * solver->P;
-    const bool open = solver->open, mom = open && solver->run_mode != SweepMode::Flat;
+    const bool open = solver->open, mom = open && (solver->run_mode == SweepMode::P1 || solver->run_mode == SweepMode::Linear);  // (PN: rt_solver_pn_pointers)
     void *p[4] = {solver->vol.p, open ? solver->t->sw_phi.p : nullptr, mom ? solver->t->sw_cur.p : nullptr, solver->phi.p};
     const int64_t l[4] = {nc, open ? nc * C : 0, mom ? 2 * nc * C : 0, nc * solver->G};
     for (int i = 0; i < 4; ++i) {

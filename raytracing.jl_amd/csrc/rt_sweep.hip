@@ -412,7 +412,7 @@ static SweepFacts sweep_facts(const rt_tracks *t, int32_t G, int32_t input, cons
                       .f32 = loan.f32 || m->sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
                       .sw_ell_valid = t->sw_ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
                       .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves, .regions = loan.n_regions,
-                      .volcorr = volcorr, .srcreg = loan.sr_n_src > 0};
+                      .volcorr = volcorr, .srcreg = loan.sr_n_src > 0, .pn = loan.pn_M};
 }
 
 namespace rtx {
@@ -561,7 +561,8 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     // what this sweep reads and how wide its passes are, from the handle's state, the options and an rt_solver's loan for its run
     const SweepLoan &loan = t->sw_loan;
     const SweepMode mode = loan.mode;
-    const bool moments = mode != SweepMode::Flat, repro = loan.repro;
+    const bool pn = mode == SweepMode::PN;
+    const bool moments = mode != SweepMode::Flat && !pn, repro = loan.repro;  // (first moments or the linear source: xs1 and cur)
     const SweepFacts facts = sweep_facts(t, G, input, loan, loan.vc_ell != nullptr);
     SweepPlan plan = plan_sweep(facts);
     if (plan.refusal) { set_error("%s", plan.message); return plan.refusal; }
@@ -602,6 +603,11 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         a.cs = as_global((const double *)t->cs.p); a.sn = as_global((const double *)t->sn.p);
         a.cen = as_global(loan.ls_cen); a.ends = as_global(loan.ls_ends);
     }
+    if (pn) {  // the solver's ratios and higher tallies for these G components, 2M + 1 and 2M per component
+        if (!loan.pn_h || !loan.pn_t) { set_error("rt_sweep: P2 / P3 scattering has no ratio and tally arrays"); return RT_ERR_INVALID; }
+        a.pn_h = as_global(loan.pn_h); a.pn_t = as_global(loan.pn_t); a.pn_M = loan.pn_M;
+        a.cs = as_global((const double *)t->cs.p); a.sn = as_global((const double *)t->sn.p);
+    }
     if (repro) {  // the cell index for the rows the plan names, and the solver's delta buffer
         int64_t rslots = 0;
         if (int rc = sweep_repro_prepare(t, &rslots)) return rc;
@@ -621,6 +627,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     if (iface) RT_HIP(hipMemsetAsync(loan.iface_S, 0, (size_t)(facts.regions + 1) * (facts.regions + 1) * G * sizeof(double), s));
     RT_HIP(hipMemsetAsync(t->sw_phi.p, 0, nphi * sizeof(double), s));
     if (moments && nphi) RT_HIP(hipMemsetAsync(t->sw_cur.p, 0, 2 * nphi * sizeof(double), s));
+    if (pn && nphi) RT_HIP(hipMemsetAsync(loan.pn_t, 0, (size_t)(2 * loan.pn_M) * nphi * sizeof(double), s));
     if (plan.rows == SweepRows::FromCompact) {
         a.stg = rt::DStage{};
         a.stg.ctab = as_global(t->sw_ctab.p); a.stg.element = as_global(t->sw_cell.p);
@@ -652,6 +659,12 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
                 return RT_ERR_INVALID;
             }
             if (int rc = launch_sweep_f32(a, take, shape.smem, shape.waves, shape.blocks, s)) return rc;
+        } else if (pn) {
+            if (!rows_read_ell(plan.rows)) {  // (checked before anything was queued; left: no memory for the ℓ rows)
+                set_error("rt_sweep: P2 / P3 scattering (rt_solver_set_scatter_pn) found no (ℓ, cell) rows to read (rows of kind 0)");
+                return RT_ERR_INVALID;
+            }
+            if (int rc = launch_sweep_pn(a, shape.smem, shape.waves, shape.blocks, s)) return rc;
         } else if (iface) {
             if (!rows_read_ell(plan.rows)) {  // (checked before anything was queued; left: no memory for the ℓ rows)
                 set_error("rt_sweep: the region currents (rt_solver_set_regions) found no (ℓ, cell) rows to read (rows of kind 0)");

@@ -13,8 +13,9 @@
 namespace rtsweep {
 
 // the shape of the source along a segment: flat, with first-moment scattering (rt_solver_set_scatter_p1) or linear
-// (rt_solver_set_linear_source) — one choice of three, here, in the loan of a solver (SweepLoan) and in rt_solver
-enum class SweepMode { Flat, P1, Linear };
+// (rt_solver_set_linear_source) — one choice of three, here, in the loan of a solver (SweepLoan) and in rt_solver; PN: a fourth,
+// P2 / P3 scattering (rt_solver_set_scatter_pn; SweepFacts::pn is its order), which has a kernel of its own (rt_sweep_pn.hip)
+enum class SweepMode { Flat, P1, Linear, PN };
 constexpr int kSweepGpP1 = 2;  // components per pass of a sweep with three tallies per component (P1, Linear), at most
 
 // what a sweep reads
@@ -52,7 +53,11 @@ struct SweepFacts {
     int regions = 0;           // R of the region currents (lent by a solver, rt_solver_set_regions); 0: off
     bool volcorr = false;      // the rows' ℓ comes from a solver's corrected copy (rt_solver_set_volume_correction)
     bool srcreg = false;       // the rows are a solver's merged rows and n_cells its n_src (rt_solver_set_source_regions)
+    int pn = 0;                // mode PN: the scattering order, 2 or 3 (2 pn + 1 tallies and ratios per component)
 };
+
+// tallies per component of a pass: 1 flat, 3 with first moments (P1, Linear), 2 L + 1 with P2 / P3 scattering
+constexpr int sweep_tallies(const SweepFacts &f) { return f.mode == SweepMode::Flat ? 1 : (f.mode == SweepMode::PN ? 2 * f.pn + 1 : 3); }
 
 constexpr int kMaxRegions = 127;  // (R + 1)² doubles of one component fit the LDS of a workgroup: 128 KiB
 
@@ -81,7 +86,7 @@ struct SweepPlan {
     // kernels are compiled for eight waves at most.
     PassShape pass_shape(int take) const {
         const bool staged = rows_staged(rows);
-        size_t smem = use_lds ? (size_t)f.n_cells * take * (f.mode != SweepMode::Flat ? 3 : 1) * sizeof(double) : 0;
+        size_t smem = use_lds ? (size_t)f.n_cells * take * sweep_tallies(f) * sizeof(double) : 0;
         smem += iface_table(take);  // (the region currents' table, behind the φ copy)
         if (!staged && (use_lds || f.repro)) smem = std::max(smem, std::min(lds_cap, (size_t)81 * 1024));
         int W = (smem > 79 * 1024 && staged) ? 16 : 8;
@@ -96,6 +101,9 @@ struct SweepPlan {
 
 #define RT_IFACE_WITH(other) "rt_sweep: the region currents (rt_solver_set_regions) together with " other " — not supported"
 #define RT_IFACE_ROWS(why) "rt_sweep: the region currents (rt_solver_set_regions) are tallied over (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
+
+#define RT_PN_WITH(other) "rt_sweep: P2 / P3 scattering (rt_solver_set_scatter_pn) together with " other " — not supported"
+#define RT_PN_ROWS(why) "rt_sweep: P2 / P3 scattering (rt_solver_set_scatter_pn) sweeps (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
 
 #define RT_VC_WITH(other) "rt_sweep: the volume correction (rt_solver_set_volume_correction) together with " other " — not supported"
 #define RT_VC_ROWS(why) "rt_sweep: the volume correction (rt_solver_set_volume_correction) scales the ℓ of (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
@@ -144,6 +152,21 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
             return refuse(RT_IFACE_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
                                         "sweep without regions first, or set option \"sweep_rows\" 2 and name the compact records"));
     }
+    // P2 / P3 scattering: k_sweep_pn, FP64 atomics, one component per pass, over (ℓ, cell) rows — refused like the region currents,
+    // before anything is queued
+    if (f.mode == SweepMode::PN) {
+        if (f.pn != 2 && f.pn != 3) return refuse("rt_sweep: P2 / P3 scattering (rt_solver_set_scatter_pn) has the order 2 or 3");
+        if (f.f32) return refuse(RT_PN_WITH("the single-precision sweep (rt_solver_set_precision, \"sweep_precision\" 1): that is another kernel"));
+        if (f.repro) return refuse(RT_PN_WITH("the reproducible tallies (rt_solver_set_reproducible): its tallies are an atomic sum"));
+        if (f.regions > 0) return refuse(RT_PN_WITH("the region currents (rt_solver_set_regions, rt_solver_set_cmfd): that is another kernel"));
+        if (f.volcorr) return refuse(RT_PN_WITH("the volume correction (rt_solver_set_volume_correction)"));
+        if (f.srcreg) return refuse(RT_PN_WITH("the source regions (rt_solver_set_source_regions)"));
+        if (p.rows == SweepRows::Records) return refuse(RT_PN_ROWS("the compact records where they lie: option \"sweep_rows\" is 0"));
+        if (p.rows == SweepRows::Staged20) return refuse(RT_PN_ROWS("the staging's 20-B rows in every pass: option \"sweep_ell\" is 0"));
+        if (p.rows == SweepRows::Staged20WriteEll)
+            return refuse(RT_PN_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
+                                     "sweep without it first, or set option \"sweep_rows\" 2 and name the compact records"));
+    }
     // volume correction: the sweep reads ℓ' = f ℓ from the solver's copy of the (ℓ, cell) rows' ℓ — rows that carry no ℓ are refused like
     // the region currents', before anything is queued; so are the linear source (its midpoints follow the running sum of ℓ) and the
     // reproducible tallies (the tracked lengths are an atomic sum)
@@ -175,7 +198,8 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
     // sweep's arithmetic).  First-moment scattering and the linear source: three tallies per component, so a mesh that fits 4
     // components fits 1; at most 2 per pass (the kernel carries two more ratios per pipeline stage and two more deltas per
     // component: see DESIGN.md for the registers).
-    const int nt = f.mode != SweepMode::Flat ? 3 : 1, gp_max = f.mode != SweepMode::Flat ? kSweepGpP1 : 4;
+    // P2 / P3 scattering: 2 L + 1 tallies per component, one component per pass (k_sweep_pn is compiled for that).
+    const int nt = sweep_tallies(f), gp_max = f.mode == SweepMode::PN ? 1 : (f.mode != SweepMode::Flat ? kSweepGpP1 : 4);
     p.lds_cap = (size_t)std::min(f.lds_per_block, 160 * 1024) - 1024;
     const auto fits = [&](int gp) { return (size_t)f.n_cells * gp * nt * sizeof(double) <= p.lds_cap; };
     const int gp_wide = std::min(f.G, gp_max), gp_opt = (f.sweep_gp >= 1 && f.sweep_gp <= 4) ? std::min(gp_wide, f.sweep_gp) : gp_wide;
@@ -209,6 +233,8 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
 #undef RT_F32_ROWS
 #undef RT_IFACE_WITH
 #undef RT_IFACE_ROWS
+#undef RT_PN_WITH
+#undef RT_PN_ROWS
 #undef RT_VC_WITH
 #undef RT_VC_ROWS
 #undef RT_SR_WITH

@@ -400,6 +400,9 @@ class ShardedSolver:
             raise ValueError('staged_geometry=True goes with scheme="linear" only')
         if self.linear and (getattr(xs, "sigma_s1", None) is not None or getattr(solver, "p1", False)):
             raise ValueError('scheme="linear" together with sigma_s1 (P1 scattering) is not supported')
+        if getattr(xs, "sigma_s2", None) is not None:
+            raise ValueError("sigma_s2 / sigma_s3 (P2 / P3 scattering, rt_solver_set_scatter_pn) on shards is not supported: the higher "
+                             "moments' tallies are not among what the ranks sum")
         if self.linear and solver is not None and not (hasattr(solver, "ls_geometry") and hasattr(solver, "ls_geometry_pointer")):
             raise ValueError('scheme="linear" needs a solver with the geometry calls ls_geometry(stage) and ls_geometry_pointer()')
         self.dt, self.rank, self.world, self.group, self.device = dt, rank, world, group, device

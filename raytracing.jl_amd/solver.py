@@ -8,7 +8,9 @@ a fold kernel and a fixed-order reduction; only k, the residual and |Δk|/k come
 The definitions (azimuthal and polar weights, volumes, fold, source, residual, normalisation) are stated
 in ``include/rt_segmentize.h``.  With ``CrossSections(..., sigma_s1=...)`` scattering is linearly anisotropic (P1): the
 sweep's source depends on the direction of travel, first angular moments are tallied and ``SolverResult.current`` is the
-net current.  With ``scheme="linear"`` the source of a cell is linear in space (LS-MOC: a coarser mesh resolves the same flux
+net current.  With ``sigma_s2`` (and ``sigma_s3``) on top scattering is P2 (P3): the sweep carries the azimuthal Fourier functions of
+its track up to that order, and ``SolverResult.angular_moments`` holds every moment φ_lm with l + m even (``rt_solver_set_scatter_pn``).
+With ``scheme="linear"`` the source of a cell is linear in space (LS-MOC: a coarser mesh resolves the same flux
 gradient); ``SolverResult.flux_moments``, ``flux_gradient`` and ``centroids`` describe the flux inside the cells.
 With ``adjoint=True`` the same iteration runs on the transposed problem (``rt_solver_set_adjoint``) and returns the adjoint flux φ†;
 ``perturbation_reactivity`` and ``kinetics_parameters`` weigh cross-section changes and kinetics data with it
@@ -55,9 +57,11 @@ class CrossSections:
     ``sigma_s`` [M, G, G] with ``sigma_s[m, g', g]`` the transfer from group g' to g (isotropic scattering).
     One material may be given without its leading axis.  ``sigma_s1`` [M, G, G] (optional): the l = 1 Legendre moment of the
     same transfer, Σs(g'→g, μ0) = (1/4π) [Σs0 + 3 Σs1 μ0] — linearly anisotropic scattering; entries may be negative but
-    must be finite with |Σs1| <= Σs0."""
+    must be finite with |Σs1| <= Σs0.  ``sigma_s2``, ``sigma_s3`` [M, G, G] (optional): the l = 2 and l = 3 moments of
+    Σs(g'→g, μ0) = (1/4π) Σ_l (2l+1) Σs_l P_l(μ0), validated like ``sigma_s1``; ``sigma_s3`` needs ``sigma_s2``, and both need
+    ``sigma_s1``.  ``scatter_order``: the highest l given (0 .. 3); ``sigma_sl``: the moments from l = 1 stacked."""
 
-    def __init__(self, sigma_t, sigma_s, nu_sigma_f, chi, sigma_s1=None):
+    def __init__(self, sigma_t, sigma_s, nu_sigma_f, chi, sigma_s1=None, sigma_s2=None, sigma_s3=None):
         st = np.asarray(sigma_t, np.float64)
         st = st.reshape(1, -1) if st.ndim <= 1 else st
         if st.ndim != 2:
@@ -75,16 +79,31 @@ class CrossSections:
         if nf.shape != (M, G) or ch.shape != (M, G):
             raise ValueError(f"nu_sigma_f and chi must have shape [M, G] = {(M, G)}")
         self.sigma_t, self.sigma_s, self.nu_sigma_f, self.chi = (np.ascontiguousarray(a) for a in (st, ss, nf, ch))
-        self.sigma_s1 = None
-        if sigma_s1 is not None:
-            s1 = np.asarray(sigma_s1, np.float64)
-            if s1.size == M * G * G and s1.ndim <= 3:
-                s1 = s1.reshape(M, G, G)
-            if s1.shape != (M, G, G):
-                raise ValueError(f"sigma_s1 must have shape [M, G, G] = {(M, G, G)}, got {np.shape(sigma_s1)}")
-            if not np.all(np.isfinite(s1)) or not np.all(np.abs(s1) <= self.sigma_s):
-                raise ValueError("every sigma_s1 must be finite with |sigma_s1| <= sigma_s")
-            self.sigma_s1 = np.ascontiguousarray(s1)
+        if sigma_s2 is not None and sigma_s1 is None:
+            raise ValueError("sigma_s2 needs sigma_s1 (the Legendre moments are given without gaps)")
+        if sigma_s3 is not None and sigma_s2 is None:
+            raise ValueError("sigma_s3 needs sigma_s2 (the Legendre moments are given without gaps)")
+        self.sigma_s1 = self.sigma_s2 = self.sigma_s3 = None
+        for name, given in (("sigma_s1", sigma_s1), ("sigma_s2", sigma_s2), ("sigma_s3", sigma_s3)):
+            if given is None:
+                continue
+            sl = np.asarray(given, np.float64)
+            if sl.size == M * G * G and sl.ndim <= 3:
+                sl = sl.reshape(M, G, G)
+            if sl.shape != (M, G, G):
+                raise ValueError(f"{name} must have shape [M, G, G] = {(M, G, G)}, got {np.shape(given)}")
+            if not np.all(np.isfinite(sl)) or not np.all(np.abs(sl) <= self.sigma_s):
+                raise ValueError(f"every {name} must be finite with |{name}| <= sigma_s")
+            setattr(self, name, np.ascontiguousarray(sl))
+
+    @property
+    def scatter_order(self) -> int:
+        return 3 if self.sigma_s3 is not None else 2 if self.sigma_s2 is not None else 1 if self.sigma_s1 is not None else 0
+
+    @property
+    def sigma_sl(self):
+        L = self.scatter_order
+        return np.stack([self.sigma_s1, self.sigma_s2, self.sigma_s3][:L]) if L else None
 
     @property
     def n_materials(self) -> int:
@@ -391,6 +410,8 @@ class SolverResult:
     source_region_info: Optional[dict] = None      # ... n_src, rows / largest count / chunks before and after the merge; both None without
     xs: Optional["CrossSections"] = None           # the cross sections of the run (what ``solve_transient`` starts from)
     krylov: Optional[dict] = None                  # krylov=...: cycles, vectors, sweeps, the last cycle's vectors / breakdown / resnorm; None without
+    angular_moments: Optional[np.ndarray] = None   # sigma_s2 (sigma_s3): φ_lm [n_cells, G, NM], NM = 6 (10), slot 0 is phi; None below order 2
+    moment_lm: Optional[np.ndarray] = None         # ... the (l, m) of every slot [NM, 2]
 
     def to_cells(self, a):
         """An array per source region (``phi``, ``volumes``, ``current``) spread over the mesh's cells: ``a[source_region]``; ``a``
@@ -531,7 +552,9 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         sv.set_source_regions(sr, n_src)
     if source is not None:
         sv.set_source(source)
-    if xs.sigma_s1 is not None:
+    if xs.scatter_order >= 2:  # (refused by the library, in a message that names both, together with what it does not run with)
+        sv.set_scatter_pn(xs.scatter_order, xs.sigma_sl)
+    elif xs.sigma_s1 is not None:
         sv.set_scatter_p1(xs.sigma_s1)
     if linear:
         sv.set_linear_source(True)
@@ -578,6 +601,8 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         bnd.update(source_region=sr, source_region_info=sv.source_region_info())
     if kry is not None:
         bnd["krylov"] = sv.krylov_info()
+    if xs.scatter_order >= 2:
+        bnd.update(sv.fetch_angular_moments())
     return SolverResult(k_eff=r["k_eff"] if mode == _capi.DeviceSolver.EIGENVALUE else None, phi=f["phi"], volumes=f["volumes"],
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,

@@ -1,5 +1,5 @@
 """Timing of the device MOC solver (rt_solver) at the headline configuration: pincell, nφ = 128, δ = 1e-3, 7 groups, TY3
-(`--p1`: with linearly anisotropic scattering, Σs1 = 0.3 Σs0; `--linear`: with the linear source; `--adjoint`: the forward
+(`--p1`: with linearly anisotropic scattering, Σs1 = 0.3 Σs0; `--pn L`: with P2 / P3 scattering, Σs_l = 0.3^l Σs0; `--linear`: with the linear source; `--adjoint`: the forward
 figures first, then the same runs in adjoint mode (rt_solver_set_adjoint) on the same solver, under "adjoint_*"; `--albedo B`: the
 forward figures first, then the same runs with the albedo B on all four sides (rt_solver_set_boundary: the hand-over and the two
 current tallies per iteration) under "albedo_*", with the leakage and the balance defect of the last run; `--reproducible`: the
@@ -100,6 +100,9 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--p1", action="store_true", help="linearly anisotropic scattering: a synthetic Σs1 = 0.3 Σs0 (rt_solver_set_scatter_p1)")
+    ap.add_argument("--pn", type=int, default=0, choices=(0, 2, 3), metavar="L",
+                    help="P2 / P3 scattering: a synthetic Σs_l = 0.3^l Σs0, l = 1 .. L (rt_solver_set_scatter_pn); not together with --p1 / --linear "
+                         "or the options that follow the forward runs, adjoint mode and an albedo apart")
     ap.add_argument("--linear", action="store_true", help="the linear source (rt_solver_set_linear_source); not together with --p1")
     ap.add_argument("--adjoint", action="store_true", help="after the forward runs, the same runs in adjoint mode (rt_solver_set_adjoint)")
     ap.add_argument("--albedo", type=float, default=None, metavar="B",
@@ -156,6 +159,8 @@ def main():
                             rt.exact_azimuthal_weights(tg.azimuthal_quadrature))
     if a.p1:
         sv.set_scatter_p1(0.3 * xs.sigma_s)
+    if a.pn:
+        sv.set_scatter_pn(a.pn, np.stack([0.3 ** l * xs.sigma_s for l in range(1, a.pn + 1)]))
     if a.linear:
         sv.set_linear_source(True)
     sv.run(0, 3, 0.0, 0.0)  # warm-up (first launches, LDS attributes, the sweep's ℓ rows)
@@ -167,7 +172,7 @@ def main():
         ev_ms.append(r["device_ms"] / r["iterations"])
         ks.append(r["k_eff"])
     out = dict(config=dict(mesh=a.mesh, n_azim=a.n_azim, delta=a.delta, groups=a.groups, polar=a.polar, components=a.groups * pq.n_polar,
-                           p1=bool(a.p1), linear=bool(a.linear), tracks=int(tg.n_total_tracks), records=int(dt.total), cells=int(tg.mesh.num_cells), iters=a.iters),
+                           p1=bool(a.p1), pn=int(a.pn), linear=bool(a.linear), tracks=int(tg.n_total_tracks), records=int(dt.total), cells=int(tg.mesh.num_cells), iters=a.iters),
                ms_per_iter_events=float(np.median(ev_ms)), ms_per_iter_host=float(np.median(host_ms)), k_eff=ks[-1],
                ms_per_iter_events_runs=[float(v) for v in ev_ms])
     swi = (_capi.C.c_int32 * 4)()
@@ -396,7 +401,7 @@ def main():
         out["steps_k_eff"] = r["k_eff"]
     if a.linear:
         out["n_degenerate"] = sv.fetch_geometry()["n_degenerate"]
-    if not a.no_sweep_probe and not a.p1 and not a.linear:  # (the handle's own rt_sweep is the isotropic one)
+    if not a.no_sweep_probe and not a.p1 and not a.linear and not a.pn:  # (the handle's own rt_sweep is the isotropic one)
         # the same sweep the solver runs: G·P components, the handle's cross sections and boundary fluxes as the solver left them
         C = a.groups * pq.n_polar
         sw = []
