@@ -834,8 +834,8 @@ class DeviceSolver:
 
     def set_precision(self, precision="single"):
         """``rt_solver_set_precision``: "single" sweeps the angular flux in binary32 for the following runs (every sum, the fold, k
-        and the residual stay FP64), "double" the FP64 sweep again.  Refused together with first-moment scattering, the linear
-        source or the reproducible tallies."""
+        and the residual stay FP64), "double" the FP64 sweep again.  What it is refused together with: DESIGN.md §8 "Option
+        compatibility"."""
         L = lib()
         if precision not in PRECISIONS:
             raise ValueError('precision must be "double" or "single"')
@@ -1056,8 +1056,7 @@ class DeviceSolver:
     def set_volume_correction(self, mode="angle"):
         """``rt_solver_set_volume_correction`` for the following runs: ``"angle"`` (chord lengths scaled per cell and azimuthal
         angle so that every tracked area equals the cell's area), ``"cell"`` (one factor per cell, A_e / V_e), None: off — the
-        track-based volumes and the rows' own ℓ again.  Refused together with the linear source or the reproducible tallies, and on
-        a shard's track set."""
+        track-based volumes and the rows' own ℓ again.  What it is refused together with: DESIGN.md §8 "Option compatibility"."""
         L = lib()
         if mode is False:
             mode = None
@@ -1098,8 +1097,8 @@ class DeviceSolver:
         """``rt_solver_set_source_regions`` for the following runs: ``cell_source_region`` int [mesh cells], every entry in
         0 .. ``n_src`` − 1 (``n_src`` None: the largest entry + 1); every region's cells carry one material.  The solver then runs on
         ``n_src`` flat-source regions — ``n_cells`` here, ``set_source``, ``fetch`` and ``pointers`` are per region — over rows merged
-        per run of cells of one region.  None: off, per mesh cell again.  Switching drops the external source.  Refused together with
-        the linear source, the reproducible tallies, regions / cmfd and the volume correction, and on a shard's track set."""
+        per run of cells of one region.  None: off, per mesh cell again.  Switching drops the external source.  What they are
+        refused together with: DESIGN.md §8 "Option compatibility"."""
         L = lib()
         if not hasattr(L, "rt_solver_set_source_regions"):
             raise RtError(f"{LIB_PATH} has no rt_solver_set_source_regions: the library is older than this binding")

@@ -43,6 +43,7 @@
 // reproducible tallies' delta buffer, single precision — goes to the handle as one SweepLoan (rt_internal.hpp) and comes back whole.
 #include "rt_internal.hpp"
 #include "rt_krylov_host.hpp"
+#include "rt_solver_options.hpp"
 
 namespace rt {
 
@@ -839,11 +840,27 @@ std::vector<double> solver_table_pn(const rt_solver *S, int32_t L, const double 
     return tab;
 }
 
-// What a solver with P2 / P3 scattering set cannot run together with: every setter of such an option asks here, and the message
-// names both sides.
-bool pn_refuses(const rt_solver *S, const char *who, const char *other) {
-    if (S->mode != SweepMode::PN) return false;
-    set_error("%s: P%d scattering is set (rt_solver_set_scatter_pn), and %s together with it is not supported", who, S->pn_order, other);
+// ---- the options that are not supported together: rt_solver_options.hpp holds the table, and every such refusal is made here ----
+using rtopt::Option;
+
+// What counts as set: the one place that decides it (a staged linear-source geometry in progress is the linear source).
+uint32_t solver_option_mask(const rt_solver *S) {
+    const auto on = [](bool set, Option o) { return set ? rtopt::bit(o) : 0u; };
+    return on(S->mode == SweepMode::P1, Option::P1) | on(S->mode == SweepMode::PN, Option::PN)
+         | on(S->mode == SweepMode::Linear || S->ls_stage != 0, Option::Linear) | on(S->single, Option::F32) | on(S->repro, Option::Repro)
+         | on(S->reg_R > 0, Option::Regions) | on(S->cm_on, Option::Cmfd) | on(S->sr_on, Option::SrcReg) | on(S->vc_mode != 0, Option::VolCorr)
+         | on(S->kry_m > 0, Option::Krylov) | on(S->adjoint, Option::Adjoint) | on(S->bnd_S > 0 && S->bnd_inc, Option::Incoming)
+         | on(S->t->sw_shard, Option::Shard);
+}
+
+// A setter's question: does something that is set (but for `ignore`) not run with `wanted`?  Then the message names both sides.
+// pn_order: the order a message names where one side is P2 / P3 scattering (0: "P2 / P3"; by default the order that is set).
+bool option_refused(const rt_solver *S, const char *who, Option wanted, int pn_order = -1, uint32_t ignore = 0) {
+    Option set;
+    if (!rtopt::first_conflict(wanted, solver_option_mask(S) & ~ignore, &set)) return false;
+    char text[rtopt::kMessageCap];
+    rtopt::format_setter(text, sizeof text, who, set, wanted, pn_order < 0 ? S->pn_order : pn_order);
+    set_error("%s", text);
     return true;
 }
 
@@ -1013,17 +1030,13 @@ int solver_repro_reserve(rt_solver *S, const char *who, int min_nv = 1) {
     return RT_SUCCESS;
 }
 
-// The volume correction of the run that begins: refused where the setters would have refused it (the links may have become a shard's
-// since), the rows the run's sweeps will read planned and made (rt_sweep's own refusals for rows without ℓ), and — when the mode, or
+// The volume correction of the run that begins: the rows the run's sweeps will read planned and made (rt_sweep's own refusals for rows without ℓ), and — when the mode, or
 // the rows, are not the ones the tables were made from — the kernels of rt_volcorr.hip queued.  `vol` holds V' from here on; the
 // track-based volumes go aside once.
 int solver_volcorr_prepare(rt_solver *S, const char *who) {
     rt_tracks *t = S->t;
     rt_mesh *m = t->mesh;
     hipStream_t s = m->stream;
-    if (S->mode == SweepMode::Linear) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction) and the linear source is on (rt_solver_set_linear_source): the two together are not supported", who); return RT_ERR_INVALID; }
-    if (S->repro) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction) and the reproducible tallies are on (rt_solver_set_reproducible): the two together are not supported", who); return RT_ERR_INVALID; }
-    if (t->sw_shard) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction) and the track set is a shard (some next uid is 0): the tracked lengths of a shard are not the cells': not supported", who); return RT_ERR_INVALID; }
     const int32_t nc = S->n_cells, N2 = S->N2;
     if ((int64_t)nc * N2 >= (1ll << 31)) { set_error("%s: the volume correction's table of %d cells x %d azimuthal indices has 2^31 entries or more", who, nc, N2); return RT_ERR_INVALID; }
     SweepLoan probe;
@@ -1064,17 +1077,12 @@ int solver_volcorr_prepare(rt_solver *S, const char *who) {
     return RT_SUCCESS;
 }
 
-// The source regions of the run that begins: refused where the setter would have refused them (the links may have become a shard's
-// since), the rows the run's sweeps would read planned and made (rt_sweep's own refusals for rows without ℓ), and — when the merged rows
+// The source regions of the run that begins: the rows the run's sweeps would read planned and made (rt_sweep's own refusals for rows without ℓ), and — when the merged rows
 // are not made from those rows as they stand — the row kernels of rt_srcreg.hip queued (V_r is made by the setter: it does not depend
 // on the rows).
 int solver_srcreg_prepare(rt_solver *S, const char *who) {
     rt_tracks *t = S->t;
     hipStream_t s = t->mesh->stream;
-    if (S->mode == SweepMode::Linear) { set_error("%s: source regions are set (rt_solver_set_source_regions) and the linear source is on (rt_solver_set_linear_source): the two together are not supported", who); return RT_ERR_INVALID; }
-    if (S->repro) { set_error("%s: source regions are set (rt_solver_set_source_regions) and the reproducible tallies are on (rt_solver_set_reproducible): the two together are not supported", who); return RT_ERR_INVALID; }
-    if (S->reg_R > 0 || S->vc_mode) { set_error("%s: source regions are set (rt_solver_set_source_regions) together with region currents or the volume correction: not supported", who); return RT_ERR_INVALID; }
-    if (t->sw_shard) { set_error("%s: source regions are set (rt_solver_set_source_regions) and the track set is a shard (some next uid is 0): not supported", who); return RT_ERR_INVALID; }
     const int32_t nsrc = S->n_cells, nm = S->n_mesh;
     SweepLoan probe;
     probe.mode = S->mode; probe.repro = S->repro; probe.f32 = S->single; probe.n_regions = S->reg_R; probe.sr_n_src = nsrc;
@@ -1127,8 +1135,6 @@ int solver_srcreg_prepare(rt_solver *S, const char *who) {
     return RT_SUCCESS;
 }
 
-const char *krylov_conflict(const rt_solver *S);  // (below, with the cycles)
-
 // keep_phi (rt_solver_transient_begin): the run starts from the φ the solver holds instead of φ⁰ = 1; the caller queues the components'
 // Σt / sin θ, F_e and the scalars itself, from the table its run reads
 int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi = false) {
@@ -1145,11 +1151,15 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
         return RT_ERR_INVALID;
     }
     const bool eigen = mode == RT_SOLVE_EIGENVALUE;
-    if (!eigen && S->kry_m > 0)  // (the setters keep the combinations apart; the links may have become a shard's since)
-        if (const char *other = krylov_conflict(S)) {
-            set_error("%s: restarted GMRES is set (rt_solver_set_krylov) and %s: the two together are not supported", who, other);
+    {  // (the setters keep the combinations apart; the links may have become a shard's since.  An eigenvalue run takes no GMRES cycles)
+        Option a, b;
+        if (rtopt::first_pair(solver_option_mask(S) & ~(eigen ? rtopt::bit(Option::Krylov) : 0u), &a, &b)) {
+            char text[rtopt::kMessageCap];
+            rtopt::format_begin(text, sizeof text, who, a, b, S->pn_order);
+            set_error("%s", text);
             return RT_ERR_INVALID;
         }
+    }
     if (t->sw_loan.borrower) solver_release(t->sw_loan.borrower);  // (another solver's unfinished run on this handle ends here)
     rt_mesh *m = t->mesh;
     if (int rc = finish_call(t)) return rc;
@@ -1179,13 +1189,6 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
     const SweepMode smode = S->mode;
     if (smode == SweepMode::Linear && !S->has_geom) { set_error("%s: the linear source has no geometry", who); return RT_ERR_INVALID; }
     if (smode == SweepMode::PN) {  // φ⁰_lm = 0 for l >= 1; the sweep's ratios and higher tallies, lent for the run
-        if (S->repro || S->single || S->reg_R > 0 || S->vc_mode || S->sr_on || t->sw_shard) {  // (the setters keep the combinations apart; the links may have become a shard's since)
-            set_error("%s: P%d scattering is set (rt_solver_set_scatter_pn) and %s: the two together are not supported", who, S->pn_order,
-                      S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)" : S->single ? "the single-precision sweep is set (rt_solver_set_precision)"
-                      : S->reg_R > 0 ? "region currents are set (rt_solver_set_regions, rt_solver_set_cmfd)" : S->vc_mode ? "the volume correction is set (rt_solver_set_volume_correction)"
-                      : S->sr_on ? "source regions are set (rt_solver_set_source_regions)" : "the track set is a shard (some next uid is 0)");
-            return RT_ERR_INVALID;
-        }
         const int32_t L = S->pn_order, NM = L == 2 ? 6 : 10;
         const size_t nm = (size_t)NM * std::max<size_t>(1, (size_t)nc * G);
         RT_HIP(S->pn_mom.reserve(nm)); RT_HIP(S->pn_qr.reserve(nm));
@@ -1206,23 +1209,15 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
         if (int rc = solver_repro_reserve(S, who)) return rc;
         loan.repro = true; loan.repro_delta = S->delta.p; loan.repro_cap = S->delta.cap;
     }
-    if (S->single) {  // (the setters keep the combinations apart; a solver that got here with one is refused like them)
-        if (smode != SweepMode::Flat || S->repro) { set_error("%s: the single-precision sweep (rt_solver_set_precision) together with first-moment scattering, the linear source or the reproducible tallies is not supported", who); return RT_ERR_INVALID; }
-        loan.f32 = true;
-    }
+    loan.f32 = S->single;
     const bool reg = S->reg_R > 0;
-    if (reg) {  // (the setters keep the combinations apart; the links may have become a shard's since)
-        if (S->repro || S->single) { set_error("%s: the region currents (rt_solver_set_regions) together with the reproducible tallies or the single-precision sweep are not supported", who); return RT_ERR_INVALID; }
-        if (t->sw_shard) { set_error("%s: region currents are set (rt_solver_set_regions) and the track set is a shard (some next uid is 0): regions on sharded runs are not supported", who); return RT_ERR_INVALID; }
+    if (reg) {
         loan.region = S->reg_cell.p; loan.iface_S = S->reg_S.p; loan.n_regions = S->reg_R;
         RT_HIP(hipMemsetAsync(S->reg_J.p, 0, (size_t)(S->reg_R + 1) * (S->reg_R + 1) * G * sizeof(double), s));
     }
     S->reg_tallied = false;
     const bool cm = reg && S->cm_on;
-    if (cm) {  // (the setters keep the two apart; a solver that got here with both is refused like them)
-        if (bnd && S->bnd_inc) { set_error("%s: the coarse-mesh acceleration is on (rt_solver_set_cmfd) and a boundary has an incoming flux (rt_solver_set_boundary): the two together are not supported", who); return RT_ERR_INVALID; }
-        RT_HIP(hipMemsetAsync(S->cm_info.p, 0, 4 * sizeof(int32_t), s));
-    }
+    if (cm) RT_HIP(hipMemsetAsync(S->cm_info.p, 0, 4 * sizeof(int32_t), s));
     S->cm_stepped = false;
     if (S->vc_mode) { loan.vc_ell = S->vc_ell.p; loan.vc_rows = S->vc_rows; loan.vc_gen = S->vc_gen; }
     if (S->sr_on) {
@@ -1368,20 +1363,6 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
 }
 
 // ---- restarted GMRES (rt_solver_set_krylov; "Krylov" in include/rt_segmentize.h) -----------------------------------------------------
-// What a solver with the option set cannot run together with, for the messages that name both sides; nullptr: nothing.
-const char *krylov_conflict(const rt_solver *S) {
-    return S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
-        : S->mode == SweepMode::PN ? "P2 / P3 scattering is set (rt_solver_set_scatter_pn)"
-        : (S->mode == SweepMode::Linear || S->ls_stage != 0) ? "the linear source is on (rt_solver_set_linear_source)"
-        : S->single ? "the single-precision sweep is set (rt_solver_set_precision)"
-        : S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
-        : (S->reg_R > 0 || S->cm_on) ? "region currents are set (rt_solver_set_regions, rt_solver_set_cmfd)"
-        : S->sr_on ? "source regions are set (rt_solver_set_source_regions)"
-        : S->vc_mode ? "the volume correction is set (rt_solver_set_volume_correction)"
-        : (S->bnd_S > 0 && S->bnd_inc) ? "a boundary has an incoming flux (rt_solver_set_boundary: the iteration without its source is then not its linear part)"
-        : S->t->sw_shard ? "the track set is a shard (some next uid is 0)" : nullptr;
-}
-
 void krylov_free(rt_solver *S) {
     S->kry_basis.release(); S->kry_x0.release(); S->kry_part.release(); S->kry_npart.release(); S->kry_coef.release(); S->kry_H.release();
     S->kry_beta.release();
@@ -1697,19 +1678,7 @@ int transient_begin_impl(rt_solver *S, int32_t D, const double *inv_velocity, co
         return RT_ERR_INVALID;
     }
     if (S->ran_adjoint) { set_error("%s: the last completed run was an adjoint run (rt_solver_set_adjoint): a transient starts from a forward eigenvalue run", who); return RT_ERR_INVALID; }
-    // the modes a transient does not run in: the message names both sides
-    const char *other = S->adjoint ? "adjoint mode is set (rt_solver_set_adjoint)"
-        : S->mode == SweepMode::Linear ? "the linear source is on (rt_solver_set_linear_source)"
-        : S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1: the time derivative of the current is not modelled)"
-        : S->mode == SweepMode::PN ? "P2 / P3 scattering is set (rt_solver_set_scatter_pn: the time derivative of the higher moments is not modelled)"
-        : S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
-        : (S->reg_R > 0 || S->cm_on) ? "region currents are set (rt_solver_set_regions, rt_solver_set_cmfd)"
-        : (S->bnd_S > 0 && S->bnd_inc) ? "a boundary has an incoming flux (rt_solver_set_boundary)"
-        : S->single ? "the single-precision sweep is set (rt_solver_set_precision)"
-        : S->vc_mode ? "the volume correction is set (rt_solver_set_volume_correction)"
-        : S->sr_on ? "source regions are set (rt_solver_set_source_regions)"
-        : S->t->sw_shard ? "the track set is a shard (some next uid is 0)" : nullptr;
-    if (other) { set_error("%s: %s, and a transient together with it is not supported", who, other); return RT_ERR_INVALID; }
+    if (option_refused(S, who, Option::Transient, 0)) return RT_ERR_INVALID;
     const int32_t G = S->G, M = S->M, nc = S->n_cells;
     const size_t mg = (size_t)M * G, md = (size_t)M * D;
     for (size_t i = 0; i < mg; ++i)
@@ -1901,10 +1870,7 @@ static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) 
     if (!S) { set_error("rt_solver_set_scatter_p1: null solver"); return RT_ERR_INVALID; }
     if (S->open) { set_error("rt_solver_set_scatter_p1: a run is open (rt_solver_begin without rt_solver_end): the tables cannot change under it"); return RT_ERR_INVALID; }
     if (!sigma_s1) { if (S->mode == SweepMode::P1) S->mode = SweepMode::Flat; return RT_SUCCESS; }
-    if (S->mode == SweepMode::Linear) { set_error("rt_solver_set_scatter_p1: the linear source is on, and the two together are not supported"); return RT_ERR_INVALID; }
-    if (pn_refuses(S, "rt_solver_set_scatter_p1", "first-moment scattering of its own (rt_solver_set_scatter_pn carries Σs1; order 0 switches it off)")) return RT_ERR_INVALID;
-    if (S->kry_m > 0) { set_error("rt_solver_set_scatter_p1: restarted GMRES is set (rt_solver_set_krylov), and first-moment scattering together with it is not supported"); return RT_ERR_INVALID; }
-    if (S->single) { set_error("rt_solver_set_scatter_p1: the single-precision sweep is set (rt_solver_set_precision), and first-moment scattering together with it is not supported"); return RT_ERR_INVALID; }
+    if (option_refused(S, "rt_solver_set_scatter_p1", Option::P1)) return RT_ERR_INVALID;
     const int32_t G = S->G, M = S->M;
     const size_t n1 = (size_t)M * G * G;
     for (size_t i = 0; i < n1; ++i)
@@ -1946,16 +1912,7 @@ static int32_t solver_set_scatter_pn_impl(rt_solver *S, int32_t order, const dou
         if (rc && was == SweepMode::PN) { S->mode = was; S->pn_order = was_order; }
         return rc;
     }
-    // what the P2 / P3 sweep does not run with: the message names both sides
-    const char *other = (S->mode == SweepMode::Linear || S->ls_stage != 0) ? "the linear source is on (rt_solver_set_linear_source)"
-        : S->single ? "the single-precision sweep is set (rt_solver_set_precision)"
-        : S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
-        : (S->reg_R > 0 || S->cm_on) ? "region currents are set (rt_solver_set_regions, rt_solver_set_cmfd)"
-        : S->sr_on ? "source regions are set (rt_solver_set_source_regions)"
-        : S->vc_mode ? "the volume correction is set (rt_solver_set_volume_correction)"
-        : S->kry_m > 0 ? "restarted GMRES is set (rt_solver_set_krylov)"
-        : S->t->sw_shard ? "the track set is a shard (some next uid is 0)" : nullptr;
-    if (other) { set_error("%s: %s, and P%d scattering together with it is not supported", who, other, order); return RT_ERR_INVALID; }
+    if (option_refused(S, who, Option::PN, order, rtopt::bit(Option::P1))) return RT_ERR_INVALID;  // (first-moment scattering that is set gives way: the table carries Σs1)
     const int32_t G = S->G, M = S->M;
     const size_t n1 = (size_t)M * G * G;
     for (int32_t l = 0; l < order; ++l)
@@ -2128,8 +2085,7 @@ static int32_t solver_set_boundary_impl(rt_solver *S, int32_t n_sides, const int
         }
         any_inc = any_inc || (incoming && incoming[i] > 0.0);
     }
-    if (any_inc && S->kry_m > 0) { set_error("%s: an incoming flux, and restarted GMRES is set (rt_solver_set_krylov) (the iteration without its source is then not its linear part): the two together are not supported", who); return RT_ERR_INVALID; }
-    if (any_inc && S->cm_on) { set_error("%s: an incoming flux, and the coarse-mesh acceleration is on (rt_solver_set_cmfd): the two together are not supported", who); return RT_ERR_INVALID; }
+    if (any_inc && option_refused(S, who, Option::Incoming)) return RT_ERR_INVALID;
     const size_t n2 = (size_t)(2 * n);
     std::vector<int8_t> side_end(std::max<size_t>(1, n2), -1), side_start(std::max<size_t>(1, n2), -1), side_entry(std::max<size_t>(1, n2), -1);
     std::vector<int32_t> src(std::max<size_t>(1, n2), -1);
@@ -2218,14 +2174,9 @@ static int32_t solver_set_regions_impl(rt_solver *S, int32_t n_regions, const in
     if (int rc = solver_check_epoch(S, who)) return rc;
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the regions cannot change under it", who); return RT_ERR_INVALID; }
     if (n_regions == 0 || !cell_region) { S->reg_R = 0; S->reg_tallied = false; S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
-    if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the coarse-mesh prolongation reads the compact records' cells), and region currents together with them are not supported", who); return RT_ERR_INVALID; }
-    if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and region currents together with it are not supported", who); return RT_ERR_INVALID; }
-    if (pn_refuses(S, who, "region currents (rt_solver_set_regions: another kernel)")) return RT_ERR_INVALID;
+    if (option_refused(S, who, Option::Regions)) return RT_ERR_INVALID;
     if (n_regions < 1 || n_regions > rtsweep::kMaxRegions) { set_error("%s: bad arguments (n_regions %d, need 1 .. %d)", who, n_regions, rtsweep::kMaxRegions); return RT_ERR_INVALID; }
-    if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and region currents — an atomic sum — together with them are not supported", who); return RT_ERR_INVALID; }
-    if (S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision: another kernel), and region currents together with it are not supported", who); return RT_ERR_INVALID; }
     rt_tracks *t = S->t;
-    if (t->sw_shard) { set_error("%s: the track set is a shard (some next uid is 0): regions on sharded runs are not supported", who); return RT_ERR_INVALID; }
     const size_t nc = (size_t)S->n_cells;
     for (size_t e = 0; e < nc; ++e)
         if (cell_region[e] < 0 || cell_region[e] >= n_regions) {
@@ -2261,12 +2212,9 @@ static int32_t solver_set_cmfd_impl(rt_solver *S, int32_t on, const double *coup
     if (int rc = solver_check_epoch(S, who)) return rc;
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the acceleration cannot change under it", who); return RT_ERR_INVALID; }
     if (!on) { S->cm_on = false; S->cm_stepped = false; return RT_SUCCESS; }
-    if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the prolongation reads the compact records' cells), and the coarse-mesh acceleration together with them is not supported", who); return RT_ERR_INVALID; }
-    if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the coarse-mesh acceleration together with it is not supported", who); return RT_ERR_INVALID; }
-    if (pn_refuses(S, who, "the coarse-mesh acceleration (rt_solver_set_cmfd: it needs the region currents)")) return RT_ERR_INVALID;
+    if (option_refused(S, who, Option::Cmfd)) return RT_ERR_INVALID;
     const int32_t R = S->reg_R, G = S->G, nc = S->n_cells;
     if (R <= 0) { set_error("%s: no regions are set (rt_solver_set_regions comes first: its regions are the coarse cells)", who); return RT_ERR_INVALID; }
-    if (S->bnd_S > 0 && S->bnd_inc) { set_error("%s: a boundary has an incoming flux (rt_solver_set_boundary), and the coarse-mesh acceleration together with it is not supported", who); return RT_ERR_INVALID; }
     if (!(relax > 0.0 && relax <= 1.0)) { set_error("%s: relax = %g (must lie in (0, 1])", who, relax); return RT_ERR_INVALID; }
     if (max_iter < 0 || !(tol >= 0.0) || !std::isfinite(tol)) { set_error("%s: bad arguments (cmfd_max_iter %d, cmfd_tol %g)", who, max_iter, tol); return RT_ERR_INVALID; }
     if (coupling)
@@ -2426,9 +2374,6 @@ static int32_t solver_ls_geometry_stage(rt_solver *S, int32_t stage, bool staged
         set_error("%s: the tracks were segmentized again after rt_solver_create: create a new solver", who);
         return RT_ERR_INVALID;
     }
-    if (S->mode == SweepMode::P1) { set_error("%s: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported", who); return RT_ERR_INVALID; }
-    if (pn_refuses(S, who, "the linear source (rt_solver_set_linear_source)")) return RT_ERR_INVALID;
-    if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the linear source together with it is not supported", who); return RT_ERR_INVALID; }
     if (staged && S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the geometry cannot change under it", who); return RT_ERR_INVALID; }
     if (stage != 0 && stage != S->ls_stage) {
         set_error("%s: stage %d out of order (%s)", who, stage,
@@ -2500,12 +2445,7 @@ int32_t rt_solver_set_linear_source(rt_solver *solver, int32_t on) {
     if (!solver) { set_error("rt_solver_set_linear_source: null solver"); return RT_ERR_INVALID; }
     if (solver->open) { set_error("rt_solver_set_linear_source: a run is open (rt_solver_begin without rt_solver_end): the source's shape cannot change under it"); return RT_ERR_INVALID; }
     if (!on) { if (solver->mode == SweepMode::Linear) solver->mode = SweepMode::Flat; return RT_SUCCESS; }
-    if (solver->mode == SweepMode::P1) { set_error("rt_solver_set_linear_source: first-moment scattering is set (rt_solver_set_scatter_p1), and the two together are not supported"); return RT_ERR_INVALID; }
-    if (pn_refuses(solver, who, "the linear source (rt_solver_set_linear_source)")) return RT_ERR_INVALID;
-    if (solver->kry_m > 0) { set_error("rt_solver_set_linear_source: restarted GMRES is set (rt_solver_set_krylov), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
-    if (solver->single) { set_error("rt_solver_set_linear_source: the single-precision sweep is set (rt_solver_set_precision), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
-    if (solver->sr_on) { set_error("rt_solver_set_linear_source: source regions are set (rt_solver_set_source_regions: the centroids and C matrices are per cell), and the linear source together with them is not supported"); return RT_ERR_INVALID; }
-    if (solver->vc_mode) { set_error("rt_solver_set_linear_source: the volume correction is set (rt_solver_set_volume_correction: scaled chords would move the linear source's midpoints off the track), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
+    if (option_refused(solver, who, Option::Linear)) return RT_ERR_INVALID;
     return guarded(who, [&]() -> int32_t {
         if (!solver->has_geom)
             for (int32_t stage = 0; stage < 3; ++stage)
@@ -2519,8 +2459,7 @@ int32_t rt_solver_ls_geometry(rt_solver *solver, int32_t stage) {
     const char *who = "rt_solver_ls_geometry";
     if (!solver) { set_error("rt_solver_ls_geometry: null solver"); return RT_ERR_INVALID; }
     if (stage < 0 || stage > 2) { set_error("rt_solver_ls_geometry: bad arguments (stage %d)", stage); return RT_ERR_INVALID; }
-    if (solver->sr_on) { set_error("rt_solver_ls_geometry: source regions are set (rt_solver_set_source_regions), and the linear source together with them is not supported"); return RT_ERR_INVALID; }
-    if (solver->vc_mode) { set_error("rt_solver_ls_geometry: the volume correction is set (rt_solver_set_volume_correction), and the linear source together with it is not supported"); return RT_ERR_INVALID; }
+    if (option_refused(solver, who, Option::Linear)) return RT_ERR_INVALID;
     return guarded("rt_solver_ls_geometry", [&] { return solver_ls_geometry_stage(solver, stage, true, who); }, [&] { solver_ls_geometry_drop(solver); });
 }
 
@@ -2535,12 +2474,7 @@ static int32_t solver_set_reproducible_impl(rt_solver *S, int32_t on) {
     if (S->ls_stage != 0) { set_error("%s: the linear source's geometry is between two stages (rt_solver_ls_geometry)", who); return RT_ERR_INVALID; }
     const bool want = on != 0;
     if (want == S->repro) return RT_SUCCESS;
-    if (want && S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
-    if (want && pn_refuses(S, who, "the reproducible tallies (rt_solver_set_reproducible: its tallies are an atomic sum)")) return RT_ERR_INVALID;
-    if (want && S->single) { set_error("%s: the single-precision sweep is set (rt_solver_set_precision), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
-    if (want && S->reg_R > 0) { set_error("%s: region currents are set (rt_solver_set_regions: their tally is an atomic sum), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
-    if (want && S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions: the tally index is per original row slot), and the reproducible tallies together with them are not supported", who); return RT_ERR_INVALID; }
-    if (want && S->vc_mode) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction: its tracked lengths are an atomic sum), and the reproducible tallies together with it are not supported", who); return RT_ERR_INVALID; }
+    if (want && option_refused(S, who, Option::Repro)) return RT_ERR_INVALID;
     rt_tracks *t = S->t;
     if (int rc = finish_call(t)) return rc;
     RT_HIP(hipSetDevice(t->mesh->device));
@@ -2616,15 +2550,7 @@ int32_t rt_solver_set_precision(rt_solver *solver, int32_t precision) {
     if (int rc = solver_check_epoch(S, who)) return rc;
     if (S->open) { set_error("%s: a run is open (rt_solver_begin without rt_solver_end): the sweep cannot change under it", who); return RT_ERR_INVALID; }
     if (precision != RT_PRECISION_DOUBLE && precision != RT_PRECISION_SINGLE) { set_error("%s: precision %d (RT_PRECISION_DOUBLE = 0 or RT_PRECISION_SINGLE = 1)", who, precision); return RT_ERR_INVALID; }
-    if (precision == RT_PRECISION_SINGLE) {
-        if (pn_refuses(S, who, "the single-precision sweep (rt_solver_set_precision: another kernel)")) return RT_ERR_INVALID;
-        const char *other = S->mode == SweepMode::P1 ? "first-moment scattering is set (rt_solver_set_scatter_p1)"
-                                  : (S->mode == SweepMode::Linear ? "the linear source is on (rt_solver_set_linear_source)"
-                                           : (S->repro ? "the reproducible tallies are on (rt_solver_set_reproducible)"
-                                                       : (S->reg_R > 0 ? "region currents are set (rt_solver_set_regions: another kernel)"
-                                                                       : (S->kry_m > 0 ? "restarted GMRES is set (rt_solver_set_krylov)" : nullptr))));
-        if (other) { set_error("%s: %s, and the single-precision sweep together with it is not supported", who, other); return RT_ERR_INVALID; }
-    }
+    if (precision == RT_PRECISION_SINGLE && option_refused(S, who, Option::F32)) return RT_ERR_INVALID;
     S->single = precision == RT_PRECISION_SINGLE;
     return RT_SUCCESS;
 }
@@ -2642,12 +2568,7 @@ static int32_t solver_set_volume_correction_impl(rt_solver *S, int32_t mode) {
     }
     if (mode == S->vc_mode) return RT_SUCCESS;
     if (mode != RT_VOLUME_CORRECTION_OFF) {
-        if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and the volume correction together with it is not supported", who); return RT_ERR_INVALID; }
-        if (pn_refuses(S, who, "the volume correction (rt_solver_set_volume_correction)")) return RT_ERR_INVALID;
-        if (S->sr_on) { set_error("%s: source regions are set (rt_solver_set_source_regions), and the volume correction — its factors are per cell — together with them is not supported", who); return RT_ERR_INVALID; }
-        if (S->mode == SweepMode::Linear || S->ls_stage != 0) { set_error("%s: the linear source is on (rt_solver_set_linear_source: scaled chords would move its midpoints off the track), and the volume correction together with it is not supported", who); return RT_ERR_INVALID; }
-        if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible), and the volume correction — its tracked lengths are an atomic sum — together with them is not supported", who); return RT_ERR_INVALID; }
-        if (S->t->sw_shard) { set_error("%s: the track set is a shard (some next uid is 0): the tracked lengths of a shard are not the cells', and the volume correction on sharded runs is not supported", who); return RT_ERR_INVALID; }
+        if (option_refused(S, who, Option::VolCorr)) return RT_ERR_INVALID;
         S->vc_mode = mode;
         return RT_SUCCESS;
     }
@@ -2730,13 +2651,7 @@ static int32_t solver_set_source_regions_impl(rt_solver *S, const int32_t *map, 
         return RT_SUCCESS;
     }
     if (n_src < 1 || n_src > nm) { set_error("%s: bad arguments (n_src %d, need 1 .. the mesh's %d cells)", who, n_src, nm); return RT_ERR_INVALID; }
-    if (S->kry_m > 0) { set_error("%s: restarted GMRES is set (rt_solver_set_krylov), and source regions together with it are not supported", who); return RT_ERR_INVALID; }
-    if (pn_refuses(S, who, "source regions (rt_solver_set_source_regions)")) return RT_ERR_INVALID;
-    if (S->mode == SweepMode::Linear || S->ls_stage != 0) { set_error("%s: the linear source is on (rt_solver_set_linear_source: its centroids and C matrices are per cell), and source regions together with it are not supported", who); return RT_ERR_INVALID; }
-    if (S->repro) { set_error("%s: the reproducible tallies are on (rt_solver_set_reproducible: their tally index is per original row slot), and source regions together with them are not supported", who); return RT_ERR_INVALID; }
-    if (S->reg_R > 0 || S->cm_on) { set_error("%s: region currents are set (rt_solver_set_regions, rt_solver_set_cmfd: the coarse-mesh prolongation reads the compact records' cells), and source regions together with them are not supported", who); return RT_ERR_INVALID; }
-    if (S->vc_mode) { set_error("%s: the volume correction is set (rt_solver_set_volume_correction: its factors are per cell), and source regions together with it are not supported", who); return RT_ERR_INVALID; }
-    if (t->sw_shard) { set_error("%s: the track set is a shard (some next uid is 0): source regions on sharded runs are not supported", who); return RT_ERR_INVALID; }
+    if (option_refused(S, who, Option::SrcReg)) return RT_ERR_INVALID;
     std::vector<int32_t> rmat((size_t)n_src, -1), first((size_t)n_src + 1, 0), cells((size_t)nm);
     for (int32_t e = 0; e < nm; ++e) {
         const int32_t g = map[e];
@@ -2943,7 +2858,7 @@ int32_t rt_solver_set_krylov(rt_solver *solver, int32_t m, double tol_lin) {
             return RT_SUCCESS;
         });
     }
-    if (const char *other = krylov_conflict(S)) { set_error("%s: %s, and restarted GMRES together with it is not supported", who, other); return RT_ERR_INVALID; }
+    if (option_refused(S, who, Option::Krylov)) return RT_ERR_INVALID;
     S->kry_m = m; S->kry_tol_lin = tol_lin;
     return RT_SUCCESS;
 }
