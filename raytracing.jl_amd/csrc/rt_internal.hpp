@@ -8,7 +8,9 @@
 //   rt_volcorr.hip     rt_solver's volume correction: tracked lengths, factors, corrected volumes, ℓ' (k_vc_tally / _factor / _apply)
 //   rt_srcreg.hip      rt_solver's source regions: the sweep's rows merged per run of cells of one region (k_sr_count / _plan / _fill / _volumes)
 //   rt_krylov.hip      rt_solver's restarted GMRES: the Krylov vector kernels (k_kry_residual / _dots / _reduce / _update / _scale_store / _combine)
-//   rt_solver.hip      rt_solver: source iteration (k_eff / fixed source) around rt_sweep, fold / source / reduction kernels
+//   rt_solver.hip      rt_solver: source iteration (k_eff / fixed source) around rt_sweep, fold / source / reduction kernels, Krylov cycle, transient
+//   rt_solver_set.hip  rt_solver's options: setters, fetches, *_pointers, bilinear forms, the linear source's geometry and their kernels
+//   rt_solver_state.hpp  struct rt_solver (one nested struct per option) and what the two solver files share
 //   rt_segmentize.hip  handles, rt_tracks_create, rt_segmentize (the call's host logic), fetches, statistics
 #pragma once
 #include <hip/hip_runtime.h>

@@ -21,7 +21,7 @@ namespace rt {
 
 constexpr int kKryBlock = 256;
 
-// deterministic block sum of NV values (thread 0 gets the block's): block_sum of rt_solver.hip
+// deterministic block sum of NV values (thread 0 gets the block's): block_sum of rt_solver_state.hpp
 template <int NV>
 __device__ __forceinline__ void kry_block_sum(double (&v)[NV], double *red /* [kKryBlock / 64][NV] LDS */) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

@@ -1,7 +1,7 @@
 // rt_krylov_host.hpp — the small least-squares problem of rt_solver's restarted GMRES, on the host: min_y ‖β e₁ − H y‖ for the
 // (k + 1) x k upper Hessenberg H that grows by one column per Krylov vector.  Givens rotations keep H triangular as it grows, so the
 // residual norm of the GMRES iterate is known after every column without solving for y.  Host-only, no HIP types: the cycle driver
-// in rt_solver.hip includes it, and tests/krylov_host.cpp drives it alone.
+// in rt_solver.hip includes it (through rt_solver_state.hpp), and tests/krylov_host.cpp drives it alone.
 #pragma once
 #include <cmath>
 #include <cstddef>

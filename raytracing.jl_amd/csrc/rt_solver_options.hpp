@@ -1,6 +1,6 @@
 // rt_solver_options.hpp — which of rt_solver's run options are not supported together, written down once: one descriptor per option,
 // one row per unsupported pair, and the two messages every refusal is made of.  Pairs that are not listed run together.  No HIP call and
-// no allocation in here: rt_solver.hip makes the mask of what is set (solver_option_mask) and asks; tests/solver_options_host.cpp checks
+// no allocation in here: rt_solver_set.hip makes the mask of what is set (solver_option_mask) and asks; tests/solver_options_host.cpp checks
 // the table on the host, against plan_sweep's own refusals too (tests/test_solver_options_cpu.py, tests/sanitize/run.sh).  DESIGN.md §8
 // "Option compatibility" shows the table as a matrix.
 #pragma once

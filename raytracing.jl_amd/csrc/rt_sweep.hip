@@ -231,7 +231,7 @@ __global__ __launch_bounds__(256) void k_sweep_reduce(const int32_t *__restrict_
 // on: its volumes and the linear source's geometry were FP64 atomics too).  k_cell_values writes NV values of every record to the
 // forward half of the delta buffer, at the record's row slot, and zeros to the backward half (x + 0 = x: the order of the nonzero
 // terms is the index's); k_cell_reduce is k_sweep_reduce's sum into out[n_cells][NV].  KIND 0: w ℓ (volumes, NV = 1); 1: w ℓ (m_x,
-// m_y), 0; 2: the second moments about `cen` — the expressions of k_solver_ls_moments (rt_solver.hip), w = w_azim[azim − 1].
+// m_y), 0; 2: the second moments about `cen` — the expressions of k_solver_ls_moments (rt_solver_set.hip), w = w_azim[azim − 1].
 template <int KIND>
 __global__ __launch_bounds__(256) void k_cell_values(const int32_t *__restrict__ counts, const int64_t *__restrict__ offsets, const int32_t *__restrict__ perm,
                                                      int64_t n, const int32_t *__restrict__ ctab, const int32_t *__restrict__ azim,

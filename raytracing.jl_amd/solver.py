@@ -2,7 +2,7 @@
 records of the last ``segmentize`` — what the tracks and segments exist to feed (the reference's README:
 "computes quantities used to solve the transport equation").
 
-The iteration runs in ``librt_segmentize.so`` (``rt_solver_*``, ``csrc/rt_solver.hip``) around ``rt_sweep``:
+The iteration runs in ``librt_segmentize.so`` (``rt_solver_*``, ``csrc/rt_solver.hip``; the options' setters in ``csrc/rt_solver_set.hip``) around ``rt_sweep``:
 per iteration a source-update kernel, one sweep over G x P components (energy groups x polar angles),
 a fold kernel and a fixed-order reduction; only k, the residual and |Δk|/k come back to the host.
 The definitions (azimuthal and polar weights, volumes, fold, source, residual, normalisation) are stated

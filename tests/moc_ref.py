@@ -1,4 +1,4 @@
-"""Numpy twin of the device MOC solver (rt_solver, csrc/rt_solver.hip): the definitions of include/rt_segmentize.h, once.
+"""Numpy twin of the device MOC solver (rt_solver, csrc/rt_solver.hip and rt_solver_set.hip): the definitions of include/rt_segmentize.h, once.
 `Twin` is the iteration in the library's steps (begin, step_sweep, step_fold, end, the linear source's geometry in its three
 stages) over a given set of records — the ORACLE's in the tests — for the flat source, P1 scattering (`sigma_s1`) or the linear
 source (`linear`); the sweeps it calls stay where they are pinned against their loop forms (tests/sweep_ref.py `sweep_fast`,

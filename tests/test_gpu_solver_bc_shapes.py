@@ -23,7 +23,7 @@ workgroup; two of them with R = 10 or 25 rows in the reduction, where only its r
 3. twelve iterations against moc_ref_bc.BoundaryTwin in the P1, linear-source and adjoint modes with idle tally threads (G = 7) and
    in the linear-source mode at S·G > 256, at the bounds of tests/test_gpu_solver_bc.py.
 
-Every case first asserts the regime it is there for from the kernels' own constants, read from csrc/rt_solver.hip (a change of
+Every case first asserts the regime it is there for from the kernels' own constants, read from csrc/rt_solver_state.hpp (a change of
 kTallyEnds or kSolveBlock fails that assertion; it does not empty the test).  rt_sweep_info refuses between rt_solver_begin and the
 first sweep of a run (so does rt_sweep_fetch), so the addresses are taken in a one-sweep run before the run that is checked, and
 every later sweep asserts that they have not moved.
@@ -81,7 +81,7 @@ ENDS = dict(tiny=120, big=2096)
 def _constants():
     from raytracing_jl_amd import _capi
 
-    with open(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "csrc", "rt_solver.hip")) as f:
+    with open(os.path.join(os.path.dirname(os.path.abspath(_capi.__file__)), "csrc", "rt_solver_state.hpp")) as f:
         src = f.read()
     return {k: int(re.search(r"constexpr int %s = (\d+);" % k, src).group(1)) for k in ("kSolveBlock", "kTallyEnds", "kMaxSides")}
 

@@ -1,4 +1,4 @@
-"""rt_solver (csrc/rt_solver.hip) at the shapes where its kernels and the sweep under it branch, against the numpy twin
+"""rt_solver (csrc/rt_solver.hip, its setters in csrc/rt_solver_set.hip) at the shapes where its kernels and the sweep under it branch, against the numpy twin
 (tests/moc_ref.py over the ORACLE's records) and against analytic infinite-medium answers:
 
 1. polar sets with P = 1 … 8 and a custom pair, G·P mod 4 = 0 … 3 (the sweep's last pass 4, 1, 2, 3 components wide);

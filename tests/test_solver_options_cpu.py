@@ -28,7 +28,12 @@ def test_options_header_is_host_only():
 
 
 def test_solver_names_no_pair_itself():
-    """rt_solver.hip holds no text of its own that names two options as unsupported together: the table's formatters make them all."""
-    text = open(os.path.join(ROOT, "raytracing.jl_amd", "csrc", "rt_solver.hip"), encoding="utf-8").read()
-    assert not re.findall(r'"[^"\n]*(?:together with|the two together)[^"\n]*"', text)
-    assert "pn_refuses" not in text and "krylov_conflict" not in text
+    """No solver source file (rt_solver.hip, rt_solver_set.hip, rt_solver_state.hpp: every rt_solver* under csrc/ but the table itself)
+    holds text of its own that names two options as unsupported together: the table's formatters make them all."""
+    csrc = os.path.join(ROOT, "raytracing.jl_amd", "csrc")
+    names = sorted(f for f in os.listdir(csrc) if f.startswith("rt_solver") and f != "rt_solver_options.hpp")
+    assert {"rt_solver.hip", "rt_solver_set.hip", "rt_solver_state.hpp"} <= set(names), names
+    for name in names:
+        text = open(os.path.join(csrc, name), encoding="utf-8").read()
+        assert not re.findall(r'"[^"\n]*(?:together with|the two together)[^"\n]*"', text), name
+        assert "pn_refuses" not in text and "krylov_conflict" not in text, name

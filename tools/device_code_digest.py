@@ -6,7 +6,7 @@
 Takes every gfx950 code object out of the library's fat binary, disassembles it (llvm-objdump of the ROCm toolchain) and prints the
 number of functions, a hash of the sorted kernel symbol list and a hash of the per-function disassembly, functions sorted by name.
 What depends only on where the linker put a function is left out: the instructions' addresses (their encodings stay), the padding
-between functions, the symbol annotation of branch targets, the compile unit's id in symbol names; a pc-relative literal (s_getpc_b64
+between functions and behind the last one of a code object, the symbol annotation of branch targets, the compile unit's id in symbol names; a pc-relative literal (s_getpc_b64
 followed by s_add_u32 with a literal) is replaced by the symbol it lands on.  Two builds whose kernels are the same instructions
 print the same two hashes, whatever order the host code instantiated them in.  `out.s`: the normalised disassembly, for diff."""
 import hashlib
@@ -78,6 +78,9 @@ def main():
                 else:
                     line = re.sub(r" <[^>]+>$", "", line)
                 funcs[name].append(re.sub(r"// [0-9A-F]+: ", "// ", line).rstrip())
+    for body in funcs.values():  # the s_nop fill behind a function's last instruction: up to the next function, or the code object's tail
+        while body and re.match(r"^\s*s_nop 0\s+// BF800000$", body[-1]):
+            body.pop()
     text = "".join("<%s>:\n%s\n" % (k, "\n".join(funcs[k])) for k in sorted(funcs))
     if len(sys.argv) > 2:
         open(sys.argv[2], "w").write(text)
