@@ -409,14 +409,28 @@ RT_HD __noinline__ int32_t find_element_fallback(const DGeo &m, double x, double
     return -1;
 }
 
-// find_element (src/mesh.jl:103-146), 0-based cell id or -1.
-template <bool WIDEK = false>
+// The fallback for a caller that is inline in a kernel's loop: the mesh view travels BY VALUE and the cell's vertices come
+// back through a Tri of the cold branch.  Handed over by reference, the caller's DGeo and Tri are address-taken and live in the
+// kernel's scratch frame: every locate — every track's first record — then stores 144 + 60 bytes per lane in front of its
+// first dependent loads and reads the vertices back behind the scan.
+template <bool WIDEK>
+RT_HD __noinline__ int32_t find_element_fallback_v(const DGeo m, double x, double y, int k, int32_t nn_id, Tri &tri) {
+    return find_element_fallback<WIDEK>(m, x, y, k, nn_id, tri);
+}
+
+// find_element (src/mesh.jl:103-146), 0-based cell id or -1.  FRAMELESS: the caller keeps `m` and `tri` in registers (k_march;
+// the out-of-line generic steps hold both in their own frames anyway and pass them on as they are).
+template <bool WIDEK = false, bool FRAMELESS = false>
 RT_HD __forceinline__ int32_t find_element(const DGeo &m, double x, double y, int k, Tri &tri) {
     const int32_t nn_id = nearest_node(m, x, y);
     if (nn_id < 0) return -1;
     const int32_t c = first_cell_containing(m, nn_id, x, y, tri);
     if (c >= 0) return c;
-    return find_element_fallback<WIDEK>(m, x, y, k, nn_id, tri);
+    if (!FRAMELESS) return find_element_fallback<WIDEK>(m, x, y, k, nn_id, tri);
+    Tri tc;
+    const int32_t cf = find_element_fallback_v<WIDEK>(m, x, y, k, nn_id, tc);
+    if (cf >= 0) tri = tc;
+    return cf;
 }
 
 // ------------------------------------------------------- intersections -------------------
@@ -587,7 +601,7 @@ struct Walk {
 
 // State for the next walk step after a segment was emitted by the generic step in `cell` with
 // its exit point on edge `ko` (0..2).
-RT_HD __forceinline__ void walk_enter(const DMesh &m, const Tri &t, Walk &w, int32_t cell, int ko) {
+RT_HD __forceinline__ void walk_enter_geom(const Tri &t, Walk &w, int32_t cell, int ko) {
     const double x1 = t.x1, y1 = t.y1, x2 = t.x2, y2 = t.y2, x3 = t.x3, y3 = t.y3;
     w.T = cell;
     // det of the barycentric system in the cell's node order, with the reference's operations (src/mesh.jl:166-168): the
@@ -599,9 +613,28 @@ RT_HD __forceinline__ void walk_enter(const DMesh &m, const Tri &t, Walk &w, int
     w.by = ko == 0 ? y2 : (ko == 1 ? y3 : y1);
     w.cx = ko == 0 ? x3 : (ko == 1 ? x1 : x2);
     w.cy = ko == 0 ? y3 : (ko == 1 ? y1 : y2);
-    const int32_t a = ko == 0 ? t.adj[0] : (ko == 1 ? t.adj[1] : t.adj[2]);
-    w.pred = a != -2 ? a : m.adjr[3 * cell + ko];
     w.last = 3 * cell + ko;
+}
+// SCALARS: the three successors are read before one is chosen — the choice among the members themselves is compiled to an
+// indexed read, which keeps the caller's Tri in scratch memory (k_march with cheap steps holds it in registers; the other
+// instantiations keep the code they had).
+template <bool SCALARS = false>
+RT_HD __forceinline__ void walk_enter(const DMesh &m, const Tri &t, Walk &w, int32_t cell, int ko) {
+    walk_enter_geom(t, w, cell, ko);
+    int32_t a;
+    if (SCALARS) {
+        const int32_t a0 = t.adj[0], a1 = t.adj[1], a2 = t.adj[2];
+        a = ko == 0 ? a0 : (ko == 1 ? a1 : a2);
+    } else {
+        a = ko == 0 ? t.adj[0] : (ko == 1 ? t.adj[1] : t.adj[2]);
+    }
+    w.pred = a != -2 ? a : m.adjr[3 * cell + ko];
+}
+// The same for a cell whose vertices come from load_tri (no successors loaded: the table serves them).  A function of its own:
+// through walk_enter the choice among three `adj` that are all -2 became an indexed read of a Tri held in scratch memory.
+RT_HD __forceinline__ void walk_enter_cell(const DMesh &m, const DGeo &g, Walk &w, int32_t cell, int ko) {
+    walk_enter_geom(load_tri(g, cell), w, cell, ko);
+    w.pred = m.adjr[3 * cell + ko];
 }
 
 enum WalkResult { kWalkGeneric = 0, kWalkSkip = 1, kWalkEmit = 2 };
@@ -940,7 +973,7 @@ RT_HD __forceinline__ bool topo_enter(const DMesh &m, const TopoTrack &tt, const
 RT_HD __forceinline__ void topo_materialize(const DMesh &m, const DGeo &g, int32_t last, double tA, double tB, double tC, Walk &wk,
                                             double &lqx, double &lqy) {
     const int32_t cell = (int32_t)((uint32_t)last / 3u), ko = last - 3 * cell;
-    walk_enter(m, load_tri(g, cell), wk, cell, ko);
+    walk_enter_cell(m, g, wk, cell, ko);
     const RT_G EdgeABC *e = m.etab + last;
     edge_exit_point(tA, tB, tC, e->A, e->B, e->C, lqx, lqy);
 }

@@ -418,7 +418,7 @@ __global__ __launch_bounds__(64 * WAVES, (SPLIT && MODE == kStage && WAVES > 1) 
             const int32_t wl = ln.wk_last[slot];
             if (wl >= 0) {
                 const int32_t cell = (int32_t)((uint32_t)wl / 3u);
-                walk_enter(m, load_tri(load_geo(m.geo), cell), wk, cell, wl - 3 * cell);
+                walk_enter_cell(m, load_geo(m.geo), wk, cell, wl - 3 * cell);
             } else { wk.T = prev_element; wk.pred = -1; }
             xpx = lqx + sx; xpy = lqy + sy;  // :165
             fl = 0;
@@ -581,7 +581,7 @@ __global__ __launch_bounds__(64 * WAVES, (SPLIT && MODE == kStage && WAVES > 1) 
             asm volatile("" ::: "memory");
             fl &= ~kFlMat;
             const int32_t cell = (int32_t)((uint32_t)ts.last / 3u);
-            walk_enter(m, load_tri(load_geo(m.geo), cell), wk, cell, ts.last - 3 * cell);
+            walk_enter_cell(m, load_geo(m.geo), wk, cell, ts.last - 3 * cell);
             {   // the exit point of the lane's last (cheap) record, as k_materialise evaluates it: the reference re-seeds from it (:165)
                 const RT_G EdgeABC *e = m.etab + ts.last;
                 edge_exit_point(tA, tB, tC, e->A, e->B, e->C, lqx, lqy);
@@ -666,7 +666,7 @@ __global__ __launch_bounds__(64 * WAVES, (SPLIT && MODE == kStage && WAVES > 1) 
         if (__builtin_expect(res == kWalkGeneric, 0)) {
             const DGeo g = load_geo(m.geo);  // scalar loads, here only: the generic step's pointers and grid parameters
             Tri tri;
-            element = find_element<WIDEK>(g, xpx, xpy, prm.k, tri);   // :122 and :138-139
+            element = find_element<WIDEK, TOPO>(g, xpx, xpy, prm.k, tri);   // :122 and :138-139 (TOPO: every track's first record — no frame)
             if (element < 0) { st = RT_TRACK_LOCATE_FAILED; break; }  // :140-143
             // Creep: a track that leaves a cell at a very small angle next to a vertex takes hundreds of tiny
             // steps here (BWR-like config 4: 229 in a row through a 7e-8 sliver), each a full locate by one
@@ -699,7 +699,7 @@ __global__ __launch_bounds__(64 * WAVES, (SPLIT && MODE == kStage && WAVES > 1) 
                                                                   offsetof(MarchArgsLayout, fail_info)) + 15,
                               (unsigned long long)__popcll(act));
             }
-            if (m.walk_ok && eq >= 0) walk_enter(m, tri, wk, element, eq);
+            if (m.walk_ok && eq >= 0) walk_enter<TOPO>(m, tri, wk, element, eq);
             else { wk.T = element; wk.pred = -1; wk.last = -1; }
         }
         }
