@@ -3,8 +3,10 @@
 //   rt_march.hip       k_march (+ k_seed, k_resolve) and their launchers
 //   rt_records.hip     staging -> records: k_compact3, k_materialise, k_finish, the offsets scan, k_volumes, k_fill_tau
 //   rt_materialise.hip k_materialise_lin: a two-phase call's records in output order
-//   rt_sweep.hip       rt_sweep: k_sweep, k_sweep_link, the sweep's host code and entry points
-//   rt_sweep_plan.hpp  what an rt_sweep call decides (rows, pass width and shape, refusals): host-only, a pure function
+//   rt_sweep.hip       rt_sweep: k_sweep, k_sweep_link, the sweep's host code (one launch for every pass) and entry points
+//   rt_sweep_f32.hip, rt_sweep_iface.hip, rt_sweep_pn.hip  k_sweep_f32, k_sweep_iface, k_sweep_pn and the table of their instantiations
+//   rt_sweep_plan.hpp  what an rt_sweep call decides (rows, pass width and shape, refusals, the kernel of a pass): host-only, pure functions
+//   rt_sweep_state.hpp what the handle keeps for rt_sweep (rt_tracks::sw) and what a solver lends it (SweepLoan)
 //   rt_volcorr.hip     rt_solver's volume correction: tracked lengths, factors, corrected volumes, ℓ' (k_vc_tally / _factor / _apply)
 //   rt_srcreg.hip      rt_solver's source regions: the sweep's rows merged per run of cells of one region (k_sr_count / _plan / _fill / _volumes)
 //   rt_krylov.hip      rt_solver's restarted GMRES: the Krylov vector kernels (k_kry_residual / _dots / _reduce / _update / _scale_store / _combine)
@@ -413,7 +415,7 @@ struct DKrylov {
     double *part, *npart;                    // block partials: the dots [blocks][kKryStride], a squared norm [blocks]
     double *coef;                            // the coefficients of one Gram–Schmidt pass, then y [m + 1]
     double *H, *beta;                        // H [m][m + 1] (column k: h_{0..k+1,k}), ‖r₀‖
-    double *phi, *psi;                       // the live pieces: rt_solver::phi, rt_tracks::sw_psi_in
+    double *phi, *psi;                       // the live pieces: rt_solver::phi, rt_tracks::sw.io.psi_in
 };
 constexpr int kKryStride = 72;               // doubles per block partial row of the dots (up to 65 of them)
 constexpr int kKryMaxBlocks = 1024;
@@ -421,42 +423,7 @@ constexpr int kKryMaxBlocks = 1024;
 }  // namespace rt
 
 // ------------------------------------------------------------------- handles -------------
-// What an rt_solver lends its handle for the rt_sweep calls of a run: assigned once by solver_begin_impl, handed back whole by solver_release.
-struct SweepLoan {
-    rt_solver *borrower = nullptr;    // the solver that holds the handle's sweep state
-    SweepMode mode = SweepMode::Flat; // P1 / Linear: sw_xs1 holds the solver's ratios, sw_cur receives the moment tallies
-    const double *ls_cen = nullptr, *ls_ends = nullptr;  // Linear: the solver's centroids and track ends (DSweep cen, ends)
-    bool repro = false;               // reproducible tallies, into the solver's delta buffer
-    double *repro_delta = nullptr;
-    size_t repro_cap = 0;             // doubles
-    bool f32 = false;                 // single-precision sweep (rt_solver_set_precision)
-    const int32_t *region = nullptr;  // region currents (rt_solver_set_regions): the cells' regions [n_cells] (DSweep if_region),
-    double *iface_S = nullptr;        // the sweep's tally S [(R + 1)][(R + 1)][components], zeroed by every sweep (DSweep if_S),
-    int32_t n_regions = 0;            // and R (0: off)
-    int32_t pn_M = 0;                 // PN: the order (2, 3), the solver's ratios [n_cells · G][2M + 1] and higher tallies [n_cells · G][2M]
-    const double *pn_h = nullptr;     // (DSweep pn_h, pn_t)
-    double *pn_t = nullptr;
-    // volume correction (rt_solver_set_volume_correction): the solver's ℓ' of every row slot (DSweep ell_rows in place of sw_ell), made
-    const double *vc_ell = nullptr;   // from the rows `vc_rows` as they stood at generation `vc_gen` (rt_tracks::sw_rows_gen)
-    rtsweep::SweepRows vc_rows = rtsweep::SweepRows::Records;
-    uint64_t vc_gen = 0;
-    // source regions (rt_solver_set_source_regions): n_src (0: off) and the solver's merged rows — chunk table, words (region + 1), ℓ',
-    // runs per uid — in place of DSweep stg.ctab, stg.element, ell_rows and counts, made from the rows `sr_rows` at generation `sr_gen`
-    int32_t sr_n_src = 0;
-    const int32_t *sr_ctab = nullptr, *sr_cell = nullptr, *sr_counts = nullptr;
-    const double *sr_ell = nullptr;
-    rtsweep::SweepRows sr_rows = rtsweep::SweepRows::Records;
-    uint64_t sr_gen = 0;
-};
-
-// rt_sweep.hip sweep_rows_for_loan: the (ℓ, cell) rows a sweep under a loan would read, made and described
-struct SweepRowsView {
-    rtsweep::SweepRows rows = rtsweep::SweepRows::Records;
-    const int32_t *ctab = nullptr, *cell_rows = nullptr;  // chunk table [n_waves][kMaxChunks]; cell words by row slot
-    const double *ell_rows = nullptr;                     // ℓ by row slot
-    int64_t slots = 0;                                    // row slots behind the two arrays
-    uint64_t gen = 0;                                     // rt_tracks::sw_rows_gen of these rows
-};
+#include "rt_sweep_state.hpp"  // SweepLoan, SweepRowsView, SweepState: rt_tracks::sw
 
 struct rt_mesh {
     int device = 0;
@@ -639,34 +606,7 @@ struct rt_tracks {
     int32_t last_completion = 0;       // rt_last_stats: the last call wrote its records beside the march
     bool in_flight = false;  // option "async": the last rt_segmentize returned while its compaction was still on the stream
     unsigned long long call_seq = 0;  // sequence number the scan writes behind its host copy of the control block
-    // rt_sweep: the gather map of the cyclic linking, per-track weights, cross sections, boundary fluxes, tallies
-    DevBuf<int32_t> sw_src;
-    DevBuf<double> sw_w, sw_xs, sw_psi_in, sw_psi_out, sw_phi;
-    DevBuf<double> sw_xs1, sw_cur;  // the P1 sweep's first-moment ratios and tallies, the linear source's gradient ratios and moment tallies
-                                    // (DSweep xs1, cur): the rt_solver that holds the loan owns their content
-    SweepLoan sw_loan;              // what an rt_solver lends for the sweeps of its run (all of it goes back at once: solver_release)
-    DevBuf<double> sw_ell;      // ℓ of every staged row (slot-indexed like the staging pool), left by the first staged pass after a call
-    bool sw_ell_valid = false;  // ... of the last rt_segmentize
-    DevBuf<int32_t> sw_cell;    // codes: cell + 1 of every staged row, beside sw_ell (k_materialise<.., ROWS>)
-    DevBuf<int32_t> sw_ctab, sw_plan;  // rows made from the COMPACT records (rt_sweep.hip ensure_rows_from_compact): their own chunk table
-    bool sw_rowsc_valid = false;       // ... sw_ell / sw_cell hold those rows for the last rt_segmentize
-    int64_t sw_rowsc_slots = 0;        // ... and their chunk table spans this many row slots
-    uint64_t sw_rows_gen = 0;          // counts every (re)making of sw_ell's content: a solver's ℓ' (SweepLoan::vc_ell) names the one it scaled
-    // reproducible tallies (rt_solver_set_reproducible; rt_sweep.hip sweep_repro_prepare): the cell index of the last rt_segmentize
-    // — CSR by cell, every cell's row slots in ascending (track uid, record index) — for the row variant `sw_ridx_kind` (0: none
-    // built; 1 the staging pool's slots, 2 the rows made from the compact records, 3 the compact records where they lie)
-    DevBuf<int32_t> sw_ridx_start, sw_ridx_list;  // [n_cells + 1], [total]
-    int sw_ridx_kind = 0;
-    int64_t sw_ridx_slots = 0;         // row slots of that variant: the delta buffer holds 2 · slots · NT · width doubles
-    int32_t sw_last_prec = 0;          // precision of the last sweep (rt_sweep_precision)
-    bool sw_links = false, sw_has_xs = false, sw_done = false;
-    bool sw_has_w = false;             // sw_w holds weights: a caller's (rt_sweep sets it) or a solver's (solver_release clears it)
-    // host copy of the links as rt_sweep_set_links got them, whatever their bc (rt_solver_set_boundary builds its own gather map
-    // from it): entry slot d'·n + v of source d·n + u (-1: the linked track is not in this track set), in [2][n]
-    std::vector<int32_t> sw_h_entry;
-    bool sw_shard = false;        // ... some next uid was 0: a shard's track set
-    uint64_t sw_links_epoch = 0;  // rt_sweep_set_links calls on this handle
-    int32_t sw_groups = 0, sw_last_input = 0, sw_last_gp = 0, sw_last_passes = 0, sw_last_rows = 0;
+    SweepState sw;  // rt_sweep: links, I/O buffers, (ℓ, cell) rows, the reproducible tallies' cell index, a solver's loan, the last sweep
     int64_t refusals[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // cheap-step refusals of the last call by certificate term
     int64_t n_near_rtol = 0, n_restarts = 0, n_exact_tally = 0;
     int64_t n_failed = 0, first_failed_uid = 0;
@@ -713,10 +653,11 @@ void launch_compaction(rt_tracks *t, const rt::DOut &out, hipStream_t s);
 int ensure_compacted(rt_tracks *t);
 int ensure_rows(rt_tracks *t);
 int ensure_rows_from_compact(rt_tracks *t);  // rt_sweep.hip
-// rt_sweep_f32.hip: one pass of the single-precision sweep kernel over `gp` components from a.g0 (a.use_lds: the tallies' LDS copy)
-int launch_sweep_f32(const rt::DSweep &a, int gp, size_t smem, int waves, unsigned blocks, hipStream_t s);
-int launch_sweep_iface(const rt::DSweep &a, SweepMode mode, size_t smem, int waves, unsigned blocks, hipStream_t s);  // rt_sweep_iface.hip
-int launch_sweep_pn(const rt::DSweep &a, size_t smem, int waves, unsigned blocks, hipStream_t s);  // rt_sweep_pn.hip
+// the sweep kernels of the three sibling units, by their template arguments (nullptr: no such instantiation); rt_sweep.hip's
+// sweep_pass_kernel is their one caller
+const void *sweep_kernel_f32(int gp, bool lds);                    // rt_sweep_f32.hip
+const void *sweep_kernel_iface(SweepMode mode, int gp, bool lds);  // rt_sweep_iface.hip
+const void *sweep_kernel_pn(int M, bool lds);                      // rt_sweep_pn.hip
 // rt_cmfd.hip: the LDS k_cmfd_solve asks for (0: does not fit; *resident: all G factors live there), and the coarse step of one fold
 size_t cmfd_solve_lds(int32_t R, int32_t G, bool *resident);
 int launch_cmfd_step(rt::DCmfd c, int32_t n_items, unsigned cblocks, hipStream_t s);

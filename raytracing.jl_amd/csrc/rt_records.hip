@@ -822,8 +822,8 @@ int launch_materialise(rt_tracks *t, const rt::DOut &out, hipStream_t s, bool re
     }
     if (rows) {
         const size_t slots = (size_t)t->pool_chunks * rt::kChunkRows * 64;
-        RT_HIP(t->sw_ell.reserve(slots > 0 ? slots : 1)); RT_HIP(t->sw_cell.reserve(slots > 0 ? slots : 1));
-        a.ell_rows = as_global(t->sw_ell.p); a.cell_rows = as_global(t->sw_cell.p);
+        RT_HIP(t->sw.rows.ell.reserve(slots > 0 ? slots : 1)); RT_HIP(t->sw.rows.cell.reserve(slots > 0 ? slots : 1));
+        a.ell_rows = as_global(t->sw.rows.ell.p); a.cell_rows = as_global(t->sw.rows.cell.p);
     }
     const unsigned blocks = (unsigned)a.n_units;
     if (records && !rows && lin_kernel_serves(t, out)) {
@@ -855,7 +855,7 @@ void launch_finish(rt_tracks *t, const rt::DOut &out, hipStream_t s, bool from_r
     const rt_tracks::CompactPlan &c = t->cplan;
     hipLaunchKernelGGL(rt::k_finish, dim3(1), dim3(rt::kFinishThreads), 0, s, c.d_whole, (const int32_t *)t->counts.p, t->status.p,
                        (const int64_t *)t->offsets.p, from_rows ? (const double *)nullptr : (const double *)t->sell.p, out.cap, c.stg,
-                       from_rows ? (const double *)t->sw_ell.p : (const double *)nullptr, c.rtol, t->marg.p,
+                       from_rows ? (const double *)t->sw.rows.ell.p : (const double *)nullptr, c.rtol, t->marg.p,
                        scale_volumes ? t->volumes.p : (double *)nullptr, t->vacc.p, t->mesh->n_cells, n_azim_2, d_ctl, h_res_dev, seq,
                        completion_order ? (const int64_t *)t->off_slot.p : (const int64_t *)nullptr);
 }
@@ -897,14 +897,12 @@ int ensure_compacted(rt_tracks *t) {
 
 // rt_sweep over a two-phase call's staging: the (ℓ, cell) rows, written by the call itself ("compact" = 0) or here on first use.
 int ensure_rows(rt_tracks *t) {
-    if (t->sw_ell_valid) return RT_SUCCESS;
+    if (t->sw.rows.ell_valid) return RT_SUCCESS;
     rt::DOut out{};
     out.delta_s = rt::as_global(t->delta_s.p);
     if (int rc = launch_materialise(t, out, t->mesh->stream, false, true, false, nullptr)) return rc;
     RT_HIP(hipGetLastError());
-    t->sw_ell_valid = true;
-    t->sw_rowsc_valid = false;  // (the same buffers)
-    ++t->sw_rows_gen;
+    t->sw.rows.hold_staged();  // (the same buffers: the rows made from the compact records are gone)
     return RT_SUCCESS;
 }
 

@@ -196,8 +196,8 @@ void free_tracks(rt_tracks *t) {
     t->volumes.release(); t->volumes_prev.release(); t->delta_s.release(); t->tau.release(); t->sigma_t.release();
     t->gpx.release(); t->gpy.release(); t->gqx.release(); t->gqy.release();
     t->gelement.release(); t->ctab.release(); t->cowner.release();
-    t->sw_src.release(); t->sw_w.release(); t->sw_xs.release(); t->sw_psi_in.release(); t->sw_psi_out.release(); t->sw_phi.release();
-    t->sw_ell.release(); t->sw_cell.release();
+    t->sw.links.src.release(); t->sw.io.w.release(); t->sw.io.xs.release(); t->sw.io.psi_in.release(); t->sw.io.psi_out.release(); t->sw.io.phi.release();
+    t->sw.rows.ell.release(); t->sw.rows.cell.release();
     t->side_px.release(); t->side_py.release(); t->side_qx.release(); t->side_qy.release(); t->side_el.release(); t->marg.release();
     t->vorder.release(); t->vw_wave.release(); t->vw_k.release(); t->w_base.release(); t->w_P.release();
     t->s_el.release(); t->s_eq.release(); t->p_count.release(); t->p_flags.release(); t->p_valid.release(); t->p_rel.release();
@@ -806,7 +806,7 @@ void rt_tracks_destroy(rt_tracks *tracks) {
     if (!tracks) return;
     (void)hipSetDevice(tracks->mesh->device);
     (void)finish_call(tracks);
-    solver_release(tracks->sw_loan.borrower);  // (a solver in the middle of a run must not reach for these tracks later)
+    solver_release(tracks->sw.loan.borrower);  // (a solver in the middle of a run must not reach for these tracks later)
     free_tracks(tracks);
 }
 
@@ -905,7 +905,7 @@ struct SegmentizeCall {
         n = t->n;
         t->segmentized = false;
         ++t->seg_epoch;
-        solver_release(t->sw_loan.borrower);  // (a solver's run in progress ends here: its records are going, and the handle's own sweeps weigh by δs again)
+        solver_release(t->sw.loan.borrower);  // (a solver's run in progress ends here: its records are going, and the handle's own sweeps weigh by δs again)
         t->tau_groups = 0;  // τ of the previous records is void
         for (double &v : t->ms) v = 0.0;
 
@@ -969,10 +969,7 @@ struct SegmentizeCall {
         out.dbg = m->compact_debug;
         t->compacted = false;
         t->completion_order = false;
-        t->sw_ell_valid = false;
-        t->sw_rowsc_valid = false;
-        ++t->sw_rows_gen;
-        t->sw_ridx_kind = 0;
+        t->sw.new_segmentation();  // (the rows and the cell index over them; the links, the I/O buffers and the last sweep's record stay)
         t->cplan = rt_tracks::CompactPlan{};
         t->last_split = 0;
         t->last_record_kernel = 0;
@@ -1435,7 +1432,7 @@ struct SegmentizeCall {
         if (pools_ok) {
             t->cplan.staged = true;
             if (do_compact) { t->compacted = !completion; t->completion_order = completion; }
-            if (topo && !do_compact) t->sw_ell_valid = true;  // (k_materialise left the (ℓ, cell) rows)
+            if (topo && !do_compact) t->sw.rows.ell_valid = true;  // (k_materialise left the (ℓ, cell) rows; the flag alone: begin() counted this call's generation)
             if (n > 0) {  // this call's scan has reset the other control block and (fused) left the accumulator zero
                 t->ctl_clean[1 - cb] = true; t->ctl_first_chunk[1 - cb] = reset_key;
                 t->vacc_clean = fuse;
@@ -1904,8 +1901,8 @@ int32_t rt_last_stats(rt_tracks *t, int64_t *stats, int32_t n) {
                    b(t->gqx) + b(t->gqy) + b(t->gelement) + b(t->ctab) + b(t->cowner) + b(t->vorder) + b(t->vw_wave) + b(t->vw_k) +
                    b(t->w_base) + b(t->w_P) + b(t->s_el) + b(t->s_eq) + b(t->p_count) + b(t->p_flags) + b(t->p_valid) + b(t->p_rel) + b(t->s_px) +
                    b(t->s_py) + b(t->s_qx) + b(t->s_qy) + b(t->s_ell) + b(t->p_sum) + b(t->vacc) + b(t->tau) +
-                   b(t->sigma_t) + b(t->sw_src) + b(t->sw_w) + b(t->sw_xs) + b(t->sw_psi_in) + b(t->sw_psi_out) + b(t->sw_phi) + b(t->sw_ell) +
-                   b(t->sw_cell) + b(t->side_px) + b(t->side_py) + b(t->side_qx) + b(t->side_qy) + b(t->side_el) + b(t->marg);
+                   b(t->sigma_t) + b(t->sw.links.src) + b(t->sw.io.w) + b(t->sw.io.xs) + b(t->sw.io.psi_in) + b(t->sw.io.psi_out) + b(t->sw.io.phi) + b(t->sw.rows.ell) +
+                   b(t->sw.rows.cell) + b(t->side_px) + b(t->side_py) + b(t->side_qx) + b(t->side_qy) + b(t->side_el) + b(t->marg);
     }
     return RT_SUCCESS;
 }

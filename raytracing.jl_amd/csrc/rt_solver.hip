@@ -468,8 +468,8 @@ namespace rtx {
 // Called with the tracks alive (rt_tracks_destroy calls it before it frees them).
 void solver_release(rt_solver *S) {
     if (!S || !S->run.open) return;
-    S->t->sw_loan = SweepLoan{};  // (an open run is the handle's borrower: solver_begin_impl ends every other one)
-    S->t->sw_has_w = false;
+    S->t->sw.loan = SweepLoan{};  // (an open run is the handle's borrower: solver_begin_impl ends every other one)
+    S->t->sw.io.has_w = false;
     S->run.open = false; S->run.swept = false;
     S->tr.open = false; S->tr.src = false;  // (a transient ends with its run: the solver's own tables were never written; kept: its tables and buffers, for the next one)
     S->kry.lin = false;
@@ -509,7 +509,7 @@ int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_m
     }
     if (G < 1 || M < 1 || P < 1 || (int64_t)G * P > 4096 || G > 256) { set_error("rt_solver_create: bad sizes (G = %d, M = %d, P = %d)", G, M, P); return RT_ERR_INVALID; }
     if (!t->segmentized) { set_error("rt_solver_create: rt_segmentize has not run"); return RT_ERR_INVALID; }
-    if (!t->sw_links) { set_error("rt_solver_create: rt_sweep_set_links has not run"); return RT_ERR_INVALID; }
+    if (!t->sw.links.set) { set_error("rt_solver_create: rt_sweep_set_links has not run"); return RT_ERR_INVALID; }
     rt_mesh *m = t->mesh;
     const int32_t nc = m->n_cells;
     const int32_t N2 = (int32_t)t->h_delta_s.size();
@@ -617,7 +617,7 @@ struct AbortRun { rt_solver *S; bool ok = false; ~AbortRun() { if (!ok) solver_r
 
 int solver_check_tracks(const rt_solver *S, const char *who) {
     if (int rc = solver_check_epoch(S, who)) return rc;
-    if (!S->t->sw_links) { set_error("%s: rt_sweep_set_links has not run", who); return RT_ERR_INVALID; }
+    if (!S->t->sw.links.set) { set_error("%s: rt_sweep_set_links has not run", who); return RT_ERR_INVALID; }
     return RT_SUCCESS;
 }
 
@@ -639,7 +639,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
     rt_tracks *t = S->t;
     if (int rc = solver_check_tracks(S, who)) return rc;
     const bool bnd = S->bnd.S > 0;
-    if (bnd && S->bnd.links_epoch != t->sw_links_epoch) {
+    if (bnd && S->bnd.links_epoch != t->sw.links.epoch) {
         set_error("%s: rt_sweep_set_links ran again after rt_solver_set_boundary (its gather map is stale): set the boundary again", who);
         return RT_ERR_INVALID;
     }
@@ -657,7 +657,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
             return RT_ERR_INVALID;
         }
     }
-    if (t->sw_loan.borrower) solver_release(t->sw_loan.borrower);  // (another solver's unfinished run on this handle ends here)
+    if (t->sw.loan.borrower) solver_release(t->sw.loan.borrower);  // (another solver's unfinished run on this handle ends here)
     rt_mesh *m = t->mesh;
     if (int rc = finish_call(t)) return rc;
     RT_HIP(hipSetDevice(m->device));
@@ -671,12 +671,12 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
         if (int rc = solver_srcreg_prepare(S, who)) return rc;
     // the handle's sweep state: C components, zero boundary fluxes, the solver's track weights
     const size_t npsi = (size_t)std::max<int64_t>(1, 2 * n * C), nxs = std::max<size_t>(1, (size_t)std::max(nc, m->n_cells) * C);  // (rt_sweep clears the mesh's cells' worth)
-    RT_HIP(t->sw_psi_in.reserve(npsi)); RT_HIP(t->sw_psi_out.reserve(npsi)); RT_HIP(t->sw_phi.reserve(nxs));
-    RT_HIP(t->sw_xs.reserve(2 * nxs));
-    RT_HIP(hipMemsetAsync(t->sw_psi_in.p, 0, npsi * sizeof(double), s));
-    RT_HIP(t->sw_w.reserve(std::max<int64_t>(1, n)));
-    if (n > 0) RT_HIP(hipMemcpyAsync(t->sw_w.p, S->w_track.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
-    t->sw_groups = C; t->sw_has_xs = true; t->sw_has_w = true; t->sw_done = false;
+    RT_HIP(t->sw.io.psi_in.reserve(npsi)); RT_HIP(t->sw.io.psi_out.reserve(npsi)); RT_HIP(t->sw.io.phi.reserve(nxs));
+    RT_HIP(t->sw.io.xs.reserve(2 * nxs));
+    RT_HIP(hipMemsetAsync(t->sw.io.psi_in.p, 0, npsi * sizeof(double), s));
+    RT_HIP(t->sw.io.w.reserve(std::max<int64_t>(1, n)));
+    if (n > 0) RT_HIP(hipMemcpyAsync(t->sw.io.w.p, S->w_track.p, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s));
+    t->sw.io.groups = C; t->sw.io.has_xs = true; t->sw.io.has_w = true; t->sw.last.done = false;
     // the run is open from here on (whatever ends it goes through solver_release); the loan becomes the handle's once nothing refuses
     SweepLoan loan = solver_loan_probe(S);
     loan.borrower = S;
@@ -698,7 +698,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
         DevBuf<double> &mom0 = p1 ? S->p1.J : S->ls.mom, &ratio = p1 ? S->p1.q1r : S->ls.gr;
         const size_t nj = 2 * std::max<size_t>(1, (size_t)nc * G);
         RT_HIP(mom0.reserve(nj)); RT_HIP(ratio.reserve(nj));
-        RT_HIP(t->sw_xs1.reserve(2 * nxs)); RT_HIP(t->sw_cur.reserve(2 * nxs));
+        RT_HIP(t->sw.io.xs1.reserve(2 * nxs)); RT_HIP(t->sw.io.cur.reserve(2 * nxs));
         RT_HIP(hipMemsetAsync(mom0.p, 0, nj * sizeof(double), s));
         if (!p1) { loan.ls_cen = S->ls.cen.p; loan.ls_ends = S->ls.ends.p; }
     }
@@ -720,13 +720,13 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
         loan.sr_n_src = nc; loan.sr_ctab = S->sr.ctab.p; loan.sr_cell = S->sr.cell.p; loan.sr_ell = S->sr.ell.p; loan.sr_counts = S->sr.counts.p;
         loan.sr_rows = S->sr.rows; loan.sr_gen = S->sr.gen;
     }
-    t->sw_loan = loan;
+    t->sw.loan = loan;
     S->bnd.tallied = false;
     if (bnd) RT_HIP(hipMemsetAsync(S->bnd.J.p, 0, (size_t)2 * S->bnd.S * G * sizeof(double), s));
     if (bnd && S->bnd.inc && n > 0)  // the first sweep already sees the incoming flux
         hipLaunchKernelGGL(rt::k_solver_bnd_link<true>, dim3((unsigned)((2 * n * C + 255) / 256)), dim3(256), 0, s, (const int32_t *)S->bnd.src.p,
                            (const int8_t *)S->bnd.side_entry.p, (const double *)S->bnd.beta.p, (const double *)S->bnd.incv.p,
-                           (const double *)nullptr, t->sw_psi_in.p, 2 * n, G, P, n);
+                           (const double *)nullptr, t->sw.io.psi_in.p, 2 * n, G, P, n);
     S->k_hist.clear();
     for (int i = 0; i < 5; ++i) S->kry.info[i] = 0;
     S->kry.res.clear(); S->kry.lin = false;
@@ -737,7 +737,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
     if (!keep_phi) {
         RT_HIP(hipMemsetAsync(S->prod.p, 0, (size_t)std::max(1, nc) * sizeof(double), s));
         hipLaunchKernelGGL(rt::k_solver_fold<true>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
-                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)nullptr, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P, S->partial.p);
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)nullptr, t->sw.io.xs.p, S->phi.p, S->prod.p, nc, G, P, S->partial.p);
         hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)d.cblocks, 1, eigen ? 1 : 0, S->scal.p);
     }
     RT_HIP(hipGetLastError());
@@ -757,17 +757,17 @@ int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
     const double *tab = S->tr.open ? S->tr.tab.p : S->tab.p;
     hipLaunchKernelGGL(rt::k_solver_source, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
                        tab, d.lds_len, (const double *)S->phi.p, (const double *)S->prod.p, ext, (const double *)S->scal.p, eig,
-                       nc, G, P, t->sw_xs.p);
+                       nc, G, P, t->sw.io.xs.p);
     if (S->run.mode == SweepMode::P1)
         hipLaunchKernelGGL(rt::k_solver_source_p1, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds1_len * sizeof(double), s, (const int32_t *)S->mat.p,
-                           (const double *)S->p1.tab.p, d.lds1_len, (const double *)S->p1.J.p, (const double *)S->pol.p, nc, G, P, S->p1.q1r.p, t->sw_xs1.p);
+                           (const double *)S->p1.tab.p, d.lds1_len, (const double *)S->p1.J.p, (const double *)S->pol.p, nc, G, P, S->p1.q1r.p, t->sw.io.xs1.p);
     if (S->run.mode == SweepMode::PN)
         hipLaunchKernelGGL(rt::k_solver_source_pn, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->pn.tab.p,
-                           (const double *)S->pn.mom.p, (const double *)S->pol.p, (const double *)t->sw_xs.p, nc, G, P, S->run.pn, S->pn.qr.p, S->pn.h.p);
+                           (const double *)S->pn.mom.p, (const double *)S->pol.p, (const double *)t->sw.io.xs.p, nc, G, P, S->run.pn, S->pn.qr.p, S->pn.h.p);
     if (S->run.mode == SweepMode::Linear)
         hipLaunchKernelGGL(rt::k_solver_source_ls, dim3(d.sblocks), dim3(rt::kSolveBlock), (size_t)d.lds_len * sizeof(double), s, (const int32_t *)S->mat.p,
                            (const double *)S->tab.p, d.lds_len, (const double *)S->ls.mom.p, (const double *)S->ls.cinv.p, (const double *)S->pol.p,
-                           (const double *)S->scal.p, eig, nc, G, P, S->ls.gr.p, t->sw_xs1.p);
+                           (const double *)S->scal.p, eig, nc, G, P, S->ls.gr.p, t->sw.io.xs1.p);
     RT_HIP(hipGetLastError());
     const int64_t n = t->n;
     const bool bnd = S->run.bnd && n > 0;  // (no tracks: J stays the zeros of rt_solver_begin)
@@ -776,7 +776,7 @@ int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
         hipLaunchKernelGGL(rt::k_solver_bnd_tally, dim3((unsigned)S->bnd.blocks), dim3(rt::kSolveBlock), 0, s, side, (const double *)S->w_track.p,
                            (const double *)S->pol.p, psi, 2 * n, n, G, P, S->bnd.S, part);
     };
-    if (bnd) tally(S->bnd.side_start.p, t->sw_psi_in.p, S->bnd.part.p + (size_t)S->bnd.blocks * SG);  // J⁻: the flux that enters this sweep
+    if (bnd) tally(S->bnd.side_start.p, t->sw.io.psi_in.p, S->bnd.part.p + (size_t)S->bnd.blocks * SG);  // J⁻: the flux that enters this sweep
     if (int32_t rc = rt_sweep(t, d.C, nullptr, nullptr, nullptr, nullptr, 0, nullptr)) return rc;
     if (S->run.reg && n > 0) {  // J of this sweep from its S, behind the last pass (no tracks: the zeros of rt_solver_begin)
         const int32_t pairs = (S->reg.R + 1) * (S->reg.R + 1);
@@ -786,12 +786,12 @@ int solver_queue_sweep(rt_solver *S, const SolverDims &d) {
     }
     S->reg.tallied = S->run.reg;
     if (bnd) {  // J⁺ of this sweep, then the hand-over behind the sided ends over what k_sweep_link wrote
-        tally(S->bnd.side_end.p, t->sw_psi_out.p, S->bnd.part.p);
+        tally(S->bnd.side_end.p, t->sw.io.psi_out.p, S->bnd.part.p);
         hipLaunchKernelGGL(rt::k_solver_bnd_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->bnd.part.p,
                            (const double *)(S->bnd.part.p + (size_t)S->bnd.blocks * SG), S->bnd.blocks, SG, S->bnd.J.p);
         hipLaunchKernelGGL(rt::k_solver_bnd_link<false>, dim3((unsigned)((2 * n * d.C + 255) / 256)), dim3(256), 0, s, (const int32_t *)S->bnd.src.p,
                            (const int8_t *)S->bnd.side_entry.p, (const double *)S->bnd.beta.p, (const double *)S->bnd.incv.p,
-                           (const double *)t->sw_psi_out.p, t->sw_psi_in.p, 2 * n, G, P, n);
+                           (const double *)t->sw.io.psi_out.p, t->sw.io.psi_in.p, 2 * n, G, P, n);
         RT_HIP(hipGetLastError());
     }
     S->bnd.tallied = S->run.bnd;
@@ -810,18 +810,18 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
         RT_HIP(hipMemcpyAsync(S->cm.prev.p, S->scal.p, rt::kSolveScalars * sizeof(double), hipMemcpyDeviceToDevice, s));
     }
     hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)(S->tr.open ? S->tr.tab.p : S->tab.p),
-                       (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, nc, G, P,
+                       (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw.io.phi.p, t->sw.io.xs.p, S->phi.p, S->prod.p, nc, G, P,
                        S->partial.p);
     if (S->run.mode == SweepMode::P1)
         hipLaunchKernelGGL(rt::k_solver_fold_p1, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->p1.tab.p,
-                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->p1.q1r.p, nc, G, P, S->p1.J.p);
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw.io.cur.p, (const double *)S->p1.q1r.p, nc, G, P, S->p1.J.p);
     if (S->run.mode == SweepMode::PN)
         hipLaunchKernelGGL(rt::k_solver_fold_pn, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->pn.tab.p,
-                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, (const double *)S->pn.t.p,
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw.io.phi.p, (const double *)S->pn.t.p,
                            (const double *)S->pn.qr.p, nc, G, P, S->run.pn, S->pn.mom.p);
     if (S->run.mode == SweepMode::Linear)
         hipLaunchKernelGGL(rt::k_solver_fold_ls, dim3(d.sblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)S->tab.p,
-                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_cur.p, (const double *)S->ls.gr.p,
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw.io.cur.p, (const double *)S->ls.gr.p,
                            (const double *)S->ls.cmat.p, (const double *)S->ls.cinv.p, nc, G, P, S->ls.mom.p);
     hipLaunchKernelGGL(rt::k_solver_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)S->partial.p, (int32_t)d.cblocks, 0, S->run.eigen ? 1 : 0, S->scal.p);
     if (cm) {  // the coarse step on φ^{n+½}, k^{n+½} and the last sweep's J: restriction, solve, prolongation, the scalars again
@@ -830,7 +830,7 @@ int solver_queue_fold(rt_solver *S, const SolverDims &d, rt_solver_result *res, 
         c.n = t->n; c.theta = S->cm.theta; c.tol = S->cm.tol;
         c.mat = S->mat.p; c.cell_region = S->reg.cell.p; c.tab = S->tab.p; c.vol = S->vol.p;
         c.ext = (!S->run.eigen && S->has_ext) ? S->ext.p : nullptr;
-        c.phi = S->phi.p; c.prod = S->prod.p; c.psi_in = t->sw_psi_in.p;
+        c.phi = S->phi.p; c.prod = S->prod.p; c.psi_in = t->sw.io.psi_in.p;
         c.mom = S->run.mode == SweepMode::P1 ? S->p1.J.p : (S->run.mode == SweepMode::Linear ? S->ls.mom.p : nullptr);
         c.phi_old = S->cm.phi_old.p; c.prod_old = S->cm.prod_old.p; c.scal_prev = S->cm.prev.p; c.scal = S->scal.p; c.partial = S->partial.p;
         c.cells = S->cm.cells.p; c.item_begin = S->cm.item_begin.p; c.item_end = S->cm.item_end.p; c.reg_first = S->cm.reg_first.p;
@@ -909,7 +909,7 @@ int solver_krylov_cycle(rt_solver *S, const SolverDims &d, int32_t budget, doubl
     rt::DKrylov a{};
     a.nphi = d.ncg; a.N = S->kry.work.N; a.Ns = S->kry.work.Ns; a.m = m; a.blocks = (int32_t)krylov_blocks(S->kry.work.N);
     a.basis = S->kry.work.basis.p; a.x0 = S->kry.work.x0.p; a.part = S->kry.work.part.p; a.npart = S->kry.work.npart.p; a.coef = S->kry.work.coef.p;
-    a.H = S->kry.work.H.p; a.beta = S->kry.work.beta.p; a.phi = S->phi.p; a.psi = t->sw_psi_in.p;
+    a.H = S->kry.work.H.p; a.beta = S->kry.work.beta.p; a.phi = S->phi.p; a.psi = t->sw.io.psi_in.p;
     const int64_t npsi = a.N - a.nphi;
     if (a.nphi > 0) RT_HIP(hipMemcpyAsync(a.x0, a.phi, (size_t)a.nphi * sizeof(double), hipMemcpyDeviceToDevice, s));
     if (npsi > 0) RT_HIP(hipMemcpyAsync(a.x0 + a.nphi, a.psi, (size_t)npsi * sizeof(double), hipMemcpyDeviceToDevice, s));
@@ -938,7 +938,7 @@ int solver_krylov_cycle(rt_solver *S, const SolverDims &d, int32_t budget, doubl
         // A v_k: the sweep and the fold of the iteration without its source (no scalars, no history: they mean nothing here)
         if (int rc = solver_queue_sweep(S, d)) return rc;
         hipLaunchKernelGGL(rt::k_solver_fold<false>, dim3(d.cblocks), dim3(rt::kSolveBlock), 0, s, (const int32_t *)S->mat.p, (const double *)(S->tr.open ? S->tr.tab.p : S->tab.p),
-                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw_phi.p, t->sw_xs.p, S->phi.p, S->prod.p, d.nc, d.G, d.P,
+                           (const double *)S->vol.p, (const double *)S->pol.p, (const double *)t->sw.io.phi.p, t->sw.io.xs.p, S->phi.p, S->prod.p, d.nc, d.G, d.P,
                            S->partial.p);
         S->run.swept = false;
         ++S->run.it; S->k_hist.push_back(1.0);
@@ -1125,7 +1125,7 @@ rt::DTransient transient_args(const rt_solver *S, double dt) {
     a.mat = S->mat.p; a.ktab = S->tr.ktab.p; a.tab = S->tr.tab.p; a.pol = S->pol.p;
     a.phi = S->phi.p; a.prod = S->prod.p;
     a.phi_prev = S->tr.phi_prev.p; a.C = S->tr.C.p; a.ext = S->tr.ext.p;
-    a.xs = S->t->sw_xs.p; a.prod_out = S->prod.p;
+    a.xs = S->t->sw.io.xs.p; a.prod_out = S->prod.p;
     return a;
 }
 
@@ -1425,7 +1425,7 @@ int32_t rt_solver_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens) {
     return solver_pointers("rt_solver_pointers", solver, ptrs_dev, lens, [&]() -> PointerList {  // (the volumes and φ always, the tallies in an open run)
         const int64_t nc = solver->n_cells, C = (int64_t)solver->G * solver->P;
         const bool open = solver->run.open, mom = open && (solver->run.mode == SweepMode::P1 || solver->run.mode == SweepMode::Linear);  // (PN: rt_solver_pn_pointers)
-        return {true, 4, {{solver->vol.p, nc}, {open ? solver->t->sw_phi.p : nullptr, open ? nc * C : 0}, {mom ? solver->t->sw_cur.p : nullptr, mom ? 2 * nc * C : 0},
+        return {true, 4, {{solver->vol.p, nc}, {open ? solver->t->sw.io.phi.p : nullptr, open ? nc * C : 0}, {mom ? solver->t->sw.io.cur.p : nullptr, mom ? 2 * nc * C : 0},
                           {solver->phi.p, nc * solver->G}}};
     });
 }

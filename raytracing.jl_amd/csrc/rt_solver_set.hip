@@ -187,7 +187,7 @@ uint32_t solver_option_mask(const rt_solver *S) {
          | on(S->mode == SweepMode::Linear || S->ls.stage != 0, Option::Linear) | on(S->single, Option::F32) | on(S->rep.on, Option::Repro)
          | on(S->reg.R > 0, Option::Regions) | on(S->cm.on, Option::Cmfd) | on(S->sr.on, Option::SrcReg) | on(S->vc.mode != 0, Option::VolCorr)
          | on(S->kry.m > 0, Option::Krylov) | on(S->adjoint, Option::Adjoint) | on(S->bnd.S > 0 && S->bnd.inc, Option::Incoming)
-         | on(S->t->sw_shard, Option::Shard);
+         | on(S->t->sw.links.shard, Option::Shard);
 }
 
 // A setter's question: does something that is set (but for `ignore`) not run with `wanted`?  Then the message names both sides.
@@ -570,8 +570,8 @@ static int32_t solver_set_boundary_impl(rt_solver *S, int32_t n_sides, const int
     if (!end_side || !albedo) { set_error("%s: null argument", who); return RT_ERR_INVALID; }
     rt_tracks *t = S->t;
     const int64_t n = t->n;
-    if (!t->sw_links || (int64_t)t->sw_h_entry.size() != 2 * n) { set_error("%s: rt_sweep_set_links has not run", who); return RT_ERR_INVALID; }
-    if (t->sw_shard) {
+    if (!t->sw.links.set || (int64_t)t->sw.links.h_entry.size() != 2 * n) { set_error("%s: rt_sweep_set_links has not run", who); return RT_ERR_INVALID; }
+    if (t->sw.links.shard) {
         set_error("%s: the track set is a shard (some next uid is 0): boundaries on sharded runs are not supported", who);
         return RT_ERR_INVALID;
     }
@@ -604,7 +604,7 @@ static int32_t solver_set_boundary_impl(rt_solver *S, int32_t n_sides, const int
     for (int64_t u = 0; u < n; ++u)
         for (int d = 0; d < 2; ++d) {
             const size_t from = (size_t)d * n + u;
-            const int32_t slot = t->sw_h_entry[from];
+            const int32_t slot = t->sw.links.h_entry[from];
             if (slot < 0) continue;
             const bool sided = side_end[from] >= 0;
             src[(size_t)slot] = sided ? (int32_t)(u * 2 + d) : -1;
@@ -631,7 +631,7 @@ static int32_t solver_set_boundary_impl(rt_solver *S, int32_t n_sides, const int
     RT_HIP(hipStreamSynchronize(s));  // (the host vectors die here)
     S->bnd.src = std::move(d_src); S->bnd.side_entry = std::move(d_entry); S->bnd.side_end = std::move(d_end); S->bnd.side_start = std::move(d_start);
     S->bnd.beta = std::move(d_beta); S->bnd.incv = std::move(d_inc); S->bnd.part = std::move(d_part); S->bnd.J = std::move(d_J);
-    S->bnd.S = n_sides; S->bnd.blocks = blocks; S->bnd.inc = any_inc; S->bnd.tallied = false; S->bnd.links_epoch = t->sw_links_epoch;
+    S->bnd.S = n_sides; S->bnd.blocks = blocks; S->bnd.inc = any_inc; S->bnd.tallied = false; S->bnd.links_epoch = t->sw.links.epoch;
     return RT_SUCCESS;
 }
 

@@ -186,7 +186,7 @@ struct rt_solver {
         rtkry::Hessenberg lsq;
     } kry;
     // the run in progress (rt_solver_begin ... rt_solver_end): `open` while this solver holds the handle's sweep state
-    // (rt_tracks::sw_loan.borrower points back here), `swept` between rt_solver_step_sweep and rt_solver_step_fold; the mode, the
+    // (rt_tracks::sw.loan.borrower points back here), `swept` between rt_solver_step_sweep and rt_solver_step_fold; the mode, the
     // order of P2 / P3 scattering and the options the run began with
     struct Run {
         bool open = false, swept = false, eigen = false, bnd = false, reg = false, cm = false;

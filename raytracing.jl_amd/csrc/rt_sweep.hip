@@ -1,6 +1,8 @@
 // rt_sweep.hip — rt_sweep: the transport sweep over the cyclic tracks, kernels, host code and entry points.
-// What a call decides — rows, pass width and shape, refusals — is plan_sweep (rt_sweep_plan.hpp, a pure function checked on the host);
-// sweep_impl fills its facts from the handle and an rt_solver's loan (rt_tracks::sw_loan), makes the rows it names and launches.
+// What a call decides — rows, pass width and shape, refusals — is plan_sweep, and the kernel of each pass pass_kernel_key (rt_sweep_plan.hpp,
+// pure functions checked on the host); sweep_impl fills the facts from the handle (rt_tracks::sw, rt_sweep_state.hpp) and an rt_solver's
+// loan (sw.loan), makes the rows the plan names and launches every pass through one function, launch_pass: sweep_pass_kernel turns the key
+// into a kernel of this file or of a sibling unit (rt_sweep_f32.hip, rt_sweep_iface.hip, rt_sweep_pn.hip: sweep_kernel_*).
 #include "rt_internal.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>  // the cell index of the reproducible tallies: one stable sort per segmentation
@@ -54,7 +56,8 @@ namespace rt {
 // (kSweepGpP1 = 2 with three tallies per component).  The instantiations without the flag compile to what they were.
 // IFACE (region currents, rt_solver_set_regions): a second constant of the shared body, false in both kernels here and true in
 // k_sweep_iface (rt_sweep_iface.hip); sweep_impl lends it the solver's region array and tally, zeroes the tally before the first
-// pass and launches it in k_sweep's place (launch_sweep_iface).  The kernels of this file compile to what they were.
+// pass and launches it in k_sweep's place (pass_kernel_key names the family, launch_pass launches it).  The kernels of this file compile
+// to what they were.
 template <bool STAGED, int GP, bool LDS, bool ELLROWS, bool P1 = false, bool LS = false>
 __global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep(DSweep a) {
     constexpr bool REPRO = false, IFACE = false;
@@ -290,32 +293,32 @@ __global__ __launch_bounds__(256) void k_cell_reduce(const int32_t *__restrict__
 }  // namespace rt
 
 namespace rtx {
-// The rows of the last segmentation from its compact records (see k_rows_fill): built once, `sw_rowsc_valid`.
+// The rows of the last segmentation from its compact records (see k_rows_fill): built once, `sw.rows.fromcompact_valid`.
 int ensure_rows_from_compact(rt_tracks *t) {
-    if (t->sw_rowsc_valid) return RT_SUCCESS;
+    if (t->sw.rows.fromcompact_valid) return RT_SUCCESS;
     if (int rc = ensure_compacted(t)) return rc;
     hipStream_t s = t->mesh->stream;
     const int64_t n = t->n;
     const int32_t n_waves = (int32_t)((n + 63) / 64);
-    if (n_waves == 0) { t->sw_rowsc_valid = true; t->sw_rowsc_slots = 1; return RT_SUCCESS; }
-    RT_HIP(t->sw_plan.reserve(2 * (size_t)n_waves + 8));
-    RT_HIP(t->sw_ctab.reserve((size_t)n_waves * rt::kMaxChunks));
-    int32_t *nch = t->sw_plan.p, *first = nch + n_waves, *total = first + n_waves;
+    if (n_waves == 0) { t->sw.rows.fromcompact_valid = true; t->sw.rows.fromcompact_slots = 1; return RT_SUCCESS; }
+    RT_HIP(t->sw.rows.plan.reserve(2 * (size_t)n_waves + 8));
+    RT_HIP(t->sw.rows.ctab.reserve((size_t)n_waves * rt::kMaxChunks));
+    int32_t *nch = t->sw.rows.plan.p, *first = nch + n_waves, *total = first + n_waves;
     hipLaunchKernelGGL(rt::k_rows_count, dim3((unsigned)((n_waves + 3) / 4)), dim3(256), 0, s, (const int32_t *)t->counts.p, (const int32_t *)t->perm.p, n, n_waves, nch);
     hipLaunchKernelGGL(rt::k_rows_plan, dim3(1), dim3(1024), 0, s, (const int32_t *)nch, n_waves, first, total);
     int32_t h_total = 0;
     RT_HIP(hipMemcpyAsync(&h_total, total, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     RT_HIP(hipStreamSynchronize(s));
     const size_t slots = (size_t)std::max(1, h_total) * rt::kChunkRows * 64;
-    RT_HIP(t->sw_ell.reserve(slots)); RT_HIP(t->sw_cell.reserve(slots));
-    t->sw_rowsc_slots = (int64_t)slots;
-    t->sw_ell_valid = false;  // (the buffers now hold rows in THIS chunk table's layout, not the staging pool's)
-    ++t->sw_rows_gen;
+    RT_HIP(t->sw.rows.ell.reserve(slots)); RT_HIP(t->sw.rows.cell.reserve(slots));
+    t->sw.rows.fromcompact_slots = (int64_t)slots;
+    t->sw.rows.ell_valid = false;  // (the buffers now hold rows in THIS chunk table's layout, not the staging pool's)
+    ++t->sw.rows.gen;
     hipLaunchKernelGGL(rt::k_rows_fill, dim3((unsigned)n_waves), dim3(256), 0, s, (const int32_t *)t->counts.p, (const int64_t *)t->offsets.p,
                        (const int32_t *)t->perm.p, n, (const double *)t->sell.p, (const int32_t *)t->element.p, (const int32_t *)first, (const int32_t *)nch,
-                       t->sw_ctab.p, t->sw_ell.p, t->sw_cell.p);
+                       t->sw.rows.ctab.p, t->sw.rows.ell.p, t->sw.rows.cell.p);
     RT_HIP(hipGetLastError());
-    t->sw_rowsc_valid = true;
+    t->sw.rows.fromcompact_valid = true;
     return RT_SUCCESS;
 }
 
@@ -334,37 +337,37 @@ int sweep_repro_prepare(rt_tracks *t, int64_t *slots_out) {
         if (int rc = ensure_rows_from_compact(t)) return rc;
     if (int rc = ensure_compacted(t)) return rc;  // (the index is built in the order of the compact records)
     const int64_t total = t->total, n = t->n;
-    const int64_t slots = kind == 1 ? std::max<int64_t>(1, t->pool_chunks) * rt::kChunkRows * 64 : (kind == 2 ? t->sw_rowsc_slots : std::max<int64_t>(1, total));
+    const int64_t slots = kind == 1 ? std::max<int64_t>(1, t->pool_chunks) * rt::kChunkRows * 64 : (kind == 2 ? t->sw.rows.fromcompact_slots : std::max<int64_t>(1, total));
     if (slots >= (1ll << 31) || total >= (1ll << 31)) {
         set_error("reproducible tallies: %lld records in %lld row slots (the cell index holds 32-bit places: fewer than 2^31 of each)", (long long)total, (long long)slots);
         return RT_ERR_INVALID;
     }
     *slots_out = slots;
-    if (t->sw_ridx_kind == kind && t->sw_ridx_slots == slots) return RT_SUCCESS;
-    t->sw_ridx_kind = 0;
+    if (t->sw.ridx.kind == kind && t->sw.ridx.slots == slots) return RT_SUCCESS;
+    t->sw.ridx.kind = 0;
     const int32_t nc = m->n_cells;
-    RT_HIP(t->sw_ridx_start.reserve((size_t)nc + 1));
-    RT_HIP(t->sw_ridx_list.reserve((size_t)std::max<int64_t>(1, total)));
+    RT_HIP(t->sw.ridx.start.reserve((size_t)nc + 1));
+    RT_HIP(t->sw.ridx.list.reserve((size_t)std::max<int64_t>(1, total)));
     if (total == 0 || n == 0) {
-        RT_HIP(hipMemsetAsync(t->sw_ridx_start.p, 0, ((size_t)nc + 1) * sizeof(int32_t), s));
+        RT_HIP(hipMemsetAsync(t->sw.ridx.start.p, 0, ((size_t)nc + 1) * sizeof(int32_t), s));
     } else {
         DevBuf<int32_t> key_in, key_out, val_in;
         DevBuf<unsigned char> temp;
         RT_HIP(key_in.reserve((size_t)total)); RT_HIP(key_out.reserve((size_t)total)); RT_HIP(val_in.reserve((size_t)total));
-        const int32_t *ctab = kind == 1 ? (const int32_t *)t->cplan.stg.ctab : (kind == 2 ? (const int32_t *)t->sw_ctab.p : nullptr);
+        const int32_t *ctab = kind == 1 ? (const int32_t *)t->cplan.stg.ctab : (kind == 2 ? (const int32_t *)t->sw.rows.ctab.p : nullptr);
         hipLaunchKernelGGL(rt::k_ridx_records, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t *)t->counts.p, (const int64_t *)t->offsets.p,
                            (const int32_t *)t->perm.p, n, (const int32_t *)t->element.p, ctab, nc, key_in.p, val_in.p);
         unsigned bits = 1;
         while (bits < 32 && (1ll << bits) <= (int64_t)nc) ++bits;  // keys 0 .. n_cells
         size_t temp_bytes = 0;
-        RT_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, key_in.p, key_out.p, val_in.p, t->sw_ridx_list.p, (size_t)total, 0u, bits, s));
+        RT_HIP(rocprim::radix_sort_pairs(nullptr, temp_bytes, key_in.p, key_out.p, val_in.p, t->sw.ridx.list.p, (size_t)total, 0u, bits, s));
         RT_HIP(temp.reserve(std::max<size_t>(1, temp_bytes)));
-        RT_HIP(rocprim::radix_sort_pairs((void *)temp.p, temp_bytes, key_in.p, key_out.p, val_in.p, t->sw_ridx_list.p, (size_t)total, 0u, bits, s));
-        hipLaunchKernelGGL(rt::k_ridx_starts, dim3((unsigned)((total + 1 + 255) / 256)), dim3(256), 0, s, (const int32_t *)key_out.p, total, nc, t->sw_ridx_start.p);
+        RT_HIP(rocprim::radix_sort_pairs((void *)temp.p, temp_bytes, key_in.p, key_out.p, val_in.p, t->sw.ridx.list.p, (size_t)total, 0u, bits, s));
+        hipLaunchKernelGGL(rt::k_ridx_starts, dim3((unsigned)((total + 1 + 255) / 256)), dim3(256), 0, s, (const int32_t *)key_out.p, total, nc, t->sw.ridx.start.p);
         RT_HIP(hipGetLastError());
         RT_HIP(hipStreamSynchronize(s));  // (the temporary buffers die here)
     }
-    t->sw_ridx_kind = kind; t->sw_ridx_slots = slots;
+    t->sw.ridx.kind = kind; t->sw.ridx.slots = slots;
     return RT_SUCCESS;
 }
 
@@ -379,7 +382,7 @@ int sweep_repro_cell_sums(rt_tracks *t, int kind, const double *w_azim, const do
     hipStream_t s = m->stream;
     const int64_t n = t->n;
     const int32_t nc = m->n_cells;
-    const int32_t *ctab = t->sw_ridx_kind == 1 ? (const int32_t *)t->cplan.stg.ctab : (t->sw_ridx_kind == 2 ? (const int32_t *)t->sw_ctab.p : nullptr);
+    const int32_t *ctab = t->sw.ridx.kind == 1 ? (const int32_t *)t->cplan.stg.ctab : (t->sw.ridx.kind == 2 ? (const int32_t *)t->sw.rows.ctab.p : nullptr);
     auto values = [&]<int KIND>() {
         if (n > 0)
             hipLaunchKernelGGL(rt::k_cell_values<KIND>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const int32_t *)t->counts.p, (const int64_t *)t->offsets.p,
@@ -390,10 +393,10 @@ int sweep_repro_cell_sums(rt_tracks *t, int kind, const double *w_azim, const do
     const unsigned rb = (unsigned)((nc + 3) / 4);
     if (kind == 0) {
         values.template operator()<0>();
-        if (nc > 0) hipLaunchKernelGGL(rt::k_cell_reduce<1>, dim3(rb), dim3(256), 0, s, (const int32_t *)t->sw_ridx_start.p, (const int32_t *)t->sw_ridx_list.p, (const double *)delta, slots, nc, out);
+        if (nc > 0) hipLaunchKernelGGL(rt::k_cell_reduce<1>, dim3(rb), dim3(256), 0, s, (const int32_t *)t->sw.ridx.start.p, (const int32_t *)t->sw.ridx.list.p, (const double *)delta, slots, nc, out);
     } else {
         if (kind == 1) values.template operator()<1>(); else values.template operator()<2>();
-        if (nc > 0) hipLaunchKernelGGL(rt::k_cell_reduce<3>, dim3(rb), dim3(256), 0, s, (const int32_t *)t->sw_ridx_start.p, (const int32_t *)t->sw_ridx_list.p, (const double *)delta, slots, nc, out);
+        if (nc > 0) hipLaunchKernelGGL(rt::k_cell_reduce<3>, dim3(rb), dim3(256), 0, s, (const int32_t *)t->sw.ridx.start.p, (const int32_t *)t->sw.ridx.list.p, (const double *)delta, slots, nc, out);
     }
     RT_HIP(hipGetLastError());
     return RT_SUCCESS;
@@ -410,7 +413,7 @@ static SweepFacts sweep_facts(const rt_tracks *t, int32_t G, int32_t input, cons
     // (source regions: the solver's n_src stands in for the mesh's cells — the LDS copy of a pass holds n_src tallies per component)
     return SweepFacts{.n = t->n, .n_cells = loan.sr_n_src > 0 ? loan.sr_n_src : m->n_cells, .G = G, .input = input, .mode = loan.mode, .repro = loan.repro,
                       .f32 = loan.f32 || m->sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
-                      .sw_ell_valid = t->sw_ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
+                      .sw_ell_valid = t->sw.rows.ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
                       .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves, .regions = loan.n_regions,
                       .volcorr = volcorr, .srcreg = loan.sr_n_src > 0, .pn = loan.pn_M};
 }
@@ -424,17 +427,17 @@ int sweep_rows_for_loan(rt_tracks *t, int32_t G, const SweepLoan &loan, bool vol
     v.rows = plan.rows;
     if (plan.rows == SweepRows::FromCompact) {
         if (int rc = ensure_rows_from_compact(t)) return rc;
-        v.ctab = t->sw_ctab.p; v.cell_rows = t->sw_cell.p; v.slots = t->sw_rowsc_slots;
+        v.ctab = t->sw.rows.ctab.p; v.cell_rows = t->sw.rows.cell.p; v.slots = t->sw.rows.fromcompact_slots;
     } else {
         if (plan.rows == SweepRows::FromCodes)
             if (int rc = ensure_rows(t)) return rc;
         v.ctab = (const int32_t *)t->cplan.stg.ctab;
-        v.cell_rows = plan.rows == SweepRows::FromCodes ? (const int32_t *)t->sw_cell.p : (const int32_t *)t->cplan.stg.element;
+        v.cell_rows = plan.rows == SweepRows::FromCodes ? (const int32_t *)t->sw.rows.cell.p : (const int32_t *)t->cplan.stg.element;
         v.slots = (int64_t)t->pool_chunks * rt::kChunkRows * 64;
     }
-    v.ell_rows = t->sw_ell.p;
-    if ((int64_t)t->sw_ell.cap < v.slots || (t->n > 0 && (!v.ctab || !v.cell_rows))) { set_error("rt_sweep: the (ℓ, cell) rows of this segmentation are incomplete"); return RT_ERR_INVALID; }
-    v.gen = t->sw_rows_gen;
+    v.ell_rows = t->sw.rows.ell.p;
+    if ((int64_t)t->sw.rows.ell.cap < v.slots || (t->n > 0 && (!v.ctab || !v.cell_rows))) { set_error("rt_sweep: the (ℓ, cell) rows of this segmentation are incomplete"); return RT_ERR_INVALID; }
+    v.gen = t->sw.rows.gen;
     *out = v;
     return RT_SUCCESS;
 }
@@ -448,7 +451,7 @@ static int32_t sweep_set_links_impl(rt_tracks *t, const int64_t *next_fwd, const
     // gather map: entry slot (direction d', track v) <- source (track u, direction d), written in the order a sequential
     // sweep hands fluxes on (uid ascending, forward before backward): the last writer wins where links are not one-to-one
     std::vector<int32_t> src((size_t)std::max<int64_t>(1, 2 * n), -1);
-    std::vector<int32_t> entry((size_t)(2 * n), -1);  // (the same links by source, whatever their bc: rt_tracks::sw_h_entry)
+    std::vector<int32_t> entry((size_t)(2 * n), -1);  // (the same links by source, whatever their bc: rt_tracks::sw.links.h_entry)
     bool shard = false;
     for (int64_t u = 0; u < n; ++u)
         for (int d = 0; d < 2; ++d) {
@@ -464,10 +467,10 @@ static int32_t sweep_set_links_impl(rt_tracks *t, const int64_t *next_fwd, const
             entry[(size_t)d * n + u] = (int32_t)(dn * n + v);
         }
     RT_HIP(hipSetDevice(t->mesh->device));
-    if (int rc = upload(t->sw_src, src.data(), src.size(), t->mesh->stream)) return rc;
+    if (int rc = upload(t->sw.links.src, src.data(), src.size(), t->mesh->stream)) return rc;
     RT_HIP(hipStreamSynchronize(t->mesh->stream));
-    t->sw_h_entry.swap(entry); t->sw_shard = shard; ++t->sw_links_epoch;
-    t->sw_links = true;
+    t->sw.links.h_entry.swap(entry); t->sw.links.shard = shard; ++t->sw.links.epoch;
+    t->sw.links.set = true;
     return RT_SUCCESS;
 }
 
@@ -498,19 +501,35 @@ static const void *sweep_reduce_kernel(bool moments, int take) {
     return take == 2 ? (const void *)rt::k_sweep_reduce<2, false> : (const void *)rt::k_sweep_reduce<1, false>;
 }
 
-// one FP64 pass of `a.ng` components from a.g0 and, behind it, the reduction of the reproducible tallies
-static int launch_sweep_f64(rt_tracks *t, const rt::DSweep &a, const SweepPlan &plan, const PassShape &shape, hipStream_t s) {
-    const bool moments = plan.f.mode != SweepMode::Flat;
-    const void *k = sweep_kernel(rows_staged(plan.rows), plan.use_lds, plan.f.mode, a.ng, plan.f.repro, rows_read_ell(plan.rows));
+// the kernel a key names: this file's ladder, or a sibling unit's table (nullptr: pass_kernel_key let through what no unit instantiates)
+static const void *sweep_pass_kernel(const PassKernelKey &k) {
+    switch (k.family) {
+    case SweepFamily::F32: return sweep_kernel_f32(k.gp, k.lds);
+    case SweepFamily::PN: return sweep_kernel_pn(k.order, k.lds);
+    case SweepFamily::Iface: return sweep_kernel_iface(k.mode, k.gp, k.lds);
+    default: return sweep_kernel(k.staged, k.lds, k.mode, k.gp, k.family == SweepFamily::F64Repro, k.ellrows);
+    }
+}
+
+// One pass of `a.ng` components from a.g0 with the kernel `key` names and, behind a reproducible pass, the reduction of its tallies.
+// A pass that wrote the staging rows' ℓ (Staged20WriteEll) leaves the plan, and the handle, with (ℓ, cell) rows for every later one.
+static int launch_pass(rt_tracks *t, const rt::DSweep &a, SweepPlan &plan, const PassShape &shape, const PassKernelKey &key, hipStream_t s) {
+    const void *k = sweep_pass_kernel(key);
+    if (!k) { set_error("rt_sweep: the kernel table has no entry for this pass (family %d, %d components)", (int)key.family, key.gp); return RT_ERR_INVALID; }
     if (shape.smem > 48 * 1024) RT_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shape.smem));
     void *args[] = {(void *)&a};
     RT_HIP(hipLaunchKernel(k, dim3(shape.blocks), dim3(64 * shape.waves), args, shape.smem, s));
-    if (plan.f.repro && a.n_cells > 0) {  // the pass's tallies, in the index's order (the next pass overwrites the delta buffer)
-        const int32_t *start = t->sw_ridx_start.p, *list = t->sw_ridx_list.p;
-        const double *delta = t->sw_loan.repro_delta;
-        double *phi = t->sw_phi.p, *cur = moments ? t->sw_cur.p : nullptr;
+    if (key.family == SweepFamily::F64Repro && a.n_cells > 0) {  // the pass's tallies, in the index's order (the next pass overwrites the delta buffer)
+        const bool moments = key.mode != SweepMode::Flat;
+        const int32_t *start = t->sw.ridx.start.p, *list = t->sw.ridx.list.p;
+        const double *delta = t->sw.loan.repro_delta;
+        double *phi = t->sw.io.phi.p, *cur = moments ? t->sw.io.cur.p : nullptr;
         void *rargs[] = {&start, &list, &delta, (void *)&a.dslots, (void *)&a.n_cells, (void *)&a.G, (void *)&a.g0, &phi, &cur};
         RT_HIP(hipLaunchKernel(sweep_reduce_kernel(moments, a.ng), dim3((unsigned)((a.n_cells + 3) / 4)), dim3(256), rargs, 0, s));
+    }
+    if (plan.rows == SweepRows::Staged20WriteEll) {  // (an FP64 pass: the other families are refused over these rows)
+        t->sw.rows.hold_staged();                    // the forward waves of this pass have written every row's ℓ
+        plan.rows = SweepRows::StagedEll;
     }
     return RT_SUCCESS;
 }
@@ -519,17 +538,17 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
                           const double *psi_in, int32_t input, double *ms) {
     if (!t || G <= 0 || G > 4096 || input < 0 || input > 2) { set_error("rt_sweep: bad arguments"); return RT_ERR_INVALID; }
     if (!t->segmentized) { set_error("rt_segmentize has not run"); return RT_ERR_NOT_SEGMENTIZED; }
-    if (!t->sw_links) { set_error("rt_sweep: rt_sweep_set_links has not run"); return RT_ERR_INVALID; }
+    if (!t->sw.links.set) { set_error("rt_sweep: rt_sweep_set_links has not run"); return RT_ERR_INVALID; }
     rt_mesh *m = t->mesh;
     RT_HIP(hipSetDevice(m->device));
     hipStream_t s = m->stream;
     const int64_t n = t->n;
     const size_t npsi = (size_t)std::max<int64_t>(1, 2 * n * G), nphi = (size_t)m->n_cells * G;
-    if (G != t->sw_groups) {  // a new group structure: no cross sections, zero boundary flux
-        t->sw_has_xs = false; t->sw_done = false;
-        RT_HIP(t->sw_psi_in.reserve(npsi)); RT_HIP(t->sw_psi_out.reserve(npsi)); RT_HIP(t->sw_phi.reserve(nphi));
-        RT_HIP(hipMemsetAsync(t->sw_psi_in.p, 0, npsi * sizeof(double), s));
-        t->sw_groups = G;
+    if (G != t->sw.io.groups) {  // a new group structure: no cross sections, zero boundary flux
+        t->sw.io.has_xs = false; t->sw.last.done = false;
+        RT_HIP(t->sw.io.psi_in.reserve(npsi)); RT_HIP(t->sw.io.psi_out.reserve(npsi)); RT_HIP(t->sw.io.phi.reserve(nphi));
+        RT_HIP(hipMemsetAsync(t->sw.io.psi_in.p, 0, npsi * sizeof(double), s));
+        t->sw.io.groups = G;
     }
     if (sigma_t) {
         std::vector<double> xs(2 * nphi);
@@ -544,22 +563,22 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
             xs[2 * i] = st;
             xs[2 * i + 1] = st > 0.0 ? q / st : 0.0;  // (a void cell: no attenuation, no source term)
         }
-        if (int rc = upload(t->sw_xs, xs.data(), xs.size(), s)) return rc;
+        if (int rc = upload(t->sw.io.xs, xs.data(), xs.size(), s)) return rc;
         RT_HIP(hipStreamSynchronize(s));  // the host vector dies here
-        t->sw_has_xs = true;
+        t->sw.io.has_xs = true;
     } else if (source) { set_error("rt_sweep: source given without sigma_t"); return RT_ERR_INVALID; }
-    if (!t->sw_has_xs) { set_error("rt_sweep: no cross sections yet (sigma_t is NULL)"); return RT_ERR_INVALID; }
+    if (!t->sw.io.has_xs) { set_error("rt_sweep: no cross sections yet (sigma_t is NULL)"); return RT_ERR_INVALID; }
     if (track_weight) {
-        if (int rc = upload(t->sw_w, track_weight, (size_t)n, s)) return rc;
-        t->sw_has_w = true;
+        if (int rc = upload(t->sw.io.w, track_weight, (size_t)n, s)) return rc;
+        t->sw.io.has_w = true;
     }
-    if (psi_in && n > 0) RT_HIP(hipMemcpyAsync(t->sw_psi_in.p, psi_in, (size_t)(2 * n * G) * sizeof(double), hipMemcpyHostToDevice, s));
+    if (psi_in && n > 0) RT_HIP(hipMemcpyAsync(t->sw.io.psi_in.p, psi_in, (size_t)(2 * n * G) * sizeof(double), hipMemcpyHostToDevice, s));
     // option "async": the sweep's kernels are queued and the call returns (no events, no wait) — what was handed over in host
     // arrays has to be on the device before that
     const bool async_sweep = m->async_calls && !m->timing;
     if (async_sweep && (track_weight || (psi_in && n > 0))) RT_HIP(hipStreamSynchronize(s));
     // what this sweep reads and how wide its passes are, from the handle's state, the options and an rt_solver's loan for its run
-    const SweepLoan &loan = t->sw_loan;
+    const SweepLoan &loan = t->sw.loan;
     const SweepMode mode = loan.mode;
     const bool pn = mode == SweepMode::PN;
     const bool moments = mode != SweepMode::Flat && !pn, repro = loan.repro;  // (first moments or the linear source: xs1 and cur)
@@ -568,13 +587,13 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     if (plan.refusal) { set_error("%s", plan.message); return plan.refusal; }
     // the solver's ℓ' stands in for the rows' ℓ: it is the copy of THESE rows as they stand, or the sweep is refused here, with nothing
     // queued (rows with ℓ exist already — the solver made them —, so nothing below makes them anew)
-    if (facts.volcorr && (!rows_read_ell(plan.rows) || plan.rows != loan.vc_rows || t->sw_rows_gen != loan.vc_gen)) {
+    if (facts.volcorr && (!rows_read_ell(plan.rows) || plan.rows != loan.vc_rows || t->sw.rows.gen != loan.vc_gen)) {
         set_error("rt_sweep: the volume correction (rt_solver_set_volume_correction) scaled other rows than this sweep reads (an option or the rows changed under the run): begin the run again");
         return RT_ERR_INVALID;
     }
     // the solver's merged rows stand in for the rows: they were made from THESE rows as they stand, or the sweep is refused here, with
     // nothing queued
-    if (facts.srcreg && (!rows_read_ell(plan.rows) || plan.rows != loan.sr_rows || t->sw_rows_gen != loan.sr_gen || !loan.sr_ctab || !loan.sr_cell ||
+    if (facts.srcreg && (!rows_read_ell(plan.rows) || plan.rows != loan.sr_rows || t->sw.rows.gen != loan.sr_gen || !loan.sr_ctab || !loan.sr_cell ||
                          !loan.sr_ell || !loan.sr_counts)) {
         set_error("rt_sweep: the source regions (rt_solver_set_source_regions) merged other rows than this sweep reads (an option or the rows changed under the run): begin the run again");
         return RT_ERR_INVALID;
@@ -591,15 +610,15 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     a.offsets = as_global((const int64_t *)t->offsets.p); a.counts = as_global((const int32_t *)t->counts.p);
     a.perm = as_global((const int32_t *)t->perm.p); a.azim = as_global((const int32_t *)t->azim.p);
     a.delta_s = as_global((const double *)t->delta_s.p);
-    a.w = t->sw_has_w ? as_global((const double *)t->sw_w.p) : nullptr;
-    a.xs = as_global((const double *)t->sw_xs.p);
-    a.psi_in = as_global((const double *)t->sw_psi_in.p); a.psi_out = as_global(t->sw_psi_out.p); a.phi = as_global(t->sw_phi.p);
+    a.w = t->sw.io.has_w ? as_global((const double *)t->sw.io.w.p) : nullptr;
+    a.xs = as_global((const double *)t->sw.io.xs.p);
+    a.psi_in = as_global((const double *)t->sw.io.psi_in.p); a.psi_out = as_global(t->sw.io.psi_out.p); a.phi = as_global(t->sw.io.phi.p);
     a.n = n; a.n_waves = (int32_t)((n + 63) / 64); a.n_cells = m->n_cells; a.G = G; a.debug = m->sweep_debug;
     a.use_lds = plan.use_lds ? 1 : 0;
-    if (moments) {  // the solver has filled sw_xs1 for these G components: first-moment ratios (P1), gradient ratios (Linear)
-        if (mode == SweepMode::Linear && (!t->sw_xs1.p || !t->sw_cur.p || !loan.ls_cen || !loan.ls_ends)) { set_error("rt_sweep: the linear-source mode has no geometry arrays"); return RT_ERR_INVALID; }
-        if (!t->sw_xs1.p || !t->sw_cur.p) { set_error("rt_sweep: the anisotropic mode has no first-moment arrays"); return RT_ERR_INVALID; }
-        a.xs1 = as_global((const double *)t->sw_xs1.p); a.cur = as_global(t->sw_cur.p);
+    if (moments) {  // the solver has filled sw.io.xs1 for these G components: first-moment ratios (P1), gradient ratios (Linear)
+        if (mode == SweepMode::Linear && (!t->sw.io.xs1.p || !t->sw.io.cur.p || !loan.ls_cen || !loan.ls_ends)) { set_error("rt_sweep: the linear-source mode has no geometry arrays"); return RT_ERR_INVALID; }
+        if (!t->sw.io.xs1.p || !t->sw.io.cur.p) { set_error("rt_sweep: the anisotropic mode has no first-moment arrays"); return RT_ERR_INVALID; }
+        a.xs1 = as_global((const double *)t->sw.io.xs1.p); a.cur = as_global(t->sw.io.cur.p);
         a.cs = as_global((const double *)t->cs.p); a.sn = as_global((const double *)t->sn.p);
         a.cen = as_global(loan.ls_cen); a.ends = as_global(loan.ls_ends);
     }
@@ -611,7 +630,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     if (repro) {  // the cell index for the rows the plan names, and the solver's delta buffer
         int64_t rslots = 0;
         if (int rc = sweep_repro_prepare(t, &rslots)) return rc;
-        if (t->sw_ridx_kind != rows_index_kind(plan.rows)) { set_error("rt_sweep: the reproducible tallies' cell index is not the one of the rows read"); return RT_ERR_INVALID; }
+        if (t->sw.ridx.kind != rows_index_kind(plan.rows)) { set_error("rt_sweep: the reproducible tallies' cell index is not the one of the rows read"); return RT_ERR_INVALID; }
         if (!loan.repro_delta || (size_t)(2 * rslots) * (size_t)((moments ? 3 : 1) * plan.gp) > loan.repro_cap) {
             set_error("rt_sweep: the delta buffer of the reproducible tallies is too small for these rows (%lld row slots): switch the option on again", (long long)rslots);
             return RT_ERR_INVALID;
@@ -625,23 +644,23 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     }
     if (!async_sweep) RT_HIP(hipEventRecord(t->ev[0], s));
     if (iface) RT_HIP(hipMemsetAsync(loan.iface_S, 0, (size_t)(facts.regions + 1) * (facts.regions + 1) * G * sizeof(double), s));
-    RT_HIP(hipMemsetAsync(t->sw_phi.p, 0, nphi * sizeof(double), s));
-    if (moments && nphi) RT_HIP(hipMemsetAsync(t->sw_cur.p, 0, 2 * nphi * sizeof(double), s));
+    RT_HIP(hipMemsetAsync(t->sw.io.phi.p, 0, nphi * sizeof(double), s));
+    if (moments && nphi) RT_HIP(hipMemsetAsync(t->sw.io.cur.p, 0, 2 * nphi * sizeof(double), s));
     if (pn && nphi) RT_HIP(hipMemsetAsync(loan.pn_t, 0, (size_t)(2 * loan.pn_M) * nphi * sizeof(double), s));
     if (plan.rows == SweepRows::FromCompact) {
         a.stg = rt::DStage{};
-        a.stg.ctab = as_global(t->sw_ctab.p); a.stg.element = as_global(t->sw_cell.p);
+        a.stg.ctab = as_global(t->sw.rows.ctab.p); a.stg.element = as_global(t->sw.rows.cell.p);
     } else if (plan.rows == SweepRows::FromCodes) {  // (which the call itself left ("compact" = 0) or which k_materialise writes now)
         if (int rc = ensure_rows(t)) return rc;
-        a.stg.element = as_global(t->sw_cell.p);
+        a.stg.element = as_global(t->sw.rows.cell.p);
     } else if (plan.try_ell) {
         const size_t slots = (size_t)t->pool_chunks * rt::kChunkRows * 64;
-        if (t->sw_ell.reserve(slots > 0 ? slots : 1) != hipSuccess) {  // (no memory for it: every pass derives ℓ itself)
+        if (t->sw.rows.ell.reserve(slots > 0 ? slots : 1) != hipSuccess) {  // (no memory for it: every pass derives ℓ itself)
             (void)hipGetLastError();
             plan.rows = SweepRows::Staged20;
         }
     }
-    a.ell_rows = rows_kind(plan.rows) ? as_global(t->sw_ell.p) : nullptr;
+    a.ell_rows = rows_kind(plan.rows) ? as_global(t->sw.rows.ell.p) : nullptr;
     if (facts.volcorr) a.ell_rows = as_global(const_cast<double *>(loan.vc_ell));  // (checked above; only read: no pass of these rows writes ℓ)
     if (facts.srcreg) {  // (checked above; only read) the merged rows, their chunk table and counts, n_src "cells"
         a.stg.ctab = as_global(const_cast<int32_t *>(loan.sr_ctab)); a.stg.element = as_global(const_cast<int32_t *>(loan.sr_cell));
@@ -653,37 +672,15 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         const int take = std::min(plan.gp, G - g0);
         const PassShape shape = plan.pass_shape(take);
         a.g0 = g0; a.ng = take;
-        if (facts.f32) {
-            if (!rows_read_ell(plan.rows)) {  // (checked before anything was queued; left: no memory for the ℓ rows)
-                set_error("rt_sweep: the single-precision sweep (\"sweep_precision\" 1) found no (ℓ, cell) rows to read (rows of kind 0)");
-                return RT_ERR_INVALID;
-            }
-            if (int rc = launch_sweep_f32(a, take, shape.smem, shape.waves, shape.blocks, s)) return rc;
-        } else if (pn) {
-            if (!rows_read_ell(plan.rows)) {  // (checked before anything was queued; left: no memory for the ℓ rows)
-                set_error("rt_sweep: P2 / P3 scattering (rt_solver_set_scatter_pn) found no (ℓ, cell) rows to read (rows of kind 0)");
-                return RT_ERR_INVALID;
-            }
-            if (int rc = launch_sweep_pn(a, shape.smem, shape.waves, shape.blocks, s)) return rc;
-        } else if (iface) {
-            if (!rows_read_ell(plan.rows)) {  // (checked before anything was queued; left: no memory for the ℓ rows)
-                set_error("rt_sweep: the region currents (rt_solver_set_regions) found no (ℓ, cell) rows to read (rows of kind 0)");
-                return RT_ERR_INVALID;
-            }
-            if (int rc = launch_sweep_iface(a, mode, shape.smem, shape.waves, shape.blocks, s)) return rc;
-        } else {
-            if (int rc = launch_sweep_f64(t, a, plan, shape, s)) return rc;
-            if (plan.rows == SweepRows::Staged20WriteEll) {  // (the forward waves of this pass have written every row's ℓ)
-                t->sw_ell_valid = true; t->sw_rowsc_valid = false; ++t->sw_rows_gen;
-                plan.rows = SweepRows::StagedEll;
-            }
-        }
+        const PassKernelKey key = pass_kernel_key(plan, take, iface);
+        if (key.refusal) { set_error("%s", key.message); return key.refusal; }
+        if (int rc = launch_pass(t, a, plan, shape, key, s)) return rc;
         g0 += take;
     }
     if (n > 0) {
         const int64_t nl = 2 * n * G;
-        hipLaunchKernelGGL(rt::k_sweep_link, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, (const int32_t *)t->sw_src.p,
-                           (const double *)t->sw_psi_out.p, t->sw_psi_in.p, 2 * n, G, n);
+        hipLaunchKernelGGL(rt::k_sweep_link, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, s, (const int32_t *)t->sw.links.src.p,
+                           (const double *)t->sw.io.psi_out.p, t->sw.io.psi_in.p, 2 * n, G, n);
     }
     if (async_sweep) {
         RT_HIP(hipGetLastError());
@@ -696,10 +693,10 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
         if (ms) { float f = 0; RT_HIP(hipEventElapsedTime(&f, t->ev[0], t->ev[7])); *ms = f; }
         t->in_flight = false;  // (the sweep waited for the stream)
     }
-    t->sw_done = true;
-    t->sw_last_input = rows_input_code(plan.rows, input); t->sw_last_rows = rows_kind(plan.rows);
-    t->sw_last_gp = plan.use_lds ? plan.gp : 0; t->sw_last_passes = passes;
-    t->sw_last_prec = facts.f32 ? RT_PRECISION_SINGLE : RT_PRECISION_DOUBLE;
+    t->sw.last.done = true;
+    t->sw.last.input = rows_input_code(plan.rows, input); t->sw.last.rows = rows_kind(plan.rows);
+    t->sw.last.gp = plan.use_lds ? plan.gp : 0; t->sw.last.passes = passes;
+    t->sw.last.prec = facts.f32 ? RT_PRECISION_SINGLE : RT_PRECISION_DOUBLE;
     return RT_SUCCESS;
 }
 
@@ -717,42 +714,42 @@ int32_t rt_sweep(rt_tracks *t, int32_t n_groups, const double *sigma_t, const do
 
 int32_t rt_sweep_fetch(rt_tracks *t, double *phi, double *psi_out, double *psi_next) {
     if (!t) { set_error("null handle"); return RT_ERR_INVALID; }
-    if (!t->sw_done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
+    if (!t->sw.last.done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
     if (int rc = finish_call(t)) return rc;
     RT_HIP(hipSetDevice(t->mesh->device));
-    const size_t npsi = (size_t)(2 * t->n * t->sw_groups), nphi = (size_t)t->mesh->n_cells * t->sw_groups;
-    if (phi) RT_HIP(hipMemcpy(phi, t->sw_phi.p, nphi * sizeof(double), hipMemcpyDeviceToHost));
-    if (psi_out && npsi) RT_HIP(hipMemcpy(psi_out, t->sw_psi_out.p, npsi * sizeof(double), hipMemcpyDeviceToHost));
-    if (psi_next && npsi) RT_HIP(hipMemcpy(psi_next, t->sw_psi_in.p, npsi * sizeof(double), hipMemcpyDeviceToHost));
+    const size_t npsi = (size_t)(2 * t->n * t->sw.io.groups), nphi = (size_t)t->mesh->n_cells * t->sw.io.groups;
+    if (phi) RT_HIP(hipMemcpy(phi, t->sw.io.phi.p, nphi * sizeof(double), hipMemcpyDeviceToHost));
+    if (psi_out && npsi) RT_HIP(hipMemcpy(psi_out, t->sw.io.psi_out.p, npsi * sizeof(double), hipMemcpyDeviceToHost));
+    if (psi_next && npsi) RT_HIP(hipMemcpy(psi_next, t->sw.io.psi_in.p, npsi * sizeof(double), hipMemcpyDeviceToHost));
     return RT_SUCCESS;
 }
 
 int32_t rt_sweep_info(rt_tracks *t, void **ptrs_dev, int32_t *info) {
     if (!t) { set_error("null handle"); return RT_ERR_INVALID; }
-    if (!t->sw_done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
+    if (!t->sw.last.done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
     // (no wait here: addresses and counts only — under "async" the caller orders its reads against the mesh's stream or rt_wait)
-    if (ptrs_dev) { ptrs_dev[0] = t->sw_phi.p; ptrs_dev[1] = t->sw_psi_out.p; ptrs_dev[2] = t->sw_psi_in.p; }
-    if (info) { info[0] = t->sw_last_input; info[1] = t->sw_last_gp; info[2] = t->sw_last_passes; info[3] = t->sw_groups; }
+    if (ptrs_dev) { ptrs_dev[0] = t->sw.io.phi.p; ptrs_dev[1] = t->sw.io.psi_out.p; ptrs_dev[2] = t->sw.io.psi_in.p; }
+    if (info) { info[0] = t->sw.last.input; info[1] = t->sw.last.gp; info[2] = t->sw.last.passes; info[3] = t->sw.io.groups; }
     return RT_SUCCESS;
 }
 
 int32_t rt_sweep_rows_kind(rt_tracks *t) {
     if (!t) { set_error("null handle"); return RT_ERR_INVALID; }
-    if (!t->sw_done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
-    return t->sw_last_rows;
+    if (!t->sw.last.done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
+    return t->sw.last.rows;
 }
 
 int32_t rt_sweep_precision(rt_tracks *t) {
     if (!t) { set_error("null handle"); return RT_ERR_INVALID; }
-    if (!t->sw_done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
-    return t->sw_last_prec;
+    if (!t->sw.last.done) { set_error("rt_sweep has not run"); return RT_ERR_NOT_SEGMENTIZED; }
+    return t->sw.last.prec;
 }
 
 int32_t rt_sweep_xs_pointer(rt_tracks *t, void **xs_dev) {
     if (!t || !xs_dev) { set_error("null argument"); return RT_ERR_INVALID; }
-    if (!t->sw_has_xs) { set_error("rt_sweep has not been given cross sections yet"); return RT_ERR_NOT_SEGMENTIZED; }
+    if (!t->sw.io.has_xs) { set_error("rt_sweep has not been given cross sections yet"); return RT_ERR_NOT_SEGMENTIZED; }
     if (int rc = finish_call(t)) return rc;
-    *xs_dev = t->sw_xs.p;
+    *xs_dev = t->sw.io.xs.p;
     return RT_SUCCESS;
 }
 

@@ -1,5 +1,5 @@
 // rt_sweep_f32.hip — k_sweep_f32: the flat, isotropic transport sweep with the angular flux in binary32 (rt_solver_set_precision,
-// rt_set_option "sweep_precision" 1; include/rt_segmentize.h states the definition), and its launcher.  A translation unit of its
+// rt_set_option "sweep_precision" 1; include/rt_segmentize.h states the definition), and the table of its instantiations.  A translation unit of its
 // own: rt_sweep.hip's kernels keep their names and instructions.
 #include "rt_internal.hpp"
 
@@ -178,25 +178,16 @@ __global__ __launch_bounds__(1024) void k_sweep_f32(DSweep a) {
 
 namespace rtx {
 
-// One pass of k_sweep_f32 over components [a.g0, a.g0 + gp) — queued on `s` with the grid and the LDS size rt_sweep chose for the
-// pass (a.use_lds: the tallies' LDS copy).  gp is 1 .. kSweepGpF32.
-int launch_sweep_f32(const rt::DSweep &a, int gp, size_t smem, int waves, unsigned blocks, hipStream_t s) {
-    auto go = [&]<int GP, bool LDS>() -> int {
-        if (smem > 48 * 1024)
-            RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep_f32<GP, LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL((rt::k_sweep_f32<GP, LDS>), dim3(blocks), dim3(64 * waves), smem, s, a);
-        return RT_SUCCESS;
-    };
-    static_assert(rt::kSweepGpF32 == 4, "the pass widths below");
-    const bool lds = a.use_lds != 0;
+// k_sweep_f32 for a pass of `gp` components (1 .. kSweepGpF32), with or without the tallies' LDS copy; nullptr: there is none
+const void *sweep_kernel_f32(int gp, bool lds) {
+    static_assert(rt::kSweepGpF32 == 4 && rtsweep::kSweepGpFlat == 4, "the pass widths below");
     switch (gp) {
-    case 1: return lds ? go.template operator()<1, true>() : go.template operator()<1, false>();
-    case 2: return lds ? go.template operator()<2, true>() : go.template operator()<2, false>();
-    case 3: return lds ? go.template operator()<3, true>() : go.template operator()<3, false>();
-    case 4: return lds ? go.template operator()<4, true>() : go.template operator()<4, false>();
+    case 1: return lds ? (const void *)rt::k_sweep_f32<1, true> : (const void *)rt::k_sweep_f32<1, false>;
+    case 2: return lds ? (const void *)rt::k_sweep_f32<2, true> : (const void *)rt::k_sweep_f32<2, false>;
+    case 3: return lds ? (const void *)rt::k_sweep_f32<3, true> : (const void *)rt::k_sweep_f32<3, false>;
+    case 4: return lds ? (const void *)rt::k_sweep_f32<4, true> : (const void *)rt::k_sweep_f32<4, false>;
     }
-    set_error("rt_sweep: no single-precision kernel for %d components per pass", gp);
-    return RT_ERR_INVALID;
+    return nullptr;
 }
 
 }  // namespace rtx

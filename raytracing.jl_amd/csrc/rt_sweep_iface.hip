@@ -1,5 +1,5 @@
 // rt_sweep_iface.hip — k_sweep_iface: the FP64 sweep over (ℓ, cell) rows that also tallies the partial currents between cell regions
-// (rt_solver_set_regions; include/rt_segmentize.h states the definition), and its launcher.  A translation unit of its own:
+// (rt_solver_set_regions; include/rt_segmentize.h states the definition), and the table of its instantiations.  A translation unit of its own:
 // rt_sweep.hip's kernels keep their names and instructions.
 #include "rt_internal.hpp"
 
@@ -22,34 +22,24 @@ __global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep_iface(DSweep a) {
 
 namespace rtx {
 
-// One pass of k_sweep_iface over components [a.g0, a.g0 + a.ng) — queued on `s` with the grid and the LDS size the plan chose for
-// the pass (a.use_lds: the tallies' LDS copy in front of the table).
-int launch_sweep_iface(const rt::DSweep &a, SweepMode mode, size_t smem, int waves, unsigned blocks, hipStream_t s) {
-    auto go = [&]<int GP, bool LDS, bool P1, bool LS>() -> int {
-        if (smem > 48 * 1024)
-            RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep_iface<GP, LDS, P1, LS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL((rt::k_sweep_iface<GP, LDS, P1, LS>), dim3(blocks), dim3(64 * waves), smem, s, a);
-        return RT_SUCCESS;
-    };
-    static_assert(rtsweep::kSweepGpP1 == 2, "the pass widths below");
-    const bool lds = a.use_lds != 0;
-    const int gp = a.ng;
-    if (mode == SweepMode::Linear) {
-        if (gp == 1) return lds ? go.template operator()<1, true, false, true>() : go.template operator()<1, false, false, true>();
-        if (gp == 2) return lds ? go.template operator()<2, true, false, true>() : go.template operator()<2, false, false, true>();
-    } else if (mode == SweepMode::P1) {
-        if (gp == 1) return lds ? go.template operator()<1, true, true, false>() : go.template operator()<1, false, true, false>();
-        if (gp == 2) return lds ? go.template operator()<2, true, true, false>() : go.template operator()<2, false, true, false>();
-    } else {
-        switch (gp) {
-        case 1: return lds ? go.template operator()<1, true, false, false>() : go.template operator()<1, false, false, false>();
-        case 2: return lds ? go.template operator()<2, true, false, false>() : go.template operator()<2, false, false, false>();
-        case 3: return lds ? go.template operator()<3, true, false, false>() : go.template operator()<3, false, false, false>();
-        case 4: return lds ? go.template operator()<4, true, false, false>() : go.template operator()<4, false, false, false>();
-        }
+// k_sweep_iface for a pass of `gp` components (1 .. 4 flat, 1 .. kSweepGpP1 with first moments or the linear source), with or without
+// the tallies' LDS copy in front of the table; nullptr: there is none
+template <bool P1, bool LS>
+static const void *sweep_kernel_iface(int gp, bool lds) {
+    static_assert(rtsweep::kSweepGpP1 == 2 && rtsweep::kSweepGpFlat == 4, "the pass widths below");
+    switch (gp) {
+    case 1: return lds ? (const void *)rt::k_sweep_iface<1, true, P1, LS> : (const void *)rt::k_sweep_iface<1, false, P1, LS>;
+    case 2: return lds ? (const void *)rt::k_sweep_iface<2, true, P1, LS> : (const void *)rt::k_sweep_iface<2, false, P1, LS>;
     }
-    set_error("rt_sweep: no region-current kernel for %d components per pass", gp);
-    return RT_ERR_INVALID;
+    if constexpr (!P1 && !LS) {
+        if (gp == 3) return lds ? (const void *)rt::k_sweep_iface<3, true, false, false> : (const void *)rt::k_sweep_iface<3, false, false, false>;
+        if (gp == 4) return lds ? (const void *)rt::k_sweep_iface<4, true, false, false> : (const void *)rt::k_sweep_iface<4, false, false, false>;
+    }
+    return nullptr;
+}
+const void *sweep_kernel_iface(SweepMode mode, int gp, bool lds) {
+    if (mode == SweepMode::Linear) return sweep_kernel_iface<false, true>(gp, lds);
+    return mode == SweepMode::P1 ? sweep_kernel_iface<true, false>(gp, lds) : sweep_kernel_iface<false, false>(gp, lds);
 }
 
 }  // namespace rtx

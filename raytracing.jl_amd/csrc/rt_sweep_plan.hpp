@@ -1,12 +1,13 @@
 // rt_sweep_plan.hpp — what one rt_sweep call decides before it queues anything, as a pure function of a dozen integers: which rows
 // it reads, how many components a pass takes and whether their tallies get an LDS copy, the launch shape of a pass, and whether the
-// call is refused (with rt_sweep's own message).  No HIP call and no allocation in here: rt_sweep.hip fills SweepFacts from the
+// call is refused (with rt_sweep's own message); and, per pass, which kernel runs it (pass_kernel_key).  No HIP call and no allocation in here: rt_sweep.hip fills SweepFacts from the
 // handle and carries the plan out; tests/sanitize/sweep_plan_san.cpp checks the decisions on the host (tests/sanitize/run.sh,
 // tests/test_sweep_plan_cpu.py).
 #pragma once
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <cstdio>
 
 #include "../../include/rt_segmentize.h"
 
@@ -34,7 +35,7 @@ constexpr bool rows_staged(SweepRows r) { return r != SweepRows::Records; }
 constexpr int rows_kind(SweepRows r) { return r == SweepRows::FromCompact ? 2 : (r == SweepRows::Records || r == SweepRows::Staged20 ? 0 : 1); }
 // every pass reads (ℓ, cell) rows (the kernels' ELLROWS flag; the single-precision kernel reads nothing else)
 constexpr bool rows_read_ell(SweepRows r) { return rows_kind(r) != 0 && r != SweepRows::Staged20WriteEll; }
-// the row variant of the reproducible tallies' cell index (rt_tracks::sw_ridx_kind): 1 staging slots, 2 rows from the compact records, 3 records
+// the row variant of the reproducible tallies' cell index (rt_tracks::sw.ridx.kind): 1 staging slots, 2 rows from the compact records, 3 records
 constexpr int rows_index_kind(SweepRows r) { return r == SweepRows::FromCompact ? 2 : (r == SweepRows::Records ? 3 : 1); }
 // rt_sweep_info's input: what the caller's records were — 1 the compact CSR records (named, or all there is), 2 the staging
 constexpr int rows_input_code(SweepRows r, int input) { return (input == 1 || r == SweepRows::FromCompact || r == SweepRows::Records) ? 1 : 2; }
@@ -227,6 +228,47 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
         }
     }
     return p;
+}
+
+// ---- the kernel of a pass ---------------------------------------------------------------------------------------------------------
+// Which kernel a pass of `take` components runs is a function of the plan and that width: the family — the kernels of rt_sweep.hip
+// with atomic (F64) or reproducible (F64Repro) tallies, k_sweep_iface, k_sweep_f32, k_sweep_pn — and the family's template arguments.
+// rt_sweep.hip's sweep_pass_kernel turns the key into the kernel's address; nothing else chooses a kernel.
+enum class SweepFamily { F64, F64Repro, Iface, F32, PN };
+constexpr int kSweepGpFlat = 4;  // components per pass of a flat sweep, at most: the widest instantiation of every family (F32: rt::kSweepGpF32)
+
+struct PassKernelKey {
+    SweepFamily family = SweepFamily::F64;
+    bool staged = false, ellrows = false, lds = false;  // the kernels' STAGED, ELLROWS and LDS flags (Iface, F32, PN: rows with ℓ only)
+    int gp = 0;                        // the kernels' GP: components of this pass
+    SweepMode mode = SweepMode::Flat;  // Flat / P1 / Linear (the kernels' P1 and LS flags); PN: `order` is the kernels' M
+    int order = 0;
+    int refusal = RT_SUCCESS;  // RT_ERR_INVALID: no kernel serves this pass ...
+    char message[160] = "";    // ... with this text
+};
+
+inline PassKernelKey pass_kernel_key(const SweepPlan &p, int take, bool iface) {
+    PassKernelKey k;
+    k.family = p.f.f32 ? SweepFamily::F32 : (p.f.mode == SweepMode::PN ? SweepFamily::PN : (iface ? SweepFamily::Iface : (p.f.repro ? SweepFamily::F64Repro : SweepFamily::F64)));
+    k.staged = rows_staged(p.rows); k.ellrows = rows_read_ell(p.rows); k.lds = p.use_lds;
+    k.gp = take; k.mode = p.f.mode; k.order = p.f.pn;
+    if (k.family == SweepFamily::F64 || k.family == SweepFamily::F64Repro) return k;
+    // the three families that read nothing but (ℓ, cell) rows (checked by plan_sweep before anything was queued; left: no memory for
+    // the ℓ rows, and the executor fell back to the staging's 20-B rows)
+    static constexpr const char *kOption[] = {"the region currents (rt_solver_set_regions)", "the single-precision sweep (\"sweep_precision\" 1)",
+                                              "P2 / P3 scattering (rt_solver_set_scatter_pn)"};  // by family, from Iface
+    k.refusal = RT_ERR_INVALID;
+    if (!k.ellrows)
+        std::snprintf(k.message, sizeof k.message, "rt_sweep: %s found no (ℓ, cell) rows to read (rows of kind 0)", kOption[(int)k.family - (int)SweepFamily::Iface]);
+    else if (k.family == SweepFamily::F32 && (take < 1 || take > kSweepGpFlat))
+        std::snprintf(k.message, sizeof k.message, "rt_sweep: no single-precision kernel for %d components per pass", take);
+    else if (k.family == SweepFamily::PN && (take != 1 || (k.order != 2 && k.order != 3)))
+        std::snprintf(k.message, sizeof k.message, "rt_sweep: no P%d kernel for %d components per pass", k.order, take);
+    else if (k.family == SweepFamily::Iface && (take < 1 || take > (k.mode == SweepMode::Flat ? kSweepGpFlat : kSweepGpP1)))
+        std::snprintf(k.message, sizeof k.message, "rt_sweep: no region-current kernel for %d components per pass", take);
+    else
+        k.refusal = RT_SUCCESS;
+    return k;
 }
 
 #undef RT_F32_WITH

@@ -1,5 +1,5 @@
 // rt_sweep_pn.hip — k_sweep_pn: the FP64 sweep over (ℓ, cell) rows with P2 / P3 anisotropic scattering (rt_solver_set_scatter_pn;
-// include/rt_segmentize.h states the definitions), and its launcher.  A translation unit of its own: the kernels of rt_sweep.hip,
+// include/rt_segmentize.h states the definitions), and the table of its instantiations.  A translation unit of its own: the kernels of rt_sweep.hip,
 // rt_sweep_iface.hip and rt_sweep_f32.hip keep their names and instructions.
 #include "rt_internal.hpp"
 
@@ -186,20 +186,11 @@ __global__ __launch_bounds__(1024) void k_sweep_pn(DSweep a) {
 
 namespace rtx {
 
-// One pass of k_sweep_pn over component a.g0 — queued on `s` with the grid and the LDS size the plan chose for the pass
-// (a.use_lds: the tallies' LDS copy, NT doubles per cell).
-int launch_sweep_pn(const rt::DSweep &a, size_t smem, int waves, unsigned blocks, hipStream_t s) {
-    auto go = [&]<int M, bool LDS>() -> int {
-        if (smem > 48 * 1024)
-            RT_HIP(hipFuncSetAttribute((const void *)rt::k_sweep_pn<M, 1, LDS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL((rt::k_sweep_pn<M, 1, LDS>), dim3(blocks), dim3(64 * waves), smem, s, a);
-        return RT_SUCCESS;
-    };
-    const bool lds = a.use_lds != 0;
-    if (a.ng == 1 && a.pn_M == 2) return lds ? go.template operator()<2, true>() : go.template operator()<2, false>();
-    if (a.ng == 1 && a.pn_M == 3) return lds ? go.template operator()<3, true>() : go.template operator()<3, false>();
-    set_error("rt_sweep: no P%d kernel for %d components per pass", a.pn_M, a.ng);
-    return RT_ERR_INVALID;
+// k_sweep_pn of order M (2, 3) — one component per pass —, with or without the tallies' LDS copy; nullptr: there is none
+const void *sweep_kernel_pn(int M, bool lds) {
+    if (M == 2) return lds ? (const void *)rt::k_sweep_pn<2, 1, true> : (const void *)rt::k_sweep_pn<2, 1, false>;
+    if (M == 3) return lds ? (const void *)rt::k_sweep_pn<3, 1, true> : (const void *)rt::k_sweep_pn<3, 1, false>;
+    return nullptr;
 }
 
 }  // namespace rtx

@@ -1,6 +1,6 @@
 """What one rt_sweep call decides — the rows it reads, the passes' width, LDS copy and launch shape, its refusals — is a pure
 function in csrc/rt_sweep_plan.hpp.  tests/sanitize/sweep_plan_san.cpp checks it on the host against the values sweep_impl computed
-when the decisions still lived in it; here the program is built without sanitizers and run (tests/sanitize/run.sh builds it with
+when the decisions still lived in it, and that every pass of a plan it does not refuse has a kernel (pass_kernel_key); here the program is built without sanitizers and run (tests/sanitize/run.sh builds it with
 AddressSanitizer + UBSan).  No GPU, no HIP header."""
 import os
 import re
