@@ -473,7 +473,28 @@ int32_t rt_set_option(rt_mesh *mesh, const char *name, int64_t value);
  *              fixed source: ‖φ^{n+1} − φ^n‖₂ / ‖φ^{n+1}‖₂ over all (cell, group) pairs
  * Stop         |k^{n+1} − k^n| / k^{n+1} < tol_k and residual < tol_flux, or max_iter iterations (converged = 0;
  *              not an error).  Eigenvalue mode scales the returned φ to F(φ) = 1.
- * Every Σt must be > 0 (void materials are rejected); all other data finite and >= 0.
+ * Every Σt must be finite and >= 0, all other data finite and >= 0; a material whose Σt is 0 is void (next paragraph).
+ *
+ * Void.  A material m is void when Σt[m][g] = 0 for every g.  Refused, with a message that names the material and the group: a
+ * material with Σt = 0 in some groups only; a void material with a non-zero Σs, Σs1 or νΣf entry (its χ is ignored); and, by
+ * rt_solver_set_source, a non-zero external source (forward or adjoint) in a cell of a void material.  In a void cell:
+ * Sweep        τ = 0 and ψ passes unchanged (the ratio slot of the sweep's cross sections is 0, as rt_sweep documents)
+ * Tally        T[e][c] += w ψ ℓ — ψ the flux the traversal carries through the record, ℓ the 2-D chord — in place of w Δψ; with
+ *              first-moment scattering Tx += w d cos φ_u ψ ℓ and Ty += w d sin φ_u ψ ℓ
+ * Fold         φ_{e,g} = Σ_p ω_p T[e][g·P + p] / V_e and J_{e,g} = Σ_p ω_p sin θ_p (Tx, Ty)[e][g·P + p] / V_e   (V_e = 0: 0)
+ *              — the Σt → 0 limits of the folds above (Δψ → ψ Σt ℓ / sin θ_p), so a problem whose void is replaced by Σt = ε tends
+ *              to this one linearly in ε
+ * Source       q = 0
+ * Reductions   a void cell takes no part in F, in the residual over the cells with fission, in the balance's reaction terms or in
+ *              the adjoint-weighted integrals of rt_solver_bilinear; it does take part in the fixed-source residual
+ * The sweep of a solver that holds a void material is k_sweep_void (rt_sweep_void.hip), over (ℓ, cell) rows; a solver without one
+ * launches what it always did, and a bare rt_sweep keeps its behaviour (a cell with sigma_t = 0 leaves ψ unchanged and tallies
+ * nothing).  Runs with: eigenvalue and fixed-source runs, first-moment scattering, adjoint mode, rt_solver_set_boundary (albedo and
+ * incoming flux, currents, balance), the stepwise calls.  Refused, by the setter on a solver that holds a void material, in a message
+ * that leads with the entry point and names both sides (the solver still runs afterwards): the linear source, P2 / P3 scattering,
+ * the single-precision sweep, the reproducible tallies, regions and the coarse-mesh acceleration, source regions, the volume
+ * correction, restarted GMRES, transients (rt_solver_transient_set_xs refuses a void table as well) and a shard's track set
+ * (rt_solver_create, rt_solver_begin).
  *
  * Linearly anisotropic (P1) scattering, rt_solver_set_scatter_p1.  sigma_s1[m][g'][g] is the l = 1 Legendre moment of the
  * transfer from g' to g in the convention Σs(g'→g, μ0) = (1/4π) [Σs0 + 3 Σs1 μ0] (Σs0 = sigma_s).  It may be negative;

@@ -4,7 +4,7 @@
 //   rt_records.hip     staging -> records: k_compact3, k_materialise, k_finish, the offsets scan, k_volumes, k_fill_tau
 //   rt_materialise.hip k_materialise_lin: a two-phase call's records in output order
 //   rt_sweep.hip       rt_sweep: k_sweep, k_sweep_link, the sweep's host code (one launch for every pass) and entry points
-//   rt_sweep_f32.hip, rt_sweep_iface.hip, rt_sweep_pn.hip  k_sweep_f32, k_sweep_iface, k_sweep_pn and the table of their instantiations
+//   rt_sweep_f32.hip, rt_sweep_iface.hip, rt_sweep_pn.hip, rt_sweep_void.hip  k_sweep_f32, k_sweep_iface, k_sweep_pn, k_sweep_void and the table of their instantiations
 //   rt_sweep_plan.hpp  what an rt_sweep call decides (rows, pass width and shape, refusals, the kernel of a pass): host-only, pure functions
 //   rt_sweep_state.hpp what the handle keeps for rt_sweep (rt_tracks::sw) and what a solver lends it (SweepLoan)
 //   rt_volcorr.hip     rt_solver's volume correction: tracked lengths, factors, corrected volumes, ℓ' (k_vc_tally / _factor / _apply)
@@ -658,6 +658,7 @@ int ensure_rows_from_compact(rt_tracks *t);  // rt_sweep.hip
 const void *sweep_kernel_f32(int gp, bool lds);                    // rt_sweep_f32.hip
 const void *sweep_kernel_iface(SweepMode mode, int gp, bool lds);  // rt_sweep_iface.hip
 const void *sweep_kernel_pn(int M, bool lds);                      // rt_sweep_pn.hip
+const void *sweep_kernel_void(SweepMode mode, int gp, bool lds);   // rt_sweep_void.hip
 // rt_cmfd.hip: the LDS k_cmfd_solve asks for (0: does not fit; *resident: all G factors live there), and the coarse step of one fold
 size_t cmfd_solve_lds(int32_t R, int32_t G, bool *resident);
 int launch_cmfd_step(rt::DCmfd c, int32_t n_items, unsigned cblocks, hipStream_t s);

@@ -30,6 +30,10 @@
 // plain iterations: one plain iteration, then up to m applications of the iteration's linear part — the same sweep and fold with the
 // external source left out — with the vector kernels of rt_krylov.hip between them and the least-squares solve of rt_krylov_host.hpp
 // on the host.  Eigenvalue runs, and a solver without the option, launch what they always did.
+// With a void material (Σt = 0 in every group; rt_solver_create takes it, "Void" in include/rt_segmentize.h) the solver launches the
+// same kernels, which test their Σt_g against 0 — ratio 0 from the source kernels, the track-length form in the folds —, and the sweep
+// it queues runs k_sweep_void (rt_sweep_void.hip; SweepLoan::has_void).  What does not run with it: void_refused (rt_solver_set.hip).
+// Without one the solver launches what it always did.
 // The handle itself, one struct per option, and what this file shares with rt_solver_set.hip (the setters, fetches and *_pointers
 // calls): rt_solver_state.hpp.
 #include "rt_solver_state.hpp"
@@ -69,7 +73,7 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_source(const int32_t *__
     const double k = eigen ? scal[0] : 1.0;
     s += X[2 * G + g] * prod[e] / k;
     if (ext) s += ext[i];
-    const double ratio = s / kFourPi / X[g];
+    const double ratio = X[g] > 0.0 ? s / kFourPi / X[g] : 0.0;  // (a void cell: no source term)
     double *x = xs + (e * G * P + (int64_t)g * P) * 2;
     for (int32_t p = 0; p < P; ++p) x[2 * p + 1] = ratio;
 }
@@ -102,14 +106,15 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_source_p1(const int32_t 
         sx += s1 * Je[2 * gp];
         sy += s1 * Je[2 * gp + 1];
     }
-    const double rx = kThreeOverFourPi * sx / X[g], ry = kThreeOverFourPi * sy / X[g];
+    const bool live = X[g] > 0.0;  // (a void cell scatters nothing)
+    const double rx = live ? kThreeOverFourPi * sx / X[g] : 0.0, ry = live ? kThreeOverFourPi * sy / X[g] : 0.0;
     q1r[2 * i] = rx; q1r[2 * i + 1] = ry;
     double *x = xs1 + (e * G * P + (int64_t)g * P) * 2;
     for (int32_t p = 0; p < P; ++p) { x[2 * p] = rx * pol[p]; x[2 * p + 1] = ry * pol[p]; }
 }
 
 // J of every (cell, group) (one thread each) from the sweep's first-moment tallies `cur` [n_cells][G·P][2]:
-// J = (4π/3) q1/Σt + Σ_p ω_p sin²θ_p (Tx, Ty) / (Σt V)
+// J = (4π/3) q1/Σt + Σ_p ω_p sin²θ_p (Tx, Ty) / (Σt V); in a void cell (Σt = 0), whose tallies are track lengths, Σ_p ω_p sin θ_p (Tx, Ty) / V
 __global__ __launch_bounds__(kSolveBlock) void k_solver_fold_p1(const int32_t *__restrict__ mat, const double *__restrict__ tab,
                                                                 const double *__restrict__ vol, const double *__restrict__ pol,
                                                                 const double *__restrict__ cur, const double *__restrict__ q1r, int32_t n_cells,
@@ -122,6 +127,12 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_fold_p1(const int32_t *_
     const double st = mat_row_p1(tab, mat[e], G)[g];
     const double *c = cur + (e * G * P + (int64_t)g * P) * 2;
     double ax = 0.0, ay = 0.0;
+    if (st == 0.0) {
+        for (int32_t p = 0; p < P; ++p) { ax += pol[P + p] * c[2 * p]; ay += pol[P + p] * c[2 * p + 1]; }  // (pol[P + p]: ω_p sin θ_p)
+        J[2 * i] = V > 0.0 ? ax / V : 0.0;
+        J[2 * i + 1] = V > 0.0 ? ay / V : 0.0;
+        return;
+    }
     for (int32_t p = 0; p < P; ++p) {
         const double wss = pol[P + p] * pol[p];  // ω_p sin²θ_p
         ax += wss * c[2 * p];
@@ -275,7 +286,9 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_fold_ls(const int32_t *_
     mom[2 * i + 1] = kFourPi * (Cm[1] * gx + Cm[2] * gy) + ay / (st * V);
 }
 
-// INIT: φ = 1, Σt_g / sin θ_p of every component; otherwise the fold of the last sweep's tallies T [n_cells][G·P].  Both: the
+// INIT: φ = 1, Σt_g / sin θ_p of every component; otherwise the fold of the last sweep's tallies T [n_cells][G·P] (a void cell: the
+// track-length form).  A void cell has νΣf = 0: it adds nothing to F or to the residual over fissile cells, and it takes part in the
+// fixed-source residual like any other cell.  Both: the
 // cell's production F_e = Σ_g νΣf φ into `prod` (the previous one is the residual's reference) and this block's partials.
 // One thread per cell.
 template <bool INIT>
@@ -303,8 +316,13 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_fold(const int32_t *__re
             } else {
                 const double *Tg = T + e * C + (int64_t)g * P;
                 double acc = 0.0;
-                for (int32_t p = 0; p < P; ++p) acc += pol[P + p] * Tg[p];
-                nw = kFourPi * x[1] + (V > 0.0 ? acc / (st * V) : 0.0);
+                if (st == 0.0) {  // a void cell: its tallies are track lengths w ψ ℓ, and φ = Σ_p ω_p T / V
+                    for (int32_t p = 0; p < P; ++p) acc += pol[P + p] / pol[p] * Tg[p];
+                    nw = V > 0.0 ? acc / V : 0.0;
+                } else {
+                    for (int32_t p = 0; p < P; ++p) acc += pol[P + p] * Tg[p];
+                    nw = kFourPi * x[1] + (V > 0.0 ? acc / (st * V) : 0.0);
+                }
             }
             const double old = phi[e * G + g];
             phi[e * G + g] = nw;
@@ -464,6 +482,55 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_iface_fold(const double 
 
 namespace rtx {
 
+// The [M]-tables of a solver, for every entry that takes them.  is_void: the entry takes void materials ("Void" in
+// include/rt_segmentize.h) and gets one flag per material — Σt = 0 in every group, and then no Σs and no νΣf (χ is ignored); a
+// material with Σt = 0 in some groups only is refused.  Null: every Σt must be > 0.
+int solver_check_xs(const char *who, int32_t M, int32_t G, const double *sigma_t, const double *sigma_s, const double *nu_sigma_f, const double *chi,
+                    std::vector<uint8_t> *is_void) {
+    const size_t mg = (size_t)M * G;
+    for (size_t i = 0; i < mg; ++i) {
+        if (!(sigma_t[i] >= 0.0) || !std::isfinite(sigma_t[i])) {
+            set_error("%s: sigma_t[%zu][%zu] = %g (every Σt must be finite and %s)", who, i / G, i % G, sigma_t[i], is_void ? ">= 0" : "> 0");
+            return RT_ERR_INVALID;
+        }
+        if (!is_void && sigma_t[i] == 0.0) {
+            set_error("%s: sigma_t[%zu][%zu] = 0 (every Σt must be finite and > 0: void materials are not supported by this call)", who, i / G, i % G);
+            return RT_ERR_INVALID;
+        }
+    }
+    size_t bad = 0;
+    if (!finite_nonneg(sigma_s, mg * G, &bad)) { set_error("%s: sigma_s[%zu] = %g (must be finite and >= 0)", who, bad, sigma_s[bad]); return RT_ERR_INVALID; }
+    if (!finite_nonneg(nu_sigma_f, mg, &bad)) { set_error("%s: nu_sigma_f[%zu] = %g (must be finite and >= 0)", who, bad, nu_sigma_f[bad]); return RT_ERR_INVALID; }
+    if (!finite_nonneg(chi, mg, &bad)) { set_error("%s: chi[%zu] = %g (must be finite and >= 0)", who, bad, chi[bad]); return RT_ERR_INVALID; }
+    if (!is_void) return RT_SUCCESS;
+    is_void->assign((size_t)M, 0);
+    for (int32_t m = 0; m < M; ++m) {
+        const double *st = sigma_t + (size_t)m * G;
+        int32_t zero = -1, pos = -1;
+        for (int32_t g = G - 1; g >= 0; --g) (st[g] == 0.0 ? zero : pos) = g;  // (the first group of each kind)
+        if (zero < 0) continue;
+        if (pos >= 0) {
+            set_error("%s: material %d has sigma_t[%d][%d] = 0 but sigma_t[%d][%d] = %g (a void material has Σt = 0 in every group)", who, m, m, zero, m, pos, st[pos]);
+            return RT_ERR_INVALID;
+        }
+        for (int32_t a = 0; a < G; ++a) {
+            for (int32_t b = 0; b < G; ++b)
+                if (sigma_s[((size_t)m * G + a) * G + b] != 0.0) {
+                    set_error("%s: material %d is void (sigma_t[%d][g] = 0 in every group) but sigma_s[%d][%d][%d] = %g (a void material scatters nothing)", who, m, m, m, a, b,
+                              sigma_s[((size_t)m * G + a) * G + b]);
+                    return RT_ERR_INVALID;
+                }
+            if (nu_sigma_f[(size_t)m * G + a] != 0.0) {
+                set_error("%s: material %d is void (sigma_t[%d][g] = 0 in every group) but nu_sigma_f[%d][%d] = %g (a void material fissions nothing)", who, m, m, m, a,
+                          nu_sigma_f[(size_t)m * G + a]);
+                return RT_ERR_INVALID;
+            }
+        }
+        (*is_void)[(size_t)m] = 1;
+    }
+    return RT_SUCCESS;
+}
+
 // The end of a run's hold on its handle, whichever way the run ends: the handle's own sweeps weigh by δs again, isotropically.
 // Called with the tracks alive (rt_tracks_destroy calls it before it frees them).
 void solver_release(rt_solver *S) {
@@ -520,15 +587,16 @@ int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_m
             return RT_ERR_INVALID;
         }
     const size_t mg = (size_t)M * G;
-    for (size_t i = 0; i < mg; ++i)
-        if (!(sigma_t[i] > 0.0) || !std::isfinite(sigma_t[i])) {
-            set_error("rt_solver_create: sigma_t[%zu][%zu] = %g (every Σt must be finite and > 0; void materials are not supported)", i / G, i % G, sigma_t[i]);
-            return RT_ERR_INVALID;
-        }
-    size_t bad = 0;
-    if (!finite_nonneg(sigma_s, mg * G, &bad)) { set_error("rt_solver_create: sigma_s[%zu] = %g (must be finite and >= 0)", bad, sigma_s[bad]); return RT_ERR_INVALID; }
-    if (!finite_nonneg(nu_sigma_f, mg, &bad)) { set_error("rt_solver_create: nu_sigma_f[%zu] = %g (must be finite and >= 0)", bad, nu_sigma_f[bad]); return RT_ERR_INVALID; }
-    if (!finite_nonneg(chi, mg, &bad)) { set_error("rt_solver_create: chi[%zu] = %g (must be finite and >= 0)", bad, chi[bad]); return RT_ERR_INVALID; }
+    std::vector<uint8_t> is_void;
+    if (int rc = solver_check_xs("rt_solver_create", M, G, sigma_t, sigma_s, nu_sigma_f, chi, &is_void)) return rc;
+    const auto first_void = std::find(is_void.begin(), is_void.end(), (uint8_t)1);
+    const bool has_void = first_void != is_void.end();
+    if (has_void && t->sw.links.shard) {  // (no solver yet to ask void_refused with)
+        char text[rtopt::kMessageCap];
+        rtvoid::format_refusal(text, sizeof text, "rt_solver_create", (int)(first_void - is_void.begin()), rtopt::Option::Shard, 0);
+        set_error("%s", text);
+        return RT_ERR_INVALID;
+    }
     double sp = 0.0;
     for (int32_t p = 0; p < P; ++p) {
         if (!(sin_polar[p] > 0.0 && sin_polar[p] <= 1.0) || !(polar_weight[p] > 0.0) || !std::isfinite(polar_weight[p])) {
@@ -559,6 +627,7 @@ int solver_create_impl(rt_tracks *t, int32_t G, int32_t M, const int32_t *cell_m
     S->t = t; S->device = m->device; S->epoch = t->seg_epoch; S->G = G; S->M = M; S->P = P; S->N2 = N2; S->n_cells = nc;
     S->n_mesh = nc; S->h_mat.assign(cell_material, cell_material + nc);
     S->h_nf.assign(nu_sigma_f, nu_sigma_f + mg); S->h_chi.assign(chi, chi + mg);
+    S->h_void.swap(is_void); S->has_void = has_void;
     const std::vector<double> tab = solver_table(S, false);
     std::vector<double> pol((size_t)2 * P);
     for (int32_t p = 0; p < P; ++p) { pol[(size_t)p] = sin_polar[p]; pol[(size_t)(P + p)] = polar_weight[p] * sin_polar[p]; }
@@ -648,6 +717,7 @@ int solver_begin_impl(rt_solver *S, int32_t mode, const char *who, bool keep_phi
         return RT_ERR_INVALID;
     }
     const bool eigen = mode == RT_SOLVE_EIGENVALUE;
+    if (void_refused(S, who, Option::Shard)) return RT_ERR_INVALID;  // (the links may have become a shard's since rt_solver_create)
     {  // (the setters keep the combinations apart; the links may have become a shard's since.  An eigenvalue run takes no GMRES cycles)
         Option a, b;
         if (rtopt::first_pair(solver_option_mask(S) & ~(eigen ? rtopt::bit(Option::Krylov) : 0u), &a, &b)) {
@@ -1059,21 +1129,6 @@ int solver_run_impl(rt_solver *S, int32_t mode, int32_t max_iter, double tol_k, 
 // ---- transient (rt_solver_transient_*; "Transient" in include/rt_segmentize.h) ------------------------------------------------------
 constexpr int32_t kMaxFamilies = 64;
 
-// The [M]-tables of a solver as rt_solver_create checks them.
-int solver_check_xs(const char *who, int32_t M, int32_t G, const double *sigma_t, const double *sigma_s, const double *nu_sigma_f, const double *chi) {
-    const size_t mg = (size_t)M * G;
-    for (size_t i = 0; i < mg; ++i)
-        if (!(sigma_t[i] > 0.0) || !std::isfinite(sigma_t[i])) {
-            set_error("%s: sigma_t[%zu][%zu] = %g (every Σt must be finite and > 0; void materials are not supported)", who, i / G, i % G, sigma_t[i]);
-            return RT_ERR_INVALID;
-        }
-    size_t bad = 0;
-    if (!finite_nonneg(sigma_s, mg * G, &bad)) { set_error("%s: sigma_s[%zu] = %g (must be finite and >= 0)", who, bad, sigma_s[bad]); return RT_ERR_INVALID; }
-    if (!finite_nonneg(nu_sigma_f, mg, &bad)) { set_error("%s: nu_sigma_f[%zu] = %g (must be finite and >= 0)", who, bad, nu_sigma_f[bad]); return RT_ERR_INVALID; }
-    if (!finite_nonneg(chi, mg, &bad)) { set_error("%s: chi[%zu] = %g (must be finite and >= 0)", who, bad, chi[bad]); return RT_ERR_INVALID; }
-    return RT_SUCCESS;
-}
-
 // χ̃_{m,g} = χ_{m,g} − Σ_d β_{m,d} χd_{m,d,g} for the given tables: >= −1e-14 everywhere, or the material and group named
 int transient_check_prompt(const rt_solver *S, const double *chi, int32_t D, const double *beta, const double *chi_delayed, const char *who) {
     const int32_t G = S->G, M = S->M;
@@ -1288,7 +1343,7 @@ int transient_set_xs_impl(rt_solver *S, const double *sigma_t, const double *sig
     if (!S || !sigma_t || !sigma_s || !nu_sigma_f || !chi) { set_error("%s: null argument", who); return RT_ERR_INVALID; }
     if (int rc = transient_enter(S, who)) return rc;
     const int32_t G = S->G, M = S->M;
-    if (int rc = solver_check_xs(who, M, G, sigma_t, sigma_s, nu_sigma_f, chi)) return rc;
+    if (int rc = solver_check_xs(who, M, G, sigma_t, sigma_s, nu_sigma_f, chi, nullptr)) return rc;  // (a transient takes no void material)
     if (int rc = transient_check_prompt(S, chi, S->tr.D, S->tr.h_beta.data(), S->tr.h_chid.data(), who)) return rc;
     const size_t mg = (size_t)M * G;
     S->tr.h_st.assign(sigma_t, sigma_t + mg); S->tr.h_ss.assign(sigma_s, sigma_s + mg * G);

@@ -83,8 +83,9 @@ constexpr int kMaxForms = 8;
 // B_f = Σ_e V_e Σ_g Σ_g' φ†[e][g] A_f[m(e)][g'][g] φ[e][g'] for n_forms <= kMaxForms forms, one thread per cell: the cell's V-weighted
 // terms into `cell` [n_forms][n_cells] (when given) and this block's sums into partial[block][kMaxForms].  The matrices A
 // [n_forms][M][G][G] from LDS when the host says they fit (a_len doubles; 0 = read them where they lie).  Cells with V_e = 0
-// contribute 0.
-__global__ __launch_bounds__(kSolveBlock) void k_solver_bilinear(const int32_t *__restrict__ mat, const double *__restrict__ A_g, int32_t a_len,
+// contribute 0, and so do void cells (`tab`: the forward solver's material table, whose rows begin with Σt[G]; Σt_0 = 0 marks a void
+// material): they take part in no reaction term.
+__global__ __launch_bounds__(kSolveBlock) void k_solver_bilinear(const int32_t *__restrict__ mat, const double *__restrict__ tab, const double *__restrict__ A_g, int32_t a_len,
                                                                  const double *__restrict__ vol, const double *__restrict__ phi_adj,
                                                                  const double *__restrict__ phi, int32_t n_cells, int32_t G, int32_t M,
                                                                  int32_t n_forms, double *__restrict__ cell, double *__restrict__ partial) {
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(kSolveBlock) void k_solver_bilinear(const int32_t *
     for (int f = 0; f < kMaxForms; ++f) v[f] = 0.0;
     if (e < n_cells) {
         const double V = vol[e];
-        if (V > 0.0) {
+        if (V > 0.0 && tab[(int64_t)mat[e] * G * (3 + G)] > 0.0) {
             const int64_t GG = (int64_t)G * G, MGG = (int64_t)M * GG;
             const double *Am = A + (int64_t)mat[e] * GG;
             const double *pa = phi_adj + e * G, *pf = phi + e * G;
@@ -190,9 +191,22 @@ uint32_t solver_option_mask(const rt_solver *S) {
          | on(S->t->sw.links.shard, Option::Shard);
 }
 
+// Void materials are no option — rt_solver_create takes them, nothing switches them off, and rtopt's table stays what it is —, so what
+// does not run with them is a list of its own (rt_void_rules.hpp, with the message: it leads with the entry point and names both sides).
+bool void_refused(const rt_solver *S, const char *who, Option wanted, int order) {
+    if (!S->has_void || !rtvoid::refuses(wanted)) return false;
+    if (wanted == Option::Shard && !S->t->sw.links.shard) return false;  // (asked by rt_solver_create and rt_solver_begin, which have no setter to ask)
+    const int32_t m = (int32_t)(std::find(S->h_void.begin(), S->h_void.end(), (uint8_t)1) - S->h_void.begin());
+    char text[rtopt::kMessageCap];
+    rtvoid::format_refusal(text, sizeof text, who, m, wanted, order < 0 ? S->pn.order : order);
+    set_error("%s", text);
+    return true;
+}
+
 // A setter's question: does something that is set (but for `ignore`) not run with `wanted`?  Then the message names both sides.
 // order: the P2 / P3 order a message names where one side is P2 / P3 scattering (0: "P2 / P3"; by default the order that is set).
 bool option_refused(const rt_solver *S, const char *who, Option wanted, int order, uint32_t ignore) {
+    if (void_refused(S, who, wanted, order)) return true;
     Option set;
     if (!rtopt::first_conflict(wanted, solver_option_mask(S) & ~ignore, &set)) return false;
     char text[rtopt::kMessageCap];
@@ -373,6 +387,16 @@ int32_t rt_solver_set_source(rt_solver *solver, const double *source) {
     const size_t ncg = (size_t)solver->n_cells * solver->G;
     size_t bad = 0;
     if (!finite_nonneg(source, ncg, &bad)) { set_error("rt_solver_set_source: source[%zu] = %g (must be finite and >= 0)", bad, source[bad]); return RT_ERR_INVALID; }
+    if (solver->has_void)  // (no source regions with void materials: n_cells is the mesh's)
+        for (size_t e = 0; e < (size_t)solver->n_cells; ++e) {
+            const int32_t m = solver->h_mat[e];
+            if (!solver->h_void[(size_t)m]) continue;
+            for (int32_t g = 0; g < solver->G; ++g)
+                if (source[e * solver->G + g] != 0.0) {
+                    set_error("rt_solver_set_source: source[%zu][%d] = %g in a cell of the void material %d (Σt = 0: a void cell has no source)", e, g, source[e * solver->G + g], m);
+                    return RT_ERR_INVALID;
+                }
+        }
     return guarded("rt_solver_set_source", [&]() -> int32_t {
         RT_HIP(hipSetDevice(solver->t->mesh->device));
         if (int rc = upload(solver->ext, source, ncg, solver->t->mesh->stream)) return rc;
@@ -388,6 +412,12 @@ static int32_t solver_set_scatter_p1_impl(rt_solver *S, const double *sigma_s1) 
     if (option_refused(S, "rt_solver_set_scatter_p1", Option::P1)) return RT_ERR_INVALID;
     const int32_t G = S->G, M = S->M;
     const size_t n1 = (size_t)M * G * G;
+    for (size_t i = 0; i < n1 && S->has_void; ++i)
+        if (S->h_void[i / ((size_t)G * G)] && sigma_s1[i] != 0.0) {
+            set_error("rt_solver_set_scatter_p1: material %zu is void (Σt = 0 in every group) but sigma_s1[%zu][%zu][%zu] = %g (a void material scatters nothing)",
+                      i / ((size_t)G * G), i / ((size_t)G * G), i / G % G, i % G, sigma_s1[i]);
+            return RT_ERR_INVALID;
+        }
     for (size_t i = 0; i < n1; ++i)
         if (!std::isfinite(sigma_s1[i]) || !(std::fabs(sigma_s1[i]) <= S->h_ss[i])) {
             set_error("rt_solver_set_scatter_p1: sigma_s1[%zu] = %g against sigma_s = %g (must be finite with |Σs1| <= Σs0)", i, sigma_s1[i], S->h_ss[i]);
@@ -544,7 +574,7 @@ static int32_t solver_bilinear_impl(rt_solver *Sa, rt_solver *Sf, int32_t n_form
     if (out_cell) RT_HIP(dcell.reserve(std::max<size_t>(1, (size_t)n_forms * nc)));
     const int32_t lds_len = a_len * sizeof(double) <= 32 * 1024 ? (int32_t)a_len : 0;  // (else read where they lie: L2-resident)
     hipLaunchKernelGGL(rt::k_solver_bilinear, dim3(blocks), dim3(rt::kSolveBlock), (size_t)lds_len * sizeof(double), s, (const int32_t *)Sf->mat.p,
-                       (const double *)dA.p, lds_len, (const double *)Sf->vol.p, (const double *)Sa->phi.p, (const double *)Sf->phi.p, nc, G, M, n_forms,
+                       (const double *)Sf->tab.p, (const double *)dA.p, lds_len, (const double *)Sf->vol.p, (const double *)Sa->phi.p, (const double *)Sf->phi.p, nc, G, M, n_forms,
                        out_cell ? dcell.p : (double *)nullptr, partial.p);
     hipLaunchKernelGGL(rt::k_solver_bilinear_reduce, dim3(1), dim3(rt::kSolveBlock), 0, s, (const double *)partial.p, (int32_t)blocks, dout.p);
     RT_HIP(hipGetLastError());

@@ -10,6 +10,7 @@
 #include "rt_internal.hpp"
 #include "rt_krylov_host.hpp"
 #include "rt_solver_options.hpp"
+#include "rt_void_rules.hpp"
 
 namespace rt {
 
@@ -57,6 +58,10 @@ struct rt_solver {
     // tables from them
     std::vector<double> h_st, h_ss, h_nf, h_chi;
     bool adjoint = false;
+    // void materials (Σt = 0 in every group; "Void" in include/rt_segmentize.h): one flag per material and whether any is set.  On the
+    // device a void material is its table row: the kernels test Σt_g == 0, which holds in every group or in none
+    std::vector<uint8_t> h_void;
+    bool has_void = false;
     // the source's shape as the setters leave it (a mode switched off keeps its table / geometry)
     SweepMode mode = SweepMode::Flat;
     // single-precision sweep (rt_solver_set_precision): lent to the handle (SweepLoan::f32) for the solver's runs
@@ -212,6 +217,9 @@ bool finite_nonneg(const double *a, size_t n, size_t *bad);
 std::vector<double> solver_table(const rt_solver *S, bool adjoint);
 uint32_t solver_option_mask(const rt_solver *S);
 bool option_refused(const rt_solver *S, const char *who, rtopt::Option wanted, int order = -1, uint32_t ignore = 0);
+bool void_refused(const rt_solver *S, const char *who, rtopt::Option wanted, int order = -1);
+int solver_check_xs(const char *who, int32_t M, int32_t G, const double *sigma_t, const double *sigma_s, const double *nu_sigma_f, const double *chi,
+                    std::vector<uint8_t> *is_void);
 int solver_repro_reserve(rt_solver *S, const char *who, int min_nv = 1);
 int solver_volcorr_prepare(rt_solver *S, const char *who);
 int solver_srcreg_prepare(rt_solver *S, const char *who);
@@ -219,7 +227,7 @@ int solver_srcreg_prepare(rt_solver *S, const char *who);
 // What the setters have chosen for the sweeps of the next run, as far as it decides which rows a sweep reads.
 inline SweepLoan solver_loan_probe(const rt_solver *S) {
     SweepLoan l;
-    l.mode = S->mode; l.repro = S->rep.on; l.f32 = S->single; l.n_regions = S->reg.R;
+    l.mode = S->mode; l.repro = S->rep.on; l.f32 = S->single; l.n_regions = S->reg.R; l.has_void = S->has_void;
     return l;
 }
 

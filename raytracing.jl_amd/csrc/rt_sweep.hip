@@ -2,7 +2,7 @@
 // What a call decides — rows, pass width and shape, refusals — is plan_sweep, and the kernel of each pass pass_kernel_key (rt_sweep_plan.hpp,
 // pure functions checked on the host); sweep_impl fills the facts from the handle (rt_tracks::sw, rt_sweep_state.hpp) and an rt_solver's
 // loan (sw.loan), makes the rows the plan names and launches every pass through one function, launch_pass: sweep_pass_kernel turns the key
-// into a kernel of this file or of a sibling unit (rt_sweep_f32.hip, rt_sweep_iface.hip, rt_sweep_pn.hip: sweep_kernel_*).
+// into a kernel of this file or of a sibling unit (rt_sweep_f32.hip, rt_sweep_iface.hip, rt_sweep_pn.hip, rt_sweep_void.hip: sweep_kernel_*).
 #include "rt_internal.hpp"
 
 #include <rocprim/device/device_radix_sort.hpp>  // the cell index of the reproducible tallies: one stable sort per segmentation
@@ -58,14 +58,17 @@ namespace rt {
 // k_sweep_iface (rt_sweep_iface.hip); sweep_impl lends it the solver's region array and tally, zeroes the tally before the first
 // pass and launches it in k_sweep's place (pass_kernel_key names the family, launch_pass launches it).  The kernels of this file compile
 // to what they were.
+// VOID (void materials, rt_solver_create with Σt = 0): a third constant of the shared body, false in both kernels here and in
+// k_sweep_iface, true in k_sweep_void (rt_sweep_void.hip), which a solver that holds a void material lends in k_sweep's place
+// (SweepLoan::has_void; a bare rt_sweep never sets it, and a cell with sigma_t = 0 then leaves ψ unchanged and tallies nothing).
 template <bool STAGED, int GP, bool LDS, bool ELLROWS, bool P1 = false, bool LS = false>
 __global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep(DSweep a) {
-    constexpr bool REPRO = false, IFACE = false;
+    constexpr bool REPRO = false, IFACE = false, VOID = false;
 #include "rt_sweep_body.hpp"
 }
 template <bool STAGED, int GP, bool ELLROWS, bool P1 = false, bool LS = false>
 __global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep_repro(DSweep a) {
-    constexpr bool REPRO = true, LDS = false, IFACE = false;
+    constexpr bool REPRO = true, LDS = false, IFACE = false, VOID = false;
 #include "rt_sweep_body.hpp"
 }
 
@@ -415,7 +418,7 @@ static SweepFacts sweep_facts(const rt_tracks *t, int32_t G, int32_t input, cons
                       .f32 = loan.f32 || m->sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
                       .sw_ell_valid = t->sw.rows.ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
                       .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves, .regions = loan.n_regions,
-                      .volcorr = volcorr, .srcreg = loan.sr_n_src > 0, .pn = loan.pn_M};
+                      .volcorr = volcorr, .srcreg = loan.sr_n_src > 0, .pn = loan.pn_M, .has_void = loan.has_void};
 }
 
 namespace rtx {
@@ -507,6 +510,7 @@ static const void *sweep_pass_kernel(const PassKernelKey &k) {
     case SweepFamily::F32: return sweep_kernel_f32(k.gp, k.lds);
     case SweepFamily::PN: return sweep_kernel_pn(k.order, k.lds);
     case SweepFamily::Iface: return sweep_kernel_iface(k.mode, k.gp, k.lds);
+    case SweepFamily::Void: return sweep_kernel_void(k.mode, k.gp, k.lds);
     default: return sweep_kernel(k.staged, k.lds, k.mode, k.gp, k.family == SweepFamily::F64Repro, k.ellrows);
     }
 }

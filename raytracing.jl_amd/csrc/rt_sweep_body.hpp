@@ -4,10 +4,13 @@
 // constant REPRO and the kernel argument `DSweep a` in scope; rt_sweep.hip's head comment describes what it does.
 // A third kernel, k_sweep_iface (rt_sweep_iface.hip), includes it with the constant IFACE = true (false in the two above, whose
 // instructions stay what they were): the partial currents between cell regions, `if constexpr (IFACE)` below.
+// A fourth, k_sweep_void (rt_sweep_void.hip), includes it with the constant VOID = true (false in the three above, whose instructions
+// stay what they were): in a cell whose Σt is 0 the tally is the track length w ψ ℓ, `if constexpr (VOID)` below.
     static_assert(STAGED || !ELLROWS, "ℓ rows belong to the staging rows");
     static_assert(!(REPRO && LDS), "the reproducible tallies keep no LDS copy");
     static_assert(!IFACE || (STAGED && ELLROWS && !REPRO), "the region currents are tallied over (ℓ, cell) rows, by atomics");
     static_assert(!(P1 && LS), "linear source with first-moment scattering is not built");
+    static_assert(!VOID || (STAGED && ELLROWS && !REPRO && !IFACE && !LS), "the void tally is built over (ℓ, cell) rows, by atomics, flat or with first moments");
     constexpr bool AN = P1 || LS;        // three tallies and two ratios per component
     constexpr int NT = AN ? 3 : 1;       // tallies per component
     constexpr int NH = LS ? 2 * GP + 2 : (P1 ? 2 * GP : 1);  // ratios of a pass (one unused slot when isotropic); LS: + the cell's centroid
@@ -174,16 +177,28 @@
                 for (int g = 0; g < GP; ++g) {
                     const double d = (psi[g] - qs[g]) * one_minus_exp_neg_thin(tau[g], poly);
                     psi[g] = psi[g] - d;
-                    wd[g] = w * d;
-                    if constexpr (P1) { wd[GP + 2 * g] = wcs * d; wd[GP + 2 * g + 1] = wsn * d; }
+                    if constexpr (VOID) {  // (Σt = 0: d is a zero and ψ kept its bits — the track length ψ ℓ in Δψ's place)
+                        const double tv = st[g] == 0.0 ? psi[g] * ell : d;
+                        wd[g] = w * tv;
+                        if constexpr (P1) { wd[GP + 2 * g] = wcs * tv; wd[GP + 2 * g + 1] = wsn * tv; }
+                    } else {
+                        wd[g] = w * d;
+                        if constexpr (P1) { wd[GP + 2 * g] = wcs * d; wd[GP + 2 * g + 1] = wsn * d; }
+                    }
                 }
             } else {
 #pragma unroll
                 for (int g = 0; g < GP; ++g) {
                     const double d = (psi[g] - qs[g]) * one_minus_exp_neg(tau[g], poly);
                     psi[g] = psi[g] - d;
-                    wd[g] = w * d;
-                    if constexpr (P1) { wd[GP + 2 * g] = wcs * d; wd[GP + 2 * g + 1] = wsn * d; }
+                    if constexpr (VOID) {
+                        const double tv = st[g] == 0.0 ? psi[g] * ell : d;
+                        wd[g] = w * tv;
+                        if constexpr (P1) { wd[GP + 2 * g] = wcs * tv; wd[GP + 2 * g + 1] = wsn * tv; }
+                    } else {
+                        wd[g] = w * d;
+                        if constexpr (P1) { wd[GP + 2 * g] = wcs * d; wd[GP + 2 * g + 1] = wsn * d; }
+                    }
                 }
             }
             // REPRO: no fold and no add — every active lane stores its NT·GP values at its (row slot, direction) of the delta buffer, and

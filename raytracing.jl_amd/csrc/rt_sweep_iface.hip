@@ -14,7 +14,7 @@ namespace rt {
 // with the φ copy and flushed with it, non-zeros only, by global FP64 atomics into DSweep::if_S.
 template <int GP, bool LDS, bool P1 = false, bool LS = false>
 __global__ __launch_bounds__(LS ? 512 : 1024) void k_sweep_iface(DSweep a) {
-    constexpr bool STAGED = true, ELLROWS = true, REPRO = false, IFACE = true;
+    constexpr bool STAGED = true, ELLROWS = true, REPRO = false, IFACE = true, VOID = false;
 #include "rt_sweep_body.hpp"
 }
 

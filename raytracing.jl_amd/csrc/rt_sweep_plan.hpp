@@ -55,6 +55,7 @@ struct SweepFacts {
     bool volcorr = false;      // the rows' ℓ comes from a solver's corrected copy (rt_solver_set_volume_correction)
     bool srcreg = false;       // the rows are a solver's merged rows and n_cells its n_src (rt_solver_set_source_regions)
     int pn = 0;                // mode PN: the scattering order, 2 or 3 (2 pn + 1 tallies and ratios per component)
+    bool has_void = false;     // some cell's Σt is 0 in every component (lent by a solver that holds a void material): k_sweep_void
 };
 
 // tallies per component of a pass: 1 flat, 3 with first moments (P1, Linear), 2 L + 1 with P2 / P3 scattering
@@ -111,6 +112,9 @@ struct SweepPlan {
 
 #define RT_SR_WITH(other) "rt_sweep: the source regions (rt_solver_set_source_regions) together with " other " — not supported"
 #define RT_SR_ROWS(why) "rt_sweep: the source regions (rt_solver_set_source_regions) merge (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
+
+#define RT_VOID_WITH(other) "rt_sweep: void materials (Σt = 0, rt_solver_create) together with " other " — not supported"
+#define RT_VOID_ROWS(why) "rt_sweep: void materials (Σt = 0, rt_solver_create) are tallied over (ℓ, cell) rows, and this sweep would read rows of kind 0 — " why
 
 inline SweepPlan plan_sweep(const SweepFacts &f) {
     SweepPlan p;
@@ -194,6 +198,22 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
             return refuse(RT_SR_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
                                      "sweep without source regions first, or set option \"sweep_rows\" 2 and name the compact records"));
     }
+    // void materials: k_sweep_void, FP64 atomics, flat or first-moment scattering, over (ℓ, cell) rows — refused like the region
+    // currents, before anything is queued
+    if (f.has_void) {
+        if (f.mode == SweepMode::Linear) return refuse(RT_VOID_WITH("the linear source (rt_solver_set_linear_source): its moment tallies are accumulated times Σt"));
+        if (f.mode == SweepMode::PN) return refuse(RT_VOID_WITH("P2 / P3 scattering (rt_solver_set_scatter_pn): that is another kernel"));
+        if (f.f32) return refuse(RT_VOID_WITH("the single-precision sweep (rt_solver_set_precision, \"sweep_precision\" 1): that is another kernel"));
+        if (f.repro) return refuse(RT_VOID_WITH("the reproducible tallies (rt_solver_set_reproducible): that is another kernel"));
+        if (f.regions > 0) return refuse(RT_VOID_WITH("the region currents (rt_solver_set_regions, rt_solver_set_cmfd): that is another kernel"));
+        if (f.volcorr) return refuse(RT_VOID_WITH("the volume correction (rt_solver_set_volume_correction)"));
+        if (f.srcreg) return refuse(RT_VOID_WITH("the source regions (rt_solver_set_source_regions)"));
+        if (p.rows == SweepRows::Records) return refuse(RT_VOID_ROWS("the compact records where they lie: option \"sweep_rows\" is 0"));
+        if (p.rows == SweepRows::Staged20) return refuse(RT_VOID_ROWS("the staging's 20-B rows in every pass: option \"sweep_ell\" is 0"));
+        if (p.rows == SweepRows::Staged20WriteEll)
+            return refuse(RT_VOID_ROWS("the staging's 20-B rows in its first pass after this rt_segmentize (a march by exact steps leaves no (ℓ, cell) rows): run one "
+                                       "sweep without void materials first, or set option \"sweep_rows\" 2 and name the compact records"));
+    }
     // components per pass: as many as an LDS-private copy of their tallies allows (up to 4); none fits: global atomics.  The last
     // pass takes what is left with the kernel compiled for that many (7 groups = 4 + 3: a padded fourth group was an eighth of the
     // sweep's arithmetic).  First-moment scattering and the linear source: three tallies per component, so a mesh that fits 4
@@ -232,9 +252,10 @@ inline SweepPlan plan_sweep(const SweepFacts &f) {
 
 // ---- the kernel of a pass ---------------------------------------------------------------------------------------------------------
 // Which kernel a pass of `take` components runs is a function of the plan and that width: the family — the kernels of rt_sweep.hip
-// with atomic (F64) or reproducible (F64Repro) tallies, k_sweep_iface, k_sweep_f32, k_sweep_pn — and the family's template arguments.
+// with atomic (F64) or reproducible (F64Repro) tallies, k_sweep_iface, k_sweep_f32, k_sweep_pn, k_sweep_void (only where the facts say
+// has_void: every other sweep keeps the key it had) — and the family's template arguments.
 // rt_sweep.hip's sweep_pass_kernel turns the key into the kernel's address; nothing else chooses a kernel.
-enum class SweepFamily { F64, F64Repro, Iface, F32, PN };
+enum class SweepFamily { F64, F64Repro, Iface, F32, PN, Void };
 constexpr int kSweepGpFlat = 4;  // components per pass of a flat sweep, at most: the widest instantiation of every family (F32: rt::kSweepGpF32)
 
 struct PassKernelKey {
@@ -249,14 +270,14 @@ struct PassKernelKey {
 
 inline PassKernelKey pass_kernel_key(const SweepPlan &p, int take, bool iface) {
     PassKernelKey k;
-    k.family = p.f.f32 ? SweepFamily::F32 : (p.f.mode == SweepMode::PN ? SweepFamily::PN : (iface ? SweepFamily::Iface : (p.f.repro ? SweepFamily::F64Repro : SweepFamily::F64)));
+    k.family = p.f.f32 ? SweepFamily::F32 : (p.f.mode == SweepMode::PN ? SweepFamily::PN : (iface ? SweepFamily::Iface : (p.f.has_void ? SweepFamily::Void : (p.f.repro ? SweepFamily::F64Repro : SweepFamily::F64))));
     k.staged = rows_staged(p.rows); k.ellrows = rows_read_ell(p.rows); k.lds = p.use_lds;
     k.gp = take; k.mode = p.f.mode; k.order = p.f.pn;
     if (k.family == SweepFamily::F64 || k.family == SweepFamily::F64Repro) return k;
-    // the three families that read nothing but (ℓ, cell) rows (checked by plan_sweep before anything was queued; left: no memory for
+    // the four families that read nothing but (ℓ, cell) rows (checked by plan_sweep before anything was queued; left: no memory for
     // the ℓ rows, and the executor fell back to the staging's 20-B rows)
     static constexpr const char *kOption[] = {"the region currents (rt_solver_set_regions)", "the single-precision sweep (\"sweep_precision\" 1)",
-                                              "P2 / P3 scattering (rt_solver_set_scatter_pn)"};  // by family, from Iface
+                                              "P2 / P3 scattering (rt_solver_set_scatter_pn)", "void materials (Σt = 0, rt_solver_create)"};  // by family, from Iface
     k.refusal = RT_ERR_INVALID;
     if (!k.ellrows)
         std::snprintf(k.message, sizeof k.message, "rt_sweep: %s found no (ℓ, cell) rows to read (rows of kind 0)", kOption[(int)k.family - (int)SweepFamily::Iface]);
@@ -266,6 +287,8 @@ inline PassKernelKey pass_kernel_key(const SweepPlan &p, int take, bool iface) {
         std::snprintf(k.message, sizeof k.message, "rt_sweep: no P%d kernel for %d components per pass", k.order, take);
     else if (k.family == SweepFamily::Iface && (take < 1 || take > (k.mode == SweepMode::Flat ? kSweepGpFlat : kSweepGpP1)))
         std::snprintf(k.message, sizeof k.message, "rt_sweep: no region-current kernel for %d components per pass", take);
+    else if (k.family == SweepFamily::Void && (k.mode == SweepMode::Linear || take < 1 || take > (k.mode == SweepMode::Flat ? kSweepGpFlat : kSweepGpP1)))
+        std::snprintf(k.message, sizeof k.message, "rt_sweep: no void-material kernel for %d components per pass", take);
     else
         k.refusal = RT_SUCCESS;
     return k;
@@ -281,5 +304,7 @@ inline PassKernelKey pass_kernel_key(const SweepPlan &p, int take, bool iface) {
 #undef RT_VC_ROWS
 #undef RT_SR_WITH
 #undef RT_SR_ROWS
+#undef RT_VOID_WITH
+#undef RT_VOID_ROWS
 
 }  // namespace rtsweep

@@ -29,6 +29,7 @@ struct SweepLoan {
     const double *sr_ell = nullptr;
     rtsweep::SweepRows sr_rows = rtsweep::SweepRows::Records;
     uint64_t sr_gen = 0;
+    bool has_void = false;            // the solver holds a void material (Σt = 0): its sweeps run k_sweep_void, which tallies w ψ ℓ there
 };
 
 // rt_sweep.hip sweep_rows_for_loan: the (ℓ, cell) rows a sweep under a loan would read, made and described

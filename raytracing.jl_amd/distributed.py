@@ -403,6 +403,9 @@ class ShardedSolver:
         if getattr(xs, "sigma_s2", None) is not None:
             raise ValueError("sigma_s2 / sigma_s3 (P2 / P3 scattering, rt_solver_set_scatter_pn) on shards is not supported: the higher "
                              "moments' tallies are not among what the ranks sum")
+        if getattr(xs, "void_materials", None) is not None and xs.void_materials.any():
+            raise ValueError("ShardedSolver: void materials (sigma_t = 0) together with a shard's track set are not supported: a void "
+                             "cell's tallies are track lengths, which the ranks' fold does not sum yet")
         if self.linear and solver is not None and not (hasattr(solver, "ls_geometry") and hasattr(solver, "ls_geometry_pointer")):
             raise ValueError('scheme="linear" needs a solver with the geometry calls ls_geometry(stage) and ls_geometry_pointer()')
         self.dt, self.rank, self.world, self.group, self.device = dt, rank, world, group, device

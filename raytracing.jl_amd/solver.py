@@ -59,7 +59,10 @@ class CrossSections:
     same transfer, Σs(g'→g, μ0) = (1/4π) [Σs0 + 3 Σs1 μ0] — linearly anisotropic scattering; entries may be negative but
     must be finite with |Σs1| <= Σs0.  ``sigma_s2``, ``sigma_s3`` [M, G, G] (optional): the l = 2 and l = 3 moments of
     Σs(g'→g, μ0) = (1/4π) Σ_l (2l+1) Σs_l P_l(μ0), validated like ``sigma_s1``; ``sigma_s3`` needs ``sigma_s2``, and both need
-    ``sigma_s1``.  ``scatter_order``: the highest l given (0 .. 3); ``sigma_sl``: the moments from l = 1 stacked."""
+    ``sigma_s1``.  ``scatter_order``: the highest l given (0 .. 3); ``sigma_sl``: the moments from l = 1 stacked.
+    A material with ``sigma_t`` = 0 in every group is *void* ("Void" in ``include/rt_segmentize.h``): it must have no ``sigma_s``,
+    ``sigma_s1`` and ``nu_sigma_f`` (its ``chi`` is ignored), and a material with ``sigma_t`` = 0 in some groups only is refused, both
+    with the messages of ``rt_solver_create``.  ``void_materials``: one bool per material."""
 
     def __init__(self, sigma_t, sigma_s, nu_sigma_f, chi, sigma_s1=None, sigma_s2=None, sigma_s3=None):
         st = np.asarray(sigma_t, np.float64)
@@ -79,6 +82,17 @@ class CrossSections:
         if nf.shape != (M, G) or ch.shape != (M, G):
             raise ValueError(f"nu_sigma_f and chi must have shape [M, G] = {(M, G)}")
         self.sigma_t, self.sigma_s, self.nu_sigma_f, self.chi = (np.ascontiguousarray(a) for a in (st, ss, nf, ch))
+        for m in np.flatnonzero((st == 0).any(1)):
+            m = int(m)
+            if (st[m] != 0).any():
+                g0, g1 = int(np.flatnonzero(st[m] == 0)[0]), int(np.flatnonzero(st[m] != 0)[0])
+                raise ValueError(f"material {m} has sigma_t[{m}][{g0}] = 0 but sigma_t[{m}][{g1}] = {st[m, g1]:g} "
+                                 "(a void material has Σt = 0 in every group)")
+            for name, a, what in (("sigma_s", ss[m], "scatters"), ("nu_sigma_f", nf[m], "fissions")):
+                if (a != 0).any():
+                    idx = tuple(int(i) for i in np.argwhere(a != 0)[0])
+                    raise ValueError(f"material {m} is void (sigma_t[{m}][g] = 0 in every group) but {name}[{m}]" + "".join(f"[{i}]" for i in idx)
+                                     + f" = {a[idx]:g} (a void material {what} nothing)")
         if sigma_s2 is not None and sigma_s1 is None:
             raise ValueError("sigma_s2 needs sigma_s1 (the Legendre moments are given without gaps)")
         if sigma_s3 is not None and sigma_s2 is None:
@@ -92,9 +106,19 @@ class CrossSections:
                 sl = sl.reshape(M, G, G)
             if sl.shape != (M, G, G):
                 raise ValueError(f"{name} must have shape [M, G, G] = {(M, G, G)}, got {np.shape(given)}")
+            for m in np.flatnonzero(self.void_materials):
+                if (sl[m] != 0).any():
+                    a, b = (int(i) for i in np.argwhere(sl[m] != 0)[0])
+                    raise ValueError(f"material {int(m)} is void (sigma_t[{int(m)}][g] = 0 in every group) but {name}[{int(m)}][{a}][{b}] = {sl[m, a, b]:g} "
+                                     "(a void material scatters nothing)")
             if not np.all(np.isfinite(sl)) or not np.all(np.abs(sl) <= self.sigma_s):
                 raise ValueError(f"every {name} must be finite with |{name}| <= sigma_s")
             setattr(self, name, np.ascontiguousarray(sl))
+
+    @property
+    def void_materials(self) -> np.ndarray:
+        """[M] bool: the materials with Σt = 0 in every group."""
+        return (self.sigma_t == 0).all(1)
 
     @property
     def scatter_order(self) -> int:
@@ -412,6 +436,7 @@ class SolverResult:
     krylov: Optional[dict] = None                  # krylov=...: cycles, vectors, sweeps, the last cycle's vectors / breakdown / resnorm; None without
     angular_moments: Optional[np.ndarray] = None   # sigma_s2 (sigma_s3): φ_lm [n_cells, G, NM], NM = 6 (10), slot 0 is phi; None below order 2
     moment_lm: Optional[np.ndarray] = None         # ... the (l, m) of every slot [NM, 2]
+    void_cells: Optional[np.ndarray] = None        # [n_cells] bool: the cells of a void material (Σt = 0); there phi is the track-length flux
 
     def to_cells(self, a):
         """An array per source region (``phi``, ``volumes``, ``current``) spread over the mesh's cells: ``a[source_region]``; ``a``
@@ -517,6 +542,18 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
         raise ValueError("volume_correction together with reproducible=True is not supported (the tracked lengths are an atomic sum)")
     if acc is not None and regions is None:
         raise ValueError("cmfd needs regions= (its coarse cells)")
+    if isinstance(xs, CrossSections) and xs.void_materials.any():  # (what rt_solver's setters refuse on a solver that holds a void material)
+        for on, what in ((scheme == "linear", 'scheme="linear" (the linear source)'),
+                         (xs.scatter_order >= 2, "sigma_s2 / sigma_s3 (P2 / P3 scattering)"),
+                         (precision == "single", 'precision="single" (the single-precision sweep)'),
+                         (reproducible, "reproducible=True (the reproducible tallies)"),
+                         (regions is not None or acc is not None, "regions= / cmfd= (region currents, the coarse-mesh acceleration)"),
+                         (source_regions is not None, "source_regions= (source regions)"),
+                         (vc is not None, "volume_correction (the volume correction)"),
+                         (kry is not None, "krylov= (restarted GMRES)")):
+            if on:
+                raise ValueError(f"solve: void materials (sigma_t = 0: material {int(np.flatnonzero(xs.void_materials)[0])}) together with {what} "
+                                 "are not supported")
     if precision not in _capi.PRECISIONS:
         raise ValueError('precision must be "double" or "single"')
     if not isinstance(xs, CrossSections):
@@ -607,7 +644,7 @@ def _solve(tg, xs, cell_material, mode, source, polar, azim_weights, tol_k, tol_
                         iterations=it, converged=r["converged"], k_history=f["k_history"],
                         ms_per_iteration=r["device_ms"] / it if it else 0.0, residual=r["residual"], solver=sv, current=current,
                         flux_moments=mom["flux_moments"], flux_gradient=mom["flux_gradient"], centroids=centroids, adjoint=bool(adjoint),
-                        reproducible=bool(reproducible), precision=precision, xs=xs, **bnd)
+                        reproducible=bool(reproducible), precision=precision, xs=xs, void_cells=xs.void_materials[np.asarray(cm_r, np.int64)], **bnd)
 
 
 def solve_eigenvalue(tg: TrackGenerator, xs: CrossSections, cell_material, polar="TY3", azim_weights="exact",
@@ -668,10 +705,11 @@ def solve_fixed_source(tg: TrackGenerator, xs: CrossSections, cell_material, sou
 
 
 # ---- adjoint-weighted integrals ------------------------------------------------------------------------------------------------
-def _bilinear(forward, adjoint, A, cell_material):
+def _bilinear(forward, adjoint, A, cell_material, void_materials=None):
     """B_f = Σ_e V_e Σ_g Σ_g' φ†[e, g] A[f, m(e), g', g] φ[e, g'] for A [n_forms, M, G, G]: on the device (``rt_solver_bilinear``)
     when the two results carry their device solvers; for host results (``solver`` None: the numpy twins of the tests) by
-    ``numpy.einsum`` with ``cell_material`` [n_cells], which they do not carry."""
+    ``numpy.einsum`` with ``cell_material`` [n_cells], which they do not carry.  Void cells (``void_materials`` [M] bool for host
+    results; the device knows its own) have zero weight: they take part in no reaction."""
     sa, sf = getattr(adjoint, "solver", None), getattr(forward, "solver", None)
     if sa is not None and sf is not None:
         return np.asarray(sa.bilinear(sf, A))
@@ -682,6 +720,8 @@ def _bilinear(forward, adjoint, A, cell_material):
     mat = np.asarray(cell_material, np.int64)
     V = np.asarray(forward.volumes, np.float64)
     live = V > 0
+    if void_materials is not None:
+        live = live & ~np.asarray(void_materials, bool)[mat]
     return np.einsum("e,eg,fehg,eh->f", V[live], np.asarray(adjoint.phi)[live], np.asarray(A)[:, mat[live]], np.asarray(forward.phi)[live])
 
 
@@ -720,7 +760,7 @@ def perturbation_reactivity(forward, adjoint, xs: CrossSections, xs_perturbed: C
     dT = np.zeros((M, G, G))
     dT[:, np.arange(G), np.arange(G)] = xs_perturbed.sigma_t - xs.sigma_t
     A = np.stack([F, _fission_form(xs_perturbed) - F, xs_perturbed.sigma_s - xs.sigma_s, dT])
-    bF, bdF, bdS, bdT = (float(b) for b in _bilinear(forward, adjoint, A, cell_material))
+    bF, bdF, bdS, bdT = (float(b) for b in _bilinear(forward, adjoint, A, cell_material, xs.void_materials))
     return dict(delta_rho=(bdF / forward.k_eff - bdT + bdS) / bF, B_F=bF, B_dF=bdF, B_dS=bdS, B_dT=bdT)
 
 
@@ -746,7 +786,7 @@ def kinetics_parameters(forward, adjoint, xs: CrossSections, inv_velocity, beta,
     V[:, np.arange(G), np.arange(G)] = iv
     Ad = (be[:, :, None] * xs.nu_sigma_f[:, None, :])[:, :, :, None] * cd[:, :, None, :]  # [M, D, g', g]
     A = np.concatenate([np.stack([_fission_form(xs), V]), Ad.transpose(1, 0, 2, 3)])
-    b = _bilinear(forward, adjoint, A, cell_material)
+    b = _bilinear(forward, adjoint, A, cell_material, xs.void_materials)
     return dict(Lambda=float(b[1] / b[0]), beta_eff=np.asarray(b[2:] / b[0]), B_F=float(b[0]))
 
 
@@ -853,6 +893,8 @@ def solve_transient(result: SolverResult, kinetics: Kinetics, dt, n_steps: int, 
         if xs is not None and x.sigma_t.shape != xs.sigma_t.shape:
             raise ValueError("the CrossSections of an event must have the materials and groups of the result's")
         ev[int(step)] = x
+    if (xs is not None and xs.void_materials.any()) or any(x.void_materials.any() for x in ev.values()):
+        raise ValueError("solve_transient: void materials (sigma_t = 0) together with a transient are not supported")
     if xs is not None:
         arrays = kinetics.arrays(xs)
         for x in ev.values():

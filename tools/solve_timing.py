@@ -132,6 +132,8 @@ def main():
     ap.add_argument("--krylov", type=int, default=0, metavar="M",
                     help="with --transient: every step in restarted-GMRES cycles of at most M Krylov vectors (rt_solver_set_krylov)")
     ap.add_argument("--krylov-tol", type=float, default=1e-2, help="tol_lin of --krylov")
+    ap.add_argument("--void", action="store_true",
+                    help="after the plain runs, the same runs with the cladding void (Σt = 0: the sweep is k_sweep_void) and with Σt = 1e-8 in its place (k_sweep); with --p1")
     ap.add_argument("--steps", action="store_true", help="also time the iteration driven step by step from Python")
     ap.add_argument("--no-sweep-probe", action="store_true", help="skip the bare-sweep measurement (profiling runs)")
     a = ap.parse_args()
@@ -178,6 +180,24 @@ def main():
     swi = (_capi.C.c_int32 * 4)()
     _capi._check(_capi.lib().rt_sweep_info(dt._h, None, swi))
     out["sweep_gp"], out["sweep_passes"] = int(swi[1]), int(swi[2])
+    if a.void:  # (what the compare and the select of k_sweep_void cost: the same problem with a void and with a nearly void cladding)
+        if a.pn or a.linear:
+            raise SystemExit("--void runs flat or with --p1 (rt_solver refuses the other modes together with a void material)")
+        for key, eps in (("void", 0.0), ("thin", 1e-8)):
+            st, ss = xs.sigma_t.copy(), xs.sigma_s.copy()
+            st[1], ss[1] = eps, 0.0
+            sv2 = _capi.DeviceSolver(dt, _cell_material(tg, cm), st, ss, xs.nu_sigma_f, xs.chi, pq.sin_theta, pq.weights,
+                                     rt.exact_azimuthal_weights(tg.azimuthal_quadrature))
+            if a.p1:
+                sv2.set_scatter_p1(0.3 * ss)
+            sv2.run(0, 3, 0.0, 0.0)
+            ms2 = []
+            for _ in range(a.repeats):
+                r = sv2.run(0, a.iters, 0.0, 0.0)
+                ms2.append(r["device_ms"] / r["iterations"])
+            out[key + "_ms_per_iter_events"] = float(np.median(ms2))
+            out[key + "_k_eff"] = r["k_eff"]
+        out["void_over_thin_events"] = out["void_ms_per_iter_events"] / out["thin_ms_per_iter_events"]
     if a.adjoint:  # (the same kernels on the transposed tables: the time per iteration is expected to equal the forward one)
         sv.set_adjoint(True)
         sv.run(0, 3, 0.0, 0.0)
