@@ -110,6 +110,29 @@ typedef void (*rt_enqueue_hook)(void *user);
 int32_t rt_mesh_set_enqueue_hook(rt_mesh *mesh, rt_enqueue_hook hook, void *user);
 
 /*
+ * Point location — find_element(mesh, x[, k]), src/mesh.jl:103-146, asked for n points at once: cell[i] is the 1-based id
+ * of the cell that holds (x[i], y[i]), or -1.  Every point takes the sequence a track's points take in _segmentize_track!
+ * (src/track.jl:122,139): find_element(mesh, p) with its default k = 2 — the cells around the nearest node in the node's
+ * stored order, then those around the next two nodes, first hit wins — and, where that fails, find_element(mesh, p, k).
+ * Points on an edge or a node belong to several cells (point_in_triangle, src/mesh.jl:158-176, has a tolerance of
+ * sqrt(eps)); the scan order decides, as in the reference.  Any k >= 0 is honoured (k < 0: RT_ERR_INVALID, as knn rejects
+ * it, src/mesh.jl:123).  A point with a non-finite coordinate (NaN, +-inf) is -1: the reference never sees one, and it is
+ * decided before the search forms any index.  Finite points outside the mesh, however far, go through the procedure.
+ * n = 0 is a success that launches nothing.  One kernel, one lane per point, on the mesh's stream.
+ *   rt_locate_points          x, y, cell: host arrays [n]; uploads, locates, copies back and waits.
+ *   rt_locate_points_device   d_x, d_y, d_cell: device arrays [n] on the mesh's device; queued on the mesh's stream, returns
+ *                             without waiting (like the other calls that take device addresses, it synchronises nothing).
+ *   rt_locate_grid[_device]   the nx x ny raster of the points (x0 + i*dx, y0 + j*dy), i < nx, j < ny, without uploading
+ *                             them: cell [ny][nx], row-major (j outer).  Each coordinate is one multiply and one add in
+ *                             binary64, rounded separately (no fused multiply-add): x0 + i*dx evaluated by the caller in
+ *                             binary64 gives the same bits.  nx * ny <= 2^31 - 1.
+ */
+int32_t rt_locate_points(rt_mesh *mesh, int64_t n, const double *x, const double *y, int32_t k, int32_t *cell);
+int32_t rt_locate_points_device(rt_mesh *mesh, int64_t n, const double *d_x, const double *d_y, int32_t k, int32_t *d_cell);
+int32_t rt_locate_grid(rt_mesh *mesh, double x0, double y0, double dx, double dy, int32_t nx, int32_t ny, int32_t k, int32_t *cell);
+int32_t rt_locate_grid_device(rt_mesh *mesh, double x0, double y0, double dx, double dy, int32_t nx, int32_t ny, int32_t k, int32_t *d_cell);
+
+/*
  * The per-track inputs of _segmentize_track! (src/track.jl:106-108: track.p, ϕ, ℓ, ABC),
  * in uid order, as produced by trace! (src/trackgenerator.jl:179-273).  cos_phi / sin_phi
  * are cos(ϕ), sin(ϕ) evaluated by the host (advance_step, src/point.jl:43, evaluates them
@@ -1155,6 +1178,19 @@ int32_t rt_solver_fetch_krylov(rt_solver *solver, int64_t *info, double *resnorm
  * and [1] H [m][m + 1] as the device left it (column k: h_{0,k} .. h_{k+1,k}), valid in an open run after its first cycle with Krylov
  * vectors (NULL / 0 otherwise).  Does not wait. */
 int32_t rt_solver_krylov_pointers(rt_solver *solver, void **ptrs_dev, int64_t *lens);
+/* The flux at points: out [n][ng] = the flux of the groups g0 .. g0 + ng - 1 in the cells cell[i] (1-based ids of the MESH's cells,
+ * as rt_locate_points returns them) at the points (x[i], y[i]), from the φ the solver holds on the device.  With source regions the
+ * cell reads its region's row; after (or inside) a run with the linear source the value is φ_g + ∇φ_g·(r − centroid), ∇φ = C⁻¹φ⃗ as
+ * rt_solver_fetch_moments returns it (every product and sum rounded on its own, left to right); every other mode samples the scalar
+ * flux.  A cell outside 1 .. n_cells (-1: not located) gives `fill` in every group.  Valid after a completed run and, in an open one,
+ * between rt_solver_step_fold and the next rt_solver_step_sweep (the φ of that fold, not normalised); RT_ERR_INVALID, with a message,
+ * when no flux is held, and for a group range outside the solver's.  n = 0 or ng = 0 is a success that launches nothing.
+ * rt_solver_sample takes device arrays, queues one kernel on the mesh's stream and does not wait; rt_solver_sample_host takes host
+ * arrays, copies and waits. */
+int32_t rt_solver_sample(rt_solver *solver, int64_t n, const int32_t *d_cell, const double *d_x, const double *d_y, int32_t g0, int32_t ng,
+                         double fill, double *d_out);
+int32_t rt_solver_sample_host(rt_solver *solver, int64_t n, const int32_t *cell, const double *x, const double *y, int32_t g0, int32_t ng,
+                              double fill, double *out);
 void rt_solver_destroy(rt_solver *solver);
 
 #ifdef __cplusplus

@@ -436,6 +436,23 @@ function solver_ls_geometry_pointer(hs::Ptr{Cvoid})
     return p[], n[]
 end
 
+# find_element(mesh, x) followed, where it finds none, by find_element(mesh, x, k) (src/track.jl:122,139) on the device, for the
+# points `xs` at once (rt_locate_points): the 1-based cell ids, -1 where no cell holds the point and for non-finite coordinates.
+# `hm`: the mesh's handle (`mesh_handle(mesh, device)`).  The reference's own find_element(mesh, x, k) skips the k = 2 attempt;
+# the two agree wherever k >= 2.
+function find_elements(hm::Ptr{Cvoid}, xs::AbstractVector; k::Integer=5)
+    n = length(xs)
+    x = Float64[p[1] for p in xs]; y = Float64[p[2] for p in xs]
+    cell = Vector{Int32}(undef, n)
+    rc = ccall((:rt_locate_points, LIB), Int32, (Ptr{Cvoid}, Int64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Int32}),
+               hm, Int64(n), x, y, Int32(k), cell)
+    rc == 0 || error("rt_locate_points failed: " * lasterror())
+    return cell
+end
+
+# One point (a Point2D or anything indexable by 1 and 2): the cell id as an Int, -1 for none
+find_element(hm::Ptr{Cvoid}, x; k::Integer=5) = Int(find_elements(hm, [x]; k=k)[1])
+
 # rt_multi_create for the generator's mesh and tracks (flattened as in segmentize_amd!)
 function multi_create(t::TrackGenerator{Float64}, devices::Vector{Int})
     tracks = t.tracks_by_uid

@@ -21,6 +21,7 @@ from .segmentize import RTOL_DEFAULT, SegmentStore, segmentize
 from .solver import (Cmfd, CrossSections, PolarQuadrature, SolverBoundary, SolverResult, azimuthal_weights, exact_azimuthal_weights, diffusion_coupling,
                      kinetics_parameters, perturbation_reactivity, solve_eigenvalue, solve_fixed_source, Kinetics, TransientResult, solve_transient, Krylov)
 from .distributed import ShardedSolver
+from ._capi import DeviceMesh, DeviceSolver  # point location and flux sampling: Mesh.find_elements / locate_grid, DeviceSolver.sample
 
 __all__ = [
     "BoundaryConditions", "BoundaryType", "Vacuum", "Reflective", "Periodic",
@@ -30,5 +31,6 @@ __all__ = [
     "CrossSections", "PolarQuadrature", "SolverResult", "azimuthal_weights", "exact_azimuthal_weights",
     "solve_eigenvalue", "solve_fixed_source", "perturbation_reactivity", "kinetics_parameters", "ShardedSolver",
     "SolverBoundary", "track_end_sides", "Cmfd", "diffusion_coupling", "Kinetics", "TransientResult", "solve_transient", "Krylov",
+    "DeviceMesh", "DeviceSolver",
     "Forward", "Backward", "bc_fwd", "bc_bwd", "dir_next_track_fwd", "dir_next_track_bwd",
 ]

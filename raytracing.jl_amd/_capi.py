@@ -42,6 +42,7 @@ SYMBOLS = (
     "rt_solver_transient_begin", "rt_solver_transient_step", "rt_solver_transient_set_xs", "rt_solver_transient_fetch",
     "rt_solver_transient_pointers", "rt_solver_transient_end",
     "rt_solver_set_krylov", "rt_solver_step_krylov", "rt_solver_fetch_krylov", "rt_solver_krylov_pointers",
+    "rt_locate_points", "rt_locate_points_device", "rt_locate_grid", "rt_locate_grid_device", "rt_solver_sample", "rt_solver_sample_host",
 )
 # Exported names that carry a digit, kept apart from SYMBOLS: tests/test_capi_symbols.py compares SYMBOLS with the header's names
 # as a scan for letters and underscores finds them, and that scan cannot see these.  tests/test_solver_p1_cpu.py holds the two
@@ -366,6 +367,22 @@ def lib():
     except AttributeError:
         if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
             raise
+    try:
+        L.rt_locate_points.restype = C.c_int32
+        L.rt_locate_points.argtypes = [_vp, C.c_int64, _dp, _dp, C.c_int32, _ip]
+        L.rt_locate_points_device.restype = C.c_int32
+        L.rt_locate_points_device.argtypes = [_vp, C.c_int64, _vp, _vp, C.c_int32, _vp]
+        L.rt_locate_grid.restype = C.c_int32
+        L.rt_locate_grid.argtypes = [_vp] + [C.c_double] * 4 + [C.c_int32] * 3 + [_ip]
+        L.rt_locate_grid_device.restype = C.c_int32
+        L.rt_locate_grid_device.argtypes = [_vp] + [C.c_double] * 4 + [C.c_int32] * 3 + [_vp]
+        L.rt_solver_sample.restype = C.c_int32
+        L.rt_solver_sample.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, _vp]
+        L.rt_solver_sample_host.restype = C.c_int32
+        L.rt_solver_sample_host.argtypes = [_vp, C.c_int64, _ip, _dp, _dp, C.c_int32, C.c_int32, C.c_double, _dp]
+    except AttributeError:
+        if not os.environ.get("RT_SEGMENTIZE_LIB"):  # development A/B against an older build (tools/solve_timing.py) only
+            raise
     if L.rt_abi_version() != 1:
         raise RtError("librt_segmentize.so: ABI version mismatch")
     _lib = L
@@ -451,6 +468,30 @@ class DeviceMesh:
 
     def set_option(self, name: str, value: int):
         _check(lib().rt_set_option(self._h, name.encode(), int(value)))
+
+    def locate_points(self, x, y, k: int = 5) -> np.ndarray:
+        """``rt_locate_points``: the 1-based id of the cell that holds every point (``find_element(mesh, p)``, then
+        ``find_element(mesh, p, k)``), -1 where none does and for non-finite coordinates.  ``x``, ``y``: [n] host arrays."""
+        x, xp = _f64(x); y, yp = _f64(y)
+        if x.ndim != 1 or x.shape != y.shape:
+            raise ValueError("x and y must be one-dimensional arrays of equal lengths")
+        cell = np.empty(len(x), np.int32)
+        _check(lib().rt_locate_points(self._h, len(x), xp, yp, int(k), cell.ctypes.data_as(_ip)))
+        return cell
+
+    def locate_points_device(self, n: int, d_x: int, d_y: int, d_cell: int, k: int = 5):
+        """``rt_locate_points_device``: the same over device arrays (addresses) of ``n`` points, queued on the mesh's stream."""
+        _check(lib().rt_locate_points_device(self._h, int(n), d_x, d_y, int(k), d_cell))
+
+    def locate_grid(self, x0, y0, dx, dy, nx: int, ny: int, k: int = 5) -> np.ndarray:
+        """``rt_locate_grid``: the cells [ny, nx] of the raster (x0 + i·dx, y0 + j·dy) — the bits of numpy's ``x0 + i*dx``."""
+        cell = np.empty((int(ny), int(nx)), np.int32)
+        _check(lib().rt_locate_grid(self._h, float(x0), float(y0), float(dx), float(dy), int(nx), int(ny), int(k), cell.ctypes.data_as(_ip)))
+        return cell
+
+    def locate_grid_device(self, x0, y0, dx, dy, nx: int, ny: int, d_cell: int, k: int = 5):
+        """``rt_locate_grid_device``: the raster's cells into a device array (address) of nx·ny int32, queued on the mesh's stream."""
+        _check(lib().rt_locate_grid_device(self._h, float(x0), float(y0), float(dx), float(dy), int(nx), int(ny), int(k), d_cell))
 
     def close(self):
         # rt_tracks_destroy reads its mesh, and the garbage collector finalizes the objects of a reference cycle in any order:
@@ -1327,6 +1368,59 @@ class DeviceSolver:
         phi = np.empty((self.n_cells, self.G)); vol = np.empty(self.n_cells); kh = np.empty(int(iterations))
         _check(lib().rt_solver_fetch(self._h, phi.ctypes.data_as(_dp), vol.ctypes.data_as(_dp), kh.ctypes.data_as(_dp) if len(kh) else None))
         return dict(phi=phi, volumes=vol, k_history=kh)
+
+    # ---- the flux at points (``rt_solver_sample``): after a completed run, or between ``step_fold`` and the next ``step_sweep``
+    def _groups(self, groups):
+        """``groups`` as (g0, ng, picked columns or None): None is every group, an int one, a slice or a sequence of ints a
+        subset — one call over the range that holds it, the columns picked afterwards."""
+        if groups is None:
+            return 0, self.G, None
+        if isinstance(groups, slice):
+            groups = range(*groups.indices(self.G))
+        g = np.atleast_1d(np.asarray(groups, np.int64))
+        if g.ndim != 1 or (len(g) and (g.min() < 0 or g.max() >= self.G)):
+            raise ValueError(f"groups must be indices in [0, {self.G})")
+        if not len(g):
+            return 0, 0, None
+        g0, ng = int(g.min()), int(g.max() - g.min()) + 1
+        return g0, ng, (None if np.array_equal(g, np.arange(g0, g0 + ng)) else g - g0)
+
+    def sample_cells(self, cells, x, y, groups=None, fill=float("nan")) -> np.ndarray:
+        """``rt_solver_sample_host``: values [n, ng] of the flux at the points (x, y) [n] in the 1-based mesh cells ``cells`` [n]
+        (-1: ``fill``) — φ of the cell (of its source region), + ∇φ·(r − centroid) with the linear source."""
+        c, cp = _i32(cells); x, xp = _f64(x); y, yp = _f64(y)
+        if c.ndim != 1 or x.shape != c.shape or y.shape != c.shape:
+            raise ValueError("cells, x and y must be one-dimensional arrays of equal lengths")
+        g0, ng, pick = self._groups(groups)
+        out = np.empty((len(c), ng))
+        _check(lib().rt_solver_sample_host(self._open(), len(c), cp, xp, yp, g0, ng, float(fill), out.ctypes.data_as(_dp)))
+        return out if pick is None else np.ascontiguousarray(out[:, pick])
+
+    def sample_device(self, n: int, d_cell: int, d_x: int, d_y: int, d_out: int, g0: int = 0, ng=None, fill=float("nan")):
+        """``rt_solver_sample``: the same over device arrays (addresses), queued on the mesh's stream; ``d_out`` [n, ng]."""
+        _check(lib().rt_solver_sample(self._open(), int(n), d_cell, d_x, d_y, int(g0), int(self.G - g0 if ng is None else ng), float(fill), d_out))
+
+    def sample(self, points, groups=None, fill=float("nan"), k: int = 5):
+        """The flux at ``points`` [n, 2]: ``(cells, values)`` with ``cells`` [n] the 1-based ids of the cells that hold them (-1:
+        none, or a non-finite coordinate — ``DeviceMesh.locate_points``) and ``values`` [n, ng] the flux of ``groups`` there
+        (None: all; an int, a slice or a sequence), ``fill`` where no cell was found."""
+        p = np.asarray(points, np.float64)
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError("points must have shape [n, 2]")
+        self._open()
+        x, y = np.ascontiguousarray(p[:, 0]), np.ascontiguousarray(p[:, 1])
+        cells = self.dtracks.dmesh.locate_points(x, y, k)
+        return cells, self.sample_cells(cells, x, y, groups, fill)
+
+    def sample_grid(self, x0, y0, dx, dy, nx: int, ny: int, groups=None, fill=float("nan"), k: int = 5):
+        """The raster form of ``sample``: ``(cells [ny, nx], values [ny, nx, ng])`` at the points (x0 + i·dx, y0 + j·dy)."""
+        self._open()
+        nx, ny = int(nx), int(ny)
+        cells = self.dtracks.dmesh.locate_grid(x0, y0, dx, dy, nx, ny, k)
+        x = np.tile(float(x0) + np.arange(nx) * float(dx), ny)
+        y = np.repeat(float(y0) + np.arange(ny) * float(dy), nx)
+        v = self.sample_cells(cells.reshape(-1), x, y, groups, fill)
+        return cells, v.reshape(ny, nx, v.shape[1])
 
     def volumes(self):
         vol = np.empty(self.n_cells)

@@ -248,6 +248,35 @@ class Mesh:
     def bb(self) -> np.ndarray:
         return np.array([self.bb_min[0], self.bb_min[1], self.bb_max[0], self.bb_max[1]], dtype=np.float64)
 
+    # ---- find_element(mesh, x[, k]) (src/mesh.jl:103-146) on the device, for many points at once.  No CPU fallback: without
+    # the built library or a GPU these raise.
+    def device_mesh(self, device: int = 0):
+        """The ``rt_mesh`` handle of this mesh on ``device`` (made on first use, kept with the mesh)."""
+        from . import _capi
+
+        dm = getattr(self, "_device_mesh", None)
+        if dm is None or dm._h is None or dm.device != device:
+            dm = self._device_mesh = _capi.DeviceMesh(self, device)
+        return dm
+
+    def find_elements(self, points, k: int = 5, device: int = 0) -> np.ndarray:
+        """The 1-based id of the cell that holds every point of ``points`` [n, 2], or -1: per point ``find_element(mesh, p)``
+        and, where that finds none, ``find_element(mesh, p, k)`` — the sequence of src/track.jl:122,139, with the reference's
+        scan order at ties (points on edges and nodes).  A non-finite coordinate gives -1."""
+        p = np.asarray(points, np.float64)
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError("points must have shape [n, 2]")
+        return self.device_mesh(device).locate_points(p[:, 0], p[:, 1], k)
+
+    def find_element(self, x: float, y: float, k: int = 5, device: int = 0) -> int:
+        """``find_elements`` for one point."""
+        return int(self.find_elements([[x, y]], k, device)[0])
+
+    def locate_grid(self, x0, y0, dx, dy, nx: int, ny: int, k: int = 5, device: int = 0) -> np.ndarray:
+        """``find_elements`` for the raster of points (x0 + i·dx, y0 + j·dy), i < nx, j < ny, made on the device: [ny, nx].
+        The coordinates are, bit for bit, numpy's ``x0 + np.arange(nx) * dx`` and ``y0 + np.arange(ny) * dy``."""
+        return self.device_mesh(device).locate_grid(x0, y0, dx, dy, nx, ny, k)
+
     def width(self) -> float:  # src/mesh.jl:76
         return self.bb_max[0] - self.bb_min[0]
 

@@ -443,6 +443,16 @@ class SolverResult:
         itself without source regions."""
         return np.asarray(a) if self.source_region is None else np.asarray(a)[self.source_region]
 
+    def sample(self, points, groups=None, fill=float("nan")):
+        """The flux at ``points`` [n, 2], from the φ the run's solver holds on the device (``DeviceSolver.sample``): ``(cells,
+        values [n, ng])`` — the cells' 1-based ids (-1: outside, ``fill`` there), φ of the cell or of its source region, with
+        ``scheme="linear"`` phi + flux_gradient·(r − centroid)."""
+        return self.solver.sample(points, groups, fill)
+
+    def sample_grid(self, x0, y0, dx, dy, nx, ny, groups=None, fill=float("nan")):
+        """``sample`` on the raster (x0 + i·dx, y0 + j·dy): ``(cells [ny, nx], values [ny, nx, ng])`` — a flux map."""
+        return self.solver.sample_grid(x0, y0, dx, dy, nx, ny, groups, fill)
+
 
 def _cell_material(tg, cell_material):
     if isinstance(cell_material, dict):

@@ -61,7 +61,12 @@ def main():
                 m = re.match(r"^[0-9a-f]{16} <(.+)>:$", line)
                 if m:
                     name = CUID.sub("__hip_cuid_X", m.group(1))
-                    assert name not in funcs, name
+                    # a device function of a shared header that two units keep out of line (rt_device.hpp's find_element_fallback in
+                    # rt_march.hip and rt_locate.hip) has one copy per code object: the later ones are told apart by a counter
+                    base, n = name, 1
+                    while name in funcs:
+                        n += 1
+                        name = "%s [copy %d]" % (base, n)
                     funcs[name] = []
                     continue
                 if name is None or not line.strip() or line.strip() == "...":
