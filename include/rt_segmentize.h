@@ -235,7 +235,10 @@ int32_t rt_device_pointers(rt_tracks *tracks, void **ptrs_dev);
  * finished its tracks takes their span of the six arrays from an atomic cursor, and the record-writing kernel runs beside the rest
  * of the march instead of behind it (C3: -20 % per step).  What describes the layout is the per-track table
  *   seg_begin[n_tracks]   first record of track u        seg_count[n_tracks]   its number of records
- * rt_record_order: 1 if the handle's records currently lie in completion order, 0 if in CSR order (uid order).
+ * rt_record_order: 1 if the handle's records currently lie in completion order, 0 if in CSR order (uid order).  A call under the
+ *   option may still end in CSR order: the plans that cannot serve it (pieces, "topo" 0, "compact" 0, "timing", "async"), a queue
+ *   that gave up, and a call that marched tracks again at the iteration cap ("iter_cap": fill_volumes is then recomputed from the
+ *   records, over the CSR ranges, and the call rewrites its records in uid order first) — rt_last_stats' stats[24] is 0 for it.
  * rt_device_table: ptrs_dev[10] = seg_begin (i64), seg_count (i32), status (i32), px, py, qx, qy, ell (f64), element (i32),
  *   volumes (f64) — valid in either order, never rewrites anything (in CSR order seg_begin is seg_offsets).
  * rt_fetch_table / rt_fetch_records: the table and the six arrays as they lie on the device, to the host.
@@ -356,7 +359,7 @@ int32_t rt_last_timing(rt_tracks *tracks, double *ms, int32_t n);
  * stats[21] the lean plan of the call's march (option "lean"; 0: one kernel), stats[22] the lanes its k_serve finished; stats[23] the
  * kernel that wrote the call's records (1 k_compact3, 2 k_materialise, 3 k_materialise_lin, 4 k_materialise writing (ℓ, cell) rows,
  * 5 k_materialise_lin with 32-track units — option "lin_unit");
- * stats[24] 1 if the call wrote its records beside the march, in completion order (option "record_order"); stats[25] side-list entries
+ * stats[24] 1 if the call wrote its records beside the march, in completion order, and left them so (option "record_order"); stats[25] side-list entries
  * the call used beyond the one reserved per track, stats[26] side-list entries allocated, stats[27] attempts the call took (> 1: a staging
  * pool, side list or result array that was too small on the first one, or a fall-back to another plan).
  * n = capacity of stats (>= 4). */

@@ -650,6 +650,7 @@ void launch_materialise_lin(const rt::DTracks &d, int32_t *status, const rt::DSt
 void launch_finish(rt_tracks *t, const rt::DOut &out, hipStream_t s, bool from_rows, bool scale_volumes, double n_azim_2,
                    unsigned long long *d_ctl, unsigned long long *h_res_dev, unsigned long long seq, bool completion_order = false);
 void launch_compaction(rt_tracks *t, const rt::DOut &out, hipStream_t s);
+void launch_records_to_csr(rt_tracks *t, const rt::DOut &out, hipStream_t s);  // records in completion order -> CSR order
 int ensure_compacted(rt_tracks *t);
 int ensure_rows(rt_tracks *t);
 int ensure_rows_from_compact(rt_tracks *t);  // rt_sweep.hip

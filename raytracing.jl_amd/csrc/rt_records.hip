@@ -874,6 +874,15 @@ void launch_compaction(rt_tracks *t, const rt::DOut &out, hipStream_t s) {
                            (const int32_t *)t->counts.p, (const int64_t *)t->offsets.p, c.stg_pieces, out, c.sp, (const int32_t *)nullptr);
 }
 
+// Records in completion order -> CSR order: the CSR offsets in slot order, and the record kernel again over the staged words
+// (`out` holds every record of the call).  For ensure_compacted, and for a call whose own repair needs the CSR layout.
+void launch_records_to_csr(rt_tracks *t, const rt::DOut &out, hipStream_t s) {
+    if (t->n > 0)
+        hipLaunchKernelGGL(rt::k_offsets_to_slots, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, s, (const int64_t *)t->offsets.p,
+                           (const int32_t *)t->iperm.p, t->n, t->off_slot.p);
+    launch_compaction(t, out, s);
+}
+
 // Option "compact" = 0 leaves the records staged; whoever needs the 44-B records (fetch, device pointers, τ) gets them here.
 int ensure_compacted(rt_tracks *t) {
     if (t->compacted) return RT_SUCCESS;
@@ -883,12 +892,12 @@ int ensure_compacted(rt_tracks *t) {
     out.delta_s = rt::as_global(t->delta_s.p);
     if (t->completion_order && t->n > 0) {
         // The last call left its records in completion order (the per-track table: rt_device_table); whoever asks for the CSR
-        // layout gets it here, once: the CSR offsets in slot order, and the record kernel again over the staged words.
-        hipLaunchKernelGGL(rt::k_offsets_to_slots, dim3((unsigned)((t->n + 255) / 256)), dim3(256), 0, t->mesh->stream, (const int64_t *)t->offsets.p,
-                           (const int32_t *)t->iperm.p, t->n, t->off_slot.p);
+        // layout gets it here, once.
+        launch_records_to_csr(t, out, t->mesh->stream);
         t->completion_order = false;
+    } else {
+        launch_compaction(t, out, t->mesh->stream);
     }
-    launch_compaction(t, out, t->mesh->stream);
     RT_HIP(hipStreamSynchronize(t->mesh->stream));
     RT_HIP(hipGetLastError());
     t->compacted = true;

@@ -1402,7 +1402,9 @@ struct SegmentizeCall {
                 RT_HIP(hipStreamSynchronize(s));
                 memcpy(fi, h_res, sizeof(fi));
             }
-            if (!fused_volumes && m->volumes_mode == 2)  // the separate volumes pass read truncated records
+            // the separate volumes pass read truncated records (never with records in completion order: that plan needs cheap
+            // steps, and those need fused volumes — choose_plan)
+            if (!fused_volumes && m->volumes_mode == 2)
                 if (int rc = recompute_volumes()) return rc;
             RT_HIP(hipStreamSynchronize(s));
         }
@@ -1419,6 +1421,12 @@ struct SegmentizeCall {
             if (!do_compact) {
                 if (int rc = reserve_records(t, total, out)) return rc;
                 launch_compaction(t, out, s);
+            }
+            if (completion) {
+                // k_volumes walks the CSR ranges and weights a record with δs of the track whose range holds it: the records go
+                // to CSR order first (as ensure_compacted rewrites them), and the call ends as one in CSR order
+                launch_records_to_csr(t, out, s);
+                completion = false;
             }
             fused_volumes = false;
             if (int rc = recompute_volumes()) return rc;
@@ -1524,6 +1532,9 @@ struct SegmentizeCall {
         t->total = total;
         t->total_last = total;
         t->n_generic_records = (int64_t)fi[15];
+        // (the lean plan counts per kernel: k_first has counted the first record of a track that k_serve then marched again from
+        //  its start, at the iteration cap, and counted whole)
+        if (lean) t->n_generic_records -= (int64_t)h_res[rt::kCtlRestarts];
         t->n_exact_walk_records = topo ? (int64_t)fi[14] : 0;
         for (int b = 0; b < 9; ++b) t->refusals[b] = m->single_pass ? (int64_t)h_res[rt::kCtlRefusal + b] : 0;
         t->n_near_rtol = (int64_t)h_res[rt::kCtlNearRtol];
@@ -1891,7 +1902,7 @@ int32_t rt_last_stats(rt_tracks *t, int64_t *stats, int32_t n) {
     if (n > 27) stats[27] = t->last_attempts;   // attempts of the last call (> 1: a staging pool / side list that was too small, a fall-back)
     if (n > 26) stats[26] = t->side_cap;        // side-list entries allocated (one reserved per march slot + the dynamic part)
     if (n > 25) stats[25] = t->side_needed_last;  // ... and used beyond the reserved ones
-    if (n > 24) stats[24] = t->last_completion;  // 1: the call wrote its records beside the march, in completion order (option "record_order")
+    if (n > 24) stats[24] = t->last_completion;  // 1: the call wrote its records beside the march, in completion order, and left them so (option "record_order")
     if (n > 23) stats[23] = t->last_record_kernel;  // 1 k_compact3, 2 k_materialise, 3 k_materialise_lin, 4 k_materialise writing (ℓ, cell) rows only, 5 k_materialise_lin with 32-track units
     if (n > 7) {  // device memory held by this handle: inputs, staging pools, tables, results
         auto b = [](const auto &d) { return (int64_t)(d.cap * sizeof(*d.p)); };

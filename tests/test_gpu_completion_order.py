@@ -19,24 +19,9 @@ def _bits(a):
     return a.view(np.int64) if a.dtype == np.float64 else a
 
 
-def _check_table(dt, ref, vol, what):
-    """The handle's records as they lie, through the table, against the checker's CSR arrays."""
-    total = int(ref["total"])
-    order = dt.record_order()
-    beg, cnt, st = dt.fetch_table()
-    recs = dt.fetch_records()
-    off = np.asarray(ref["offsets"], np.int64)
-    assert np.array_equal(cnt, np.diff(off)), what
-    assert np.array_equal(st, ref["status"]), what
-    live = cnt > 0
-    if total:
-        b, e = np.sort(beg[live]), np.sort((beg + cnt)[live])
-        assert b[0] == 0 and e[-1] == total and np.array_equal(b[1:], e[:-1]), (what, "the tracks' spans tile [0, total)")
-    idx = np.repeat(beg - off[:-1], cnt) + np.arange(total)  # record r of the CSR layout lies at idx[r]
-    for k in KEYS:
-        assert np.array_equal(_bits(recs[k][idx]), _bits(np.asarray(ref[k]))), (k, what)
-    assert np.allclose(dt.fetch_volumes(), vol, rtol=1e-10, atol=1e-300), what
-    return order
+# The handle's records as they lie, through the table, against the checker's CSR arrays (counts, status, the spans' tiling, the six
+# arrays bit for bit, the volumes within rtol 1e-10): tests/recovery_cases.py, shared with the recovery matrix.  Returns the order.
+from recovery_cases import check_call as _check_table  # noqa: E402
 
 
 def _check_csr(dt, ref, what):

@@ -513,6 +513,7 @@ def test_cheap_steps_keep_the_iteration_guard_exact(rt, orc, traced, iter_cap):
     no track of this batch really reaches it (the bound does); cap = 40: most do.  Status, counts and records equal the
     checker's at the same cap."""
     from raytracing_jl_amd import _capi
+    from recovery_cases import skewed_delta_s
 
     tg = traced(8, 2e-2)
     om = orc.OracleMesh.from_mesh(tg.mesh, omp=True)
@@ -523,7 +524,10 @@ def test_cheap_steps_keep_the_iteration_guard_exact(rt, orc, traced, iter_cap):
     dm.set_option("iter_cap", iter_cap)
     dt = _capi.DeviceTracks(dm, tg.px, tg.py, tg.phi, tg.cos_phi, tg.sin_phi, tg.A, tg.B, tg.C, tg.ell, tg.azim_idx)
     aq = tg.azimuthal_quadrature
-    assert dt.segmentize(tg.tiny_step, 5, rt.RTOL_DEFAULT, aq.delta_s, aq.n_azim_2) == ref["total"]
+    # (all four δs of this quadrature are equal: records under another track's weight would give the same volumes.  One weight
+    #  per azimuthal index instead — tests/recovery_cases.py)
+    delta_s = skewed_delta_s(aq)
+    assert dt.segmentize(tg.tiny_step, 5, rt.RTOL_DEFAULT, delta_s, aq.n_azim_2) == ref["total"]
     off, st = dt.fetch_offsets()
     s = dt.fetch_segments()
     assert np.array_equal(st, ref["status"]) and np.array_equal(off, ref["offsets"]) and np.array_equal(s["element"], ref["element"])
@@ -535,7 +539,7 @@ def test_cheap_steps_keep_the_iteration_guard_exact(rt, orc, traced, iter_cap):
     # records (the oracle's fill_volumes over ITS records is the reference here, restart or not)
     stats = dt.stats()
     assert stats["tracks_restarted"] > 0
-    vol = om.fill_volumes(ref["offsets"], tg.azim_idx, aq.delta_s, aq.n_azim_2)
+    vol = om.fill_volumes(ref["offsets"], tg.azim_idx, delta_s, aq.n_azim_2)
     assert np.allclose(dt.fetch_volumes(), vol, rtol=1e-10, atol=0)
     print(f"iter_cap={iter_cap}: {stats}, failing {int(np.count_nonzero(st))}")
 
