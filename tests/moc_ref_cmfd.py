@@ -39,6 +39,84 @@ def lu_solve(F, b):
     return x
 
 
+def assemble(c, pb, bad, J, coupling=None, force_bad_pivot=None):
+    """A [G, R, R] of the regions that are in (identity rows and columns for the others).  c: the restriction's dict; pb [R, G];
+    J [R + 1, R + 1, G]; coupling: D̂ [R, R, G] or None."""
+    R, G = pb.shape
+    D = np.zeros((R, R, G)) if coupling is None else coupling
+    good = ~bad
+    Jt = J[:R, :R] + 0.5 * D * (pb[:, None, :] + pb[None, :, :])  # [a, b, g]: c_ab φ̄_a
+    Jt = np.where(good[:, None, None] & good[None, :, None], Jt, 0.0)  # (a region that is out couples to nothing, whatever its J holds)
+    Jt[np.arange(R), np.arange(R)] = 0.0
+    diag = Jt.sum(1) + (J[:R, R] - J[R, :R]) + c["T"] - c["S"][:, np.arange(G), np.arange(G)]  # [a, g]
+    A = -(Jt / pb[:, None, :]).transpose(2, 1, 0)  # A[g, a, b] = −c_ba = −Jt[b, a, g] / φ̄_b
+    A[:, np.arange(R), np.arange(R)] = np.where(good[:, None], diag / pb, 1.0).T
+    if force_bad_pivot is not None and good[force_bad_pivot]:
+        A[:, force_bad_pivot, force_bad_pivot] = -1.0
+    return A
+
+
+def coarse_solve(c, k0, J, coupling, eigen, relax, max_iter, tol, solver="lu", force_bad_pivot=None, trace=None):
+    """(f [R, G], k, iterations, skipped regions, skipped: bool) of the coarse data c (V [R], Phi, T, P, Q [R, G], S, X [R, G, G]).
+    trace: a dict that receives what the path tests look at — `passes`: per factorisation pass (A as assembled, the factors as the
+    pass left them, the step of the refused pivot or None), `bad` [R] and `x` [R, G] at the end, `x_lowest`: the smallest (NaN first)
+    x of a region that is in, over every solve of every iteration, `k_last`: the coarse k as the iteration left it."""
+    R, G = c["Phi"].shape
+    with np.errstate(all="ignore"):
+        pb = c["Phi"] / c["V"][:, None]
+    bad = ~(c["V"] > 0) | ~np.all(np.isfinite(pb) & (pb > 0), axis=1)
+    pb = np.where(bad[:, None], 1.0, pb)
+    passes = []
+    for _ in range(R + 1):
+        A = assemble(c, pb, bad, J, coupling, force_bad_pivot)
+        F = A.copy()
+        with np.errstate(all="ignore"):
+            p = lu_nopivot(F)
+        passes.append((A, F, p))
+        if p is None:
+            break
+        bad[p] = True
+        pb[p] = 1.0
+    x, r = pb.copy(), np.ones((R, G))
+    good = ~bad
+    k = np.float64(k0 if eigen else 1.0)
+    production = lambda rr: np.float64((c["P"] * rr).sum())  # (numpy scalars: 0 / 0 is NaN as on the device, not an exception)
+    Pold, iters, fine = production(r), 0, True
+    x_lowest = np.inf
+    for m in range(max_iter):
+        fs = np.einsum("ahg,ah->ag", c["X"], r)
+        dxm = xm = 0.0
+        for g in range(G):
+            others = np.arange(G) != g
+            with np.errstate(all="ignore"):
+                rhs = fs[:, g] / k + (c["S"][:, others, g] * r[:, others]).sum(1)
+            if not eigen:
+                rhs = rhs + c["Q"][:, g]
+            rhs = np.where(good, rhs, 1.0)
+            with np.errstate(all="ignore"):
+                xn = np.linalg.solve(A[g], rhs) if solver == "numpy" else lu_solve(F[g], rhs)
+            if not np.all(np.isfinite(xn[good]) & (xn[good] > 0)):
+                fine = False
+            if good.any():
+                x_lowest = np.min([x_lowest, np.min(xn[good])])  # (np.min keeps a NaN)
+            if good.any():
+                dxm, xm = max(dxm, float(np.abs(xn - x[:, g])[good].max())), max(xm, float(np.abs(xn)[good].max()))
+            x[:, g] = np.where(good, xn, x[:, g])
+            r[:, g] = np.where(good, xn / pb[:, g], 1.0)
+        Pnew = production(r)
+        with np.errstate(all="ignore"):
+            kn = k * Pnew / Pold if eigen else np.float64(1.0)
+            dk = abs(kn - k) / kn
+        k, Pold, iters = kn, Pnew, m + 1
+        if dk <= tol and dxm <= 10.0 * tol * xm:
+            break
+    skip = (not fine) or not (math.isfinite(k) and k > 0)
+    f = np.where(bad[:, None] | skip, 1.0, 1.0 + relax * (r - 1.0))
+    if trace is not None:
+        trace.update(passes=passes, bad=bad.copy(), x=x.copy(), x_lowest=float(x_lowest), k_last=float(k))
+    return f, float(k0 if skip else k), iters, int(bad.sum()), skip
+
+
 class CmfdTwin:
     """it: a moc_ref_iface.IfaceTwin.  coupling: D̂ [R, R, G] or None; relax, max_iter, tol: as rt_solver_set_cmfd.  After every
     step_fold: `factors` [R, G], `iterations`, `skipped_regions`, and `skipped_steps` since begin; `coarse_k` the coarse k."""
@@ -64,68 +142,11 @@ class CmfdTwin:
                     S=add(tw.ss * Vp[:, :, None]), X=add((tw.nf * Vp)[:, :, None] * tw.ch[:, None, :]))
 
     def assemble(self, c, pb, bad):
-        """A [G, R, R] of the regions that are in (identity rows and columns for the others)."""
-        R, G, J = self.it.R, self.tw.G, self.it.J
-        D = np.zeros((R, R, G)) if self.coupling is None else self.coupling
-        good = ~bad
-        Jt = J[:R, :R] + 0.5 * D * (pb[:, None, :] + pb[None, :, :])  # [a, b, g]: c_ab φ̄_a
-        Jt = Jt * (good[:, None, None] & good[None, :, None])
-        Jt[np.arange(R), np.arange(R)] = 0.0
-        diag = Jt.sum(1) + (J[:R, R] - J[R, :R]) + c["T"] - c["S"][:, np.arange(G), np.arange(G)]  # [a, g]
-        A = -(Jt / pb[:, None, :]).transpose(2, 1, 0)  # A[g, a, b] = −c_ba = −Jt[b, a, g] / φ̄_b
-        A[:, np.arange(R), np.arange(R)] = np.where(good[:, None], diag / pb, 1.0).T
-        if self.force_bad_pivot is not None and good[self.force_bad_pivot]:
-            A[:, self.force_bad_pivot, self.force_bad_pivot] = -1.0
-        return A
+        return assemble(c, pb, bad, self.it.J, self.coupling, self.force_bad_pivot)
 
     def coarse_solve(self, c, k0):
-        """(f [R, G], k, iterations, skipped regions, skipped: bool)."""
-        tw, R = self.tw, self.it.R
-        G = tw.G
-        with np.errstate(all="ignore"):
-            pb = c["Phi"] / c["V"][:, None]
-        bad = ~(c["V"] > 0) | ~np.all(np.isfinite(pb) & (pb > 0), axis=1)
-        pb = np.where(bad[:, None], 1.0, pb)
-        for _ in range(R + 1):
-            A = self.assemble(c, pb, bad)
-            F = A.copy()
-            p = lu_nopivot(F)
-            if p is None:
-                break
-            bad[p] = True
-            pb[p] = 1.0
-        x, r = pb.copy(), np.ones((R, G))
-        good = ~bad
-        eigen = tw.eigen
-        k = k0 if eigen else 1.0
-        production = lambda rr: float((c["P"] * rr).sum())
-        Pold, iters, fine = production(r), 0, True
-        for m in range(self.max_iter):
-            fs = np.einsum("ahg,ah->ag", c["X"], r)
-            dxm = xm = 0.0
-            for g in range(G):
-                others = np.arange(G) != g
-                rhs = fs[:, g] / k + (c["S"][:, others, g] * r[:, others]).sum(1)
-                if not eigen:
-                    rhs = rhs + c["Q"][:, g]
-                rhs = np.where(good, rhs, 1.0)
-                xn = np.linalg.solve(A[g], rhs) if self.solver == "numpy" else lu_solve(F[g], rhs)
-                if not np.all(np.isfinite(xn[good]) & (xn[good] > 0)):
-                    fine = False
-                if good.any():
-                    dxm, xm = max(dxm, float(np.abs(xn - x[:, g])[good].max())), max(xm, float(np.abs(xn)[good].max()))
-                x[:, g] = np.where(good, xn, x[:, g])
-                r[:, g] = np.where(good, xn / pb[:, g], 1.0)
-            Pnew = production(r)
-            with np.errstate(all="ignore"):
-                kn = k * Pnew / Pold if eigen else 1.0
-                dk = abs(kn - k) / kn
-            k, Pold, iters = kn, Pnew, m + 1
-            if dk <= self.tol and dxm <= 10.0 * self.tol * xm:
-                break
-        skip = (not fine) or not (math.isfinite(k) and k > 0)
-        f = np.where(bad[:, None] | skip, 1.0, 1.0 + self.relax * (r - 1.0))
-        return f, (k0 if skip else k), iters, int(bad.sum()), skip
+        return coarse_solve(c, k0, self.it.J, self.coupling, self.tw.eigen, self.relax, self.max_iter, self.tol, self.solver,
+                            self.force_bad_pivot)
 
     # ---- the twin's steps --------------------------------------------------------------------------------------------------------
     def set_source(self, q):
