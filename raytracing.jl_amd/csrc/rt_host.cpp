@@ -24,7 +24,7 @@
 #include "../../include/rt_segmentize.h"
 
 namespace rthost {
-void set_error(const char *fmt, ...);  // defined in rt_segmentize.hip (thread-local last error)
+void set_error(const char *fmt, ...);  // defined in rt_handles.hip (thread-local last error)
 
 constexpr double kPi = 3.141592653589793;  // Float64(π)
 constexpr double kRtol = 1.4901161193847656e-8;

@@ -1,5 +1,5 @@
 // rt_hostpar.hpp — the host-side, device-free parts of rt_tracks_create and of the pipelined fetch (librt_segmentize.so): the team of
-// host threads, the march order / reserved-chunk / compaction-order plan of a track set, the packing of a track set's image into a
+// host threads, the march order / reserved-chunk / compaction-order plan and the split plan of a track set, the packing of a track set's image into a
 // page-locked block, the copy of a fetched piece into the caller's arrays.  No HIP call in here: tests/sanitize/hostpar_san.cpp
 // builds this header with AddressSanitizer + UBSan and with ThreadSanitizer (tests/sanitize/run.sh), with the device copies of the
 // callers replaced by memcpy.
@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdlib>
@@ -237,6 +238,63 @@ inline void plan_march_order(const double *ell, size_t n, int sort_mode, double 
             std::stable_sort(h_corder.begin(), h_corder.end(), [&](int32_t a, int32_t b) { return perm[(size_t)a * 64] < perm[(size_t)b * 64]; });
         }
     }
+}
+
+// Σℓ in a fixed order (blocks of 4096 tracks, added in block order) whatever the number of threads, added to *sum_ell; the range of
+// azim_idx, folded into *azim_min / *azim_max
+inline void sum_ell_azim_range(const double *ell, const int32_t *azim_idx, size_t n, double *sum_ell, int32_t *azim_min, int32_t *azim_max) {
+    const size_t nb = (n + 4095) / 4096;
+    std::vector<double> bs(nb, 0.0);
+    std::vector<int32_t> bmin(nb, 0x7fffffff), bmax(nb, (int32_t)0x80000000);
+    par_ranges(nb, 16, [&](size_t b0, size_t b1) {
+        for (size_t b = b0; b < b1; ++b) {
+            double sl = 0.0;
+            int32_t lo = 0x7fffffff, hi = (int32_t)0x80000000;
+            for (size_t i = b * 4096; i < std::min(n, b * 4096 + 4096); ++i) { sl += ell[i]; lo = std::min(lo, azim_idx[i]); hi = std::max(hi, azim_idx[i]); }
+            bs[b] = sl; bmin[b] = lo; bmax[b] = hi;
+        }
+    });
+    for (size_t b = 0; b < nb; ++b) { *sum_ell += bs[b]; *azim_min = std::min(*azim_min, bmin[b]); *azim_max = std::max(*azim_max, bmax[b]); }
+}
+
+// The split plan of a track set (DSplit): pieces per wave of 64 consecutive uids, canonical numbering, dispatch order.  n_vwaves = 0
+// and empty vectors: the set marches whole.
+struct SplitPlan {
+    std::vector<int32_t> vorder, vw_wave, vw_k, w_base, w_P;
+    int32_t n_vwaves = 0;
+};
+// split_option: the handle's "split" (-1 auto, 0 off, > 0 pieces of about that many expected segments); max_iter: MAX_ITER
+inline void plan_split(const double *ell, size_t n, int split_option, double kappa, int max_iter, SplitPlan &out) {
+    out = SplitPlan{};
+    // Splitting pays when the batch has far too few waves to fill the chip (the march is then bound by its
+    // longest dependent chain).  Pieces march with exact steps (k_march<SPLIT>), whole tracks with the two-phase march's cheap
+    // steps since round 4 — and against THAT march the pieces win only below ≈150 waves (same box, ms per call whole / in pieces,
+    // profiles/r05/exp_split_threshold.log: 7 waves 0.127 / 0.116, 26 waves 0.184 / 0.131, 103 waves (C2) 0.181 / 0.160;
+    // 204 waves 0.167 / 0.218, 510 waves 0.161 / 0.272, 1,019 waves — C3 on two GPUs — 0.199 / 0.310, 1,530 waves 0.259 / 0.448).
+    // Rounds 2-4 split every batch below 1,536 waves, a rule measured against the exact-step march of round 2.
+    const size_t nw = (n + 63) / 64;
+    const bool auto_split = split_option < 0 && nw < 160;
+    const int p_auto = auto_split ? (int)std::min<size_t>(16, (2048 + nw - 1) / std::max<size_t>(1, nw)) : 1;
+    if (!(split_option > 0 || (auto_split && p_auto > 1)) || n == 0) return;
+    out.w_base.resize(nw); out.w_P.resize(nw);
+    std::vector<double> piece_len;
+    int32_t nv = 0;
+    for (size_t w = 0; w < nw; ++w) {
+        double lmax = 0.0;
+        for (size_t l = 0; l < 64 && w * 64 + l < n; ++l) lmax = std::max(lmax, ell[w * 64 + l]);
+        const double est = lmax * kappa;  // expected segments of the longest track of the wave
+        int32_t P = split_option > 0 ? std::min(8, (int32_t)std::ceil(est / (double)split_option))
+                                     : std::min(p_auto, (int32_t)(est / 12.0));  // auto: pieces of >= ~12 segments
+        P = std::max(1, P);
+        if (est > 0.5 * max_iter) P = 1;  // MAX_ITER (src/track.jl:104) counts whole tracks
+        out.w_base[w] = nv; out.w_P[w] = P;
+        for (int32_t k = 0; k < P; ++k) { out.vw_wave.push_back((int32_t)w); out.vw_k.push_back(k); piece_len.push_back(lmax / P); }
+        nv += P;
+    }
+    out.vorder.resize(nv);
+    std::iota(out.vorder.begin(), out.vorder.end(), 0);
+    std::stable_sort(out.vorder.begin(), out.vorder.end(), [&](int32_t a, int32_t b) { return piece_len[a] > piece_len[b]; });
+    out.n_vwaves = nv;
 }
 
 // The image of tracks [i0, i0 + m) as it lies in the arena / in a range's half of the staging block: nine double arrays of `stride`

@@ -13,7 +13,10 @@
 //   rt_solver.hip      rt_solver: source iteration (k_eff / fixed source) around rt_sweep, fold / source / reduction kernels, Krylov cycle, transient
 //   rt_solver_set.hip  rt_solver's options: setters, fetches, *_pointers, bilinear forms, the linear source's geometry and their kernels
 //   rt_solver_state.hpp  struct rt_solver (one nested struct per option) and what the two solver files share
-//   rt_segmentize.hip  handles, rt_tracks_create, rt_segmentize (the call's host logic), fetches, statistics
+//   rt_handles.hip     the error text, the two handles (rt_mesh_create, rt_tracks_create, their destroyers), the staging pool, rt_set_option
+//                      over rt_mesh_options.hpp (rt_mesh::opt: the options' struct and one table of name / member / rule, host-only)
+//   rt_segmentize.hip  rt_segmentize: one call's host logic (SegmentizeCall), rt_wait, rt_failed_tracks
+//   rt_fetch.hip       fetches, device pointers and tables, τ, statistics, timings
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,13 +37,14 @@
 
 #include "../../include/rt_segmentize.h"
 #include "rt_device.hpp"
+#include "rt_mesh_options.hpp"
 #include "rt_mesh_prep.hpp"
 #include "rt_sweep_plan.hpp"
 using rtsweep::SweepMode;
 
 namespace rthost {
 extern thread_local std::string g_last_error;
-void set_error(const char *fmt, ...);  // (defined in rt_segmentize.hip; shared with rt_host.cpp and rt_multi.hip)
+void set_error(const char *fmt, ...);  // (defined in rt_handles.hip; shared with rt_host.cpp and rt_multi.hip)
 }  // namespace rthost
 using rthost::g_last_error;
 using rthost::set_error;
@@ -58,8 +62,8 @@ template <typename T>
 struct DevBuf {
     T *p = nullptr;
     size_t cap = 0;  // elements
-    // owns its allocation: a handle's buffers are released when the handle is deleted, whether or not free_tracks /
-    // free_mesh list them (a forgotten member leaked 1 GB per C5 handle in round 3)
+    // owns its allocation: a handle's buffers are released when the handle is deleted — free_tracks / free_mesh list none of
+    // them (a member forgotten in such a list leaked 1 GB per C5 handle in round 3)
     DevBuf() = default;
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
@@ -442,51 +446,15 @@ struct rt_mesh {
     rt::DMesh d{};
     rt_enqueue_hook enqueue_hook = nullptr;  // see rt_mesh_set_enqueue_hook
     void *enqueue_hook_user = nullptr;
-    int64_t iter_cap = 4000000;
+    rtmesh::MeshOptions opt;  // what rt_set_option sets (rt_mesh_options.hpp)
     bool walk_available = false;
-    int volumes_mode = 2;  // 0: skip (measurement only), 1: fused global atomics in the fill march, 2: separate LDS-privatised pass
-    int single_pass = 1;   // 1: staged single-pass march + compaction, 0: count / scan / fill (two marches)
-    int split = -1;         // track splitting (see DSplit), read by rt_tracks_create: -1 auto (only batches that leave the chip
-                            // underfilled), 0 off, > 0 pieces of about `split` expected segments
     int n_cus = 256;
     int lds_per_block = 64 * 1024;  // hipDeviceAttributeMaxSharedMemoryPerBlock
-    int sweep_gp = 0, sweep_waves = 0;  // rt_sweep: groups per pass / waves per workgroup (0: automatic)
-    int fetch_hugepages = 1;  // rt_fetch_* into the caller's arrays: ask for transparent huge pages on the destination (once per array)
-    int sweep_rows = 1; // rt_sweep over the compact records: as (ℓ, cell) rows (the staging's, or made once from the records); 0: where they lie
-    int sweep_ell = 1;  // rt_sweep over staged rows: keep ℓ of every row from the first pass for the later ones (0: every pass derives it)
-    int sweep_debug = 0, compact_debug = 0;
-    int sweep_precision = 0;  // rt_sweep without a solver: 1 the angular flux in binary32 (k_sweep_f32), 0 FP64
-    int mat_kernel = 0;      // records of a two-phase call: 0 k_materialise_lin (output order, 16-B stores), 1 k_materialise (chunk tiles; A/B)
-    int lin_unit = 0;        // tracks per workgroup of k_materialise_lin: 16, 32, or 0 — by the call's records per track (choose_lin_unit)
-    int march_waves = 0;     // 4 / 6: waves per workgroup of the fused march (0: automatic)
-    int topo = 1;          // 1: cheap steps (k_march<..., TOPO>) for whole-track batches when the mesh allows it; 2: forced — also on
-                           // meshes where fewer than 90 % of the walkable records carry a cheap certificate, and a wave that is
-                           // refused often does not hand back to exact steps (tests and fuzzing: every cheap certificate is exercised)
-    int async_calls = 0;   // 1: rt_segmentize returns once total, status summary and offsets' scan are known to the host; the
-                           // compaction may still be running on the stream (every entry point that touches results waits)
-    int record_order = 0;  // 0: the records in CSR order (uid order); 1: in completion order when the plan allows it and every march
-                           // workgroup is resident at once (the record kernel then runs beside the march); 2: whenever the plan allows
-    int lean = 0;          // the march of a two-phase call in three kernels (DLean): 0 no, 1 k_serve behind k_cheap, 2 beside it (second stream)
-    int serve_blocks = 0;  // workgroups of k_serve (0: 64)
-    int cheap_per_cu = 0;  // experiments: workgroups of k_cheap per CU (0: automatic)
     hipStream_t side_stream = nullptr;
     hipEvent_t side_ev[2] = {nullptr, nullptr};
-    int timing = 0;        // 1: record HIP events between the kernels of a call for rt_last_timing (≈4 µs of stream time each)
     bool topo_available = false;
     double topo_tiny_max = 0.0, topo_rmax = 0.0, topo_end_err = 0.0, tally_a = 0.0, tally_b = 0.0;
-    bool fused_scan = true;  // two-phase calls: the march leaves the scan's tile sums, one scan kernel (0: the two-launch scan; A/B)
-    int64_t test_reserved_pct = -1;  // tests only: the staging chunks reserved per wave as a percentage of the estimate (< 0: all of it)
-    int64_t test_tally_tau = 0;  // tests, A/B: the relative error allowed to a cheap record's chord in fill_volumes, in 1e-12 (0: 8e-11; < 0: none — every cheap record tallied by k_materialise)
     int64_t n_records_topo = 0;
-    int fuse_volumes = 1;  // 1: fill_volumes inside the single-pass march (LDS-private) when the mesh fits
-    int compact = 1;       // 0: rt_segmentize stops after march + scan (offsets, status, volumes); the 44-B records are produced on
-                           // demand (rt_fetch_segments*, rt_device_pointers, rt_fill_tau), and rt_sweep reads the staged rows directly
-    int64_t pool_chunks_hint = 0;  // > 0: initial staging-pool size in chunks (tests force the overflow path)
-    int64_t test_out_records = 0;   // tests only: capacity of the output arrays on a handle's first call (forces the re-compaction path)
-    int test_volumes_fallback = 0;  // tests only: take the split mode's volumes recomputation path unconditionally
-    int test_exact_sums = 0;        // tests only: every track's Σℓ check by k_finish's left-to-right sum (two-phase march)
-    int64_t side_entries_hint = 0;  // tests only: capacity of the dynamic part of the side list on a handle's first call (forces its overflow path)
-    int sort_mode = 2;     // march order: 0 uid order, 1 longest track first, 2 uid-contiguous waves, longest wave first
     double kappa = 0.0;    // expected segments per unit track length (sizes the staging pool)
     std::string prep_note;
     // diagnostics of the host preprocessing (rt_mesh_info)
@@ -500,7 +468,6 @@ template <typename T>
 struct DevView {
     T *p = nullptr;
     size_t cap = 0;  // (counted with the arena, not here)
-    void release() { p = nullptr; }
 };
 
 struct rt_tracks {
@@ -616,6 +583,15 @@ struct rt_tracks {
 
 // ------------------------------------------------------------------- host helpers that cross a TU boundary
 namespace rtx {
+// rt_handles.hip: the process-wide pool of page-locked staging blocks (rt_tracks_create's upload, rt_fetch.hip's pipelined fetch).
+// A block belongs to the device that was current when it was made: its two events can only be recorded on that device's streams
+// (an event of device A on a stream of device B is hipErrorInvalidHandle), so a caller gets a block of ITS device or a new one.
+constexpr size_t kStageBytes = 32u << 20;
+struct StagingBlock { void *p = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; bool busy = false; int device = -1; };
+int staging_acquire(StagingBlock *out, int device);  // the block's slot, or -1: no page-locked block to be had
+void staging_release(int slot);
+// rt_fetch.hip
+void pin_release_to_cache(rt_tracks *t);  // the handle's page-locked record buffers go to the process-wide cache (or are freed)
 // rt_segmentize.hip
 hipError_t wait_stream(hipStream_t s);
 hipError_t wait_seq(const unsigned long long *h_res, unsigned long long seq, hipStream_t s);

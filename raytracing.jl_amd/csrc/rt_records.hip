@@ -784,7 +784,7 @@ int reserve_records(rt_tracks *t, int64_t tot, rt::DOut &out) {
 
 // (k_materialise_lin addresses the result arrays through 32-bit buffer offsets: arrays below 4 GB, i.e. 2^29 records)
 bool lin_kernel_serves(const rt_tracks *t, const rt::DOut &out) {
-    return t->mesh->mat_kernel != 1 && out.cap < ((int64_t)1 << 29) - 64 && t->cplan.stg.side_cap > 0;
+    return t->mesh->opt.mat_kernel != 1 && out.cap < ((int64_t)1 << 29) - 64 && t->cplan.stg.side_cap > 0;
 }
 
 // Tracks per workgroup of k_materialise_lin (option "lin_unit"; 0: chosen here).  A 32-track unit pays a unit's fixed phases — the
@@ -796,7 +796,7 @@ constexpr int64_t kLinUnit32MaxMean = 100;
 static int choose_lin_unit(const rt_tracks *t, bool queue) {
     const rt_mesh *m = t->mesh;
     if (queue) return 16;
-    if (m->lin_unit == 16 || m->lin_unit == 32) return m->lin_unit;
+    if (m->opt.lin_unit == 16 || m->opt.lin_unit == 32) return m->opt.lin_unit;
     const int64_t est = t->total_last > 0 ? t->total_last : (int64_t)(1.08 * m->kappa * t->sum_ell) + 2 * t->n;
     return est <= kLinUnit32MaxMean * t->n ? 32 : 16;
 }
@@ -814,7 +814,7 @@ int launch_materialise(rt_tracks *t, const rt::DOut &out, hipStream_t s, bool re
     a.etab_bytes = (int32_t)(uint32_t)std::min<uint64_t>((uint64_t)3 * (uint64_t)m->n_cells * sizeof(rt::EdgeABC), 0xffffffffull);
     a.n_units = 4 * c.n_whole_waves; a.rtol = c.rtol; a.tally = tally ? 1 : 0;
     a.coord_max = std::max(std::max(fabs(m->d.bx0), fabs(m->d.bx1)), std::max(fabs(m->d.by0), fabs(m->d.by1)));
-    a.force_exact = m->test_exact_sums; a.ctl = d_ctl; a.vacc = as_global(t->vacc.p);
+    a.force_exact = m->opt.test_exact_sums; a.ctl = d_ctl; a.vacc = as_global(t->vacc.p);
     if (tally) {
         RT_HIP(t->marg.reserve((size_t)c.n_whole_waves * 64 + 1));
         if (!t->marg_clean) { RT_HIP(hipMemsetAsync(t->marg.p, 0, sizeof(int32_t), s)); t->marg_clean = true; }

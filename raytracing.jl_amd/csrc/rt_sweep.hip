@@ -330,7 +330,7 @@ static bool sweep_staged_ok(const rt_tracks *t) { return t->cplan.staged && !t->
 
 // which rows a sweep with input 0 (an rt_solver's) reads, as the cell index's kind: 1 the staging rows, 2 rows made from the compact
 // records, 3 those records where they lie ("sweep_rows" 0) — the plan's choice, before a sweep has run
-static int sweep_rows_variant(const rt_tracks *t) { return sweep_staged_ok(t) ? 1 : (t->mesh->sweep_rows ? 2 : 3); }
+static int sweep_rows_variant(const rt_tracks *t) { return sweep_staged_ok(t) ? 1 : (t->mesh->opt.sweep_rows ? 2 : 3); }
 
 int sweep_repro_prepare(rt_tracks *t, int64_t *slots_out) {
     rt_mesh *m = t->mesh;
@@ -415,9 +415,9 @@ static SweepFacts sweep_facts(const rt_tracks *t, int32_t G, int32_t input, cons
     const rt_mesh *m = t->mesh;
     // (source regions: the solver's n_src stands in for the mesh's cells — the LDS copy of a pass holds n_src tallies per component)
     return SweepFacts{.n = t->n, .n_cells = loan.sr_n_src > 0 ? loan.sr_n_src : m->n_cells, .G = G, .input = input, .mode = loan.mode, .repro = loan.repro,
-                      .f32 = loan.f32 || m->sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
-                      .sw_ell_valid = t->sw.rows.ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->sweep_rows,
-                      .sweep_ell = m->sweep_ell, .sweep_gp = m->sweep_gp, .sweep_waves = m->sweep_waves, .regions = loan.n_regions,
+                      .f32 = loan.f32 || m->opt.sweep_precision == 1, .staged_ok = sweep_staged_ok(t), .codes = t->cplan.codes,
+                      .sw_ell_valid = t->sw.rows.ell_valid, .lds_per_block = m->lds_per_block, .sweep_rows = m->opt.sweep_rows,
+                      .sweep_ell = m->opt.sweep_ell, .sweep_gp = m->opt.sweep_gp, .sweep_waves = m->opt.sweep_waves, .regions = loan.n_regions,
                       .volcorr = volcorr, .srcreg = loan.sr_n_src > 0, .pn = loan.pn_M, .has_void = loan.has_void};
 }
 
@@ -579,7 +579,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     if (psi_in && n > 0) RT_HIP(hipMemcpyAsync(t->sw.io.psi_in.p, psi_in, (size_t)(2 * n * G) * sizeof(double), hipMemcpyHostToDevice, s));
     // option "async": the sweep's kernels are queued and the call returns (no events, no wait) — what was handed over in host
     // arrays has to be on the device before that
-    const bool async_sweep = m->async_calls && !m->timing;
+    const bool async_sweep = m->opt.async_calls && !m->opt.timing;
     if (async_sweep && (track_weight || (psi_in && n > 0))) RT_HIP(hipStreamSynchronize(s));
     // what this sweep reads and how wide its passes are, from the handle's state, the options and an rt_solver's loan for its run
     const SweepLoan &loan = t->sw.loan;
@@ -617,7 +617,7 @@ static int32_t sweep_impl(rt_tracks *t, int32_t G, const double *sigma_t, const 
     a.w = t->sw.io.has_w ? as_global((const double *)t->sw.io.w.p) : nullptr;
     a.xs = as_global((const double *)t->sw.io.xs.p);
     a.psi_in = as_global((const double *)t->sw.io.psi_in.p); a.psi_out = as_global(t->sw.io.psi_out.p); a.phi = as_global(t->sw.io.phi.p);
-    a.n = n; a.n_waves = (int32_t)((n + 63) / 64); a.n_cells = m->n_cells; a.G = G; a.debug = m->sweep_debug;
+    a.n = n; a.n_waves = (int32_t)((n + 63) / 64); a.n_cells = m->n_cells; a.G = G; a.debug = m->opt.sweep_debug;
     a.use_lds = plan.use_lds ? 1 : 0;
     if (moments) {  // the solver has filled sw.io.xs1 for these G components: first-moment ratios (P1), gradient ratios (Linear)
         if (mode == SweepMode::Linear && (!t->sw.io.xs1.p || !t->sw.io.cur.p || !loan.ls_cen || !loan.ls_ends)) { set_error("rt_sweep: the linear-source mode has no geometry arrays"); return RT_ERR_INVALID; }

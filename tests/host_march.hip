@@ -3,7 +3,7 @@
 // The geometry of the march (csrc/rt_device.hpp: walk_step and its certificates, find_element,
 // intersections) and the mesh preprocessing (csrc/rt_mesh_prep.hpp) are plain FP64 arithmetic that
 // compiles for the host as well.  This file drives them with the control flow of one lane of k_march
-// (csrc/rt_segmentize.hip; reference: _segmentize_track!, src/track.jl:106-178), so that the walk
+// (csrc/rt_march.hip; reference: _segmentize_track!, src/track.jl:106-178), so that the walk
 // step's certificates can be fuzzed against the CPU checker on thousands of meshes without a GPU:
 // walk on == walk off == checker, bit for bit (tests/test_walk_certificates_cpu.py, tools/fuzz_cpu.py).
 // It is not part of the product: the library never marches on the host, nothing in raytracing.jl_amd/

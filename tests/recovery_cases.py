@@ -2,7 +2,7 @@
 tests/test_gpu_recovery_matrix.py (every plan under every repair, on the device), tests/test_recovery_cases_cpu.py (the checks
 themselves, on a synthetic layout) and tests/test_gpu_completion_order.py.
 
-A call that an attempt leaves to repair (``Call::after_attempt``, rt_segmentize.hip: a plan that gave up, result arrays that were
+A call that an attempt leaves to repair (``SegmentizeCall::after_attempt``, csrc/rt_segmentize.hip: a plan that gave up, result arrays that were
 too short, surplus records of the split plan, tracks marched again at the iteration cap, pools that overflowed) must end with the
 checker's records, status and volumes whichever plan marched it.  The volumes are the weak spot of such a check: fill_volumes
 (src/trackgenerator.jl:371-386) weights a record with δs of ITS track's azimuthal index, and the quadrature's own δs are nearly

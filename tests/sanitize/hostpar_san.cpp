@@ -5,6 +5,8 @@
 //     caller that finds the team busy does its work alone), with ranges that do not divide evenly, and an exception in a worker;
 //   * plan_march_order on track sets whose size is and is not a multiple of 64, in the three sort modes: the march order is a
 //     permutation, reserved-chunk prefixes shrink with the chunk index, the compaction order is a permutation of the waves;
+//   * plan_split (pieces per wave, canonical numbering, dispatch order) at the sizes where its rule turns, in its three modes, and
+//     three plans worked by hand;
 //   * the upload's two forms — one image, and ranges through the two halves of a staging block with a "copy engine" thread that
 //     drains a half while the host fills the other (the events of the real code are a mutex + condition variable here);
 //   * the fetch's drain: pieces through two halves into a fresh destination.
@@ -74,6 +76,91 @@ static void test_plan(size_t n, int sort_mode, std::mt19937 &rng) {
     if (sort_mode == 2)  // waves of consecutive uids, longest wave first
         for (size_t s = 0; s + 1 < n; ++s)
             if ((p.perm[s] & 63) != 63 && (size_t)p.perm[s] + 1 < n) CHECK(p.perm[s + 1] == p.perm[s] + 1);
+}
+
+// plan_split on random lengths: the properties every plan has, from the rule as rt_hostpar.hpp states it (κ = 45 throughout)
+static void test_split(size_t n, int split, int max_iter, std::mt19937 &rng) {
+    const double kappa = 45.0;
+    std::vector<double> ell(n);
+    std::uniform_real_distribution<double> U(0.01, 3.0);
+    for (auto &v : ell) v = U(rng);
+    SplitPlan p;
+    p.vorder.assign(3, 7); p.n_vwaves = 3;  // (what a plan held before is gone)
+    plan_split(ell.data(), n, split, kappa, max_iter, p);
+    const size_t nw = (n + 63) / 64;
+    const int p_auto = (int)std::min<size_t>(16, (2048 + nw - 1) / std::max<size_t>(1, nw));
+    if (n == 0 || split == 0 || (split < 0 && nw >= 160)) {  // whole tracks: 160 waves and more never split on their own
+        CHECK(p.n_vwaves == 0 && p.vorder.empty() && p.vw_wave.empty() && p.vw_k.empty() && p.w_base.empty() && p.w_P.empty());
+        return;
+    }
+    CHECK(p.w_base.size() == nw && p.w_P.size() == nw);
+    if (p.w_base.size() != nw || p.w_P.size() != nw) return;
+    std::vector<double> piece_len;
+    int32_t sum = 0;
+    for (size_t w = 0; w < nw; ++w) {
+        double lmax = 0.0;
+        for (size_t i = w * 64; i < std::min(n, w * 64 + 64); ++i) lmax = std::max(lmax, ell[i]);
+        const int32_t P = p.w_P[w];
+        CHECK(p.w_base[w] == sum);  // the exclusive prefix sum of w_P
+        CHECK(P >= 1 && P <= (split > 0 ? 8 : p_auto));
+        if (lmax * kappa > 0.5 * max_iter) CHECK(P == 1);
+        for (int32_t k = 0; k < P; ++k) {  // (w, 0 .. P − 1) in order
+            const size_t v = (size_t)sum + (size_t)k;
+            CHECK(v < p.vw_wave.size() && v < p.vw_k.size());
+            if (v < p.vw_wave.size() && v < p.vw_k.size()) CHECK(p.vw_wave[v] == (int32_t)w && p.vw_k[v] == k);
+            piece_len.push_back(lmax / P);
+        }
+        sum += P;
+    }
+    CHECK(sum == p.n_vwaves && p.vorder.size() == (size_t)sum && p.vw_wave.size() == (size_t)sum && p.vw_k.size() == (size_t)sum);
+    if (p.vorder.size() != (size_t)sum) return;
+    std::vector<char> seen((size_t)sum, 0);
+    for (int32_t v : p.vorder) { CHECK(v >= 0 && v < sum); if (v >= 0 && v < sum) { CHECK(!seen[v]); seen[v] = 1; } else return; }
+    for (size_t k = 1; k < p.vorder.size(); ++k) {  // longest pieces first; equal pieces in their canonical order (stable)
+        const double a = piece_len[p.vorder[k - 1]], b = piece_len[p.vorder[k]];
+        CHECK(a > b || (a == b && p.vorder[k - 1] < p.vorder[k]));
+    }
+}
+
+// three plans worked by hand from the rule
+static void test_split_by_hand() {
+    using V = std::vector<int32_t>;
+    SplitPlan p;
+    {   // one track, auto: 1 wave < 160, p_auto = min(16, ceil(2048 / 1)) = 16; est = 2.0 · 45 = 90 expected segments,
+        // P = min(16, int(90 / 12 = 7.5)) = 7 pieces of 2/7 each: equal, so dispatched in canonical order
+        const double ell[1] = {2.0};
+        plan_split(ell, 1, -1, 45.0, 10000, p);
+        CHECK(p.n_vwaves == 7 && p.w_base == V{0} && p.w_P == V{7});
+        CHECK((p.vw_wave == V{0, 0, 0, 0, 0, 0, 0}) && (p.vw_k == V{0, 1, 2, 3, 4, 5, 6}) && (p.vorder == V{0, 1, 2, 3, 4, 5, 6}));
+    }
+    std::vector<double> ell(65, 0.5);
+    {   // 65 tracks, "split" = 4, κ = 10.  Wave 0 (64 lanes): ℓmax = 1.0, est = 10, P = min(8, ceil(10 / 4 = 2.5)) = 3, pieces of 1/3.
+        // Wave 1 (one lane): ℓ = 0.39, est = 3.9, P = ceil(0.975) = 1, one piece of 0.39 > 1/3: it is dispatched first
+        ell[10] = 1.0; ell[64] = 0.39;
+        plan_split(ell.data(), 65, 4, 10.0, 10000, p);
+        CHECK(p.n_vwaves == 4 && (p.w_base == V{0, 3}) && (p.w_P == V{3, 1}));
+        CHECK((p.vw_wave == V{0, 0, 0, 1}) && (p.vw_k == V{0, 1, 2, 0}) && (p.vorder == V{3, 0, 1, 2}));
+        // ... and with MAX_ITER = 18: wave 0's est = 10 > 0.5 · 18 marches whole, wave 1's 3.9 does not change
+        plan_split(ell.data(), 65, 4, 10.0, 18, p);
+        CHECK(p.n_vwaves == 2 && (p.w_base == V{0, 1}) && (p.w_P == V{1, 1}) && (p.vw_k == V{0, 0}) && (p.vorder == V{0, 1}));
+    }
+    {   // the same 65 tracks, auto, κ = 10: 2 waves < 160, p_auto = min(16, ceil(2048 / 2) = 1024) = 16.  Wave 0: ℓmax = 6.0, est = 60,
+        // P = min(16, int(60 / 12)) = 5, pieces of 1.2.  Wave 1: ℓ = 2.5, est = 25, P = int(25 / 12 = 2.08) = 2, pieces of 1.25: first
+        ell[10] = 6.0; ell[64] = 2.5;
+        plan_split(ell.data(), 65, -1, 10.0, 10000, p);
+        CHECK(p.n_vwaves == 7 && (p.w_base == V{0, 5}) && (p.w_P == V{5, 2}));
+        CHECK((p.vw_wave == V{0, 0, 0, 0, 0, 1, 1}) && (p.vw_k == V{0, 1, 2, 3, 4, 0, 1}) && (p.vorder == V{5, 6, 0, 1, 2, 3, 4}));
+    }
+}
+
+// every split-plan check (also run alone, without sanitizers, by tests/test_split_plan_cpu.py: argument "split")
+static void test_split_all(std::mt19937 &rng) {
+    test_split_by_hand();
+    // 65: the second wave has one lane; 159 · 64 and 160 · 64: the two sides of the rule that splits on its own
+    for (size_t n : {(size_t)0, (size_t)1, (size_t)64, (size_t)65, (size_t)159 * 64, (size_t)160 * 64})
+        for (int split : {-1, 0, 4})
+            for (int max_iter : {10000, 100})  // (100: waves whose longest track expects more than 50 segments march whole)
+                test_split(n, split, max_iter, rng);
 }
 
 // The upload as rt_tracks_create makes it, against a "device" that is host memory: returns the arena image
@@ -240,8 +327,14 @@ static void test_stream_copy() {
             }
 }
 
-int main() {
+int main(int argc, char **argv) {
     std::mt19937 rng(20261004);
+    if (argc > 1 && !strcmp(argv[1], "split")) {  // the split plan alone
+        test_split_all(rng);
+        printf("hostpar_san: %s\n", g_fail ? "FAILED" : "split plans (6 sizes x 3 modes x 2 caps, 3 by hand): ok");
+        return g_fail ? 1 : 0;
+    }
+    test_split_all(rng);
     test_stream_copy();
     test_result_block(1000, 300000, true);
     test_result_block(1, 1, false);
@@ -261,6 +354,6 @@ int main() {
         for (int c = 0; c < 4; ++c) th.emplace_back([c] { std::mt19937 r2(77 + c); test_upload(90000 + 1000 * (size_t)c, 2u << 20, r2); test_fetch((5u << 20) + c, 1u << 20, r2); });
         for (auto &t : th) t.join();
     }
-    printf("hostpar_san: %s\n", g_fail ? "FAILED" : "par_ranges, march plans (18 sets x 3 modes), uploads (image / ranges / concurrent), fetch drains, result blocks: ok");
+    printf("hostpar_san: %s\n", g_fail ? "FAILED" : "par_ranges, march plans (18 sets x 3 modes), split plans (6 sizes x 3 modes x 2 caps, 3 by hand), uploads (image / ranges / concurrent), fetch drains, result blocks: ok");
     return g_fail ? 1 : 0;
 }
